@@ -15,10 +15,13 @@ work is fixed; N > 1 adds the RCCL gradient all-reduce (overlapped with backward
 Since round 5 the timed run is the library default, padding-free execution (the encoder layers run on the packed unmasked
 token rows; loss, decoded tags and parameter gradients are those of the padded run: tests/test_unpad_gpu.py, the `pad_mode`
 fixture): `config.workload` says so, every roofline / fraction in the line counts EXECUTED flops only (never SURVEY 8d's
-F_train, which credits masked rows nobody computes), and the line carries the `padded` run (--padded / MTVAF_UNPAD=0) and the
-`full_length` run (nothing to skip) beside `value`.
+F_train, which credits masked rows nobody computes), and with --full the line carries the `padded` run (--padded / MTVAF_UNPAD=0)
+and the `full_length` run (nothing to skip) beside `value`.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run sets up, warms up, times the K steps and prints the line;
+`--full` adds everything else after the timed region: the optimizer-free, padded and full-length runs, the gradient-exchange
+timing (N > 1), `roofline`, the other BASELINE configurations, the front-end cache build, `cpu_baseline` and `parity` (the
+`--no-*` flags drop parts of it).  `--dump-outputs DIR` writes what the last timed step computed as .npy files (`dump_outputs`).
 """
 from __future__ import annotations
 
@@ -427,6 +430,31 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 4096  # elements per parameter tensor in params_sample.npy
+
+
+def dump_outputs(dirname, out, model, B, S):
+    """--dump-outputs: what the last timed step computed, for comparing two builds output for output on the same seeded
+    inputs.  loss.npy: the step's loss (float64, [1]); tags.npy: the decoded Viterbi paths (float32, [B, S], -1 past each
+    sentence's length); params_sample.npy: every parameter after the step's optimizer update, DUMP_SAMPLE elements of each at
+    fixed positions (seed 0; all of a smaller tensor), concatenated in `named_parameters()` order (float32, a few MB)."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"), np.array([float(out.loss.detach())], dtype=np.float64))
+    tags = np.full((B, S), -1.0, dtype=np.float32)
+    for i, row in enumerate(out.logits):
+        tags[i, :len(row)] = row
+    np.save(os.path.join(dirname, "tags.npy"), tags)
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g) if n > DUMP_SAMPLE else torch.arange(n)
+            parts.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(dirname, "params_sample.npy"), torch.cat(parts).numpy())
+
+
 def launch_ranks(n, argv, script=None, timeout_s=3000.0, extra_env=None):
     """`bench.py --gpus N` started WITHOUT a launcher (WORLD_SIZE unset): start the N ranks as fresh child processes --
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, as torch.distributed.run would -- wait for
@@ -524,12 +552,24 @@ def main():
                     help="N > 1: every rank draws its own ragged batch (seed 1234 + rank) instead of taking its length-balanced share "
                          "of ONE global batch of N x batch sentences (mtvaf_amd.parallel.balanced_shards: sort by length, deal in "
                          "snake order) -- under padding-free execution a rank's step time follows its token rows")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline: the optimizer-free, "
+                         "padded and full-length runs, the gradient-exchange timing (N > 1), the roofline pass, the other "
+                         "BASELINE configurations, the front-end cache build, the CPU baseline and the oracle parity report")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity report")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline pass")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary figures (fwd+bwd without the optimizer, padding-free): profiler runs, so that "
-                         "every kernel launch in the trace belongs to the headline workload")
+                    help="--full without the secondary figures (fwd+bwd without the optimizer, padded, full-length, other "
+                         "configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (loss, decoded tags, a fixed sample of the "
+                         "updated parameters; see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        # a plain run times the headline and nothing else: every figure beside it takes runs of its own
+        a.no_cpu_baseline = a.no_roofline = a.no_secondary = True
 
     import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
@@ -693,6 +733,8 @@ def main():
     if hip.streamk_errors():
         raise SystemExit("a stream-K launch of the bf16 GEMM reported a timed-out wait (mtvaf_amd.hip.streamk_errors)")
     log(f"timed region done: {dt:.3f}s for {a.steps} steps, loss {loss_val:.4f}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, model, B, S)
     value = world * B * a.steps / dt
     per_gpu = value / world
     ftrain = 3 * f_fwd(S, P)
@@ -816,7 +858,7 @@ def main():
         log(f"per-rank step times differ by {100 * rank_ms_spread:.1f} % (>= 3 %): the slowest rank sets `value`")
     res["n_ranks_seen"] = dist.get_world_size() if world > 1 else 1
     res["backend"] = dist.get_backend() if world > 1 else None
-    if sync is not None:
+    if sync is not None and a.full:
         # 3 further steps with an event pair around every exchange (outside the timed region: the events are not free)
         sync.timing = True
         for _ in range(3):
@@ -846,7 +888,6 @@ def main():
         attn_tflop = (sum(3 * 12 * 4 * int(n) * (int(n) + P) * 768 for n in lens_host) if a.unpad
                       else B * 3 * 12 * 4 * S * (S + P) * 768) / 1e12
         res["mfma_fraction_of_step_executed"] = round((ex + attn_tflop) / (1e-3 * res["ms_per_step"]) / PEAK_TFLOPS[peak_key], 4)
-    if rank == 0:
         log("roofline pass done")
     if rank == 0 and world == 1 and not a.no_secondary and not a.graph and (B, S, a.aux, a.dtype, a.model, a.unpad) == (32, 128, 8, "fp32", "bert", True):
         # the other BASELINE configurations that fit one GPU, measured by the same process AFTER the headline (secondary

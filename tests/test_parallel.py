@@ -474,8 +474,8 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["MTVAF_BENCH_ONE_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "8", "--seq", "64", "--aux", "3", "--no-cpu-baseline", "--no-roofline", "--no-secondary",
-                        "--grad-wire", "fp32"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "8", "--seq", "64", "--aux", "3", "--full", "--no-cpu-baseline", "--no-roofline",
+                        "--no-secondary", "--grad-wire", "fp32"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -524,9 +524,9 @@ def test_bench_self_launch_four_ranks_on_one_gpu_bf16_wire_with_sequence_check()
     env["MTVAF_BENCH_ONE_DEVICE"] = "1"
     env["MTVAF_CHECK_COLLECTIVES"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--batch", "8", "--seq", "128", "--aux", "3", "--dtype", "bf16", "--no-cpu-baseline", "--no-roofline",
-                        "--no-secondary", "--grad-wire", "bf16", "--grad-buckets", "2"], env=env, capture_output=True, text=True,
-                       timeout=1200)
+                        "--batch", "8", "--seq", "128", "--aux", "3", "--dtype", "bf16", "--full", "--no-cpu-baseline",
+                        "--no-roofline", "--no-secondary", "--grad-wire", "bf16", "--grad-buckets", "2"], env=env, capture_output=True,
+                       text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 4096

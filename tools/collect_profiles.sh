@@ -18,15 +18,15 @@ stats() {  # <name> <env assignment> <bench args...>
   rm -rf $O/prof_$name
 }
 if [ $PHASE = lines ]; then
-python bench.py --steps 20 --warmup 5 > $O/${T}_bench_line.json 2> $O/bench_fp32.err
+python bench.py --full --steps 20 --warmup 5 > $O/${T}_bench_line.json 2> $O/bench_fp32.err
 cp bench_detail.json $O/${T}_bench_detail.json
-python bench.py --steps 20 --warmup 5 --f32-pipe --no-cpu-baseline --no-secondary > $O/${T}_bench_line_fp32_pipe.json 2> $O/bench_pipe.err
-python bench.py --steps 20 --warmup 5 --full-length --no-cpu-baseline --no-secondary > $O/${T}_bench_line_full_length.json 2> $O/bench_full.err
-python bench.py --steps 20 --warmup 5 --padded --no-cpu-baseline --no-secondary > $O/${T}_bench_line_padded.json 2> $O/bench_padded.err
-python bench.py --steps 20 --warmup 5 --dtype bf16 --model roberta --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c3.json 2> $O/bench_c3.err
-python bench.py --steps 20 --warmup 5 --dtype bf16 --batch 64 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c4.json 2> $O/bench_c4.err
-python bench.py --steps 5 --warmup 4 --dtype bf16 --batch 128 --seq 512 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c5.json 2> $O/bench_c5.err
-python bench.py --steps 5 --warmup 4 --batch 128 --seq 512 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_fp32_c5.json 2> $O/bench_c5f.err
+python bench.py --full --steps 20 --warmup 5 --f32-pipe --no-cpu-baseline --no-secondary > $O/${T}_bench_line_fp32_pipe.json 2> $O/bench_pipe.err
+python bench.py --full --steps 20 --warmup 5 --full-length --no-cpu-baseline --no-secondary > $O/${T}_bench_line_full_length.json 2> $O/bench_full.err
+python bench.py --full --steps 20 --warmup 5 --padded --no-cpu-baseline --no-secondary > $O/${T}_bench_line_padded.json 2> $O/bench_padded.err
+python bench.py --full --steps 20 --warmup 5 --dtype bf16 --model roberta --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c3.json 2> $O/bench_c3.err
+python bench.py --full --steps 20 --warmup 5 --dtype bf16 --batch 64 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c4.json 2> $O/bench_c4.err
+python bench.py --full --steps 5 --warmup 4 --dtype bf16 --batch 128 --seq 512 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_bf16_c5.json 2> $O/bench_c5.err
+python bench.py --full --steps 5 --warmup 4 --batch 128 --seq 512 --no-cpu-baseline --no-secondary > $O/${T}_bench_line_fp32_c5.json 2> $O/bench_c5f.err
 python tools/f32x3_bench.py > $O/${T}_f32x3_microbench.txt 2>/dev/null
 python tools/f32x3_bench.py 2432 >> $O/${T}_f32x3_microbench.txt 2>/dev/null
 python tools/x3_trace.py 4096 3072 768 5 > $O/${T}_x3_trace.txt 2>/dev/null
