@@ -373,7 +373,7 @@ int mtvaf_f32p_trace(void* buf);
  * N_i % 256 == 0).  Among the admitted tiles a launch takes the cheapest by an estimate of rounds x tile time (QKV forward at 2432
  * rows: 192 columns, one round of 228 tiles; FFN-1: 256; N = 768 and 4096-row launches: mostly 128 x 128).  8 = never the 128 x 128
  * tile where another can serve (tests), 16 = never the 128 x 192 tile.  mask >= 0 sets, -1 queries; returns the mask in force
- * (default: MTVAF_P16_WIDE, 7 if unset).  Process-global; placement only -- the kernels issue the same MFMA products in the same
+ * (default 7).  Process-global; placement only -- the kernels issue the same MFMA products in the same
  * order for every output element and agree bit for bit. */
 int mtvaf_f32p_wide(int mask);
 /* research entry: up to four weight-gradient products C_i [M_i][N_i] = A_i^T . B_i from plane images (A_i [K][M_i], B_i [K][N_i], the

@@ -19,8 +19,6 @@
 // every product is permuted (step t, lane group g <-> k = 4g + t) identically on both operands.
 #include "attention_args.h"
 
-#include <cstdlib>
-
 namespace mtvaf {
 
 constexpr int LDT = 68;    // LDS row stride (floats) for 64-wide tiles: conflict-free b32 column reads
@@ -568,11 +566,7 @@ int mtvaf_f32_split(int on);  // (gemm.hip)
 
 // Round 6: under the split arithmetic (the library default: mtvaf_f32_split) the attention products are split bf16 products too
 // (csrc/attention_f32s.hip: same interface, geometry and outputs); the fp32 MFMA pipe keeps the kernels of this file.
-// MTVAF_ATTN_SPLIT=0: the kernels of this file in either arithmetic.
-static bool attn_split_on() {
-  static const int env = [] { const char* e = getenv("MTVAF_ATTN_SPLIT"); return e ? atoi(e) : 1; }();
-  return env != 0 && mtvaf_f32_split(-1) != 0;
-}
+static bool attn_split_on() { return mtvaf_f32_split(-1) != 0; }
 
 static void fill_common(AttnArgs& a, int B, int S, int P, int NH, float p_drop, uint64_t seed, uint64_t offset) {
   a.B = B; a.S = S; a.P = P; a.NH = NH; a.H = NH * D;

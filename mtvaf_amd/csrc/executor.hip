@@ -74,7 +74,6 @@ int mtvaf_prefix_attn_varlen_bwd_planes(const float* dctx, const float* qkv, con
                                         int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
                                         void* dqkv_planes, int rows, hipStream_t st);
 int mtvaf_zero_f32(float* p, long n, hipStream_t st);
-int mtvaf_f32_split_planes(const float* src, void* dst, int rows, int cols, int ld, long s_plane, long s_row, long s_kt, hipStream_t stream);
 int mtvaf_gemm_f32p(int layout_a, const void* Aplanes, long a_plane, long a_row, long a_kt, long a_col, int layout_b, const void* Bplanes,
                     long b_plane, long b_row, long b_kt, long b_col, float* C, int ldc, int M, int N, int K, const float* bias, int epi,
                     float* aux, int ldaux, int accumulate, int splits, void* workspace, size_t workspace_bytes, int ablate,
@@ -161,17 +160,13 @@ using namespace mtvaf;
 // Round 5: where a dense product in front of a LayerNorm runs as split-K slabs (the N = 768 products of a packed batch: 114
 // tiles x 2 splits), the LayerNorm adds the slabs itself -- forward Wo / FFN-2 (+ bias), backward the accumulating FFN-1 dX -- instead
 // of a reduction launch in between: 36 launches and as many passes over [M, H] less per step; same bits (the sum runs in the
-// reduction launch's order).  MTVAF_LN_SLABS=0: the reduction launches, as before.
-static bool ln_slabs_on() {
-  static const int on = [] { const char* e = getenv("MTVAF_LN_SLABS"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
+// reduction launch's order).  Without a workspace the product reduces its slabs itself.
 
 // dense product (+ bias) -> dropout + residual + LayerNorm, with the split-K slabs of the product handed to the LayerNorm
 static int dense_ln_fwd(const float* A, int K, const float* W, const float* bias, float* x_out, const float* res, const float* gamma,
                         const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
                         uint64_t offset, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (ln_slabs_on() && ws) {
+  if (ws) {
     int ns = 1;
     const int rc = mtvaf_gemm_f32_slabs(0, 0, A, K, W, K, x_out, H, M, H, K, bias, 0, ws, ws_bytes, &ns, st);
     if (rc != MTVAF_OK) return rc;
@@ -186,9 +181,6 @@ static int dense_ln_fwd(const float* A, int K, const float* W, const float* bias
 }
 
 // ---- pre-split operands (round 5; csrc/gemm_f32p.hip): tile-blocked plane images [cols / 32][3][rows][32] ----
-static int planes_of(const float* src, void* dst, int rows, int cols, hipStream_t st) {
-  return mtvaf_f32_split_planes(src, dst, rows, cols, cols, (long)rows * 64, 64, (long)3 * rows * 64, st);
-}
 // the split-K plan of a forward / dX product on the pre-split kernel: two slabs where the 128 x 128 tiles alone leave half the
 // CUs idle (the 768-wide results of a packed batch: 114 tiles), measured best in tools/f32p_bench.py at 2432 and 4096 rows
 static int p16_splits(int M, int N, int K) {
@@ -260,9 +252,11 @@ struct mtvaf_layer_grads_t {
   const int* kcnt;
   int zero_tail;                               // the caller's word: token rows behind a sentence's last unmasked position carry exactly-zero
                                                // gradients (what a k-tile list implies): attention backward stops its query loops there
-  float *lnpart2, *lnpart1;                    // optional (both or neither): per-layer LayerNorm-backward partials of the FFN / attention
-                                               // block (mtvaf_ln_bwd_workspace_bytes each) -- their column sums then run on `side`
-  void *df_p, *dpre_p, *da_p, *dqkv_p;         // pre-split operands: scratch plane images of df / dpre / da / dqkv, or NULL
+  float *lnpart2, *lnpart1;                    // optional (both or neither; required with plane images): per-layer LayerNorm-backward
+                                               // partials of the FFN / attention block (mtvaf_ln_bwd_workspace_bytes each) -- their column
+                                               // sums then run on `side`
+  void *df_p, *dpre_p, *da_p, *dqkv_p;         // pre-split operands: scratch plane images of df / dpre / da / dqkv (with `part`, both
+                                               // lnpart and ws_main: required when the layer struct has plane images), or NULL
 };
 
 // fp32 mode with pre-split operands: every plane image present, packed rows (whole 128-row tiles), whole 128-column tiles
@@ -273,17 +267,6 @@ static int p16_ep(int lb, const void* Ap, const void* Wp, void* Cp, float* colpa
   const long bp = (long)(lb == 0 ? N : K) * 64, bkt = lb == 0 ? (long)3 * N * 64 : 2048, bc = lb == 0 ? 0 : (long)12 * K * 64;
   return mtvaf_gemm_f32p_ep(0, Ap, ap, 64, akt, 0, lb, Wp, bp, 64, bkt, bc, nullptr, 0, Cp, colpart, M, N, K, bias, epi, aux, ldaux, 0, st);
 }
-// MTVAF_P16_EP=0: the GELU / GELU' results as fp32 tensors + a split pass each (the first form of the pre-split path)
-static bool p16_ep_on() {
-  static const int on = [] { const char* e = getenv("MTVAF_P16_EP"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
-
-// MTVAF_ATTN_PLANES=0: the attention kernels write fp32 only and a split pass follows
-static bool attn_planes_on() {
-  static const int on = [] { const char* e = getenv("MTVAF_ATTN_PLANES"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
 
 static bool planes_mode(const mtvaf_layer_t* L) {
   return !L->bf16 && L->cu && L->x_p && L->cx_p && L->h1_p && L->act_p && L->wqkv_h && L->wo_h && L->w1_h && L->w2_h && L->Mp % 128 == 0 &&
@@ -291,27 +274,15 @@ static bool planes_mode(const mtvaf_layer_t* L) {
 }
 
 // dense product on the pre-split kernel (+ bias) -> dropout + residual + LayerNorm, the product's split-K slabs handed to the LayerNorm
-// MTVAF_LN_PLANES=0: the LayerNorm kernels write fp32 only and a split pass follows (the first form of the pre-split path)
-static bool ln_planes_on() {
-  static const int on = [] { const char* e = getenv("MTVAF_LN_PLANES"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
 static int dense_ln_fwd_p(const void* Ap, int K, const void* Wp, const float* bias, float* x_out, const float* res, const float* gamma,
                           const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
                           uint64_t offset, void* ws, size_t ws_bytes, void* out_planes, hipStream_t st) {
   int ns = 1;
-  int rc = p16(0, Ap, Wp, x_out, H, M, H, K, bias, X_EPI_NONE, nullptr, 0, 0, ws, ws_bytes, ln_slabs_on() ? &ns : nullptr, st);
+  const int rc = p16(0, Ap, Wp, x_out, H, M, H, K, bias, X_EPI_NONE, nullptr, 0, 0, ws, ws_bytes, &ns, st);
   if (rc != MTVAF_OK) return rc;
-  if (out_planes && ln_planes_on())  // (the LayerNorm writes the plane image of its output itself)
+  if (out_planes)  // (the LayerNorm writes the plane image of its output itself)
     return mtvaf_dropout_res_ln_fwd_planes(ns > 1 ? static_cast<const float*>(ws) : x_out, ns > 1 ? ns : 0, bias, x_out, res, gamma, beta, out,
                                            mean, rstd, M, H, eps, p_drop, seed, offset, out_planes, st);
-  if (out_planes) {
-    rc = ns > 1 ? mtvaf_dropout_res_ln_fwd_slabs(static_cast<const float*>(ws), ns, bias, x_out, res, gamma, beta, out, mean, rstd, M, H, eps,
-                                                 p_drop, seed, offset, nullptr, st)
-                : mtvaf_dropout_res_ln_fwd(x_out, res, gamma, beta, out, mean, rstd, M, H, eps, p_drop, seed, offset, nullptr, st);
-    if (rc != MTVAF_OK) return rc;
-    return planes_of(out, out_planes, M, H, st);
-  }
   if (ns > 1)
     return mtvaf_dropout_res_ln_fwd_slabs(static_cast<const float*>(ws), ns, bias, x_out, res, gamma, beta, out, mean, rstd, M, H, eps, p_drop,
                                           seed, offset, nullptr, st);
@@ -352,25 +323,16 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
   float* act = static_cast<float*>(L->act);
   if (planes_mode(L)) {
     // pre-split operands (round 5): the same layer on the kernels of csrc/gemm_f32p.hip; every GEMM operand is read as a plane
-    // image -- weights written once per optimizer step, activations by one pass behind the kernel that produces them
+    // image -- weights written once per optimizer step, activations by the kernel that produces them (the attention forward, the
+    // LayerNorms and the FFN-1 epilogue write plane images themselves)
     MTVAF_TRY(p16(0, L->x_p, L->wqkv_h, qkv, 3 * H, M, 3 * H, H, L->bqkv, X_EPI_NONE, nullptr, 0, 0, L->ws, L->ws_bytes, nullptr, st));
-    if (attn_planes_on()) {  // (the attention kernel writes the context's plane image itself)
-      MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_planes(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                                    L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset,
-                                                    L->cx_p, M, st));
-    } else {
-      MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                             L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset, st));
-      MTVAF_TRY(planes_of(cx, L->cx_p, M, H, st));
-    }
+    MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_planes(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                  L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset,
+                                                  L->cx_p, M, st));
     MTVAF_TRY(dense_ln_fwd_p(L->cx_p, H, L->wo_h, L->bo, L->a, L->x, L->g1, L->b1, L->h1, L->mean1, L->rstd1, M, H, L->eps, L->p_hidden,
                              L->seed, L->offset + 1, L->ws, L->ws_bytes, L->h1_p, st));
-    if (p16_ep_on()) {  // (the GELU output is read by GEMMs only: it leaves the FFN-1 epilogue as a plane image, no fp32 copy)
-      MTVAF_TRY(p16_ep(0, L->h1_p, L->w1_h, L->act_p, nullptr, M, I, H, L->bi1, X_EPI_GELU, pre, I, st));
-    } else {
-      MTVAF_TRY(p16(0, L->h1_p, L->w1_h, act, I, M, I, H, L->bi1, X_EPI_GELU, pre, I, 0, L->ws, L->ws_bytes, nullptr, st));
-      MTVAF_TRY(planes_of(act, L->act_p, M, I, st));
-    }
+    // (the GELU output is read by GEMMs only: it leaves the FFN-1 epilogue as a plane image, no fp32 copy -- L->act is not read)
+    MTVAF_TRY(p16_ep(0, L->h1_p, L->w1_h, L->act_p, nullptr, M, I, H, L->bi1, X_EPI_GELU, pre, I, st));
     MTVAF_TRY(dense_ln_fwd_p(L->act_p, I, L->w2_h, L->bi2, L->f, L->h1, L->g2, L->b2, L->h2, L->mean2, L->rstd2, M, H, L->eps, L->p_hidden,
                              L->seed, L->offset + 2, L->ws, L->ws_bytes, L->h2_p, st));
     return MTVAF_OK;
@@ -420,11 +382,6 @@ int mtvaf_dw_group_wanted(int rows, int H, int I) {
   if (rows <= 0 || rows % 32 || H % 128 || I % 128) return 0;
   if (rows <= mtvaf_dw_group_rows(-1) && H % 96 == 0 && I % 96 == 0) return 1;
   return (x3_group && rows > 1024 && mtvaf_f32_split(-1)) ? 1 : 0;
-}
-
-static bool attn_tail_on() {  // MTVAF_ATTN_TAIL=0: the attention backward keeps its full query loops under a k-tile list too
-  static const int on = [] { const char* e = getenv("MTVAF_ATTN_TAIL"); return e ? atoi(e) : 1; }();
-  return on != 0;
 }
 
 // LayerNorm backward of one block of the layer, then the fork the weight gradients behind it need anyway.  With per-layer
@@ -479,7 +436,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     } else {
       MTVAF_TRY(mtvaf_prefix_attn_bf16_bwd_tail(g->dctx, L->qkv, L->pk, L->pv, L->addmask, L->cx, L->lse, g->dqkv, g->dpk, g->dpv, g->partq,
                                                 g->partkv, B, S, P, NH, 64, L->p_attn, L->seed, L->offset,
-                                                ((g->klist != nullptr || g->zero_tail) && attn_tail_on()) ? 1 : 0, mainS));
+                                                (g->klist != nullptr || g->zero_tail) ? 1 : 0, mainS));
     }
     MTVAF_TRY(fork_to(mainS, side));
     MTVAF_TRY(mtvaf_colsum_small(g->partq, B * ((S + 63) / 64), H, g->dbqkv, 0, side));
@@ -506,64 +463,29 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     const float* cx = static_cast<const float*>(L->cx);
     float* pre = static_cast<float*>(L->pre);
     const float* act = static_cast<const float*>(L->act);
-    if (planes_mode(L) && g->df_p && g->dpre_p && g->da_p && g->dqkv_p && g->ws_main) {
-      // pre-split operands (round 5): the dX chain and the grouped weight gradients on the kernels of csrc/gemm_f32p.hip
-      // (df and da are read by GEMMs only: with per-layer partial buffers and a second stream the LayerNorm backward kernels write
-      // their plane images themselves and no fp32 copy)
-      const bool lnp = ln_planes_on() && g->lnpart2 && g->lnpart1;
-      if (lnp) {  // (its column sums -- dgamma, dbeta, the FFN-2 bias gradient -- are jobs of the grouped weight-gradient launch below)
-        MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh, nullptr, 0, L->f, L->h1, L->g2, L->mean2, L->rstd2, nullptr, g->dh1, 0, M, H,
-                                                       L->p_hidden, L->seed, L->offset + 2, g->lnpart2, g->df_p, mainS));
-      } else {
-        MTVAF_TRY(ln_bwd_forked(g->dh, L->f, L->h1, L->g2, L->mean2, L->rstd2, df, g->dh1, g->dg2, g->db2, g->dbi2, M, H, L->p_hidden, L->seed,
-                                L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
-        MTVAF_TRY(planes_of(df, g->df_p, M, H, mainS));
-      }
-      const bool ep = p16_ep_on() && g->part != nullptr;
-      if (ep) {  // (dpre is read by GEMMs only -- and summed over its rows for the FFN-1 bias gradient: per-tile sums from the epilogue)
-        MTVAF_TRY(p16_ep(1, g->df_p, L->w2_h, g->dpre_p, g->part, M, I, H, nullptr, X_EPI_DGELU, pre, I, mainS));
-      } else {
-        MTVAF_TRY(p16(1, g->df_p, L->w2_h, dpre, I, M, I, H, nullptr, X_EPI_DGELU, pre, I, 0, g->ws_main, g->ws_main_bytes, nullptr, mainS));
-        MTVAF_TRY(planes_of(dpre, g->dpre_p, M, I, mainS));
-      }
-      int ns1 = 1;
-      const bool slabs1 = ln_slabs_on() && g->lnpart1 && (lnp || side != mainS);  // (the LayerNorm's partials must not share the slabs' scratch)
-      MTVAF_TRY(p16(1, g->dpre_p, L->w1_h, g->dh1, H, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes,
-                    slabs1 ? &ns1 : nullptr, mainS));
-      if (lnp) {
-        MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh1, static_cast<const float*>(g->ws_main), ns1 > 1 ? ns1 : 0, L->a, L->x, L->g1,
-                                                       L->mean1, L->rstd1, nullptr, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1,
-                                                       g->lnpart1, g->da_p, mainS));
-      } else {
-        if (ns1 > 1) {
-          MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_slabs(g->dh1, static_cast<const float*>(g->ws_main), ns1, L->a, L->x, L->g1, L->mean1,
-                                                        L->rstd1, da, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1, g->lnpart1, nullptr,
-                                                        mainS));
-          MTVAF_TRY(fork_to(mainS, side));
-          MTVAF_TRY(mtvaf_dropout_res_ln_bwd_finish(g->lnpart1, M, H, g->dg1, g->db1, g->dbo, 0, side));
-        } else {
-          MTVAF_TRY(ln_bwd_forked(g->dh1, L->a, L->x, L->g1, L->mean1, L->rstd1, da, g->dh, g->dg1, g->db1, g->dbo, M, H, L->p_hidden, L->seed,
-                                  L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
-        }
-        MTVAF_TRY(planes_of(da, g->da_p, M, H, mainS));
-      }
+    if (planes_mode(L)) {
+      // pre-split operands (round 5): the dX chain and the grouped weight gradients on the kernels of csrc/gemm_f32p.hip.  df, dpre
+      // and da are read by GEMMs only: the LayerNorm backward kernels and the GELU' epilogue write their plane images and no fp32
+      // copy (the arena holds none), so every buffer of that form must be there
+      if (!g->df_p || !g->dpre_p || !g->da_p || !g->dqkv_p || !g->part || !g->lnpart2 || !g->lnpart1 || !g->ws_main) return MTVAF_ERR_ARG;
+      // (the LayerNorm's column sums -- dgamma, dbeta, the FFN-2 bias gradient -- are jobs of the grouped weight-gradient launch below)
+      MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh, nullptr, 0, L->f, L->h1, L->g2, L->mean2, L->rstd2, nullptr, g->dh1, 0, M, H,
+                                                     L->p_hidden, L->seed, L->offset + 2, g->lnpart2, g->df_p, mainS));
+      // (dpre is also summed over its rows for the FFN-1 bias gradient: per-tile sums from the epilogue)
+      MTVAF_TRY(p16_ep(1, g->df_p, L->w2_h, g->dpre_p, g->part, M, I, H, nullptr, X_EPI_DGELU, pre, I, mainS));
+      int ns1 = 1;  // (the LayerNorm's partials have buffers of their own: the product's split-K slabs stay in ws_main for it)
+      MTVAF_TRY(p16(1, g->dpre_p, L->w1_h, g->dh1, H, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
+      MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh1, static_cast<const float*>(g->ws_main), ns1 > 1 ? ns1 : 0, L->a, L->x, L->g1,
+                                                     L->mean1, L->rstd1, nullptr, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1,
+                                                     g->lnpart1, g->da_p, mainS));
       MTVAF_TRY(p16(1, g->da_p, L->wo_h, dctx, H, M, H, H, nullptr, X_EPI_NONE, nullptr, 0, 0, g->ws_main, g->ws_main_bytes, nullptr, mainS));
-      if (attn_planes_on()) {
-        MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_planes(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                                      L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
-                                                      L->seed, L->offset, g->dqkv_p, M, mainS));
-      } else {
-        MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                               L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
-                                               L->seed, L->offset, mainS));
-        MTVAF_TRY(planes_of(dqkv, g->dqkv_p, M, 3 * H, mainS));
-      }
+      MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_planes(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                    L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
+                                                    L->seed, L->offset, g->dqkv_p, M, mainS));
       MTVAF_TRY(fork_to(mainS, side));
-      // second stream: the two bias gradients that are column sums of dY, then the four weight gradients as ONE launch
-      if (!ep) MTVAF_TRY(mtvaf_colsum(dpre, M, I, I, g->dbi1, 0, g->ws_side, g->ws_side_bytes, side));
-      // (the small reductions of the layer are COLUMN-SUM JOBS of the grouped launch below -- extra blocks that fill the CUs its
-      // last round of tiles leaves idle: the QKV bias gradient = column sums of dQ|dK|dV, the FFN-1 bias gradient from the GELU'
-      // epilogue's per-tile sums, the two LayerNorm finishes = three column blocks of their partial rows each)
+      // second stream: the four weight gradients as ONE launch.  The small reductions of the layer are COLUMN-SUM JOBS of it -- extra
+      // blocks that fill the CUs its last round of tiles leaves idle: the QKV bias gradient = column sums of dQ|dK|dV, the FFN-1 bias
+      // gradient from the GELU' epilogue's per-tile sums, the two LayerNorm finishes = three column blocks of their partial rows each
       {
         const void* const As[4] = {g->df_p, g->dpre_p, g->da_p, g->dqkv_p};
         const void* const Bs[4] = {L->act_p, L->h1_p, L->cx_p, L->x_p};
@@ -573,27 +495,15 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
         for (int i = 0; i < 8; ++i) {  // (every image has M rows: plane M * 64, k-row 64, k-tile 2048, 128-column block 12 * M * 64)
           strides[4 * i] = (long)M * 64; strides[4 * i + 1] = 64; strides[4 * i + 2] = 2048; strides[4 * i + 3] = (long)12 * M * 64;
         }
-        static const int jobs_on = [] { const char* e = getenv("MTVAF_DW_JOBS"); return e ? atoi(e) : 1; }();  // (0: one launch per reduction)
-        if (!jobs_on) {
-          MTVAF_TRY(mtvaf_colsum(dqkv, M, 3 * H, 3 * H, g->dbqkv, 0, g->ws_side, g->ws_side_bytes, side));
-          if (ep) MTVAF_TRY(mtvaf_colsum_small(g->part, M / 128, I, g->dbi1, 0, side));
-          if (lnp) {
-            MTVAF_TRY(mtvaf_dropout_res_ln_bwd_finish(g->lnpart2, M, H, g->dg2, g->db2, g->dbi2, 0, side));
-            MTVAF_TRY(mtvaf_dropout_res_ln_bwd_finish(g->lnpart1, M, H, g->dg1, g->db1, g->dbo, 0, side));
-          }
-        }
         const float* js[8]; float* jd[8]; int jr[8], jc[8], jl[8], nj = 0;
         auto job = [&](const float* src, int rows, int cols, int ld, float* dst) {
           if (dst) { js[nj] = src; jr[nj] = rows; jc[nj] = cols; jl[nj] = ld; jd[nj] = dst; ++nj; }
         };
         job(dqkv, M, 3 * H, 3 * H, g->dbqkv);
-        if (ep) job(g->part, M / 128, I, I, g->dbi1);
-        if (lnp) {
-          const int G = (int)(mtvaf_ln_bwd_workspace_bytes(M, H) / ((size_t)16 * H));  // partial rows [G][3][H] of each LayerNorm backward
-          job(g->lnpart2, G, H, 3 * H, g->dg2); job(g->lnpart2 + H, G, H, 3 * H, g->db2); job(g->lnpart2 + 2 * H, G, H, 3 * H, g->dbi2);
-          job(g->lnpart1, G, H, 3 * H, g->dg1); job(g->lnpart1 + H, G, H, 3 * H, g->db1); job(g->lnpart1 + 2 * H, G, H, 3 * H, g->dbo);
-        }
-        if (!jobs_on) nj = 0;
+        job(g->part, M / 128, I, I, g->dbi1);
+        const int G = (int)(mtvaf_ln_bwd_workspace_bytes(M, H) / ((size_t)16 * H));  // partial rows [G][3][H] of each LayerNorm backward
+        job(g->lnpart2, G, H, 3 * H, g->dg2); job(g->lnpart2 + H, G, H, 3 * H, g->db2); job(g->lnpart2 + 2 * H, G, H, 3 * H, g->dbi2);
+        job(g->lnpart1, G, H, 3 * H, g->dg1); job(g->lnpart1 + H, G, H, 3 * H, g->db1); job(g->lnpart1 + 2 * H, G, H, 3 * H, g->dbo);
         if (nj > 0) MTVAF_TRY(mtvaf_gemm_f32p_dw_group_colsum(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, nj, js, jr, jc, jl, jd, side));
         else MTVAF_TRY(mtvaf_gemm_f32p_dw_group(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, side));
       }
@@ -617,7 +527,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     // (the LayerNorm backward behind this accumulating product adds its split-K slabs itself when its column sums have their
     // own partial buffer -- otherwise its scratch would be the workspace that holds the slabs)
     int ns1 = 1;
-    if (ln_slabs_on() && g->lnpart1 && side != mainS && g->ws_main) {
+    if (g->lnpart1 && side != mainS && g->ws_main) {
       MTVAF_TRY(mtvaf_gemm_f32_slabs(X_KC, X_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
     } else {
       MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1, 1, g->ws_main,
@@ -645,7 +555,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       // last unmasked position)
       MTVAF_TRY(mtvaf_prefix_attn_bwd_tail(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->addmask, cx,
                                            L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn, L->seed, L->offset,
-                                           ((g->klist != nullptr || g->zero_tail) && attn_tail_on()) ? 1 : 0, mainS));
+                                           (g->klist != nullptr || g->zero_tail) ? 1 : 0, mainS));
     }
     MTVAF_TRY(fork_to(mainS, side));
     if (!grp) MTVAF_TRY(mtvaf_colsum(dqkv, M, 3 * H, 3 * H, g->dbqkv, 0, g->ws_side, g->ws_side_bytes, side));

@@ -751,25 +751,13 @@ void prof_end(int i, hipStream_t stream) {
 // blocks, so time ~ rounds over the 256 CUs x work per tile / efficiency of that tile shape (calibrated
 // with tools/gemm_sweep.py on MI355X at M = 4096), plus, for split-K, the slab write + ordered reduce.
 static bool x3_tile96_ok(int M, int N, int la, int lb) {
-  static const int tile96 = [] { const char* e = getenv("MTVAF_X3_TILE96"); return e ? atoi(e) : 1; }();
-  return M % 128 == 0 && N % 96 == 0 && (tile96 == 2 || (tile96 == 1 && la == 0 && lb == 0));
+  return M % 128 == 0 && N % 96 == 0 && la == 0 && lb == 0;
 }
 
 // 128x128 tiles of the wave-specialised split kernel may hang over the result (clamped loads, guarded stores): any M, N that
-// are multiples of 4 and at least one tile -- the prompt generator's N = 800 (MTVAF_X3_RAGGED=0: whole tiles only)
-static bool x3_tile64_ok(int M, int N) {
-  static const int on = [] { const char* e = getenv("MTVAF_X3_TILE64"); return e ? atoi(e) : 1; }();
-  return on && M % 128 == 0 && N % 64 == 0;
-}
-
+// are multiples of 4 and at least one tile -- the prompt generator's N = 800
 static bool x3_ragged_ok(int M, int N) {
-  static const int on = [] { const char* e = getenv("MTVAF_X3_RAGGED"); return e ? atoi(e) : 1; }();
-  return on && M % 4 == 0 && N % 4 == 0 && M >= 128 && N >= 128;
-}
-
-static double x3_e64() {
-  static const double e = [] { const char* v = getenv("MTVAF_X3_E64"); return v ? atof(v) : 0.47; }();
-  return e;
+  return M % 4 == 0 && N % 4 == 0 && M >= 128 && N >= 128;
 }
 
 static void choose(int M, int N, int K, int allow_split, int la, int lb, int epi, int* cfg_out, int* splits_out,
@@ -797,12 +785,12 @@ static void choose(int M, int N, int K, int allow_split, int la, int lb, int epi
   for (int c = 0; c < kNumCfgs; ++c) {
     if (eff[c] <= 0.0) continue;
     if (compute == 1 && !(c == 6 || c == 5 || c == 3)) continue;  // bf16 kernels exist for 128x96, 128x128, 64x64
-    // (the 128x96 split tile: forward products only by default -- with a k-major B operand or as a weight gradient it
-    // measured level or behind 128x128 + split-K in the bench step; MTVAF_X3_TILE96 = 0 never, 2 every layout)
+    // (the 128x96 split tile: forward products only -- with a k-major B operand or as a weight gradient it measured level or
+    // behind 128x128 + split-K in the bench step)
     const bool c6_ok = x3_tile96_ok(M, N, la, lb);
     // (128x64, round 5: the wave-specialised kernel's third layout, for row counts that leave the wider tiles on half the CUs --
-    // packed batches; every layout; MTVAF_X3_TILE64=0 never)
-    const bool c4_ok = x3_tile64_ok(M, N);
+    // packed batches; every layout)
+    const bool c4_ok = M % 128 == 0 && N % 64 == 0;
     if (compute == 2 && !((c == 5 && ((M % 128 == 0 && N % 128 == 0) || ragged5)) || (c == 6 && c6_ok) || (c == 4 && c4_ok) || (c == 3 && M % 64 == 0 && N % 64 == 0))) continue;
     const int bm = kCfgs[c].bm, bn = kCfgs[c].bn, bk = compute != 0 ? 32 : kCfgs[c].bk;
     const long tiles = cdiv(M, bm) * cdiv(N, bn);
@@ -810,9 +798,8 @@ static void choose(int M, int N, int K, int allow_split, int la, int lb, int epi
     // K = 2304 / 3072 now run as 192 unsplit tiles.  They sit on the main chain of a backward pass while the grouped weight
     // gradients share the chip on the second stream, so what a split costs is its CU time (6 us of prologue + epilogue per
     // block, a slab pass and a reduction launch) rather than what it saves in latency alone: 4 splits measured 15.20-15.26 ms
-    // per step, this cap 14.85-14.97 (MTVAF_X3_DX_MAXSPLIT overrides)
-    static const int dx_max_s = [] { const char* e = getenv("MTVAF_X3_DX_MAXSPLIT"); return e ? atoi(e) : 2; }();
-    const int max_s = allow_split ? ((compute == 2 && la == 0 && lb == 1 && tiles >= 128) ? dx_max_s : 16) : 1;
+    // per step, this cap 14.85-14.97
+    const int max_s = allow_split ? ((compute == 2 && la == 0 && lb == 1 && tiles >= 128) ? 2 : 16) : 1;
     for (int s = 1; s <= max_s; ++s) {
       if (s > 1 && K / s < 256) break;
       const long rounds = cdiv(tiles * s, 256);
@@ -828,7 +815,7 @@ static void choose(int M, int N, int K, int allow_split, int la, int lb, int epi
       // split kernels (one block per CU, whole rounds decide): 128x128 a little ahead of 128x96 at equal rounds x area
       // (fewer operand bytes per flop), the 64x64 every-wave kernel well behind both
       // (128x64: 192 staged rows per k-tile for half the products of 128x128's 256 -- 0.70 x 0.5 / 0.75)
-      const double e = compute == 2 ? (c == 5 ? 0.70 : (c == 6 ? 0.68 : (c == 4 ? x3_e64() : 0.45))) : ((c >= 16 && tiles * s <= 256) ? 1.0 : eff[c]);
+      const double e = compute == 2 ? (c == 5 ? 0.70 : (c == 6 ? 0.68 : (c == 4 ? 0.47 : 0.45))) : ((c >= 16 && tiles * s <= 256) ? 1.0 : eff[c]);
       double cost = (double)rounds * bm * bn * kc / 128.0 / (e * occ2);
       cost += 3000.0;  // fill/drain + launch  (charging the split kernels' traced 6.2 us of prologue + epilogue per ROUND instead
                        // was tried in round 4: with the k-tile lists of the bench batch the weight gradients then take 4
@@ -908,7 +895,6 @@ int mtvaf_gemm_f32_plan(int layout_a, int layout_b, int M, int N, int K, int epi
 // gelu'(aux)), 4 dtanh (multiply by 1-aux^2).  accumulate: C += result.  allow_split: permit a
 // deterministic split-K (slabs in workspace + ordered reduction); cfg/splits < 0 = heuristic.
 static long long* g_x3_trace = nullptr;
-static int g_x3_tile_walk = [] { const char* e = getenv("MTVAF_X3_TILE_WALK"); return e ? atoi(e) : 0; }();
 
 static int gemm_dispatch(int compute, int layout_a, int layout_b, const float* A, int lda, const float* B, int ldb,
                          float* C, int ldc, int M, int N, int K, const float* bias, int epi, float* aux, int ldaux,
@@ -941,7 +927,7 @@ static int gemm_dispatch(int compute, int layout_a, int layout_b, const float* A
     // (few output tiles -- the 256-token products of BASELINE configs[0] -- leave most CUs without a block of the 128x128
     // kernel: the fp32 pipe's 64x64 tiles are faster there, measured 4.37 vs 4.53 ms per C1 step)
     const long tiles96 = can6 ? (long)(M / 128) * (N / 96) : 0;
-    const long tiles64 = (can4 && x3_tile64_ok(M, N)) ? (long)(M / 128) * (N / 64) : 0;
+    const long tiles64 = can4 ? (long)(M / 128) * (N / 64) : 0;
     const long tiles = std::max(std::max(rag5 ? cdiv(M, 128) * cdiv(N, 128) : (long)(M / 128) * (N / 128), tiles96), tiles64);
     // ... unless the reduction is deep enough for split-K to fill the chip anyway (the [768 x 768] weight gradient over 4096
     // token rows: 36 tiles x 7 splits, 38-41 us against 46-51 on the fp32 pipe)
@@ -966,7 +952,7 @@ static int gemm_dispatch(int compute, int layout_a, int layout_b, const float* A
   GemmArgs a;
   a.klist = nullptr; a.kcnt = nullptr; a.ngrp = 0;
   a.trace = g_x3_trace;
-  a.tile_walk = g_x3_tile_walk;
+  a.tile_walk = 0;
   a.A = A; a.B = B; a.bias = bias; a.aux = aux;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldaux = ldaux;
   a.epi = epi; a.accumulate = accumulate;
@@ -1220,8 +1206,7 @@ static int dw_group_impl(int n, const float* const* A, const int* lda, const flo
       } else {
         g.C = C[i]; g.ldc = ldc[i]; g.slab_stride = 0;
       }
-      static const int fuse_bias = [] { const char* e = getenv("MTVAF_X3_DW_BIAS"); return e ? atoi(e) : 1; }();  // (0: always mtvaf_colsum)
-      g.colsum = (fuse_bias && splits == 1 && dbias && dbias[i] && (((uintptr_t)dbias[i] & 15) == 0)) ? dbias[i] : nullptr;
+      g.colsum = (splits == 1 && dbias && dbias[i] && (((uintptr_t)dbias[i] & 15) == 0)) ? dbias[i] : nullptr;
     }
     a.ngrp = n;
     a.A = a.grp[0].A; a.B = a.grp[0].B; a.C = a.grp[0].C;

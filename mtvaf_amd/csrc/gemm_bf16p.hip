@@ -59,7 +59,6 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdlib>
 #include <type_traits>
 
 namespace mtvaf {
@@ -618,9 +617,8 @@ static int p256_check(const GemmArgsX& a) {
 int launch_p256(const GemmArgsX& a, int layout_a, int layout_b, dim3 grid, hipStream_t st) {
   if (int rc = p256_check(a)) return rc;
   P256SK sk = {};
-  // more than one round of tiles, unsplit: one block per CU walks the tiles (MTVAF_P256_PERSIST=0: one tile per block as before)
-  static const int persist = [] { const char* e = getenv("MTVAF_P256_PERSIST"); return e ? atoi(e) : 1; }();
-  if (persist && grid.z == 1 && grid.x > 256) {
+  // more than one round of tiles, unsplit: one block per CU walks the tiles
+  if (grid.z == 1 && grid.x > 256) {
     sk.total = grid.x;
     grid.x = 256;
   }
@@ -644,11 +642,10 @@ int launch_p256_streamk(const GemmArgsX& a, P256SK sk, int layout_a, int layout_
   // choice -- equal pieces in whole rounds of the CUs); 0: the step line is cut into grid_blocks equal runs wherever they fall
   const long g = std::min<long>(grid_blocks, sk.total);
   sk.W = steps_per_run > 0 ? steps_per_run : (int)((sk.total + g - 1) / g);
-  static const int kmajor_env = [] { const char* e = getenv("MTVAF_P256_SK_KMAJOR"); return e ? atoi(e) : 0; }();
-  // (measured, round 6, profiles/r06_p256_sk_kmajor.txt: 2560 / 4864 / 38912 token rows 65.1 / 93.4 / 649 us tile-major against 70.7 /
-  // 97.9 / 642 us k-major; C4 8387 vs 8402, C5 3385 vs 3399 sentences/s -- the launch is not bound by the fabric traffic the k-major
-  // placement saves: off by default)
-  sk.kmajor = kmajor_env;
+  // (tile-major placement; measured, round 6, profiles/r06_p256_sk_kmajor.txt: 2560 / 4864 / 38912 token rows 65.1 / 93.4 / 649 us
+  // tile-major against 70.7 / 97.9 / 642 us k-major; C4 8387 vs 8402, C5 3385 vs 3399 sentences/s -- the launch is not bound by the
+  // fabric traffic the k-major placement saves)
+  sk.kmajor = 0;
   const long runs = (sk.total + sk.W - 1) / sk.W;
   if (steps_per_run > 0 && sk.KT % steps_per_run) return MTVAF_ERR_ARG;
   if (runs > grid_blocks && !(sk.W % sk.KT == 0)) return MTVAF_ERR_WORKSPACE;  // one slab / flag per run (runs of whole tiles need none)

@@ -458,19 +458,17 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
   }
 }
 
-static int g_bf16x_dma_waves = [] { const char* e = getenv("MTVAF_BF16X_DMA_WAVES"); return (e && atoi(e) == 0) ? 0 : 1; }();
-
 // DMA waves pay where a product is at most two tiles per CU (measured, tools/bf16x_bench.py + bench.py: C3, 4096 token rows,
 // 4252 -> 4668 sentences/s; with more tiles per CU the co-resident blocks already hide the requests, and the doubled block
 // size costs: C4 at 8192 rows 5700 -> 5568 with the waves everywhere)
-static bool bf16x_use_dma_waves(dim3 grid) { return g_bf16x_dma_waves && (long)grid.x * grid.z <= 512; }
+static bool bf16x_use_dma_waves(dim3 grid) { return (long)grid.x * grid.z <= 512; }
 
 template <int BM, int BN, int WM, int WN, bool A_KM, bool B_KM, int NSTAGE, bool KLIST = false, bool DW = false>
 static int launch_x(const GemmArgsX& a, dim3 grid, hipStream_t st) {
   if constexpr (A_KM && B_KM && !KLIST && NSTAGE == 2) {  // (the k-tile list: 2-stage weight-gradient kernels only)
     if (a.klist) return launch_x<BM, BN, WM, WN, A_KM, B_KM, NSTAGE, true, DW>(a, grid, st);
   }
-  if constexpr (WM * WN == 4 && !DW && NSTAGE <= 3) {  // four-wave tiles: the requests in waves of their own (MTVAF_BF16X_DMA_WAVES=0: off)
+  if constexpr (WM * WN == 4 && !DW && NSTAGE <= 3) {  // four-wave tiles: the requests in waves of their own
     if (bf16x_use_dma_waves(grid)) return launch_x<BM, BN, WM, WN, A_KM, B_KM, NSTAGE, KLIST, true>(a, grid, st);
   }
   size_t smem = (size_t)NSTAGE * (BM + BN) * 128;
@@ -703,7 +701,7 @@ static int gemm_bf16x_core(int layout_a, int layout_b, const void* A, int lda, c
   // co-resides anyway, and two k-tiles in flight feed the MFMA waves that no longer stop to issue requests (M = 4096, 128x96:
   // FFN-2 forward 35.9 -> 25.6 us, FFN-1 dX 35.1 -> 25.4, QKV dX 27.9 -> 20.7; with several tiles per CU the two co-resident
   // blocks of the 2-deep ring stay ahead: FFN-1 forward 35.3 vs 46.6)
-  if (stages < 2 || stages > 5) stages = bm == 256 ? 3 : ((g_bf16x_dma_waves && !a.klist && tiles * splits <= 256) ? 3 : 2);
+  if (stages < 2 || stages > 5) stages = bm == 256 ? 3 : ((!a.klist && tiles * splits <= 256) ? 3 : 2);
   if (bn == 192) stages = 2;  // (the only ring that fits: 2 x 56 KB)
   if (bn == 256) { stages = 2; a.klist = a.kcnt = nullptr; }
   if (a.klist && stages != 2) a.klist = a.kcnt = nullptr;  // (list mode exists for the 2-stage kernels: otherwise reduce over everything)

@@ -527,16 +527,12 @@ static long long* g_f32p_trace = nullptr;
 // (k-major B), 4: weight gradients (k-major A and B; the grouped launch) -- among the tiles the mask admits a launch takes the
 // cheapest by gemm_f32p_run's rounds x tile-time estimate; 8: never the 128 x 128 tile where another can serve (tests; research);
 // 16: never the 128 x 192 tile (unsplit or split forward products without a plane-image result, N % 192 == 0).
-static int g_p16_wide = -1;  // -1: MTVAF_P16_WIDE
-static int p16_wide_mask() {
-  static const int v = [] { const char* e = getenv("MTVAF_P16_WIDE"); return e ? atoi(e) & 31 : 7; }();
-  return g_p16_wide < 0 ? v : g_p16_wide;
-}
+static int g_p16_wide = 7;
 // mask >= 0: set; -1: only query.  Returns the mask in force.  Process-global, like mtvaf_f32_split; placement only -- the two
 // kernels agree bit for bit.
 int mtvaf_f32p_wide(int mask) {
   if (mask >= 0) g_p16_wide = mask & 31;
-  return p16_wide_mask();
+  return g_p16_wide;
 }
 
 int mtvaf_f32p_trace(void* buf) {
@@ -580,7 +576,7 @@ static int gemm_f32p_run(int layout_a, const void* Aplanes, long a_plane, long a
   // profiles/r06_p16_wide_tile_probe.txt): per k-tile 1850 / 3378 / 2560 (k-major B: 1975 / 3493), fixed 13 k / 21 k / 17 k (+ 5 k with
   // a plane-image epilogue).  Ties go to the larger tile.  (At 2432 rows: QKV forward 2 rounds of 342 / 1 of 171 / 1 of 228 -> 192;
   // FFN-1 forward 2 of 456 / 1 of 228 / 2 of 304 -> 256; at 4096 rows 3 of 768 / 2 of 384 -> 128 x 128 again.)
-  const int wmask = p16_wide_mask();
+  const int wmask = g_p16_wide;
   const long tm = M / 128, nkb = kc / 32;
   auto cost = [&](int bn_, long per_k, long fixed) {
     const long tiles = tm * (N / bn_) * splits, t = nkb * per_k + fixed + (c_planes ? 5000 : 0) * (bn_ / 128);
@@ -607,8 +603,7 @@ static int gemm_f32p_run(int layout_a, const void* Aplanes, long a_plane, long a
   a.ablate = ablate;
   // (measured at the headline shape, same box, two runs each: G = 0 / 2 / 4 / 8 -> 3394 - 3397 / 3406 - 3421 / 3418 - 3418 / 3407 - 3410
   // sentences/s, all GEMMs 0.436 - 0.452 / 0.453 / 0.454 - 0.455 / 0.454 of the split-product peak)
-  static const int walk_env = [] { const char* e = getenv("MTVAF_P16_WALK_G"); return e ? atoi(e) : 4; }();
-  a.walk_g = walk_env;
+  a.walk_g = 4;
   a.trace = g_f32p_trace;
   dim3 grid((unsigned)((M / 128) * a.tiles_n), 1, (unsigned)splits);
   // (launch profiler of gemm.hip: key 400 + 4 [k-major A] + 8 [k-major B] + 32 [128 x 256 tile] + 64 [128 x 192]; hip.kernel_symbol names the instantiation)
@@ -666,7 +661,7 @@ static int f32p_dw_group_run(int n, const void* const* Aplanes, const void* cons
   GemmArgsP a = {};
   a.K = K; a.k_chunk = K; a.slab_stride = 0; a.epi = EPI_NONE; a.ngrp = n;
   long tiles = 0;
-  bool wide = (p16_wide_mask() & 4) != 0;
+  bool wide = (g_p16_wide & 4) != 0;
   for (int i = 0; i < n && wide; ++i) wide = N[i] > 0 && N[i] % 256 == 0;
   const int bn = wide ? 256 : 128;
   for (int i = 0; i < n; ++i) {

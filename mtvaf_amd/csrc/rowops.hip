@@ -703,12 +703,8 @@ static inline void zero_f32(float* p, long n, hipStream_t st) {
 
 static inline int row_grid(int M) { return std::max(1, std::min((M + 3) / 4, 1024)); }
 // LN backward keeps per-block column partials: fewer, fatter blocks (2 per CU) keep the partial slab small
-// blocks of the LayerNorm backward (4 rows per block and pass; each block leaves one row of column partials).
-// MTVAF_LN_BWD_BLOCKS overrides the cap (experiment switch; read once: the partial-buffer size follows it).
-static inline int row_grid_bwd(int M) {
-  static const int cap = [] { const char* e = getenv("MTVAF_LN_BWD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  return std::max(1, std::min((M + 3) / 4, cap));
-}
+// blocks of the LayerNorm backward (4 rows per block and pass; each block leaves one row of column partials)
+static inline int row_grid_bwd(int M) { return std::max(1, std::min((M + 3) / 4, 512)); }
 
 // the lean LayerNorm backward (ln_bwd_lean_kernel) wherever its shape rule holds; MTVAF_LN_LEAN=0: the one-wave-per-row kernel
 static inline bool ln_lean(int M, int H, int nslab) {
@@ -874,8 +870,7 @@ int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgam
   if (H % 4 || H > MAXC * 256 || M <= 0) return MTVAF_ERR_SHAPE;
   if (!part) return MTVAF_ERR_ARG;
   OutPtrs outs{{dgamma, dbeta, dbias_x, nullptr}};
-  static const int rg32 = [] { const char* e = getenv("MTVAF_LN_FINISH_RG32"); return e ? atoi(e) : 1; }();
-  if (rg32 && row_grid_bwd(M) >= 128)
+  if (row_grid_bwd(M) >= 128)
     hipLaunchKernelGGL((colsum_final_multi_kernel<32>), dim3((3 * H + 31) / 32), dim3(1024), 0, st, part, row_grid_bwd(M), H, 3, outs,
                        accumulate);
   else

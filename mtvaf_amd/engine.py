@@ -121,8 +121,8 @@ def _weights_bf16(w: LayerWeights):
     its update kernel and stamps it; otherwise the image is rebuilt (one cast kernel per layer) when the masters may have
     changed: after ANY torch optimizer step (global post-step hook -- the fused optimizers update parameters without
     moving their version counters) or when a weight Parameter's version counter has moved (load_state_dict, in-place
-    updates through the Parameter).  Writes through ``.data`` are invisible to both: MTVAF_BF16_WCACHE=0 rebuilds in
-    every forward pass (85 M parameters, ~0.1 ms per step)."""
+    updates through the Parameter).  Writes through ``.data`` are invisible to both: MTVAF_WEIGHT_IMAGES=rebuild (or
+    BF16_WCACHE = False) rebuilds in every forward pass (85 M parameters, ~0.1 ms per step)."""
     ver = shadow_version(w) if (BF16_WCACHE and not FORCE_SHADOW_REFRESH) else None
     c = w._h
     if ver is None or c is None or c[0] != ver:
@@ -179,7 +179,7 @@ try:  # every optimizer step invalidates the bf16 weight shadows
 except Exception:  # pragma: no cover - very old torch: never cache
     _HAVE_OPT_HOOK = False
 WEIGHT_IMAGES_REBUILD = os.environ.get("MTVAF_WEIGHT_IMAGES", "cache") == "rebuild"  # every forward rebuilds (debug: .data writes)
-BF16_WCACHE = os.environ.get("MTVAF_BF16_WCACHE", "1") != "0" and _HAVE_OPT_HOOK and not WEIGHT_IMAGES_REBUILD
+BF16_WCACHE = _HAVE_OPT_HOOK and not WEIGHT_IMAGES_REBUILD
 # fp32 mode, PRE-SPLIT OPERANDS (round 5; csrc/gemm_f32p.hip): on packed rows every GEMM operand of an encoder layer is read as a
 # tile-blocked plane image (the three bf16 planes of the split arithmetic, written once per tensor) by kernels that split nothing
 # inside their k-loops -- the eight forward / dX products and the layer's four weight gradients as one grouped launch.  Weights:
@@ -191,8 +191,7 @@ F32_PLANES = os.environ.get("MTVAF_F32_PLANES", "1") != "0" and _HAVE_OPT_HOOK
 # (few-token layers -- BASELINE configs[0]: 256 rows -- are a handful of 128 x 128 tiles: the planner's small-tile kernels win there.
 # Measured, bench.py --batch b, same box, path on / off: bs 4 x S 64 832 / 903 sentences/s, bs 4 x 128 770 / 812, bs 8 (640 packed
 # rows) 1374 / 1238, bs 12 2015 / 1708, bs 16 2443 / 2342, bs 24 2726 / 2480)
-F32_PLANES_MIN_ROWS = int(os.environ.get("MTVAF_F32_PLANES_MIN_ROWS", "512"))
-P16_EP = os.environ.get("MTVAF_P16_EP", "1") != "0"  # (the same switch csrc/executor.hip reads)
+F32_PLANES_MIN_ROWS = 512
 
 
 def _f32_planes_on(use_h, pack, H, I) -> bool:
@@ -254,7 +253,7 @@ def planes_rewrite(w: "LayerWeights"):
         _wplane_fill(w, w._pl[2])
         w._pl[0] = shadow_version(w, 1)
 FORCE_SHADOW_REFRESH = False  # set while a whole-step graph is captured (mtvaf_amd.graph): the cast becomes a graph node
-BF16_OPERANDS = os.environ.get("MTVAF_BF16_OPERANDS", "1") != "0"  # 0: fp32-operand bf16 kernels only (gemm_bf16.hip)
+BF16_OPERANDS = True  # False: fp32-operand bf16 kernels only (gemm_bf16.hip)
 
 
 def _bf16_ok(M, H, I):
@@ -272,10 +271,7 @@ N_LAYER_PARAMS = 16  # q.w q.b k.w k.b v.w v.b ao.w ao.b ln1.w ln1.b i.w i.b o.w
 DW_SIDE_STREAM = os.environ.get("MTVAF_DW_STREAM", "1") != "0"
 # Below this many token rows the second stream loses (bs 4, 256 rows: 4.87 ms per step with it against 4.33-4.59 without, same
 # box): the products are short latency chains there and the cross-stream events cost more than the overlap returns.
-DW_STREAM_MIN_ROWS = int(os.environ.get("MTVAF_DW_STREAM_MIN_ROWS", "1024"))
-# LayerNorm backward's column sums (dgamma, dbeta, dense bias gradient) on the weight-gradient stream (MTVAF_LN_SUMS_SIDE=0: on
-# the main chain, as before round 4)
-LN_SUMS_ON_SIDE = os.environ.get("MTVAF_LN_SUMS_SIDE", "1") != "0"
+DW_STREAM_MIN_ROWS = 1024
 _side_streams = {}
 
 
@@ -283,7 +279,7 @@ def _side_stream(device) -> "torch.cuda.Stream":
     key = torch.device(device).index or 0
     st = _side_streams.get(key)
     if st is None:
-        st = _side_streams[key] = torch.cuda.Stream(device=device, priority=int(os.environ.get("MTVAF_DW_PRIORITY", "0")))
+        st = _side_streams[key] = torch.cuda.Stream(device=device)
     return st
 
 
@@ -329,8 +325,8 @@ class padding_free:
 # The gradient of a token row nothing downstream reads is EXACTLY zero (a masked key has probability exp(-10000) = 0, a
 # masked query feeds only itself, the CRF is masked), so the skipped terms of dW = sum_rows dY[r]^T X[r] are zeros: every
 # output of the step is unchanged.  Only for callers that vouch for it (cfg[5], BertModel.allow_unpad).
-SKIP_PAD_DW = os.environ.get("MTVAF_SKIP_PAD_DW", "1") != "0"
-SKIP_PAD_DW_BF16 = os.environ.get("MTVAF_SKIP_PAD_DW", "1") == "2"
+SKIP_PAD_DW = True
+SKIP_PAD_DW_BF16 = False  # (the mixed-precision kernels take the k-tile lists only when set: measured slower there)
 # Debug switch for the masked-rows contract (MTVAF_CHECK_CONTRACT=1 / engine.CHECK_CONTRACT = True): whenever a backward pass
 # is about to rely on it -- k-tile lists, the attention backward's shortened query loops (zero_tail), padding-free execution --
 # the incoming hidden-state gradients are read back and every row at a masked position must be exactly zero; a head that reads
@@ -339,8 +335,7 @@ SKIP_PAD_DW_BF16 = os.environ.get("MTVAF_SKIP_PAD_DW", "1") == "2"
 CHECK_CONTRACT = os.environ.get("MTVAF_CHECK_CONTRACT", "0") == "1"
 # Padding-free execution: the varlen attention launches take the sentences longest first (placement only, bit-identical results: a
 # launch lasts as long as its busiest CU, and in sorted order a CU's blocks come from the long, middle and short third of the
-# batch).  MTVAF_ATTN_ORDER=0: sentence z in grid slot z, as before round 6.
-ATTN_ORDER = os.environ.get("MTVAF_ATTN_ORDER", "1") != "0"
+# batch).
 LAST_PACK = None  # the Packing of the most recent native forward (None: it ran padded)
 _PENDING_PACK = None  # packing started by Packing.begin, consumed by the next Packing.build
 _PACK_HOST = {}
@@ -381,13 +376,13 @@ class Packing:
             return  # (the row count cannot reach the host inside a capture: this step runs the padded layout)
         B, T = addmask.shape
         dev = addmask.device
-        # (cu: B + 1 row offsets and, behind them, the sentence order of the attention launches -- longest first: ATTN_ORDER)
+        # (cu: B + 1 row offsets and, behind them, the sentence order of the attention launches -- longest first)
         cu = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
         inv = torch.empty(B * S, dtype=torch.int32, device=dev)
         rowmap = torch.empty(B * S, dtype=torch.int32, device=dev)
         mv = torch.empty(1, dtype=torch.int32, device=dev)
-        build = hip.lib().mtvaf_build_packing_ordered if ATTN_ORDER else hip.lib().mtvaf_build_packing
-        hip._ck(build(hip._p(addmask), B, T, Pn, S, hip._p(cu), hip._p(inv), hip._p(rowmap), hip._p(mv), hip._st()), "mtvaf_build_packing")
+        hip._ck(hip.lib().mtvaf_build_packing_ordered(hip._p(addmask), B, T, Pn, S, hip._p(cu), hip._p(inv), hip._p(rowmap), hip._p(mv),
+                                                      hip._st()), "mtvaf_build_packing_ordered")
         key = dev.index or 0
         host = _PACK_HOST.get(key)
         if host is None:
@@ -460,9 +455,9 @@ def _fwd_layout(M, H, I, B, NH, S, use_h, planes=False):
     if lay is None:
         e = 2 if use_h else 4
         pl = 6 if planes else 0
-        # (pre-split path: the GELU output leaves the FFN-1 epilogue as a plane image only -- csrc/executor.hip, p16_ep_on -- so no
-        # fp32 `act` exists; MTVAF_P16_EP=0 puts the fp32 tensor + split pass back)
-        act_b = 0 if (planes and P16_EP) else M * I * e
+        # (pre-split path: the GELU output leaves the FFN-1 epilogue as a plane image only -- csrc/executor.hip, p16_ep -- so no
+        # fp32 `act` exists)
+        act_b = 0 if planes else M * I * e
         lay = _layouts[key] = _layout([("qkv", M * 3 * H * e), ("cx", M * H * e), ("lse", B * NH * S * 4), ("a", M * H * 4),
                                        ("h1", M * H * 4), ("h1_h", M * H * 2 if use_h else 0), ("mean1", M * 4), ("rstd1", M * 4),
                                        ("pre", M * I * e), ("act", act_b), ("f", M * H * 4), ("h2", M * H * 4),
@@ -482,8 +477,8 @@ def _bwd_layout(M, H, I, B, NH, S, Pn, use_h, planes=False):
                                        ("part", (M // 128) * I * 4 if (use_h or planes) else 0), ("partq", B * nqt * H * 4 if use_h else 0),
                                        ("partkv", B * nkt * 2 * H * 4 if use_h else 0), ("delta", 0 if use_h else B * NH * S * 4),
                                        # (the layer's own LayerNorm-backward partials: their column sums run on the second stream)
-                                       ("lnpart2", int(hip.lib().mtvaf_ln_bwd_workspace_bytes(M, H)) if LN_SUMS_ON_SIDE else 0),
-                                       ("lnpart1", int(hip.lib().mtvaf_ln_bwd_workspace_bytes(M, H)) if LN_SUMS_ON_SIDE else 0),
+                                       ("lnpart2", int(hip.lib().mtvaf_ln_bwd_workspace_bytes(M, H))),
+                                       ("lnpart1", int(hip.lib().mtvaf_ln_bwd_workspace_bytes(M, H))),
                                        ("df_p", M * H * 6 if planes else 0), ("dpre_p", M * I * 6 if planes else 0),
                                        ("da_p", M * H * 6 if planes else 0), ("dqkv_p", M * 3 * H * 6 if planes else 0)])
     return lay
@@ -491,7 +486,7 @@ def _bwd_layout(M, H, I, B, NH, S, Pn, use_h, planes=False):
 
 def _streamk_on(stream, device) -> bool:
     """Attach the stream-K scratch of the 256x256 bf16 kernel to `stream` (None: the current one) if it is not yet, and say
-    whether that stream has one (hip.STREAMK / MTVAF_STREAMK=0 switch it off)."""
+    whether that stream has one."""
     if stream is None:
         return hip.streamk_ensure(device)
     with torch.cuda.stream(stream):
@@ -722,7 +717,7 @@ def _native_backward(ctx, douts):
     bk = 64 if use_h else 32  # k-tile of the dW kernels
     # (mixed-precision mode: measured SLOWER with the list -- 7.85 vs 7.56 ms at C3, 11.71 vs 11.60 at C4: 64-row tiles skip
     # only ~19 % of a 33-us product and the device-side count delays its first loads -- so the list is an fp32-mode lever;
-    # MTVAF_SKIP_PAD_DW=2 forces it for the bf16 kernels too)
+    # SKIP_PAD_DW_BF16 forces it for the bf16 kernels too)
     if (SKIP_PAD_DW and (not use_h or SKIP_PAD_DW_BF16) and pack is None and need_param_grads and len(cfg) > 5 and cfg[5] and (B * S) % bk == 0
             and addmask.dtype == torch.float32 and addmask.is_contiguous()):
         klist = torch.empty(B * S // bk, dtype=torch.int32, device=dev)

@@ -321,7 +321,7 @@ def f32p_wide(mask=None) -> int:
     """The pre-split GEMM's tiles (csrc/gemm_f32pw.hip, round 6): a mask of the products that may leave the 128 x 128 tile -- 1 forward
     (128 x 256, or 128 x 192 without a plane-image result), 2 dX, 4 weight gradients; a launch takes the cheapest admitted tile by the
     library's rounds x tile-time estimate; 8 = never 128 x 128 where another tile can serve (tests), 16 = never 128 x 192; True = 15,
-    False = 0, None queries.  Placement only: the kernels agree bit for bit.  Default: MTVAF_P16_WIDE (7 if unset)."""
+    False = 0, None queries.  Placement only: the kernels agree bit for bit.  Default: 7."""
     if mask is True:
         mask = 15
     return int(lib().mtvaf_f32p_wide(-1 if mask is None else int(mask)))
@@ -735,15 +735,12 @@ def gemm_bf16x(a, layout_a, b, layout_b, M, N, K, out32=None, out16=None, bias=N
 
 
 _sk_scratch = {}
-STREAMK = os.environ.get("MTVAF_STREAMK", "1") != "0"
 
 
 def streamk_ensure(device) -> bool:
     """Attach (once per device and stream) the scratch of the stream-K launches of the 256x256 bf16 kernel to the CURRENT
-    stream: 4 KiB of flag words + one 256-KiB slab per CU, zero-initialised, owned here.  MTVAF_STREAMK=0 / STREAMK = False:
-    no scratch is attached and the library keeps to its tile-per-block / split-K launches."""
-    if not STREAMK:
-        return False
+    stream: 4 KiB of flag words + one 256-KiB slab per CU, zero-initialised, owned here.  False: the library serves no more
+    streams and keeps to its tile-per-block / split-K launches on this one."""
     key = (torch.device(device).index or 0, _st())
     if key not in _sk_scratch:
         nbytes = int(lib().mtvaf_streamk_scratch_bytes(256))

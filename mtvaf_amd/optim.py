@@ -21,8 +21,6 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
-import os
-
 import torch
 
 from . import hip
@@ -142,14 +140,14 @@ class AdamW(torch.optim.Optimizer):
     # an update enqueued from inside the backward pass runs beside MFMA-bound products: on 128 blocks it trickles under
     # them (csrc/optim.hip); below this many token rows a layer's backward is shorter than such an update and it would
     # only pile up behind the pass
-    BACKGROUND_MIN_ROWS = int(os.environ.get("MTVAF_ADAMW_BG_MIN_ROWS", "2048"))
-    BACKGROUND_BLOCKS = int(os.environ.get("MTVAF_ADAMW_BG_BLOCKS", "128"))
+    BACKGROUND_MIN_ROWS = 2048
+    BACKGROUND_BLOCKS = 128
     # (the pre-split path's second stream is lighter -- one grouped launch per layer -- and the update also writes the weights' plane
     # images: 256 blocks measured best there, 3257 - 3260 sentences/s against 3237 - 3238 at 128, 3220 - 3225 at 512, 3128 - 3133 at 64)
-    BACKGROUND_BLOCKS_PLANES = int(os.environ.get("MTVAF_ADAMW_BG_BLOCKS", "256"))
+    BACKGROUND_BLOCKS_PLANES = 256
     # (bf16 mode below 4096 token rows -- C3: a layer's backward pass is 260 us, shorter than a 128-block trickle of its update --
     # 256 blocks: 5.52 - 5.54 -> 5.41 - 5.43 ms median step, same box; at 4864 rows (C4) 128 / 192 / 256 measure equal)
-    BACKGROUND_BLOCKS_SHORT = int(os.environ.get("MTVAF_ADAMW_BG_BLOCKS", "256"))
+    BACKGROUND_BLOCKS_SHORT = 256
     BACKGROUND_SHORT_ROWS = 4096
 
     def _update_layer_flat(self, li: int, group: dict, store, background: bool = False, rows: int = 0):
