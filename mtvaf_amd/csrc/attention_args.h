@@ -1,6 +1,8 @@
-// Argument block and the small device helpers shared by the fp32 prefix-attention kernels: csrc/attention.hip (fp32 MFMA pipe)
-// and csrc/attention_f32s.hip (round 6: the same attention with its products formed as split bf16 products, the arithmetic of
-// csrc/gemm_f32x3.hip).  Same launch geometry, same key order, same dropout hash, same outputs in both.
+// Argument block of the fp32 prefix-attention kernels -- csrc/attention.hip (fp32 MFMA pipe) and csrc/attention_f32s.hip (round 6: the
+// same attention with its products formed as split bf16 products, the arithmetic of csrc/gemm_f32x3.hip): same launch geometry, same
+// key order, same dropout hash, same outputs in both -- and the small device / host helpers that csrc/attention_bf16.hip uses too
+// (written over any argument struct with cu, B, S, addmask).  The two fp32 files share their kernel bodies as well: they live once
+// in csrc/attention_skeleton.h, templates over an arithmetic (LDS tile format, staging registers, register operand, products).
 #pragma once
 #include "common.h"
 #include "planes.h"
@@ -59,7 +61,8 @@ struct Sent {
   long tok0;  // first token row of the sentence
   int n;      // its text tokens (queries; text keys)
 };
-__device__ __forceinline__ Sent sentence(const AttnArgs& a, int b) {
+template <class Args>
+__device__ __forceinline__ Sent sentence(const Args& a, int b) {
   if (a.cu) {
     const int c0 = b ? a.cu[b] : 0;  // (cu[0] = -1 marks a launch order behind the offsets: slot_sentence)
     return Sent{(long)c0, a.cu[b + 1] - c0};
@@ -67,11 +70,14 @@ __device__ __forceinline__ Sent sentence(const AttnArgs& a, int b) {
   return Sent{(long)b * a.S, a.S};
 }
 // the sentence of grid slot z (mtvaf_build_packing_ordered: longest first; identity without the list)
-__device__ __forceinline__ int slot_sentence(const AttnArgs& a, int z) { return (a.cu && a.cu[0] < 0) ? a.cu[a.B + 1 + z] : z; }
-__device__ __forceinline__ float mask_at(const AttnArgs& a, int b, int Tf, int t) {
+template <class Args>
+__device__ __forceinline__ int slot_sentence(const Args& a, int z) {
+  return (a.cu && a.cu[0] < 0) ? a.cu[a.B + 1 + z] : z;
+}
+template <class Args>
+__device__ __forceinline__ float mask_at(const Args& a, int b, int Tf, int t) {
   return a.cu ? 0.f : a.addmask[(long)b * Tf + t];
 }
-
 
 // Keys behind the LAST unmasked text position of a sentence (trailing padding: additive mask -10000) contribute exactly 0
 // to every probability sum -- exp2 underflows to 0 -- and leave the running maximum untouched, so whole key tiles made of
@@ -93,17 +99,24 @@ __device__ __forceinline__ int effective_keys(const float* __restrict__ addmask_
 // values; their probabilities are exactly 0 through the -1e30 entry of the mask tile).  The source pointer is
 // selected with bit arithmetic (a ternary on pointers compiles to divergent branches whose loads the compiler
 // then serialises with vmcnt(0) waits), and all loads of a tile are issued before the first LDS store.
-struct KvSrc {
-  const float* pre;  // prefix slab of this (b, h), + the thread's column offset
-  const float* txt;  // text rows of this (b, h), + the thread's column offset
+template <class T>
+struct KvSrcT {
+  const T* pre;  // prefix slab of this (b, h), + the thread's column offset
+  const T* txt;  // text rows of this (b, h), + the thread's column offset
 };
-__device__ __forceinline__ const float* kv_row_ptr(const KvSrc& s, int t, int P, int ld_txt) {
+typedef KvSrcT<float> KvSrc;
+template <class T>
+__device__ __forceinline__ const T* kv_row_ptr(const KvSrcT<T>& s, int t, int P, int ld_txt) {
   const bool ispre = t < P;
   const uint64_t m = ispre ? ~0ull : 0ull;
   const uint64_t base = (uint64_t)s.txt ^ (((uint64_t)s.txt ^ (uint64_t)s.pre) & m);
   const int off = ispre ? t * D : (t - P) * ld_txt;
-  return reinterpret_cast<const float*>(base) + off;
+  return reinterpret_cast<const T*>(base) + off;
 }
+// byte offset of 16-byte chunk c (0..7) of row r in a [64][64] bf16 tile image (128-byte rows): conflict-free for the row reads
+// (ds_read_b128) and for the transposing reads (ds_read_b64_tr_b16) alike
+__device__ __forceinline__ int tile_off(int r, int c) { return r * 128 + ((c ^ (((r >> 1) & 3) << 1)) << 4); }
+
 // XCD-aware block order (round 5).  Workgroups are dealt round-robin over the 8 XCDs by their linear id, x fastest: the nx blocks
 // of one (sentence, head) -- 2 query tiles forward; 2 query + 3 key tiles backward, which all read the same q / k / v / dO / O
 // slices (3.5x the unique bytes: 165 - 205 MB per backward launch by the PMC counters against ~50 MB) -- landed on nx different
@@ -122,6 +135,30 @@ __device__ __forceinline__ void xcd_group(int nx, int ny, int nz, int& x, int& y
   x = slot % nx;
   y = gi % ny;
   z = gi / ny;
+}
+
+// host side: the dropout key (replica of attn_dropout_key) and keep threshold of a launch; the fields that every launcher fills in
+// and the tests it makes first
+inline uint32_t attn_drop_key(uint64_t seed, uint64_t offset) {
+  auto mix = [](uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; };
+  return mix((uint32_t)seed ^ mix((uint32_t)(seed >> 32) ^ mix((uint32_t)offset ^ 0x9E3779B9u)));
+}
+inline uint32_t attn_drop_thr(float p_drop) { return p_drop > 0.f ? (uint32_t)fminf(p_drop * 4294967296.0f, 4294967040.0f) : 0u; }
+template <class Args>
+void attn_fill_common(Args& a, int B, int S, int P, int NH, float p_drop, uint64_t seed, uint64_t offset) {
+  a.B = B; a.S = S; a.P = P; a.NH = NH; a.H = NH * D;
+  a.scale = 0.125f; a.p_drop = p_drop;
+  a.drop_thr = attn_drop_thr(p_drop);
+  a.drop_key = attn_drop_key(seed, offset);
+  a.epoch = rng_epoch_ptr();
+}
+template <class Args>
+int attn_check(const Args& a) {
+  if (a.B <= 0 || a.S <= 0 || a.P < 0 || a.NH <= 0 || a.H != a.NH * D) return MTVAF_ERR_SHAPE;
+  if ((long)a.B * a.NH * a.S >= (1L << 32)) return MTVAF_ERR_SHAPE;
+  if (a.p_drop < 0.f || a.p_drop >= 1.f) return MTVAF_ERR_ARG;
+  if (a.P > 0 && (!a.pk || !a.pv)) return MTVAF_ERR_ARG;
+  return MTVAF_OK;
 }
 
 // launchers of the split-product kernels (csrc/attention_f32s.hip); grid / block as the fp32-pipe kernels of attention.hip

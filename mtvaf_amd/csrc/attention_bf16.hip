@@ -18,16 +18,12 @@
 // matching A operand V^T comes from the row-major V tile by two transposing reads (ds_read_b64_tr_b16).  All [64][64]
 // bf16 tiles (128-byte rows) use ONE LDS image that is conflict-free for both the row reads and the transposing reads:
 // 16-byte chunk c of row r at chunk c ^ (((r >> 1) & 3) << 1).
-#include "common.h"
+// (tile_off; the sentence / mask / key-axis helpers and the host-side tests are those of attention_args.h, shared with the fp32 kernels)
+#include "attention_args.h"
 
 namespace mtvaf {
 
 namespace ab {
-
-constexpr int D = 64;
-constexpr int KT = 64;
-constexpr float NEG_BIG = -1.0e30f;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -54,44 +50,13 @@ struct Args {
   float scale, p_drop;
   uint32_t drop_key, drop_thr;
   const uint64_t* epoch;  // device-side dropout epoch (captured launches), or NULL
-  const int* cu;          // PACKED token rows (see attention.hip): [B+1] row offsets of the sentences, or NULL
+  const int* cu;          // PACKED token rows (see AttnArgs, attention_args.h): [B+1] row offsets of the sentences, or NULL
   int pad_rows;           // rows behind the last sentence that pad the packed image: zero-filled by the z-slice b == B
   int zero_tail;          // backward, padded layout: dctx is exactly zero behind a sentence's last unmasked position (the caller's
-                          // word, as in attention.hip): the key side's query loop stops there
+                          // word, as AttnArgs::zero_tail): the key side's query loop stops there
 };
 
-struct Sent {
-  long tok0;
-  int n;
-};
-__device__ __forceinline__ Sent sentence(const Args& a, int b) {
-  if (a.cu) {
-    const int c0 = b ? a.cu[b] : 0;  // (cu[0] = -1 marks a launch order behind the offsets: slot_sentence)
-    return Sent{(long)c0, a.cu[b + 1] - c0};
-  }
-  return Sent{(long)b * a.S, a.S};
-}
-// the sentence of grid slot z (mtvaf_build_packing_ordered: longest first; identity without the list)
-__device__ __forceinline__ int slot_sentence(const Args& a, int z) { return (a.cu && a.cu[0] < 0) ? a.cu[a.B + 1 + z] : z; }
-__device__ __forceinline__ float mask_at(const Args& a, int b, int Tf, int t) {
-  return a.cu ? 0.f : a.addmask[(long)b * Tf + t];
-}
-
-// byte offset of 16-byte chunk c (0..7) of row r in a [64][64] bf16 tile image
-__device__ __forceinline__ int tile_off(int r, int c) { return r * 128 + ((c ^ (((r >> 1) & 3) << 1)) << 4); }
-
-// [prefix ; text] row pointer selected with bit arithmetic (no divergent branches: see attention.hip)
-struct KvSrc {
-  const __bf16* pre;
-  const __bf16* txt;
-};
-__device__ __forceinline__ const __bf16* kv_row_ptr(const KvSrc& s, int t, int P, int ld_txt) {
-  const bool ispre = t < P;
-  const uint64_t m = ispre ? ~0ull : 0ull;
-  const uint64_t base = (uint64_t)s.txt ^ (((uint64_t)s.txt ^ (uint64_t)s.pre) & m);
-  const int off = ispre ? t * D : (t - P) * ld_txt;
-  return reinterpret_cast<const __bf16*>(base) + off;
-}
+typedef KvSrcT<__bf16> KvSrc;
 
 // stage a [64][64] bf16 tile: 512 chunks of 16 B, two per thread (rows r and r + 32, chunk c = tid & 7)
 __device__ __forceinline__ void tile_load_kv(bf16x8 (&reg)[2], const KvSrc& s, int P, int T, int ld_txt, int t0) {
@@ -130,23 +95,6 @@ __device__ __forceinline__ float dot8(const bf16x8& a, const bf16x8& b) {
   return s;
 }
 
-
-// Keys behind the LAST unmasked text position of a sentence (trailing padding: additive mask -10000) contribute exactly 0
-// to every probability sum -- exp2 underflows to 0 -- and leave the running maximum untouched, so whole key tiles made of
-// them can be skipped with bit-identical results.  -> T_eff = P + 1 + max{s : addmask[b][P+s] > -5000}; the full T when
-// no text key is unmasked (nothing is skipped then).  Masked keys BEFORE that position ("holes") stay in the loop.
-__device__ __forceinline__ int effective_keys(const float* __restrict__ addmask_row, int P, int S, int* lds_slot) {
-  if (threadIdx.x == 0) *lds_slot = -1;
-  __syncthreads();
-  int last = -1;
-  for (int t = threadIdx.x; t < S; t += blockDim.x)
-    if (addmask_row[P + t] > -5000.f) last = t;
-  if (last >= 0) atomicMax(lds_slot, last);
-  __syncthreads();
-  const int l = *lds_slot;
-  return l >= 0 ? P + l + 1 : P + S;
-}
-
 // ---------------------------------------------------------------------------------------------
 // forward: grid (ceil(S/64), NH, B), 256 threads; wave w owns queries q0+16w .. +15
 // ---------------------------------------------------------------------------------------------
@@ -174,7 +122,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Args a) {
   __shared__ int t_eff_slot;
   const int T = a.cu ? a.P + Sb : effective_keys(a.addmask + (long)b * Tf, a.P, a.S, &t_eff_slot);  // trailing padding keys are skipped
   const bool qok = q < Sb;
-  const bool wave_live = __builtin_amdgcn_readfirstlane(q - lq) < Sb;  // (round 6, as attention.hip: dead waves skip the arithmetic)
+  const bool wave_live = __builtin_amdgcn_readfirstlane(q - lq) < Sb;  // (dead waves skip the arithmetic: see attention_skeleton.h)
   const float inv_keep = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
   const uint32_t rowh = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), (uint32_t)((b * a.NH + h) * a.S + q));
   const float sc2 = a.scale * LOG2E;
@@ -614,16 +562,10 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_bwd_kernel(Args a, int nq) {
 }
 
 static int check(const Args& a) {
-  if (a.B <= 0 || a.S <= 0 || a.P < 0 || a.NH <= 0 || a.H != a.NH * D) return MTVAF_ERR_SHAPE;
-  if ((long)a.B * a.NH * a.S >= (1L << 32)) return MTVAF_ERR_SHAPE;
-  if (a.p_drop < 0.f || a.p_drop >= 1.f) return MTVAF_ERR_ARG;
-  if (a.P > 0 && (!a.pk || !a.pv)) return MTVAF_ERR_ARG;
+  const int rc = attn_check(a);
+  if (rc) return rc;
   if (((uintptr_t)a.qkv | (uintptr_t)a.pk | (uintptr_t)a.pv) & 15) return MTVAF_ERR_ALIGN;
   return MTVAF_OK;
-}
-static uint32_t host_drop_key(uint64_t seed, uint64_t offset) {  // host-side replica of attn_dropout_key
-  auto mix = [](uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; };
-  return mix((uint32_t)seed ^ mix((uint32_t)(seed >> 32) ^ mix((uint32_t)offset ^ 0x9E3779B9u)));
 }
 
 }  // namespace ab
@@ -636,15 +578,11 @@ extern "C" {
 static int attn16_fwd_launch(const void* qkv16, const void* pk16, const void* pv16, const float* addmask, const int* cu, int pad_rows,
                              void* ctx16, float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
                              hipStream_t st) {
-  if (head_dim != ab::D) return MTVAF_ERR_SHAPE;
+  if (head_dim != D) return MTVAF_ERR_SHAPE;
   ab::Args a{};
   a.qkv = static_cast<const __bf16*>(qkv16); a.pk = static_cast<const __bf16*>(pk16); a.pv = static_cast<const __bf16*>(pv16);
   a.addmask = addmask; a.cu = cu; a.pad_rows = pad_rows; a.ctx = static_cast<__bf16*>(ctx16); a.lse = lse;
-  a.B = B; a.S = S; a.P = P; a.NH = NH; a.H = NH * ab::D;
-  a.scale = 0.125f; a.p_drop = p_drop;
-  a.drop_thr = p_drop > 0.f ? (uint32_t)fminf(p_drop * 4294967296.0f, 4294967040.0f) : 0u;
-  a.drop_key = ab::host_drop_key(seed, offset);
-  a.epoch = rng_epoch_ptr();
+  attn_fill_common(a, B, S, P, NH, p_drop, seed, offset);
   int rc = ab::check(a);
   if (rc) return rc;
   if (!ctx16 || !lse || (!addmask && !cu) || pad_rows < 0 || (pad_rows && !cu)) return MTVAF_ERR_ARG;
@@ -657,18 +595,14 @@ static int attn16_bwd_launch(const void* dctx16, const void* qkv16, const void* 
                              const int* cu, int pad_rows, const void* ctx16, const float* lse, void* dqkv16, float* dpk, float* dpv, float* partq,
                              float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
                              hipStream_t st, int zero_tail = 0) {
-  if (head_dim != ab::D) return MTVAF_ERR_SHAPE;
+  if (head_dim != D) return MTVAF_ERR_SHAPE;
   ab::Args a{};
   a.zero_tail = zero_tail;
   a.qkv = static_cast<const __bf16*>(qkv16); a.pk = static_cast<const __bf16*>(pk16); a.pv = static_cast<const __bf16*>(pv16);
   a.addmask = addmask; a.cu = cu; a.pad_rows = pad_rows; a.ctx = static_cast<__bf16*>(const_cast<void*>(ctx16)); a.lse = const_cast<float*>(lse);
   a.dctx = static_cast<const __bf16*>(dctx16); a.dqkv = static_cast<__bf16*>(dqkv16); a.dpk = dpk; a.dpv = dpv;
   a.partq = partq; a.partkv = partkv;
-  a.B = B; a.S = S; a.P = P; a.NH = NH; a.H = NH * ab::D;
-  a.scale = 0.125f; a.p_drop = p_drop;
-  a.drop_thr = p_drop > 0.f ? (uint32_t)fminf(p_drop * 4294967296.0f, 4294967040.0f) : 0u;
-  a.drop_key = ab::host_drop_key(seed, offset);
-  a.epoch = rng_epoch_ptr();
+  attn_fill_common(a, B, S, P, NH, p_drop, seed, offset);
   int rc = ab::check(a);
   if (rc) return rc;
   if (!dctx16 || !ctx16 || !lse || !dqkv16 || !partq || !partkv || (!addmask && !cu)) return MTVAF_ERR_ARG;
