@@ -209,8 +209,9 @@ int mtvaf_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed,
 /* ---- linear-chain CRF head --------------------------------------------------------------------------------
  * replaces torchcrf.CRF(num_tags, batch_first=True): forward(..., reduction='mean') negated at
  * bert_model.py:521 and decode at :511.  emissions [B,S,C], tags int64 [B,S], mask uint8 [B,S] with
- * mask[:,0] == 1, C <= 16.  loss[0] = -mean_b(score(gold) - logZ).  The workspace written by the forward
- * is read by the backward.  tags_out int32 [B,S] (-1 padded), lens_out int32 [B]. */
+ * mask[:,0] == 1, 1 <= C <= 64; for 16 < C <= 64 also S <= 512.  Other shapes: MTVAF_ERR_SHAPE before any
+ * launch, and mtvaf_crf_workspace_bytes returns 0.  loss[0] = -mean_b(score(gold) - logZ).  The workspace
+ * written by the forward is read by the backward.  tags_out int32 [B,S] (-1 padded), lens_out int32 [B]. */
 size_t mtvaf_crf_workspace_bytes(int B, int S, int C);
 int mtvaf_crf_nll_fwd(const float* emissions, const int64_t* tags, const uint8_t* mask, const float* start,
                       const float* end, const float* trans, float* loss, int B, int S, int C, void* workspace,

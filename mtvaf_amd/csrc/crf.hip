@@ -13,6 +13,7 @@
 //   * whatever is not part of the serial chain is a small GEMM over all time steps on the matrix cores
 //     (v_mfma_f32_16x16x4_f32): the predicted alphas of the backward pass and the summed edge marginals.
 #include "common.h"
+#include "crf_wide.h"
 
 namespace mtvaf {
 
@@ -793,8 +794,11 @@ int crf_allow_lds(K kernel, size_t bytes) {  // dynamic LDS beyond the 64 KB def
 
 extern "C" {
 
-// alpha [B,S,16] | logZ [B] | llh [B] | parameter-gradient partials [B, 2C + C*C]
+// C <= 16: alpha [B,S,16] | logZ [B] | llh [B] | parameter-gradient partials [B, 2C + C*C].
+// 16 < C <= 64 (S <= 512): the wide path's layout (crf_wide.h).  0 for a shape neither path takes.
+static bool crf_wide_shape(int S, int C) { return C > CMAX && C <= CRF_WIDE_CMAX && S <= CRF_WIDE_SMAX; }
 size_t mtvaf_crf_workspace_bytes(int B, int S, int C) {
+  if (C > CMAX) return crf_wide_shape(S, C) && B > 0 && S > 0 ? crf_wide_workspace_floats(B, S, C) * sizeof(float) : 0;
   return ((size_t)B * S * CMAX + (size_t)B * 2 + (size_t)B * (2 * C + C * C)) * sizeof(float);
 }
 
@@ -802,8 +806,15 @@ size_t mtvaf_crf_workspace_bytes(int B, int S, int C) {
 int mtvaf_crf_nll_fwd(const float* emissions, const int64_t* tags, const uint8_t* mask, const float* start,
                       const float* end, const float* trans, float* loss, int B, int S, int C, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || C > CMAX) return MTVAF_ERR_SHAPE;
+  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  if (C > CMAX) {
+    const CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    if (int rc = crf_wide_fwd(emissions, tags, mask, start, end, trans, w, B, S, C, st)) return rc;
+    hipLaunchKernelGGL(crf_loss_kernel, dim3(1), dim3(64), 0, st, w.llh, loss, B);
+    MTVAF_LAUNCH_CHECK();
+    return MTVAF_OK;
+  }
   float* alpha = (float*)workspace;
   float* logz = alpha + (size_t)B * S * CMAX;
   float* llh = logz + B;
@@ -823,8 +834,17 @@ int mtvaf_crf_nll_bwd(const float* grad_out, const float* emissions, const int64
                       const float* start, const float* end, const float* trans, float* demissions, float* dstart,
                       float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || C > CMAX) return MTVAF_ERR_SHAPE;
+  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  if (C > CMAX) {
+    const CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    if (int rc = crf_wide_bwd(grad_out, emissions, tags, mask, end, trans, demissions, w, B, S, C, st)) return rc;
+    const int n = 2 * C + C * C;
+    hipLaunchKernelGGL(crf_param_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.partial, grad_out, B, C, dstart,
+                       dend, dtrans, accumulate);
+    MTVAF_LAUNCH_CHECK();
+    return MTVAF_OK;
+  }
   float* alpha = (float*)workspace;
   float* logz = alpha + (size_t)B * S * CMAX;
   float* partial = logz + 2 * B;
@@ -843,7 +863,8 @@ int mtvaf_crf_nll_bwd(const float* grad_out, const float* emissions, const int64
 // tags_out [B,S] int32 (best path, -1 padded), lens_out [B] int32.
 int mtvaf_crf_viterbi(const float* emissions, const uint8_t* mask, const float* start, const float* end,
                       const float* trans, int32_t* tags_out, int32_t* lens_out, int B, int S, int C, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || C > CMAX) return MTVAF_ERR_SHAPE;
+  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
+  if (C > CMAX) return crf_wide_viterbi(emissions, mask, start, end, trans, tags_out, lens_out, B, S, C, st);
   const size_t S8 = ((size_t)S + 7) >> 3;
   const size_t lds_v = ((size_t)S * C + 16) * sizeof(float) + S8 * 16 * sizeof(uint32_t) + (size_t)S * sizeof(int) + (size_t)S;
 #define CRF_VIT_LAUNCH(CT)                                                                                            \

@@ -88,8 +88,9 @@ class CRF(nn.Module):
     def __init__(self, num_tags: int, batch_first: bool = False) -> None:
         if num_tags <= 0:
             raise ValueError(f"invalid number of tags: {num_tags}")
-        if num_tags > 16:
-            raise NotImplementedError("the CRF kernels keep one tag per lane with a 16-wide transition tile")
+        if num_tags > 64:
+            raise NotImplementedError(f"num_tags={num_tags}: the CRF kernels support at most 64 tags (one tag per lane "
+                                      f"of a wavefront)")
         super().__init__()
         self.num_tags = num_tags
         self.batch_first = batch_first
