@@ -101,6 +101,19 @@ int mtvaf_prefix_attn_bwd_tail(const float* dctx, const float* qkv, const float*
                                int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset, int zero_tail,
                                mtvaf_stream_t stream);
 
+/* The attention probabilities on request (output_attentions; modeling_bert.py:325, 339): the forward without V, by the same
+ * arithmetic (mtvaf_f32_split).  probs [B,NH,S,P+S] dense fp32 = softmax_t(Q.[Kp;K]^T / 8 + addmask), before dropout; EVERY element
+ * is written (no memset needed), keys behind a sentence's last unmasked text position as exactly 0.  prefix_mass [B,NH,S] (may be
+ * NULL) = sum_{t<P} probs[b,h,q,t], the share of a token's attention that goes to the visual slots.  zero_masked_queries != 0: the
+ * row (and the mass) of a query whose own key is masked (addmask[b,P+q] <= -5000) is stored as zeros -- for hidden states of a
+ * padding-free run, which carry nothing there.  Only the Q and K thirds of qkv are read; rows of probs need no alignment.
+ * mtvaf_prefix_attn_mass: prefix_mass alone -- the second pass over the keys ends behind the prefix and nothing of size P+S is stored. */
+int mtvaf_prefix_attn_probs(const float* qkv, const float* pk, const float* addmask, float* probs,
+                            float* prefix_mass /* may be NULL */, int B, int S, int P, int NH, int head_dim,
+                            int zero_masked_queries, mtvaf_stream_t stream);
+int mtvaf_prefix_attn_mass(const float* qkv, const float* pk, const float* addmask, float* prefix_mass, int B, int S, int P,
+                           int NH, int head_dim, int zero_masked_queries, mtvaf_stream_t stream);
+
 /* The same attention over PACKED token rows (padding-free execution): cu [B+1] int32 -- sentence b owns rows
  * cu[b] .. cu[b+1]-1 of qkv / ctx / dctx / dqkv (its unmasked tokens in order, at most S).  Every kept key is unmasked,
  * so no additive mask is read (a masked key contributes exp(-10000) = 0 in the padded form: dropping it is exact);

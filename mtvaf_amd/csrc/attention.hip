@@ -204,6 +204,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   attn_fwd_body<PipeF32>(a, PipeF32::RowTile{Ks}, PipeF32::ColTile{Vs}, Ms, &t_eff_slot);
 }
 
+// (the forward's LDS with the transposing buffer in the place of the V tile)
+__global__ __launch_bounds__(256) void attn_probs_kernel(AttnArgs a, ProbsOut o) {
+  __shared__ __attribute__((aligned(16))) float Ks[KT * PipeF32::LDK];
+  __shared__ __attribute__((aligned(16))) float Ps[KT * LDP];
+  __shared__ __attribute__((aligned(16))) float Ms[KT];
+  __shared__ int t_eff_slot;
+  attn_probs_body<PipeF32>(a, o, PipeF32::RowTile{Ks}, Ps, Ms, &t_eff_slot);
+}
+
 // (each side of the backward is VALU / issue bound at ~40 % MFMA utilisation on its own)
 __global__ __launch_bounds__(256, 3) void attn_bwd_kernel(AttnArgs a, int nq) {  // 4 per SIMD spills 10 VGPRs
   __shared__ __attribute__((aligned(16))) float tile0[KT * PipeF32::LDK];
@@ -268,6 +277,39 @@ static int attn_bwd_launch(const float* dctx, const float* qkv, const float* pk,
   hipLaunchKernelGGL(attn_bwd_kernel, grid, dim3(256), 0, st, a, nq);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
+}
+
+static int attn_probs_launch(const float* qkv, const float* pk, const float* addmask, float* probs, float* prefix_mass, int B, int S,
+                             int P, int NH, int head_dim, int zero_masked_queries, hipStream_t st) {
+  if (head_dim != D) return MTVAF_ERR_SHAPE;
+  if (!qkv || !addmask) return MTVAF_ERR_ARG;
+  AttnArgs a{};
+  a.qkv = qkv; a.pk = pk; a.pv = pk; a.addmask = addmask;  // (no V: the value sources are never read)
+  attn_fill_common(a, B, S, P, NH, 0.f, 0, 0);
+  int rc = attn_check(a);
+  if (rc) return rc;
+  const ProbsOut o{probs, prefix_mass, zero_masked_queries};
+  const dim3 grid((S + 63) / 64, NH, B);
+  if (attn_split_on()) return launch_attn_f32s_probs(a, o, grid, st);
+  hipLaunchKernelGGL(attn_probs_kernel, grid, dim3(256), 0, st, a, o);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+// probs[B,NH,S,P+S] (every element written), prefix_mass[B,NH,S] (or NULL) <- softmax(Q.[Kp;K]^T / sqrt(D) + addmask): the
+// probabilities the forward never materialises, by the arithmetic it runs with (mtvaf_f32_split).  Only the Q and K thirds of qkv
+// are read.
+int mtvaf_prefix_attn_probs(const float* qkv, const float* pk, const float* addmask, float* probs, float* prefix_mass, int B, int S,
+                            int P, int NH, int head_dim, int zero_masked_queries, hipStream_t st) {
+  if (!probs) return MTVAF_ERR_ARG;
+  return attn_probs_launch(qkv, pk, addmask, probs, prefix_mass, B, S, P, NH, head_dim, zero_masked_queries, st);
+}
+
+// prefix_mass alone: the same kernel without the [B,NH,S,P+S] stores (its second pass ends behind the prefix slots).
+int mtvaf_prefix_attn_mass(const float* qkv, const float* pk, const float* addmask, float* prefix_mass, int B, int S, int P, int NH,
+                           int head_dim, int zero_masked_queries, hipStream_t st) {
+  if (!prefix_mass) return MTVAF_ERR_ARG;
+  return attn_probs_launch(qkv, pk, addmask, nullptr, prefix_mass, B, S, P, NH, head_dim, zero_masked_queries, st);
 }
 
 // ctx[B*S,H], lse[B,NH,S] <- attention over [prefix ; text] keys.  head_dim must be 64.

@@ -47,6 +47,14 @@ struct AttnArgs {
   long Mrows;
 };
 
+// outputs of the probabilities-on-request kernel (attn_probs_body): beside AttnArgs, so that the training kernels' argument block
+// stays as it is
+struct ProbsOut {
+  float* probs;  // NULL: only mass is wanted -- the second pass stops behind the prefix slots
+  float* mass;   // or NULL
+  int zero_masked_queries;  // rows of queries whose own key is masked (addmask <= -5000): zeros
+};
+
 // the stores of the two results that are GEMM operands downstream: fp32, and the plane image when the caller asked for it
 __device__ __forceinline__ void store_ctx(const AttnArgs& a, long row, int col, const f32x4 v) {
   *reinterpret_cast<f32x4*>(a.ctx + row * a.H + col) = v;
@@ -164,5 +172,6 @@ int attn_check(const Args& a) {
 // launchers of the split-product kernels (csrc/attention_f32s.hip); grid / block as the fp32-pipe kernels of attention.hip
 int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st);
 int launch_attn_f32s_bwd(const AttnArgs& a, int nq, dim3 grid, hipStream_t st);
+int launch_attn_f32s_probs(const AttnArgs& a, const ProbsOut& o, dim3 grid, hipStream_t st);
 
 }  // namespace mtvaf

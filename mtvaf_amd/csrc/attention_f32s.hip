@@ -225,6 +225,14 @@ __global__ __launch_bounds__(256) void attn_f32s_fwd_kernel(AttnArgs a) {
   attn_fwd_body<Split3>(a, Ks, Vs, Ms, &t_eff_slot);
 }
 
+__global__ __launch_bounds__(256) void attn_f32s_probs_kernel(AttnArgs a, ProbsOut o) {
+  __shared__ __attribute__((aligned(16))) unsigned char Ks[TILE_B];
+  __shared__ __attribute__((aligned(16))) float Ps[KT * LDP];
+  __shared__ __attribute__((aligned(16))) float Ms[KT];
+  __shared__ int t_eff_slot;
+  attn_probs_body<Split3>(a, o, Ks, Ps, Ms, &t_eff_slot);
+}
+
 __global__ __launch_bounds__(256, 2) void attn_f32s_bwd_kernel(AttnArgs a, int nq) {
   __shared__ __attribute__((aligned(16))) unsigned char tile0[TILE_B];
   __shared__ __attribute__((aligned(16))) unsigned char tile1[TILE_B];
@@ -237,6 +245,11 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_bwd_kernel(AttnArgs a, int n
 
 int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(as3::attn_f32s_fwd_kernel, grid, dim3(256), 0, st, a);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+int launch_attn_f32s_probs(const AttnArgs& a, const ProbsOut& o, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(as3::attn_f32s_probs_kernel, grid, dim3(256), 0, st, a, o);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

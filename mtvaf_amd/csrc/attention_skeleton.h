@@ -1,6 +1,6 @@
-// The fp32 prefix-attention kernels, ONCE: forward, backward query side (dQ), backward key side (dK, dV) and the backward dispatch,
-// as __device__ __forceinline__ templates over an ARITHMETIC -- how a [64][64] tile lies in LDS and how the products over it are
-// formed.  csrc/attention.hip (fp32 MFMA pipe) and csrc/attention_f32s.hip (split bf16 products) each provide one and the thin
+// The fp32 prefix-attention kernels, ONCE: forward, the probabilities on request (the forward without V), backward query side (dQ),
+// backward key side (dK, dV) and the backward dispatch, as __device__ __forceinline__ templates over an ARITHMETIC -- how a [64][64]
+// tile lies in LDS and how the products over it are formed.  csrc/attention.hip (fp32 MFMA pipe) and csrc/attention_f32s.hip (split bf16 products) each provide one and the thin
 // __global__ kernels (their LDS, their __launch_bounds__) that call the bodies below.  Everything else -- launch geometry, the
 // zero-fill slice of a packed launch, key order, masking, the log2-domain online softmax, the dropout hash, the register -> LDS
 // double buffering with its two barriers, the stores -- is here and is therefore the same in both.
@@ -140,6 +140,129 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::Row
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store_ctx(a, sn.tok0 + q, h * D + 16 * dt + 4 * g, oacc[dt] * inv_l);
     if (g == 0) a.lse[((long)b * a.NH + h) * a.S + q] = (m_run + log2f(l_run)) * LN2;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// attention probabilities on request (output_attentions): the forward without V.  probs [B, NH, S, P + S] dense fp32, EVERY element
+// written; mass [B, NH, S] = sum of a row over the prefix slots.  Same grid, staging, key order, masking and log2-domain scores as
+// the forward (padded layout only).  TWO passes over the key tiles of a 64-query tile: the first keeps the running (max, sum), the
+// second recomputes the scores and stores exp2(s - m) / l -- no [64][T] score tile is parked in LDS.  A score block has a query on a
+// lane (consecutive lanes = consecutive ROWS of the output); each wave turns its [16 queries][64 keys] block through its own
+// [16][LDP] slice of Ps so that a store instruction writes 64 consecutive keys of one row (4-byte stores: T is not a multiple of 4).
+// ---------------------------------------------------------------------------------------------
+constexpr int LDP = 68;  // row stride (floats) of the transposing buffer: 16-byte aligned rows for the b128 writes
+
+template <class A>
+__device__ __forceinline__ void attn_probs_body(const AttnArgs& a, const ProbsOut& o, typename A::RowTile Ks, float* Ps, float* Ms,
+                                                int* t_eff_slot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lq = lane & 15, g = lane >> 4;
+  int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
+  const Sent sn = sentence(a, b);
+  const int S = a.S, Tf = a.P + a.S;
+  // keys behind the last unmasked text position: exact zeros in the reference too (exp(-10000 - max) underflows), stored below
+  const int T = effective_keys(a.addmask + (long)b * Tf, a.P, S, t_eff_slot);
+  const int qw = bx * 64 + wave * 16;  // first query of this wave
+  const int q = qw + lq;
+  const bool wave_live = qw < S;
+  const float sc2 = a.scale * LOG2E;
+  const bool zrow = o.zero_masked_queries && a.addmask[(long)b * Tf + a.P + min(q, S - 1)] <= -5000.f;
+
+  KvSrc ksrc, vsrc;
+  kv_sources(a, sn, b, h, A::stage_col(), ksrc, vsrc);
+  const int ldt = 3 * a.H;
+  const typename A::Operand qf = A::load_operand(a.qkv + (sn.tok0 + min(q, S - 1)) * 3 * a.H + h * D + A::operand_col(g));
+
+  // one sweep over the key tiles [0, Tend): stage (next tile in flight as in the forward), scores of the live waves -> tile(t0, s)
+  auto sweep = [&](int Tend, auto&& tile) {
+    typename A::Stage kst;
+    float mreg = NEG_BIG;
+    auto fetch = [&](int t0) {
+      A::fetch_kv(kst, ksrc, a.P, T, ldt, t0);
+      if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
+    };
+    if (Tend > 0) fetch(0);
+    for (int t0 = 0; t0 < Tend; t0 += KT) {
+      __syncthreads();
+      A::store(Ks, kst);
+      if (threadIdx.x < KT) Ms[threadIdx.x] = (t0 + (int)threadIdx.x < T) ? mreg * LOG2E : NEG_BIG;
+      __syncthreads();
+      if (t0 + KT < Tend) fetch(t0 + KT);
+      if (!wave_live) continue;  // (wave-uniform) no query of this wave exists: it only stages and synchronises
+      const int nsub = min(4, (T - t0 + 15) >> 4);
+      f32x4 s[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s[j] = f32x4{NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
+        if (j < nsub) {
+          const f32x4 acc = A::rows_dot(Ks, j, qf, lq, g);
+          const f32x4 mv = *reinterpret_cast<const f32x4*>(Ms + 16 * j + 4 * g);
+          s[j] = acc * sc2 + mv;
+        }
+      }
+      tile(t0, s);
+    }
+  };
+
+  float m_run = NEG_BIG, l_run = 0.f;
+  sweep(T, [&](int, f32x4(&s)[4]) {
+    float tmax = NEG_BIG;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, fmaxf(fmaxf(s[j].x, s[j].y), fmaxf(s[j].z, s[j].w)));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_run, tmax);
+    float psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) psum += __builtin_amdgcn_exp2f(s[j][r] - m_new);
+    psum += __shfl_xor(psum, 16, 64);
+    psum += __shfl_xor(psum, 32, 64);
+    l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + psum;
+    m_run = m_new;
+  });
+
+  const float inv_l = zrow ? 0.f : 1.f / l_run;  // (every probability is finite: 0 * p = 0 exactly)
+  const long row0 = ((long)b * a.NH + h) * S;    // first row of this (sentence, head) in probs / mass
+  float* Pw = Ps + wave * 16 * LDP;
+  float pmass = 0.f;
+  sweep(o.probs ? T : a.P, [&](int t0, f32x4(&s)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[j][r] = __builtin_amdgcn_exp2f(s[j][r] - m_run) * inv_l;  // keys beyond T: exp2(-1e30 - m) = 0
+        pmass += (t0 + 16 * j + 4 * g + r < a.P) ? s[j][r] : 0.f;
+      }
+    }
+    if (!o.probs) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Pw + lq * LDP + 16 * j + 4 * g) = s[j];
+    // one wave: LDS operations execute in program order, the fences only keep the compiler from moving the reads above the writes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (t0 + lane < Tf) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (qw + i < S) o.probs[(row0 + qw + i) * Tf + t0 + lane] = Pw[i * LDP + lane];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();  // (the next tile overwrites the slice)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  });
+  if (!wave_live) return;
+  if (o.probs) {  // whole key tiles of trailing padding
+    for (int t = ((T + KT - 1) / KT) * KT + lane; t < Tf; t += KT)
+      for (int i = 0; i < 16 && qw + i < S; ++i) o.probs[(row0 + qw + i) * Tf + t] = 0.f;
+  }
+  if (o.mass) {
+    pmass += __shfl_xor(pmass, 16, 64);
+    pmass += __shfl_xor(pmass, 32, 64);
+    if (g == 0 && q < S) o.mass[row0 + q] = pmass;
   }
 }
 

@@ -439,6 +439,28 @@ class Packing:
         return out
 
 
+def attention_maps(h_in: torch.Tensor, w: "LayerWeights", pk: Optional[torch.Tensor], addmask: torch.Tensor, NH: int,
+                   want_probs: bool = True, want_mass: bool = False, zero_masked_queries: bool = False):
+    """The attention probabilities of ONE layer on request (``output_attentions``), recomputed outside the step from the layer's
+    INPUT hidden state: h_in [B,S,H], w the layer's weights, pk its prefix key slab [B,P*H] (or None), addmask [B,P+S].
+    -> (probs [B,NH,S,P+S] or None, prefix_mass [B,NH,S] or None), fp32, no gradient; the probabilities BEFORE dropout.
+
+    One Q|K projection through ``hip.linear_fwd`` -- so it follows the process's compute mode (``hip.COMPUTE``, ``hip.f32_split``),
+    bf16 operand rounding included -- and one launch of the probabilities kernel (csrc/attention_skeleton.h, attn_probs_body).
+    The forward kernels keep only the log-sum-exp; nothing of the training step is touched.  ``zero_masked_queries``: rows of
+    queries whose own key is masked are zeros (a padding-free run's hidden states carry nothing there)."""
+    B, S, H = h_in.shape
+    Pn = addmask.shape[1] - S
+    with torch.no_grad():
+        x = h_in.detach().contiguous().view(B * S, H)
+        qkv = _empty(B * S, 3 * H, like=x)  # (the kernel's token-major Q | K | V rows; the V third is neither written nor read)
+        hip.linear_fwd(x, w.wqkv[:2 * H], w.bqkv[:2 * H], qkv)
+        probs = _empty(B, NH, S, Pn + S, like=x) if want_probs else None
+        mass = _empty(B, NH, S, like=x) if want_mass else None
+        hip.prefix_attn_probs(qkv, pk if Pn else None, addmask, probs, mass, B, S, Pn, NH, zero_masked_queries)
+    return probs, mass
+
+
 def _layout(fields):
     off, out = 0, []
     for name, nbytes in fields:

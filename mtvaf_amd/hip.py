@@ -54,6 +54,8 @@ _SIGS = {
     "mtvaf_prefix_attn_fwd": (c_int, [P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_bwd_tail": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, I, P]),
+    "mtvaf_prefix_attn_probs": (c_int, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    "mtvaf_prefix_attn_mass": (c_int, [P, P, P, P, I, I, I, I, I, I, P]),
     "mtvaf_prefix_attn_varlen_fwd": (c_int, [P, P, P, P, I, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_varlen_bwd": (c_int, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_varlen_fwd_planes": (c_int, [P, P, P, P, I, P, P, I, I, I, I, I, F, U64, U64, P, I, P]),
@@ -575,6 +577,19 @@ def dropout_res_ln_bwd(dout, x, res, gamma, mean, rstd, dx, dres, dres_accumulat
 def prefix_attn_fwd(qkv, pk, pv, addmask, ctx, lse, B, S, Pn, NH, p, seed, offset):
     _ck(lib().mtvaf_prefix_attn_fwd(_p(qkv), _p(pk), _p(pv), _p(addmask), _p(ctx), _p(lse), B, S, Pn, NH, 64, float(p),
                                     seed, offset, _st()), "mtvaf_prefix_attn_fwd")
+
+
+def prefix_attn_probs(qkv, pk, addmask, probs, prefix_mass, B, S, Pn, NH, zero_masked_queries=False):
+    """probs [B,NH,S,Pn+S] (or None: prefix_mass alone) and prefix_mass [B,NH,S] (or None) <- the attention probabilities of
+    qkv [B*S,3H] (Q and K thirds) over [prefix ; text] keys; every element of both is written.  zero_masked_queries: rows of
+    queries whose own key is masked are zeros."""
+    _f32(qkv, pk, addmask, probs, prefix_mass)
+    if probs is None:
+        _ck(lib().mtvaf_prefix_attn_mass(_p(qkv), _p(pk), _p(addmask), _p(prefix_mass), B, S, Pn, NH, 64,
+                                         int(bool(zero_masked_queries)), _st()), "mtvaf_prefix_attn_mass")
+        return
+    _ck(lib().mtvaf_prefix_attn_probs(_p(qkv), _p(pk), _p(addmask), _p(probs), _p(prefix_mass), B, S, Pn, NH, 64,
+                                      int(bool(zero_masked_queries)), _st()), "mtvaf_prefix_attn_probs")
 
 
 def prefix_attn_bwd(dctx, qkv, pk, pv, addmask, ctx, lse, delta, dqkv, dpk, dpv, B, S, Pn, NH, p, seed, offset, zero_tail=False):

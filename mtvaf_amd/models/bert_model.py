@@ -147,6 +147,7 @@ class TVNetSAModel2(nn.Module):
         # this head reads hidden states through the mask only (fc -> CRF with mask=attention_mask): padding-free execution
         # (engine.UNPAD) may leave zeros at masked positions.  TVNetSAModel's position softmax reads every position: no flag.
         self.bert.allow_unpad = True
+        self.last_prefix_mass = None  # [L,B,NH,S] after a forward with args.output_prefix_mass
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -191,9 +192,16 @@ class TVNetSAModel2(nn.Module):
         else:
             prefix_guids = None
             prompt_attention_mask = attention_mask
+        # The attention maps are made on request only (the reference hard-codes output_attentions=True, bert_model.py:496-502, and
+        # never reads them): args.output_attentions (True or layer indices) fills TokenClassifierOutput.attentions,
+        # args.output_prefix_mass fills self.last_prefix_mass [L,B,NH,S] -- each token's attention on the visual slots --
+        # without the full maps.  Without the switches the step launches nothing for them.
+        self.bert.encoder.output_prefix_mass = bool(_arg(self.args, "output_prefix_mass"))
         bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
-                                token_type_ids=token_type_ids, past_key_values=prefix_guids, output_attentions=True,
-                                output_hidden_states=True, return_dict=True)
+                                token_type_ids=token_type_ids, past_key_values=prefix_guids,
+                                output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
+                                return_dict=True)
+        self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
         sequence_output = engine.dropout(bert_output["last_hidden_state"], self.dropout.p, self.training)
         emissions = engine.LinearFunction.apply(sequence_output, self.fc.weight, self.fc.bias, False)
         mask_u8 = attention_mask.to(torch.uint8)
@@ -222,7 +230,7 @@ class TVNetSAModel2(nn.Module):
             # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
             # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)
             torch.cuda.current_stream().wait_event(decoded)
-        return TokenClassifierOutput(loss=loss, logits=logits)
+        return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
 
     # ------------------------------------------------------------------------------------------------
     def _region_features(self, images, aux_imgs):
@@ -395,8 +403,9 @@ class TVNetSAModel(nn.Module):
             last_hidden = cutoff._training_step_with_cutoff(self.args.aug_type)[0]
         else:
             last_hidden = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
-                                    token_type_ids=token_type_ids, past_key_values=prefix_guids, output_attentions=True,
-                                    output_hidden_states=True, return_dict=True)["last_hidden_state"]
+                                    token_type_ids=token_type_ids, past_key_values=prefix_guids,
+                                    output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
+                                    return_dict=True)["last_hidden_state"]
         sequence_output = engine.dropout(last_hidden, self.dropout.p, self.training)
         ae_logits = engine.LinearFunction.apply(sequence_output, self.binary_affine.weight, self.binary_affine.bias, False)
         return ae_logits, sequence_output

@@ -9,8 +9,12 @@ work unchanged) -- but the sub-modules are only parameter containers: the arithm
 forward/backward runs in hand-written HIP kernels through ``mtvaf_amd.engine``.
 
 Deliberate deviations (documented in DESIGN.md):
-  * ``attentions`` is returned as ``None``: the [B,12,S,P+S] probability tensors are never
-    materialised (nothing in the reference reads them: models/bert_model.py:496-506).
+  * ``attentions`` are made ON REQUEST only: the training kernels never materialise the [B,12,S,P+S] probability tensors
+    (nothing in the reference reads them: models/bert_model.py:496-506).  ``output_attentions=False`` / ``None`` returns
+    ``None`` and launches nothing; ``True`` returns one fp32 tensor per layer; an iterable of layer indices returns a tuple of
+    the same length with ``None`` for the other layers.  The maps are recomputed eagerly inside the call from each layer's
+    input hidden state (``engine.attention_maps``: one Q|K projection + one kernel launch per layer), detached, and are the
+    probabilities BEFORE dropout in training mode too.  In a padding-free run the rows of masked queries are zeros.
   * head pruning, cross-attention/decoder mode, relative position embeddings, gradient checkpointing
     and ``head_mask`` are not part of the path and raise if requested.
 """
@@ -257,6 +261,10 @@ class BertEncoder(nn.Module):
         self.gradient_checkpointing = False
         self._stores: Optional[List[_LayerStore]] = None
         self._sink: Optional[GradSink] = None
+        # set by a caller that wants the share of every token's attention on the prefix slots without the full maps:
+        # each forward then fills ``last_prefix_mass`` [L,B,NH,S] (TVNetSAModel2: args.output_prefix_mass)
+        self.output_prefix_mass = False
+        self.last_prefix_mass = None
 
     def _prepare(self):
         if self._stores is None or not all(st.valid(l) for st, l in zip(self._stores, self.layer)):
@@ -302,11 +310,54 @@ class BertEncoder(nn.Module):
         all_hidden = (hidden_states,) + tuple(outs) if output_hidden_states else None
         if all_hidden is not None and len(outs) > 1 and outs[0].dim() == 2:
             all_hidden = _LazyHiddenStates(all_hidden, engine.LAST_PACK)  # padding-free run: intermediate states are packed
+        layers = _attention_layers(output_attentions, len(self.layer))
+        want_mass = bool(getattr(self, "output_prefix_mass", False))
+        attn = None
+        if layers is not None or want_mass:
+            attn, self.last_prefix_mass = self._attention_maps(hidden_states, outs, stores, pkv, addmask, layers, want_mass)
         if not return_dict:
-            return tuple(v for v in [outs[-1], all_hidden] if v is not None)
+            return tuple(v for v in [outs[-1], all_hidden, attn] if v is not None)
         return BaseModelOutputWithPastAndCrossAttentions(last_hidden_state=outs[-1], past_key_values=None,
-                                                         hidden_states=all_hidden, attentions=None,
+                                                         hidden_states=all_hidden, attentions=attn,
                                                          cross_attentions=None)
+
+    def _attention_maps(self, h0, outs, stores, pkv, addmask, layers, want_mass):
+        """-> (attentions: a tuple of L entries, [B,NH,S,P+S] for the requested ``layers`` and None elsewhere, or None when no
+        layer is requested; prefix mass [L,B,NH,S] or None).  Layer i is recomputed from its input hidden state: ``h0`` or
+        ``outs[i - 1]`` -- PACKED rows in a padding-free run, scattered back with zeros at the masked positions
+        (``Packing.unpack``); rows of masked queries carry no information there and are returned as zeros."""
+        B, S, H = h0.shape
+        L, NH = len(self.layer), self.config.num_attention_heads
+        pack = engine.LAST_PACK if (engine.NATIVE_EXEC and L) else None  # the Packing of THIS forward (None: it ran padded)
+        probs, mass = [None] * L, []
+        for i in range(L):
+            if not (want_mass or i in layers):
+                continue
+            h = h0 if i == 0 else outs[i - 1]
+            if h.dim() == 2:
+                h = pack.unpack(h.detach())
+            p, m = engine.attention_maps(h.view(B, S, H), stores[i].weights, None if pkv is None else pkv[i, 0], addmask, NH,
+                                         want_probs=layers is not None and i in layers, want_mass=want_mass,
+                                         zero_masked_queries=pack is not None)
+            probs[i] = p
+            mass.append(m)
+        return (tuple(probs) if layers is not None else None), (torch.stack(mass) if want_mass else None)
+
+
+def _attention_layers(output_attentions, L: int):
+    """``output_attentions`` -> None (nothing requested) or the set of requested layer indices: True = all, an iterable of
+    indices (negative ones count from the last layer) = those."""
+    if output_attentions is None or output_attentions is False:
+        return None
+    if isinstance(output_attentions, (bool, int)):
+        return set(range(L)) if output_attentions else None
+    idx = set()
+    for i in output_attentions:
+        i = int(i)
+        if not -L <= i < L:
+            raise IndexError(f"output_attentions names layer {i} of {L}")
+        idx.add(i % L)
+    return idx
 
 
 class _LazyHiddenStates(tuple):
@@ -511,17 +562,17 @@ class BertModel(nn.Module):
             engine.Packing.begin(ext.view(B, -1), ext.shape[-1] - S, S)
         emb = self.embeddings(input_ids=input_ids, token_type_ids=token_type_ids, position_ids=position_ids,
                               inputs_embeds=inputs_embeds, past_key_values_length=0)
-        enc = self.encoder(emb, attention_mask=ext, past_key_values=past_key_values,
+        enc = self.encoder(emb, attention_mask=ext, past_key_values=past_key_values, output_attentions=output_attentions,
                            output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok)
         seq = enc.last_hidden_state
         # the pooler output is consumed only by the span model's DualGCN head; TVNetSAModel2 never reads it
         # (models/bert_model.py:496-506) and sets `skip_pooler` so the [B,H]x[H,H] product is not launched
         pooled = self.pooler(seq) if (self.pooler is not None and not getattr(self, "skip_pooler", False)) else None
         if not return_dict:
-            return (seq, pooled) + ((enc.hidden_states,) if enc.hidden_states is not None else ())
+            return (seq, pooled) + tuple(v for v in (enc.hidden_states, enc.attentions) if v is not None)
         return BaseModelOutputWithPoolingAndCrossAttentions(last_hidden_state=seq, pooler_output=pooled,
                                                             past_key_values=None, hidden_states=enc.hidden_states,
-                                                            attentions=None, cross_attentions=None)
+                                                            attentions=enc.attentions, cross_attentions=None)
 
     def get_embedding_output(self, input_ids, token_type_ids=None, position_ids=None):
         """reference: models/modeling_bert.py:1117-1125 (Cutoff augmentation entry)"""
