@@ -27,7 +27,7 @@ namespace mtvaf {
 
 // The fp32-pipe arithmetic: [64][64] fp32 tiles, padded rows; the operand of a row is its 64 values, 4 consecutive d per lane at
 // 16 db + 4 g .. + 3 (db = 0 .. 3); every product is 16 v_mfma_f32_16x16x4_f32 over d (or over the 16 rows of a block).
-struct PipeF32 {
+struct PipeF32 : F32Io {
   typedef float Lds;
   static constexpr int LDT = 68;  // LDS row stride (floats) of a tile that is also read by columns: conflict-free b32 column reads
   static constexpr int LDK = 72;  // ... of a tile read as row fragments only: conflict-free ds_read_b128 (slot = 2*row + k-chunk mod 16)
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel(AttnArgs a, int nq) { 
   __shared__ __attribute__((aligned(16))) float tile1[KT * PipeF32::LDK];
   __shared__ __attribute__((aligned(16))) float small[3 * KT];
   __shared__ int t_eff_slot;
-  attn_bwd_body<PipeF32>(a, nq, tile0, tile1, small, &t_eff_slot);
+  attn_bwd_body<PipeF32>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot);
 }
 
 }  // namespace mtvaf

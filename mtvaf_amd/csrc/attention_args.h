@@ -1,8 +1,10 @@
-// Argument block of the fp32 prefix-attention kernels -- csrc/attention.hip (fp32 MFMA pipe) and csrc/attention_f32s.hip (round 6: the
-// same attention with its products formed as split bf16 products, the arithmetic of csrc/gemm_f32x3.hip): same launch geometry, same
-// key order, same dropout hash, same outputs in both -- and the small device / host helpers that csrc/attention_bf16.hip uses too
-// (written over any argument struct with cu, B, S, addmask).  The two fp32 files share their kernel bodies as well: they live once
-// in csrc/attention_skeleton.h, templates over an arithmetic (LDS tile format, staging registers, register operand, products).
+// Argument blocks of the prefix-attention kernels: AttnArgs of the two fp32 arithmetics -- csrc/attention.hip (fp32 MFMA pipe) and
+// csrc/attention_f32s.hip (round 6: the same attention with its products formed as split bf16 products, the arithmetic of
+// csrc/gemm_f32x3.hip) -- and ab::Args of the mixed-precision one (csrc/attention_bf16.hip): same launch geometry, same key order,
+// same dropout hash in all three.  With them the stores of the results that are GEMM operands downstream (store_ctx / store_dqkv, one
+// overload per block) and the small device / host helpers, written over any argument struct with cu, B, S, addmask.  The kernel
+// bodies live once in csrc/attention_skeleton.h, templates over an arithmetic (element type and argument block, LDS tile format,
+// staging registers, register operand, products, output hooks).
 #pragma once
 #include "common.h"
 #include "planes.h"
@@ -47,6 +49,36 @@ struct AttnArgs {
   long Mrows;
 };
 
+namespace ab {
+
+// The mixed-precision mode: Q | K | V, the prefix slabs, the context and their gradients are bf16 (no fp32 copies of these tensors
+// exist), and the per-head column sums of dQ | dK | dV (the QKV bias gradient) leave the backward kernel as per-block partials.
+struct Args {
+  const __bf16* qkv;
+  const __bf16* pk;
+  const __bf16* pv;
+  const float* addmask;
+  __bf16* ctx;
+  float* lse;
+  // backward
+  const __bf16* dctx;
+  __bf16* dqkv;
+  float* dpk;
+  float* dpv;
+  float* partq;   // [B * nqt][H]   column sums of dQ per query-tile block
+  float* partkv;  // [B * nkt][2H]  column sums of dK | dV (text keys only) per key-tile block
+  int B, S, P, NH, H;
+  float scale, p_drop;
+  uint32_t drop_key, drop_thr;
+  const uint64_t* epoch;  // device-side dropout epoch (captured launches), or NULL
+  const int* cu;          // PACKED token rows (see AttnArgs): [B+1] row offsets of the sentences, or NULL
+  int pad_rows;           // rows behind the last sentence that pad the packed image: zero-filled by the z-slice b == B
+  int zero_tail;          // backward, padded layout: dctx is exactly zero behind a sentence's last unmasked position (the caller's
+                          // word, as AttnArgs::zero_tail): the key side's query loop stops there
+};
+
+}  // namespace ab
+
 // outputs of the probabilities-on-request kernel (attn_probs_body): beside AttnArgs, so that the training kernels' argument block
 // stays as it is
 struct ProbsOut {
@@ -63,6 +95,15 @@ __device__ __forceinline__ void store_ctx(const AttnArgs& a, long row, int col, 
 __device__ __forceinline__ void store_dqkv(const AttnArgs& a, long row, int col, const f32x4 v) {
   *reinterpret_cast<f32x4*>(a.dqkv + row * 3 * a.H + col) = v;
   if (a.dqkv_p) planes_store4(a.dqkv_p, a.Mrows, row, col, v);
+}
+
+// ... of the mixed-precision mode: rounded to bf16, four values per store
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_ctx(const ab::Args& a, long row, int col, const f32x4 v) {
+  *reinterpret_cast<bf16x4*>(a.ctx + row * a.H + col) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
+}
+__device__ __forceinline__ void store_dqkv(const ab::Args& a, long row, int col, const f32x4 v) {
+  *reinterpret_cast<bf16x4*>(a.dqkv + row * 3 * a.H + col) = bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
 }
 
 struct Sent {

@@ -17,59 +17,21 @@
 // O^T[d][q] = V^T.P^T when the k-slot (g, j) of that product is defined as key 16*(2u + (j >> 2)) + 4g + (j & 3); the
 // matching A operand V^T comes from the row-major V tile by two transposing reads (ds_read_b64_tr_b16).  All [64][64]
 // bf16 tiles (128-byte rows) use ONE LDS image that is conflict-free for both the row reads and the transposing reads:
-// 16-byte chunk c of row r at chunk c ^ (((r >> 1) & 3) << 1).
-// (tile_off; the sentence / mask / key-axis helpers and the host-side tests are those of attention_args.h, shared with the fp32 kernels)
-#include "attention_args.h"
+// 16-byte chunk c of row r at chunk c ^ (((r >> 1) & 3) << 1)  (tile_off, attention_args.h).
+//
+// The kernel bodies are those of csrc/attention_skeleton.h; this file provides their bf16 arithmetic (ab::Bf16), whose output hooks
+// reduce the bias-gradient partials, and the C entry points.
+#include "attention_skeleton.h"
 
 namespace mtvaf {
 
 namespace ab {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 #define MFMA_BF(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-struct Args {
-  const __bf16* qkv;
-  const __bf16* pk;
-  const __bf16* pv;
-  const float* addmask;
-  __bf16* ctx;
-  float* lse;
-  // backward
-  const __bf16* dctx;
-  __bf16* dqkv;
-  float* dpk;
-  float* dpv;
-  float* partq;   // [B * nqt][H]   column sums of dQ per query-tile block
-  float* partkv;  // [B * nkt][2H]  column sums of dK | dV (text keys only) per key-tile block
-  int B, S, P, NH, H;
-  float scale, p_drop;
-  uint32_t drop_key, drop_thr;
-  const uint64_t* epoch;  // device-side dropout epoch (captured launches), or NULL
-  const int* cu;          // PACKED token rows (see AttnArgs, attention_args.h): [B+1] row offsets of the sentences, or NULL
-  int pad_rows;           // rows behind the last sentence that pad the packed image: zero-filled by the z-slice b == B
-  int zero_tail;          // backward, padded layout: dctx is exactly zero behind a sentence's last unmasked position (the caller's
-                          // word, as AttnArgs::zero_tail): the key side's query loop stops there
-};
-
-typedef KvSrcT<__bf16> KvSrc;
-
-// stage a [64][64] bf16 tile: 512 chunks of 16 B, two per thread (rows r and r + 32, chunk c = tid & 7)
-__device__ __forceinline__ void tile_load_kv(bf16x8 (&reg)[2], const KvSrc& s, int P, int T, int ld_txt, int t0) {
-  const int c = threadIdx.x & 7, r = threadIdx.x >> 3;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-    reg[i] = *reinterpret_cast<const bf16x8*>(kv_row_ptr(s, min(t0 + r + 32 * i, T - 1), P, ld_txt) + c * 8);
-}
-__device__ __forceinline__ void tile_store(unsigned char* dst, const bf16x8 (&reg)[2]) {
-  const int c = threadIdx.x & 7, r = threadIdx.x >> 3;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) *reinterpret_cast<bf16x8*>(dst + tile_off(r + 32 * i, c)) = reg[i];
-}
 
 // A operand of a "rows x d" product: row (16*blk + lane&15), the 8 d values 32*ks + 8g .. +7
 __device__ __forceinline__ bf16x8 row_frag(const unsigned char* tile, int blk, int ks, int lr, int g) {
@@ -95,470 +57,199 @@ __device__ __forceinline__ float dot8(const bf16x8& a, const bf16x8& b) {
   return s;
 }
 
-// ---------------------------------------------------------------------------------------------
-// forward: grid (ceil(S/64), NH, B), 256 threads; wave w owns queries q0+16w .. +15
-// ---------------------------------------------------------------------------------------------
+// The bf16 arithmetic: a tile is one [64][64] bf16 image; the operand of a row is its 64 values, 8 consecutive d per lane at
+// 32 ks + 8 g .. + 7 (ks = 0, 1); a product over d is two bf16 MFMA products, a product over a tile's rows two per 16 d.
+struct Bf16 {
+  typedef __bf16 Elem;
+  typedef ab::Args Args;
+  // (prefetching the next key tile into registers, as the backward does, measured 6 % SLOWER in the forward: 13.6 -> 14.5 us)
+  static constexpr bool FWD_FETCH_AHEAD = false;
+  static constexpr bool XCD_GROUP = false;  // (never measured for these kernels: placement only, but it moves their time)
+  typedef unsigned char Lds;
+  typedef unsigned char* RowTile;  // (one image serves the row reads and the transposing reads)
+  typedef unsigned char* ColTile;
+
+  // staging: thread -> rows r, r + 32 (r = tid >> 3), the 16-byte chunk c = tid & 7
+  static __device__ __forceinline__ int stage_col() { return (threadIdx.x & 7) * 8; }
+  static __device__ __forceinline__ int operand_col(int g) { return 8 * g; }
+  struct Stage {
+    bf16x8 v[2];
+  };
+  // (rows beyond T re-read row T - 1: finite values, probability exactly 0 through the mask tile)
+  static __device__ __forceinline__ void fetch_kv(Stage& s, const KvSrcT<__bf16>& src, int P, int T, int ld_txt, int t0) {
+    const int r = threadIdx.x >> 3;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) s.v[i] = *reinterpret_cast<const bf16x8*>(kv_row_ptr(src, min(t0 + r + 32 * i, T - 1), P, ld_txt));
+  }
+  // rows q0 + r (clamped to n - 1) of Q (row stride 3 H), dO and O (row stride H)
+  static __device__ __forceinline__ void fetch_rows(Stage& q, Stage& d, Stage& o, const __bf16* qsrc, const __bf16* dsrc, const __bf16* osrc,
+                                                    int H, int q0, int n) {
+    const int r = threadIdx.x >> 3;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int qq = min(q0 + r + 32 * i, n - 1);
+      q.v[i] = *reinterpret_cast<const bf16x8*>(qsrc + (long)qq * 3 * H);
+      d.v[i] = *reinterpret_cast<const bf16x8*>(dsrc + (long)qq * H);
+      o.v[i] = *reinterpret_cast<const bf16x8*>(osrc + (long)qq * H);
+    }
+  }
+  static __device__ __forceinline__ void store(unsigned char* tile, const Stage& s) {
+    const int c = threadIdx.x & 7, r = threadIdx.x >> 3;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *reinterpret_cast<bf16x8*>(tile + tile_off(r + 32 * i, c)) = s.v[i];
+  }
+  struct StageDelta {
+    float s[2];
+    __device__ __forceinline__ void reduce(const Stage& o, const Stage& d) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) s[i] = dot8(d.v[i], o.v[i]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {  // the 8 threads of a row are 8 consecutive lanes
+        s[i] += __shfl_xor(s[i], 1, 64);
+        s[i] += __shfl_xor(s[i], 2, 64);
+        s[i] += __shfl_xor(s[i], 4, 64);
+      }
+    }
+    __device__ __forceinline__ void store(float* del_s) const {
+      if ((threadIdx.x & 7) == 0) {
+        del_s[threadIdx.x >> 3] = s[0];
+        del_s[(threadIdx.x >> 3) + 32] = s[1];
+      }
+    }
+  };
+
+  struct Operand {
+    bf16x8 k[2];
+  };
+  static __device__ __forceinline__ Operand load_operand(const __bf16* p) {
+    Operand x;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) x.k[ks] = *reinterpret_cast<const bf16x8*>(p + 32 * ks);
+    return x;
+  }
+  static __device__ __forceinline__ Operand load_operand_dot(const __bf16* p, const __bf16* op, float& dot) {
+    Operand x;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      x.k[ks] = *reinterpret_cast<const bf16x8*>(p + 32 * ks);
+      dot += dot8(x.k[ks], *reinterpret_cast<const bf16x8*>(op + 32 * ks));
+    }
+    return x;
+  }
+
+  static __device__ __forceinline__ f32x4 rows_dot(const unsigned char* tile, int blk, const Operand& x, int lr, int g) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) acc = MFMA_BF(row_frag(tile, blk, ks, lr, g), x.k[ks], acc);
+    return acc;
+  }
+  static __device__ __forceinline__ void rows_dot2(const unsigned char* tile0, const Operand& x0, f32x4& r0, const unsigned char* tile1,
+                                                   const Operand& x1, f32x4& r1, int blk, int lr, int g) {
+    r0 = r1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      r0 = MFMA_BF(row_frag(tile0, blk, ks, lr, g), x0.k[ks], r0);
+      r1 = MFMA_BF(row_frag(tile1, blk, ks, lr, g), x1.k[ks], r1);
+    }
+  }
+  // The whole tile's probabilities first, then two 16-row blocks per product: slot u = the register pair p[2u], p[2u + 1] rounded to
+  // bf16, k-depth 32.
+  static constexpr int FOLD = 4;
+  static __device__ __forceinline__ void cols_acc(const unsigned char* tile, int, const f32x4* p, int nsub, int lane, f32x4 (&acc)[4]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (2 * u < nsub) {
+        const bf16x8 b = pack8(p[2 * u], p[2 * u + 1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) acc[dt] = MFMA_BF(tr_frag(tile, u, dt, lane), b, acc[dt]);
+      }
+    }
+  }
+  static __device__ __forceinline__ void cols_acc2(const unsigned char* tile0, const f32x4* p0, f32x4 (&acc0)[4], const unsigned char* tile1,
+                                                   const f32x4* p1, f32x4 (&acc1)[4], int, int nsub, int lane) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (2 * u < nsub) {
+        const bf16x8 b0 = pack8(p0[2 * u], p0[2 * u + 1]), b1 = pack8(p1[2 * u], p1[2 * u + 1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          acc0[dt] = MFMA_BF(tr_frag(tile0, u, dt, lane), b0, acc0[dt]);
+          acc1[dt] = MFMA_BF(tr_frag(tile1, u, dt, lane), b1, acc1[dt]);
+        }
+      }
+    }
+  }
+
+  // Output hooks.  No delta leaves the dQ side and it has neither of the fp32 kernels' whole-tile exits; instead every block writes
+  // the column sums of its rows -- zeros from a block that leaves before its loop.
+  static __device__ __forceinline__ bool tile_without_gradient(const Operand&, bool, float*) { return false; }
+  static __device__ __forceinline__ bool dq_tail_exit(const Args&) { return false; }
+  static __device__ __forceinline__ void store_delta(const Args&, long, float) {}
+  // x [4] (the MFMA result layout: d = 16 dt + 4 g + r of this lane's row) summed over the 16 rows of a wave -> red [wave][64]
+  static __device__ __forceinline__ void wave_col_sums(const f32x4 (&x)[4], bool ok, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = ok ? x[dt][r] : 0.f;
+        v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+        if ((lane & 15) == 0) red[wave * 64 + 16 * dt + 4 * (lane >> 4) + r] = v;
+      }
+  }
+  // (the sentence index as a scalar: as a 64-bit lane value it would hold a register pair through the whole tile loop, and the
+  // backward kernel sits at 168 VGPRs, the last count that leaves three waves per SIMD)
+  static __device__ __forceinline__ float* partq_row(const Args& a, int qtile, int b, int h) {
+    return a.partq + ((long)__builtin_amdgcn_readfirstlane(b) * ((a.S + 63) / 64) + qtile) * a.H + h * D;
+  }
+  // (rows of partkv per sentence: the padded key count, whatever the layout)
+  static __device__ __forceinline__ float* partkv_row(const Args& a, int ktile, int b, int h) {
+    return a.partkv + ((long)__builtin_amdgcn_readfirstlane(b) * ((a.P + a.S + 63) / 64) + ktile) * 2 * a.H + h * D;
+  }
+  static __device__ __forceinline__ void dq_sums_zero(const Args& a, int qtile, int b, int h) {
+    if (threadIdx.x < 64) partq_row(a, qtile, b, h)[threadIdx.x] = 0.f;
+  }
+  // column sums of this block's dQ rows (the query-bias gradient): over the 16 query lanes, then the 4 waves
+  static __device__ __forceinline__ void dq_sums(const Args& a, int qtile, int b, int h, const f32x4 (&dq)[4], bool qok, float* red) {
+    __syncthreads();
+    wave_col_sums(dq, qok, red);
+    __syncthreads();
+    if (threadIdx.x < 64)
+      partq_row(a, qtile, b, h)[threadIdx.x] = red[threadIdx.x] + red[64 + threadIdx.x] + red[128 + threadIdx.x] + red[192 + threadIdx.x];
+  }
+  static __device__ __forceinline__ void dkv_sums_zero(const Args& a, int ktile, int b, int h) {
+    if (threadIdx.x < 128) partkv_row(a, ktile, b, h)[(threadIdx.x >> 6) * a.H + (threadIdx.x & 63)] = 0.f;
+  }
+  // column sums over this block's TEXT keys (the key / value bias gradients): dK through red [0 .. 255], dV through red [256 .. 511]
+  static __device__ __forceinline__ void dkv_sums(const Args& a, int ktile, int b, int h, const f32x4 (&dk)[4], const f32x4 (&dv)[4],
+                                                  bool is_text, float* red) {
+    __syncthreads();
+    wave_col_sums(dk, is_text, red);
+    wave_col_sums(dv, is_text, red + 256);
+    __syncthreads();
+    if (threadIdx.x < 128) {
+      const int which = threadIdx.x >> 6, d = threadIdx.x & 63;
+      const float* rr = red + which * 256 + d;
+      partkv_row(a, ktile, b, h)[which * a.H + d] = rr[0] + rr[64] + rr[128] + rr[192];
+    }
+  }
+};
+
 __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char Ks[KT * 128];
   __shared__ __attribute__((aligned(16))) unsigned char Vs[KT * 128];
   __shared__ __attribute__((aligned(16))) float Ms[KT];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lq = lane & 15, g = lane >> 4;
-  int b = blockIdx.z;
-  const int h = blockIdx.y;
-  const int q = blockIdx.x * 64 + wave * 16 + lq;
-  if (a.cu && b == a.B) {  // (block-uniform) the rows that pad the packed image: zeros
-    const int r0 = a.cu[a.B];
-    const bf16x8 z = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-    for (int r = blockIdx.x * 32 + (threadIdx.x >> 3); r < a.pad_rows; r += gridDim.x * 32)
-      *reinterpret_cast<bf16x8*>(a.ctx + (long)(r0 + r) * a.H + h * D + (threadIdx.x & 7) * 8) = z;
-    return;
-  }
-  b = slot_sentence(a, b);
-  const Sent sn = sentence(a, b);
-  const int Sb = sn.n;
-  if ((int)blockIdx.x * 64 >= Sb) return;  // (block-uniform; packed rows: a query tile beyond the sentence)
-  const int Tf = a.P + a.S;  // row length of the additive mask
   __shared__ int t_eff_slot;
-  const int T = a.cu ? a.P + Sb : effective_keys(a.addmask + (long)b * Tf, a.P, a.S, &t_eff_slot);  // trailing padding keys are skipped
-  const bool qok = q < Sb;
-  const bool wave_live = __builtin_amdgcn_readfirstlane(q - lq) < Sb;  // (dead waves skip the arithmetic: see attention_skeleton.h)
-  const float inv_keep = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
-  const uint32_t rowh = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), (uint32_t)((b * a.NH + h) * a.S + q));
-  const float sc2 = a.scale * LOG2E;
-
-  KvSrc ksrc, vsrc;
-  ksrc.pre = a.pk + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-  vsrc.pre = a.pv + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-  ksrc.txt = a.qkv + sn.tok0 * 3 * a.H + a.H + h * D;
-  vsrc.txt = ksrc.txt + a.H;
-  const int ldt = 3 * a.H;
-
-  bf16x8 qf[2];
-  {
-    const __bf16* qp = a.qkv + (sn.tok0 + min(q, Sb - 1)) * 3 * a.H + h * D + 8 * g;
-    qf[0] = *reinterpret_cast<const bf16x8*>(qp);
-    qf[1] = *reinterpret_cast<const bf16x8*>(qp + 32);
-  }
-  f32x4 oacc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) oacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run = NEG_BIG, l_run = 0.f;
-
-  // (prefetching the next key tile into registers, as the backward kernels do, measured 6 % SLOWER here: 13.6 -> 14.5 us)
-  for (int t0 = 0; t0 < T; t0 += KT) {
-    bf16x8 kreg[2], vreg[2];
-    tile_load_kv(kreg, ksrc, a.P, T, ldt, t0);
-    tile_load_kv(vreg, vsrc, a.P, T, ldt, t0);
-    float mreg = NEG_BIG;
-    if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
-    __syncthreads();
-    tile_store(Ks, kreg);
-    tile_store(Vs, vreg);
-    if (threadIdx.x < KT) Ms[threadIdx.x] = (t0 + (int)threadIdx.x < T) ? mreg * LOG2E : NEG_BIG;
-    __syncthreads();
-    if (!wave_live) continue;  // (wave-uniform) a wave whose 16 queries all lie beyond the sentence only stages and synchronises
-    const int nsub = min(4, (T - t0 + 15) >> 4);  // 16-key blocks of this tile that hold real keys
-    f32x4 s[4];
-    float tmax = NEG_BIG;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] = f32x4{NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
-      if (j < nsub) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = MFMA_BF(row_frag(Ks, j, 0, lq, g), qf[0], acc);
-        acc = MFMA_BF(row_frag(Ks, j, 1, lq, g), qf[1], acc);
-        const f32x4 mv = *reinterpret_cast<const f32x4*>(Ms + 16 * j + 4 * g);
-        s[j] = acc * sc2 + mv;
-        tmax = fmaxf(tmax, fmaxf(fmaxf(s[j].x, s[j].y), fmaxf(s[j].z, s[j].w)));
-      }
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    float psum = 0.f;
-    const uint32_t cterm0 = (uint32_t)(t0 + 4 * g) * ATTN_DROP_C2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(s[j][r] - m_new);
-        psum += p;
-        float pd = p;
-        if (a.p_drop > 0.f)
-          pd = attn_dropout_keep2(rowh, cterm0 + (uint32_t)(16 * j + r) * ATTN_DROP_C2, a.drop_thr) ? p * inv_keep : 0.f;
-        s[j][r] = pd;
-      }
-    psum += __shfl_xor(psum, 16, 64);
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] *= alpha;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (2 * u < nsub) {
-        const bf16x8 pb = pack8(s[2 * u], s[2 * u + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oacc[dt] = MFMA_BF(tr_frag(Vs, u, dt, lane), pb, oacc[dt]);
-      }
-    }
-  }
-  if (qok) {
-    const float inv_l = 1.f / l_run;
-    __bf16* op = a.ctx + (sn.tok0 + q) * a.H + h * D + 4 * g;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const f32x4 o = oacc[dt] * inv_l;
-      *reinterpret_cast<bf16x4*>(op + 16 * dt) = bf16x4{(__bf16)o.x, (__bf16)o.y, (__bf16)o.z, (__bf16)o.w};
-    }
-    if (g == 0) a.lse[((long)b * a.NH + h) * a.S + q] = (m_run + log2f(l_run)) * LN2;
-  }
+  attn_fwd_body<Bf16>(a, Ks, Vs, Ms, &t_eff_slot);
 }
 
-// ---------------------------------------------------------------------------------------------
-// backward, query side: dQ for 64 queries per block (wave w: 16 of them), loop over key tiles
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bwd_dq_body(const Args& a, int qtile, unsigned char* Ks, unsigned char* Vs, float* Ms, float* red,
-                                            int* t_eff_slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lq = lane & 15, g = lane >> 4;
-  const int b = slot_sentence(a, blockIdx.z), h = blockIdx.y;
-  const int q = qtile * 64 + wave * 16 + lq;
-  const Sent sn = sentence(a, b);
-  const int Sb = sn.n;
-  if (qtile * 64 >= Sb) {  // (block-uniform) a query tile beyond the sentence: its column-sum partial is zero
-    if (threadIdx.x < 64) a.partq[((long)b * ((a.S + 63) / 64) + qtile) * a.H + h * D + threadIdx.x] = 0.f;
-    return;
-  }
-  const int Tf = a.P + a.S;
-  const int T = a.cu ? a.P + Sb : effective_keys(a.addmask + (long)b * Tf, a.P, a.S, t_eff_slot);
-  const bool qok = q < Sb;
-  const bool wave_live = __builtin_amdgcn_readfirstlane(q - lq) < Sb;
-  const float inv_keep = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
-  const uint32_t rowh = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), (uint32_t)((b * a.NH + h) * a.S + q));
-  const float sc2 = a.scale * LOG2E;
-
-  KvSrc ksrc, vsrc;
-  ksrc.pre = a.pk + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-  vsrc.pre = a.pv + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-  ksrc.txt = a.qkv + sn.tok0 * 3 * a.H + a.H + h * D;
-  vsrc.txt = ksrc.txt + a.H;
-  const int ldt = 3 * a.H;
-
-  bf16x8 qf[2], dof[2];
-  float dl = 0.f;
-  {
-    const long qrow = sn.tok0 + min(q, Sb - 1);
-    const __bf16* qp = a.qkv + qrow * 3 * a.H + h * D + 8 * g;
-    const __bf16* dop = a.dctx + qrow * a.H + h * D + 8 * g;
-    const __bf16* op = a.ctx + qrow * a.H + h * D + 8 * g;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 32 * ks);
-      dof[ks] = *reinterpret_cast<const bf16x8*>(dop + 32 * ks);
-      dl += dot8(dof[ks], *reinterpret_cast<const bf16x8*>(op + 32 * ks));
-    }
-  }
-  dl += __shfl_xor(dl, 16, 64);
-  dl += __shfl_xor(dl, 32, 64);
-  // rows beyond S: lse = +1e30 makes every probability (and with it ds) exactly 0
-  const float lse2 = qok ? a.lse[((long)b * a.NH + h) * a.S + q] * LOG2E : 1.0e30f;
-
-  f32x4 dq[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // the next key tile travels global -> registers while the current one is multiplied (first needed at the top of the
-  // next iteration)
-  bf16x8 kreg[2], vreg[2];
-  float mreg = NEG_BIG;
-  auto fetch = [&](int t0) {
-    tile_load_kv(kreg, ksrc, a.P, T, ldt, t0);
-    tile_load_kv(vreg, vsrc, a.P, T, ldt, t0);
-    if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
-  };
-  fetch(0);
-  for (int t0 = 0; t0 < T; t0 += KT) {
-    __syncthreads();
-    tile_store(Ks, kreg);
-    tile_store(Vs, vreg);
-    if (threadIdx.x < KT) Ms[threadIdx.x] = (t0 + (int)threadIdx.x < T) ? mreg * LOG2E : NEG_BIG;
-    __syncthreads();
-    if (t0 + KT < T) fetch(t0 + KT);
-    if (!wave_live) continue;  // (wave-uniform; dq stays zero: the column sums below read it through qok)
-    const int nsub = min(4, (T - t0 + 15) >> 4);
-    const uint32_t cterm0 = (uint32_t)(t0 + 4 * g) * ATTN_DROP_C2;
-    f32x4 ds[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      ds[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (j < nsub) {
-        f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          s = MFMA_BF(row_frag(Ks, j, ks, lq, g), qf[ks], s);
-          dp = MFMA_BF(row_frag(Vs, j, ks, lq, g), dof[ks], dp);
-        }
-        const f32x4 mv = *reinterpret_cast<const f32x4*>(Ms + 16 * j + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(s[r] * sc2 + mv[r] - lse2);
-          float dpe = dp[r];
-          if (a.p_drop > 0.f)
-            dpe = attn_dropout_keep2(rowh, cterm0 + (uint32_t)(16 * j + r) * ATTN_DROP_C2, a.drop_thr) ? dpe * inv_keep : 0.f;
-          ds[j][r] = p * (dpe - dl) * a.scale;
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (2 * u < nsub) {
-        const bf16x8 dsb = pack8(ds[2 * u], ds[2 * u + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[dt] = MFMA_BF(tr_frag(Ks, u, dt, lane), dsb, dq[dt]);
-      }
-    }
-  }
-  if (qok) {
-    __bf16* dqp = a.dqkv + (sn.tok0 + q) * 3 * a.H + h * D + 4 * g;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      *reinterpret_cast<bf16x4*>(dqp + 16 * dt) = bf16x4{(__bf16)dq[dt].x, (__bf16)dq[dt].y, (__bf16)dq[dt].z, (__bf16)dq[dt].w};
-  }
-  // column sums of this block's dQ rows (the query-bias gradient): over the 16 query lanes, then the 4 waves
-  __syncthreads();
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float v = qok ? dq[dt][r] : 0.f;
-      v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-      if (lq == 0) red[wave * 64 + 16 * dt + 4 * g + r] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int nqt = (a.S + 63) / 64;
-    a.partq[((long)b * nqt + qtile) * a.H + h * D + threadIdx.x] =
-        red[threadIdx.x] + red[64 + threadIdx.x] + red[128 + threadIdx.x] + red[192 + threadIdx.x];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// backward, key side: dK, dV for 64 keys of the [prefix ; text] axis per block; loops over query tiles.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bwd_dkv_body(const Args& a, int ktile, unsigned char* Qs, unsigned char* dOs, float* lse_s,
-                                             float* del_s, uint32_t* rh_s, float* red, int* t_eff_slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lk = lane & 15, g = lane >> 4;
-  const int b = slot_sentence(a, blockIdx.z), h = blockIdx.y;
-  const Sent sn = sentence(a, b);
-  const int Sb = sn.n;
-  const int nkt = (a.P + a.S + 63) / 64;  // rows of partkv per sentence (allocation: the padded key count)
-  const int T = a.cu ? a.P + Sb : effective_keys(a.addmask + (long)b * (a.P + a.S), a.P, a.S, t_eff_slot);  // keys >= T: trailing padding, dK = dV = 0
-  const int Tf = a.cu ? T : a.P + a.S;  // (packed rows: keys beyond the sentence do not exist)
-  const int key = ktile * 64 + wave * 16 + lk;
-  if (ktile * 64 >= T) {  // (block-uniform) a key tile of trailing padding only: exact zeros, no query loop
-    if (key < Tf) {
-      __bf16* dkrow = a.dqkv + (sn.tok0 + (key - a.P)) * 3 * a.H + a.H + h * D + 4 * g;
-      const bf16x4 z = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *reinterpret_cast<bf16x4*>(dkrow + 16 * dt) = z;
-        *reinterpret_cast<bf16x4*>(dkrow + a.H + 16 * dt) = z;
-      }
-    }
-    if (threadIdx.x < 128)
-      a.partkv[((long)b * nkt + ktile) * 2 * a.H + (threadIdx.x >> 6) * a.H + h * D + (threadIdx.x & 63)] = 0.f;
-    return;
-  }
-  const bool kok = key < T;
-  const bool wave_live = (int)(ktile * 64 + wave * 16) < T;
-  const int keyc = min(key, T - 1);
-  const float inv_keep = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
-  const float mval2 = kok ? mask_at(a, b, Tf, key) * LOG2E : NEG_BIG;  // keys beyond T: probability exactly 0
-  const float sc2 = a.scale * LOG2E;
-  const uint32_t cterm = (uint32_t)key * ATTN_DROP_C2;
-
-  bf16x8 kf[2], vf[2];
-  {
-    KvSrc ksrc, vsrc;
-    ksrc.pre = a.pk + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-    vsrc.pre = a.pv + ((long)b * a.P * a.NH + (long)h * a.P) * D;
-    ksrc.txt = a.qkv + sn.tok0 * 3 * a.H + a.H + h * D;
-    vsrc.txt = ksrc.txt + a.H;
-    const __bf16* krow = kv_row_ptr(ksrc, keyc, a.P, 3 * a.H) + 8 * g;
-    const __bf16* vrow = kv_row_ptr(vsrc, keyc, a.P, 3 * a.H) + 8 * g;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      kf[ks] = *reinterpret_cast<const bf16x8*>(krow + 32 * ks);
-      vf[ks] = *reinterpret_cast<const bf16x8*>(vrow + 32 * ks);
-    }
-  }
-  f32x4 dk[4], dv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dk[i] = dv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int c8 = threadIdx.x & 7, r0 = threadIdx.x >> 3;  // staging: rows r0, r0 + 32; 16-byte chunk c8
-  const __bf16* qsrc = a.qkv + sn.tok0 * 3 * a.H + h * D + c8 * 8;
-  const __bf16* dosrc = a.dctx + sn.tok0 * a.H + h * D + c8 * 8;
-  const __bf16* osrc = a.ctx + sn.tok0 * a.H + h * D + c8 * 8;
-  const uint32_t row_base = (uint32_t)((b * a.NH + h) * a.S);
-
-  // the next query tile (Q, dO, O rows, lse) is fetched while the current one is multiplied
-  bf16x8 qr[2], orr[2], ofw[2];
-  float lreg = 1.0e30f;
-  auto fetch = [&](int q0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int qq = min(q0 + r0 + 32 * i, Sb - 1);
-      qr[i] = *reinterpret_cast<const bf16x8*>(qsrc + (long)qq * 3 * a.H);
-      orr[i] = *reinterpret_cast<const bf16x8*>(dosrc + (long)qq * a.H);
-      ofw[i] = *reinterpret_cast<const bf16x8*>(osrc + (long)qq * a.H);
-    }
-    if (threadIdx.x < KT) lreg = a.lse[((long)b * a.NH + h) * a.S + min(q0 + (int)threadIdx.x, Sb - 1)] * LOG2E;
-  };
-  const int Sq = (a.zero_tail && !a.cu) ? min(Sb, T - a.P) : Sb;  // (queries behind it have dO = 0: they add exactly nothing)
-  if (Sq > 0) fetch(0);
-  for (int q0 = 0; q0 < Sq; q0 += KT) {
-    float dsum[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) dsum[i] = dot8(orr[i], ofw[i]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {  // the 8 threads of a row are 8 consecutive lanes
-      dsum[i] += __shfl_xor(dsum[i], 1, 64);
-      dsum[i] += __shfl_xor(dsum[i], 2, 64);
-      dsum[i] += __shfl_xor(dsum[i], 4, 64);
-    }
-    const float lcur = lreg;
-    __syncthreads();
-    tile_store(Qs, qr);
-    tile_store(dOs, orr);
-    if (c8 == 0) {
-      del_s[r0] = dsum[0];
-      del_s[r0 + 32] = dsum[1];
-    }
-    if (threadIdx.x < KT) {
-      const int qq = q0 + threadIdx.x;
-      lse_s[threadIdx.x] = qq < Sb ? lcur : 1.0e30f;
-      rh_s[threadIdx.x] = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), row_base + (uint32_t)qq);
-    }
-    __syncthreads();
-    if (q0 + KT < Sq) fetch(q0 + KT);
-    // a wave whose 16 keys all lie beyond T (last key tile) only takes part in the staging and the barriers
-    const int nsub = wave_live ? min(4, (Sq - q0 + 15) >> 4) : 0;
-    f32x4 pd[4], ds[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      pd[i] = ds[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (i < nsub) {
-        f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          s = MFMA_BF(row_frag(Qs, i, ks, lk, g), kf[ks], s);     // S[q][key]: lane = key, rows q = 16i + 4g + r
-          dp = MFMA_BF(row_frag(dOs, i, ks, lk, g), vf[ks], dp);  // dP[q][key]
-        }
-        const f32x4 lse4 = *reinterpret_cast<const f32x4*>(lse_s + 16 * i + 4 * g);
-        const f32x4 del4 = *reinterpret_cast<const f32x4*>(del_s + 16 * i + 4 * g);
-        const uint4 rh4 = *reinterpret_cast<const uint4*>(rh_s + 16 * i + 4 * g);
-        const uint32_t rh[4] = {rh4.x, rh4.y, rh4.z, rh4.w};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(s[r] * sc2 + mval2 - lse4[r]);
-          float dpe = dp[r], pdr = p;
-          if (a.p_drop > 0.f) {
-            const bool keep = attn_dropout_keep2(rh[r], cterm, a.drop_thr);
-            pdr = keep ? p * inv_keep : 0.f;
-            dpe = keep ? dpe * inv_keep : 0.f;
-          }
-          pd[i][r] = pdr;
-          ds[i][r] = p * (dpe - del4[r]) * a.scale;
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (2 * u < nsub) {
-        const bf16x8 pb = pack8(pd[2 * u], pd[2 * u + 1]), dsb = pack8(ds[2 * u], ds[2 * u + 1]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          dv[dt] = MFMA_BF(tr_frag(dOs, u, dt, lane), pb, dv[dt]);  // dV^T[d][key] += dO^T[d][q] Pd[q][key]
-          dk[dt] = MFMA_BF(tr_frag(Qs, u, dt, lane), dsb, dk[dt]);  // dK^T[d][key] += Q^T[d][q] dS[q][key]
-        }
-      }
-    }
-  }
-  const bool is_text = kok && key >= a.P;
-  if (!kok && key < Tf) {  // trailing padding inside a partially valid tile
-    __bf16* dkrow = a.dqkv + (sn.tok0 + (key - a.P)) * 3 * a.H + a.H + h * D + 4 * g;
-    const bf16x4 z = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      *reinterpret_cast<bf16x4*>(dkrow + 16 * dt) = z;
-      *reinterpret_cast<bf16x4*>(dkrow + a.H + 16 * dt) = z;
-    }
-  }
-  if (kok) {
-    if (key < a.P) {
-      float* dkrow = a.dpk + ((long)b * a.P * a.NH + (long)h * a.P + key) * D + 4 * g;
-      float* dvrow = a.dpv + ((long)b * a.P * a.NH + (long)h * a.P + key) * D + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *reinterpret_cast<f32x4*>(dkrow + 16 * dt) = dk[dt];
-        *reinterpret_cast<f32x4*>(dvrow + 16 * dt) = dv[dt];
-      }
-    } else {
-      __bf16* dkrow = a.dqkv + (sn.tok0 + (key - a.P)) * 3 * a.H + a.H + h * D + 4 * g;
-      __bf16* dvrow = dkrow + a.H;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *reinterpret_cast<bf16x4*>(dkrow + 16 * dt) = bf16x4{(__bf16)dk[dt].x, (__bf16)dk[dt].y, (__bf16)dk[dt].z, (__bf16)dk[dt].w};
-        *reinterpret_cast<bf16x4*>(dvrow + 16 * dt) = bf16x4{(__bf16)dv[dt].x, (__bf16)dv[dt].y, (__bf16)dv[dt].z, (__bf16)dv[dt].w};
-      }
-    }
-  }
-  // column sums over this block's TEXT keys (the key / value bias gradients)
-  __syncthreads();
-#pragma unroll
-  for (int which = 0; which < 2; ++which)
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = is_text ? (which ? dv[dt][r] : dk[dt][r]) : 0.f;
-        v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-        if (lk == 0) red[(which * 4 + wave) * 64 + 16 * dt + 4 * g + r] = v;
-      }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int which = threadIdx.x >> 6, d = threadIdx.x & 63;
-    const float* rr = red + which * 256 + d;
-    a.partkv[((long)b * nkt + ktile) * 2 * a.H + which * a.H + h * D + d] = rr[0] + rr[64] + rr[128] + rr[192];
-  }
-}
-
-// One launch for the whole attention backward: blocks [0, nq) of x are query tiles (dQ), the rest key tiles (dK, dV).
 __global__ __launch_bounds__(256, 2) void attn_bf16_bwd_kernel(Args a, int nq) {
   __shared__ __attribute__((aligned(16))) unsigned char tile0[KT * 128];
   __shared__ __attribute__((aligned(16))) unsigned char tile1[KT * 128];
   __shared__ __attribute__((aligned(16))) float small[3 * KT];
   __shared__ __attribute__((aligned(16))) float red[8 * 64];
   __shared__ int t_eff_slot;
-  if (a.cu && (int)blockIdx.z == a.B) {  // (block-uniform) zero dQ | dK | dV of the rows that pad the packed image
-    const int r0 = a.cu[a.B], h = blockIdx.y;
-    const bf16x8 z = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-    for (int r = blockIdx.x * 32 + (threadIdx.x >> 3); r < a.pad_rows; r += gridDim.x * 32)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        *reinterpret_cast<bf16x8*>(a.dqkv + (long)(r0 + r) * 3 * a.H + c * a.H + h * D + (threadIdx.x & 7) * 8) = z;
-    return;
-  }
-  if ((int)blockIdx.x < nq) {
-    bwd_dq_body(a, blockIdx.x, tile0, tile1, small, red, &t_eff_slot);
-  } else {
-    bwd_dkv_body(a, blockIdx.x - nq, tile0, tile1, small, small + KT, reinterpret_cast<uint32_t*>(small + 2 * KT), red, &t_eff_slot);
-  }
+  attn_bwd_body<Bf16>(a, nq, tile0, tile1, small, red, &t_eff_slot);
 }
 
 static int check(const Args& a) {

@@ -71,7 +71,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile, int pl, int
 
 // The split-product arithmetic: a tile is three [64][64] bf16 plane images, split while it is staged; the operand of a row is its
 // 64 values as planes, 8 consecutive d per lane at 32 ks + 8 g .. + 7 (ks = 0, 1); every product is six bf16 MFMA products.
-struct Split3 {
+struct Split3 : F32Io {
   typedef unsigned char Lds;
   typedef unsigned char* RowTile;  // (one image serves the row reads and the transposing reads)
   typedef unsigned char* ColTile;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_bwd_kernel(AttnArgs a, int n
   __shared__ __attribute__((aligned(16))) unsigned char tile1[TILE_B];
   __shared__ __attribute__((aligned(16))) float small[3 * KT];
   __shared__ int t_eff_slot;
-  attn_bwd_body<Split3>(a, nq, tile0, tile1, small, &t_eff_slot);
+  attn_bwd_body<Split3>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot);
 }
 
 }  // namespace as3

@@ -1,11 +1,16 @@
-// The fp32 prefix-attention kernels, ONCE: forward, the probabilities on request (the forward without V), backward query side (dQ),
+// The prefix-attention kernels, ONCE: forward, the probabilities on request (the forward without V), backward query side (dQ),
 // backward key side (dK, dV) and the backward dispatch, as __device__ __forceinline__ templates over an ARITHMETIC -- how a [64][64]
-// tile lies in LDS and how the products over it are formed.  csrc/attention.hip (fp32 MFMA pipe) and csrc/attention_f32s.hip (split bf16 products) each provide one and the thin
-// __global__ kernels (their LDS, their __launch_bounds__) that call the bodies below.  Everything else -- launch geometry, the
-// zero-fill slice of a packed launch, key order, masking, the log2-domain online softmax, the dropout hash, the register -> LDS
-// double buffering with its two barriers, the stores -- is here and is therefore the same in both.
+// tile lies in LDS and how the products over it are formed.  csrc/attention.hip (fp32 MFMA pipe), csrc/attention_f32s.hip (split bf16
+// products) and csrc/attention_bf16.hip (bf16 operands, fp32 accumulation) each provide one and the thin __global__ kernels (their
+// LDS, their __launch_bounds__) that call the bodies below.  Everything else -- launch geometry, the zero-fill slice of a packed
+// launch, key order, masking, the log2-domain online softmax, the dropout hash, the register -> LDS double buffering with its two
+// barriers, the stores -- is here and is therefore the same in all three.
 //
 // An arithmetic A provides (all static, __device__ __forceinline__):
+//   Elem, Args                element type of Q | K | V, the context and their gradients in global memory (float / __bf16) and the
+//                             argument block of its kernels (AttnArgs / ab::Args, attention_args.h, with their store_ctx / store_dqkv)
+//   FWD_FETCH_AHEAD           whether the forward fetches key tile t + 1 behind the barrier that publishes tile t (the backward always
+//                             does); XCD_GROUP: whether its blocks are regrouped by XCD (xcd_group)
 //   Lds                       element type of its LDS tiles; RowTile / ColTile: views of one tile that is read as row fragments only /
 //                             as row fragments AND columns (constructible from an Lds*)
 //   stage_col()               first column of the chunk this thread stages; operand_col(g): first column a lane of group g holds
@@ -16,19 +21,42 @@
 //                             load_operand(p), load_operand_dot(p, o, dot) (also adds this lane's share of rowsum(p . o))
 //   rows_dot(tile, blk, x, lr, g)        [4 rows of 16-row block blk per lane group] . x over d = 64, as the MFMA result layout;
 //                             rows_dot2(tile0, x0, r0, tile1, x1, r1, blk, lr, g): two of them, interleaved as the arithmetic likes it
-//   FOLD                      how many 16-row blocks of probabilities / dS it gathers before it multiplies them on (1: fp32 pipe, 4, the whole tile: split)
+//   FOLD                      how many 16-row blocks of probabilities / dS it gathers before it multiplies them on (1: fp32 pipe, 4, the
+//                             whole tile: split and bf16)
 //   cols_acc(tile, j0, p, nsub, lane, acc)   acc[dt] += tile^T(d, rows) . p over the blocks j0 .. j0 + FOLD - 1 that lie below nsub; p [FOLD]
 //                             in the layout of rows_dot; cols_acc2(tile0, p0, acc0, tile1, p1, acc1, j0, nsub, lane): two of them
 //   tile_without_gradient(dO, qok, Ms)   dQ side only: may report that the whole query tile has dO == 0 (see there)
+//   dq_tail_exit(a)           dQ side only: whether a query tile of trailing padding writes zeros and leaves (AttnArgs::zero_tail)
+//   store_delta(a, i, v)      dQ side: delta[i] = rowsum(dO . O) of a query, where the argument block has a delta
+//   dq_sums(a, qtile, b, h, dq, qok, red), dkv_sums(a, ktile, b, h, dk, dv, is_text, red)   behind the stores of a block: the column sums
+//                             of its dQ / of its dK | dV over text keys, where the argument block takes them; dq_sums_zero / dkv_sums_zero
+//                             (a, tile, b, h): the same for a block that leaves before its loop
 // The order of operations inside a product is the arithmetic's own (which blocks it folds together, plane pairs smallest first,
-// MFMA operand order); the bodies never ask which arithmetic they run.
+// MFMA operand order), and a hook that does not apply to an arithmetic is an empty inline; the bodies never ask which arithmetic
+// they run.
 #pragma once
 #include "attention_args.h"
 
 namespace mtvaf {
 
+// What the two fp32 arithmetics have in common: fp32 tensors, AttnArgs, fetch-ahead and XCD grouping everywhere, delta and the
+// zero_tail exit on the dQ side, no column sums.
+struct F32Io {
+  typedef float Elem;
+  typedef AttnArgs Args;
+  static constexpr bool FWD_FETCH_AHEAD = true;
+  static constexpr bool XCD_GROUP = true;
+  static __device__ __forceinline__ bool dq_tail_exit(const AttnArgs& a) { return a.zero_tail && !a.cu; }
+  static __device__ __forceinline__ void store_delta(const AttnArgs& a, long i, float v) { a.delta[i] = v; }
+  static __device__ __forceinline__ void dq_sums_zero(const AttnArgs&, int, int, int) {}
+  static __device__ __forceinline__ void dq_sums(const AttnArgs&, int, int, int, const f32x4 (&)[4], bool, float*) {}
+  static __device__ __forceinline__ void dkv_sums_zero(const AttnArgs&, int, int, int) {}
+  static __device__ __forceinline__ void dkv_sums(const AttnArgs&, int, int, int, const f32x4 (&)[4], const f32x4 (&)[4], bool, float*) {}
+};
+
 // sources of the K and V tiles of (sentence b, head h), + the caller's column offset
-__device__ __forceinline__ void kv_sources(const AttnArgs& a, const Sent& sn, int b, int h, int col, KvSrc& k, KvSrc& v) {
+template <class Args, class T>
+__device__ __forceinline__ void kv_sources(const Args& a, const Sent& sn, int b, int h, int col, KvSrcT<T>& k, KvSrcT<T>& v) {
   k.pre = a.pk + ((long)b * a.P * a.NH + (long)h * a.P) * D + col;
   v.pre = a.pv + ((long)b * a.P * a.NH + (long)h * a.P) * D + col;
   k.txt = a.qkv + sn.tok0 * 3 * a.H + a.H + h * D + col;
@@ -40,12 +68,12 @@ __device__ __forceinline__ void kv_sources(const AttnArgs& a, const Sent& sn, in
 // Ms [KT]: additive mask * log2(e) of the tile's keys (-1e30 beyond T)
 // ---------------------------------------------------------------------------------------------
 template <class A>
-__device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::RowTile Ks, typename A::ColTile Vs, float* Ms,
+__device__ __forceinline__ void attn_fwd_body(const typename A::Args& a, typename A::RowTile Ks, typename A::ColTile Vs, float* Ms,
                                               int* t_eff_slot) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lq = lane & 15, g = lane >> 4;
   int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
+  if constexpr (A::XCD_GROUP) xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
   const int q = bx * 64 + wave * 16 + lq;
   if (a.cu && b == a.B) {  // (block-uniform) the rows that pad the packed image: zeros (0 x NaN of an unwritten row would poison dW)
     const int r0 = a.cu[a.B];
@@ -68,7 +96,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::Row
   const uint32_t rowh = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), (uint32_t)((b * a.NH + h) * a.S + q));
   const float sc2 = a.scale * LOG2E;  // scores are kept in the log2 domain: one v_exp_f32 per probability
 
-  KvSrc ksrc, vsrc;
+  KvSrcT<typename A::Elem> ksrc, vsrc;
   kv_sources(a, sn, b, h, A::stage_col(), ksrc, vsrc);
   const int ldt = 3 * a.H;
 
@@ -79,7 +107,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::Row
   float m_run = NEG_BIG, l_run = 0.f;
 
   // The next key tile travels global -> registers while the current one is being multiplied: its loads are issued
-  // right behind the barrier that publishes the current tile and are first needed at the top of the next iteration.
+  // right behind the barrier that publishes the current tile and are first needed at the top of the next iteration
+  // (A::FWD_FETCH_AHEAD; an arithmetic without it loads a tile at the top of its own iteration).
   typename A::Stage kst, vst;
   float mreg = NEG_BIG;
   auto fetch = [&](int t0) {
@@ -87,14 +116,17 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::Row
     A::fetch_kv(vst, vsrc, a.P, T, ldt, t0);
     if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
   };
-  fetch(0);
+  if constexpr (A::FWD_FETCH_AHEAD) fetch(0);
   for (int t0 = 0; t0 < T; t0 += KT) {
+    if constexpr (!A::FWD_FETCH_AHEAD) fetch(t0);
     __syncthreads();
     A::store(Ks, kst);
     A::store(Vs, vst);
     if (threadIdx.x < KT) Ms[threadIdx.x] = (t0 + (int)threadIdx.x < T) ? mreg * LOG2E : NEG_BIG;
     __syncthreads();
-    if (t0 + KT < T) fetch(t0 + KT);
+    if constexpr (A::FWD_FETCH_AHEAD) {
+      if (t0 + KT < T) fetch(t0 + KT);
+    }
     if (!wave_live) continue;  // (wave-uniform) no live query in this wave: it only stages and synchronises
     const int nsub = min(4, (T - t0 + 15) >> 4);  // 16-key blocks of this tile that hold real keys
     f32x4 s[4];
@@ -154,12 +186,12 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, typename A::Row
 constexpr int LDP = 68;  // row stride (floats) of the transposing buffer: 16-byte aligned rows for the b128 writes
 
 template <class A>
-__device__ __forceinline__ void attn_probs_body(const AttnArgs& a, const ProbsOut& o, typename A::RowTile Ks, float* Ps, float* Ms,
+__device__ __forceinline__ void attn_probs_body(const typename A::Args& a, const ProbsOut& o, typename A::RowTile Ks, float* Ps, float* Ms,
                                                 int* t_eff_slot) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lq = lane & 15, g = lane >> 4;
   int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
+  if constexpr (A::XCD_GROUP) xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
   const Sent sn = sentence(a, b);
   const int S = a.S, Tf = a.P + a.S;
   // keys behind the last unmasked text position: exact zeros in the reference too (exp(-10000 - max) underflows), stored below
@@ -170,7 +202,7 @@ __device__ __forceinline__ void attn_probs_body(const AttnArgs& a, const ProbsOu
   const float sc2 = a.scale * LOG2E;
   const bool zrow = o.zero_masked_queries && a.addmask[(long)b * Tf + a.P + min(q, S - 1)] <= -5000.f;
 
-  KvSrc ksrc, vsrc;
+  KvSrcT<typename A::Elem> ksrc, vsrc;
   kv_sources(a, sn, b, h, A::stage_col(), ksrc, vsrc);
   const int ldt = 3 * a.H;
   const typename A::Operand qf = A::load_operand(a.qkv + (sn.tok0 + min(q, S - 1)) * 3 * a.H + h * D + A::operand_col(g));
@@ -267,27 +299,31 @@ __device__ __forceinline__ void attn_probs_body(const AttnArgs& a, const ProbsOu
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward, query side: dQ (and delta = rowsum(dO.O)) for 64 queries per block; loop over key tiles as in the forward
+// backward, query side: dQ for 64 queries per block; loop over key tiles as in the forward.  What leaves the block beside dQ is the
+// arithmetic's (its output hooks: delta = rowsum(dO.O), or the column sums of dQ through red)
 // ---------------------------------------------------------------------------------------------
 template <class A>
-__device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, int b, int h, typename A::ColTile Ks, typename A::RowTile Vs,
-                                                 float* Ms, int* t_eff_slot) {
+__device__ __forceinline__ void attn_bwd_dq_body(const typename A::Args& a, int qtile, int b, int h, typename A::ColTile Ks,
+                                                 typename A::RowTile Vs, float* Ms, float* red, int* t_eff_slot) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lq = lane & 15, g = lane >> 4;
   const int q = qtile * 64 + wave * 16 + lq;
   const Sent sn = sentence(a, b);
   const int Sb = sn.n;
-  if (qtile * 64 >= Sb) return;  // (block-uniform)
+  if (qtile * 64 >= Sb) {  // (block-uniform) a query tile beyond the sentence
+    A::dq_sums_zero(a, qtile, b, h);
+    return;
+  }
   const int Tf = a.P + a.S;
   const int T = a.cu ? a.P + Sb : effective_keys(a.addmask + (long)b * Tf, a.P, a.S, t_eff_slot);
   const bool qok = q < Sb;
   const bool wave_live = __builtin_amdgcn_readfirstlane(q - lq) < Sb;
-  if (a.zero_tail && !a.cu && qtile * 64 >= T - a.P) {  // (block-uniform) a tile of trailing padding: dQ = 0, nothing to read
+  if (A::dq_tail_exit(a) && qtile * 64 >= T - a.P) {  // (block-uniform) a tile of trailing padding: dQ = 0, nothing to read
     if (qok) {
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) store_dqkv(a, sn.tok0 + q, h * D + 16 * dt + 4 * g, z);
-      if (g == 0) a.delta[((long)b * a.NH + h) * a.S + q] = 0.f;
+      if (g == 0) A::store_delta(a, ((long)b * a.NH + h) * a.S + q, 0.f);
     }
     return;
   }
@@ -295,7 +331,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, i
   const uint32_t rowh = attn_dropout_rowhash(attn_epoch_key(a.drop_key, a.epoch), (uint32_t)((b * a.NH + h) * a.S + q));
   const float sc2 = a.scale * LOG2E;
 
-  KvSrc ksrc, vsrc;
+  KvSrcT<typename A::Elem> ksrc, vsrc;
   kv_sources(a, sn, b, h, A::stage_col(), ksrc, vsrc);
   const int ldt = 3 * a.H;
 
@@ -308,7 +344,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, i
   dl += __shfl_xor(dl, 32, 64);
   // rows beyond S: lse = +1e30 makes every probability (and with it ds) exactly 0
   const float lse2 = qok ? a.lse[((long)b * a.NH + h) * a.S + q] * LOG2E : 1.0e30f;
-  if (qok && g == 0) a.delta[((long)b * a.NH + h) * a.S + q] = dl;
+  if (qok && g == 0) A::store_delta(a, ((long)b * a.NH + h) * a.S + q, dl);
 
   f32x4 dq[4];
 #pragma unroll
@@ -336,7 +372,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, i
     if (threadIdx.x < KT) Ms[threadIdx.x] = (t0 + (int)threadIdx.x < T) ? mreg * LOG2E : NEG_BIG;
     __syncthreads();
     if (t0 + KT < T) fetch(t0 + KT);
-    if (!wave_live) continue;  // (wave-uniform; as in the forward)
+    if (!wave_live) continue;  // (wave-uniform; as in the forward.  dq stays zero: dq_sums reads it through qok)
     const int nsub = min(4, (T - t0 + 15) >> 4);
     const uint32_t cterm0 = (uint32_t)(t0 + 4 * g) * ATTN_DROP_C2;
 #pragma unroll
@@ -367,6 +403,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, i
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store_dqkv(a, sn.tok0 + q, h * D + 16 * dt + 4 * g, dq[dt]);
   }
+  A::dq_sums(a, qtile, b, h, dq, qok, red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -374,11 +411,12 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnArgs& a, int qtile, i
 // flows on to the prompt generator); loop over query tiles.
 // lse_s [KT] = lse * log2(e) (+1e30 for rows beyond S); del_s [KT] = rowsum(dO.O), computed here from the staged dO tile and the
 // matching O rows so that this side does not depend on the query side (both run in one launch); rh_s [KT] = dropout row hashes of
-// the tile's queries.
+// the tile's queries.  Output hook: the column sums of dK | dV over the block's text keys (through red).
 // ---------------------------------------------------------------------------------------------
 template <class A>
-__device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, int ktile, int b, int h, typename A::ColTile Qs, typename A::ColTile dOs,
-                                                  float* lse_s, float* del_s, uint32_t* rh_s, int* t_eff_slot) {
+__device__ __forceinline__ void attn_bwd_dkv_body(const typename A::Args& a, int ktile, int b, int h, typename A::ColTile Qs,
+                                                  typename A::ColTile dOs, float* lse_s, float* del_s, uint32_t* rh_s, float* red,
+                                                  int* t_eff_slot) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lk = lane & 15, g = lane >> 4;
   const Sent sn = sentence(a, b);
@@ -395,6 +433,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, int ktile, 
         store_dqkv(a, sn.tok0 + (key - a.P), 2 * a.H + h * D + 16 * dt + 4 * g, z);
       }
     }
+    A::dkv_sums_zero(a, ktile, b, h);
     return;
   }
   const bool kok = key < T;
@@ -405,7 +444,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, int ktile, 
   const float sc2 = a.scale * LOG2E;
   const uint32_t cterm = (uint32_t)key * ATTN_DROP_C2;
 
-  KvSrc ksrc, vsrc;
+  KvSrcT<typename A::Elem> ksrc, vsrc;
   kv_sources(a, sn, b, h, A::operand_col(g), ksrc, vsrc);
   const typename A::Operand kf = A::load_operand(kv_row_ptr(ksrc, keyc, a.P, 3 * a.H));
   const typename A::Operand vf = A::load_operand(kv_row_ptr(vsrc, keyc, a.P, 3 * a.H));
@@ -413,9 +452,9 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, int ktile, 
 #pragma unroll
   for (int i = 0; i < 4; ++i) dk[i] = dv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const float* qsrc = a.qkv + sn.tok0 * 3 * a.H + h * D + A::stage_col();
-  const float* dosrc = a.dctx + sn.tok0 * a.H + h * D + A::stage_col();
-  const float* osrc = a.ctx + sn.tok0 * a.H + h * D + A::stage_col();
+  const typename A::Elem* qsrc = a.qkv + sn.tok0 * 3 * a.H + h * D + A::stage_col();
+  const typename A::Elem* dosrc = a.dctx + sn.tok0 * a.H + h * D + A::stage_col();
+  const typename A::Elem* osrc = a.ctx + sn.tok0 * a.H + h * D + A::stage_col();
   const uint32_t row_base = (uint32_t)((b * a.NH + h) * a.S);
 
   // the next query tile (Q, dO, O rows, lse) is fetched while the current one is multiplied
@@ -502,14 +541,16 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs& a, int ktile, 
       }
     }
   }
+  A::dkv_sums(a, ktile, b, h, dk, dv, kok && key >= a.P, red);
 }
 
 // One launch for the whole attention backward: blocks [0, nq) of x are query tiles (dQ), the rest key tiles (dK, dV).  The two
 // sides are independent (the key side recomputes delta), so they share the machine and need neither atomics nor a second stream.
-// tile0, tile1: two LDS tiles of the arithmetic; small [3 KT] floats.
+// tile0, tile1: two LDS tiles of the arithmetic; small [3 KT] floats; red: what the arithmetic's column-sum hooks reduce through
+// ([8 * 64] floats, or NULL where they are empty).
 template <class A>
-__device__ __forceinline__ void attn_bwd_body(const AttnArgs& a, int nq, typename A::Lds* tile0, typename A::Lds* tile1, float* small,
-                                              int* t_eff_slot) {
+__device__ __forceinline__ void attn_bwd_body(const typename A::Args& a, int nq, typename A::Lds* tile0, typename A::Lds* tile1,
+                                              float* small, float* red, int* t_eff_slot) {
   if (a.cu && (int)blockIdx.z == a.B) {  // (block-uniform) zero dQ | dK | dV of the rows that pad the packed image
     const int r0 = a.cu[a.B], h = blockIdx.y;
     for (int r = blockIdx.x * 16 + (threadIdx.x >> 4); r < a.pad_rows; r += gridDim.x * 16)
@@ -519,13 +560,13 @@ __device__ __forceinline__ void attn_bwd_body(const AttnArgs& a, int nq, typenam
     return;
   }
   int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
+  if constexpr (A::XCD_GROUP) xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
   b = slot_sentence(a, b);
   if (bx < nq) {
-    attn_bwd_dq_body<A>(a, bx, b, h, typename A::ColTile{tile0}, typename A::RowTile{tile1}, small, t_eff_slot);
+    attn_bwd_dq_body<A>(a, bx, b, h, typename A::ColTile{tile0}, typename A::RowTile{tile1}, small, red, t_eff_slot);
   } else {
     attn_bwd_dkv_body<A>(a, bx - nq, b, h, typename A::ColTile{tile0}, typename A::ColTile{tile1}, small, small + KT,
-                         reinterpret_cast<uint32_t*>(small + 2 * KT), t_eff_slot);
+                         reinterpret_cast<uint32_t*>(small + 2 * KT), red, t_eff_slot);
   }
 }
 
