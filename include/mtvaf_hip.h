@@ -237,6 +237,25 @@ int mtvaf_crf_viterbi(const float* emissions, const uint8_t* mask, const float* 
                       const float* trans, int32_t* tags_out, int32_t* lens_out, int B, int S, int C,
                       mtvaf_stream_t stream);
 
+/* per-sentence likelihoods and tag marginals: same shapes, error codes and workspace (mtvaf_crf_workspace_bytes) as
+ * the entry points above; no host sync, no allocation, safe under stream capture.
+ *   llh_fwd   llh[b] = score(gold_b) - logZ_b (torchcrf's sign); leaves in the workspace what llh_bwd reads.
+ *   llh_bwd   grad_llh [B] = d(total)/d(llh[b]): demissions[b,t,:] = grad_llh[b] (onehot(gold) - marginal) at unmasked
+ *             steps, exact zeros at masked ones; dstart/dend/dtrans = sum_b grad_llh[b] d(llh[b])/d(.), overwritten
+ *             or accumulated.
+ *   marginals marg[b,t,j] = p(y_t = j | emissions_b) at unmasked steps, exact zeros at masked ones (holes included);
+ *             takes no tags; logz [B] may be NULL.  Overwrites the workspace of a preceding forward. */
+int mtvaf_crf_llh_fwd(const float* emissions, const int64_t* tags, const uint8_t* mask, const float* start,
+                      const float* end, const float* trans, float* llh, int B, int S, int C, void* workspace,
+                      size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_llh_bwd(const float* grad_llh, const float* emissions, const int64_t* tags, const uint8_t* mask,
+                      const float* start, const float* end, const float* trans, float* demissions, float* dstart,
+                      float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
+                      size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_marginals(const float* emissions, const uint8_t* mask, const float* start, const float* end,
+                        const float* trans, float* marg, float* logz, int B, int S, int C, void* workspace,
+                        size_t workspace_bytes, mtvaf_stream_t stream);
+
 /* ---- visual prompt generator + VAO loss ----------------------------------------------------------------------
  * replaces TVNetSAModel2.get_visual_prompt's split-mean / gates / gated sums / cat / reshape
  * (bert_model.py:544-545, 566-585) and the KLDiv(batchmean) ANP loss (:549-563).

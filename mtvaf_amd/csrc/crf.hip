@@ -159,7 +159,9 @@ __device__ __forceinline__ unsigned long long mask_word(const uint8_t* mk, int t
   return __ballot((t0 + lane < S) && mk[(t0 + lane < S) ? t0 + lane : 0] != 0);
 }
 
-// forward: alpha_ws[b,t,0:16] = scaled alpha after step t (sum 1 for t >= 1), logZ[b], llh[b] = score(gold) - logZ
+// forward: alpha_ws[b,t,0:16] = scaled alpha after step t (sum 1 for t >= 1), logZ[b], llh[b] = score(gold) - logZ.
+// GOLD = false (tag marginals): no tags are read and no gold-path score is formed; logZ[b] is the only result besides alpha_ws.
+template <bool GOLD>
 __global__ __launch_bounds__(64) void crf_fwd_kernel(const float* __restrict__ em, const int64_t* __restrict__ tags,
                                                     const uint8_t* __restrict__ mask, const float* __restrict__ start,
                                                     const float* __restrict__ end, const float* __restrict__ trans,
@@ -174,7 +176,8 @@ __global__ __launch_bounds__(64) void crf_fwd_kernel(const float* __restrict__ e
   uint8_t* mk = reinterpret_cast<uint8_t*>(tg + S);     // [S]
   const int b = blockIdx.x, lane = threadIdx.x;
   crf_stage(em, mask, b, S, S16 + 1, C, xs16, mxs, mk, lane);
-  for (int t = lane; t < S; t += 64) tg[t] = (int)tags[(long)b * S + t];
+  if constexpr (GOLD)
+    for (int t = lane; t < S; t += 64) tg[t] = (int)tags[(long)b * S + t];
   __syncthreads();
   const int j = lane & 15, g4 = lane >> 4, d = rot_dir(lane);
   const bool act = j < C;
@@ -252,18 +255,20 @@ __global__ __launch_bounds__(64) void crf_fwd_kernel(const float* __restrict__ e
     cnt += mk[t] ? 1 : 0;
     if (t >= 1 && mk[t]) {
       lz += __logf(ys16[t * 16]) + mxs[t] + tmax;
-      sc += trans[tg[t - 1] * C + tg[t]] + em[((long)b * S + t) * C + tg[t]];
+      if constexpr (GOLD) sc += trans[tg[t - 1] * C + tg[t]] + em[((long)b * S + t) * C + tg[t]];
     }
   }
   lz = wave_sum(lz);
-  sc = wave_sum(sc);
+  if constexpr (GOLD) {
+    sc = wave_sum(sc);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  }
   if (lane == 0) {
     const float z = c0 + lz + __logf(fin) + em_;
-    sc += start[tg[0]] + em[((long)b * S) * C + tg[0]] + end[tg[cnt - 1]];
+    if constexpr (GOLD) sc += start[tg[0]] + em[((long)b * S) * C + tg[0]] + end[tg[cnt - 1]];
     logz[b] = z;
-    llh[b] = sc - z;
+    if constexpr (GOLD) llh[b] = sc - z;
   }
 }
 
@@ -283,7 +288,14 @@ __global__ void crf_loss_kernel(const float* __restrict__ llh, float* __restrict
 //      row sum per step; the normalised  ui_t = u / (sp_t . u)  and the node marginal  sp_t ui_t  go to LDS;
 //   3. summed edge marginals  sum_t a_{t-1}[i] E[i][j] ui_t[j] = E[i][j] (A^T UI)[i][j]: a [16,S] x [S,16] product on the
 //      matrix cores; d(emissions) leaves LDS in one coalesced pass (gold one-hots subtracted there).
+// GRAD selects what leaves the kernel (crf_wide.h):
+//   CRF_GRAD_MEAN      the batch-mean NLL's gradients, scaled by *gout / B (gout = NULL: 1 / B);
+//   CRF_GRAD_SENTENCE  the gradients of sum_b gout[b] llh[b]: d(emissions) = gout[b] (one-hot - marginal); the partials are
+//                      written as for MEAN and take their weight in crf_param_reduce_kernel;
+//   CRF_MARGINALS      dem = the node marginals themselves.  No tags are read; the gold counts, the ui rows, the edge-marginal
+//                      product (3.) and the partials are skipped.
 // ---------------------------------------------------------------------------------------------
+template <int GRAD>
 __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ em, const int64_t* __restrict__ tags,
                                                     const uint8_t* __restrict__ mask, const float* __restrict__ end,
                                                     const float* __restrict__ trans, const float* __restrict__ alpha_ws,
@@ -304,14 +316,19 @@ __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ e
     crf_f4* dst = reinterpret_cast<crf_f4*>(al16);
     for (int i = lane; i < S16 * 4; i += 64) dst[i] = i < S * 4 ? src[i] : crf_f4{0.f, 0.f, 0.f, 0.f};
   }
-  for (int t = lane; t < S; t += 64) tg[t] = (int)tags[(long)b * S + t];
-  for (int i = lane; i < CMAX * CMAX; i += 64) gold[i] = 0.f;
+  constexpr bool MARG = GRAD == CRF_MARGINALS;
+  if constexpr (!MARG) {
+    for (int t = lane; t < S; t += 64) tg[t] = (int)tags[(long)b * S + t];
+    for (int i = lane; i < CMAX * CMAX; i += 64) gold[i] = 0.f;
+  }
   __syncthreads();
-  for (int t = 1 + lane; t < S; t += 64)
-    if (mk[t]) atomicAdd(&gold[tg[t - 1] * C + tg[t]], 1.f);  // (integer-valued sums: exact, order-independent)
+  if constexpr (!MARG)
+    for (int t = 1 + lane; t < S; t += 64)
+      if (mk[t]) atomicAdd(&gold[tg[t - 1] * C + tg[t]], 1.f);  // (integer-valued sums: exact, order-independent)
   const int j = lane & 15, g4 = lane >> 4, d = rot_dir(lane);
   const bool act = j < C;
-  const float g = (gout ? *gout : 1.f) / B;
+  // (marginal - one-hot) below is d(-llh): the per-sentence weight enters negated
+  const float g = MARG ? 1.f : (GRAD == CRF_GRAD_SENTENCE ? -gout[b] : (gout ? *gout : 1.f) / B);
   float tm = NEG;
   for (int i = 0; i < C; ++i) tm = fmaxf(tm, act ? trans[i * C + j] : NEG);
   const float tmax = row_max16(tm);
@@ -342,15 +359,18 @@ __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ e
     wr[k] = (act && i < C) ? __expf(trans[j * C + i] - tmax) : 0.f;
   }
   int cnt = 0;
-  for (int t = lane; t < S; t += 64) cnt += mk[t] ? 1 : 0;
+  int last_tag = 0;
+  if constexpr (!MARG) {
+    for (int t = lane; t < S; t += 64) cnt += mk[t] ? 1 : 0;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  const int last_tag = (int)tg[cnt - 1];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    last_tag = (int)tg[cnt - 1];
+  }
   const float em_ = row_max16(act ? end[j] : NEG);
   float bt = act ? __expf(end[j] - em_) : 0.f;  // beta of the last position, any positive scale
   __syncthreads();
-  float dend;
-  {
+  float dend = 0.f;
+  if constexpr (!MARG) {
     const float pe = al16[(S - 1) * 16 + j] * bt;
     const float pen = pe * __frcp_rn(row_sum16(pe));
     dend = pen - (j == last_tag ? 1.f : 0.f);
@@ -369,7 +389,7 @@ __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ e
     spp = sr[(t_s - 1) * 16];                                                                                          \
     float ui = 0.f, pm = 0.f;                                                                                          \
     if (on_) crf_bwd_step(bt, x, sp, wr, ui, pm); /* (wave-uniform, scalar) */                                        \
-    sr[t_s * 16] = ui;                                                                                                 \
+    if constexpr (!MARG) sr[t_s * 16] = ui;                                                                            \
     xw[t_s * 16] = pm;                                                                                                 \
   }
     int t = S - 1;
@@ -391,15 +411,25 @@ __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ e
     const float p0 = al16[j] * bt;
     const float p0n = p0 * __frcp_rn(row_sum16(p0));
     xs16[j] = p0n;
-    sp16[j] = 0.f;  // no edge into step 0
-    for (int i = S * 16 + lane; i < S16 * 16; i += 64) sp16[i] = 0.f;  // rows beyond S: no edges either
-    float* pp = partial + (long)b * (2 * C + C * C);
-    if (lane < C) {
-      pp[j] = p0n - (j == (int)tg[0] ? 1.f : 0.f);
-      pp[C + j] = dend;
+    if constexpr (!MARG) {
+      sp16[j] = 0.f;  // no edge into step 0
+      for (int i = S * 16 + lane; i < S16 * 16; i += 64) sp16[i] = 0.f;  // rows beyond S: no edges either
+      float* pp = partial + (long)b * (2 * C + C * C);
+      if (lane < C) {
+        pp[j] = p0n - (j == (int)tg[0] ? 1.f : 0.f);
+        pp[C + j] = dend;
+      }
     }
   }
   __syncthreads();
+  if constexpr (MARG) {  // the node marginals, coalesced; exact zeros at masked steps
+    float* mo = dem + (long)b * S * C;
+    for (int idx = lane; idx < S * C; idx += 64) {
+      const int t = idx / C, jj = idx - t * C;
+      mo[idx] = (t == 0 || mk[t]) ? xs16[t * 16 + jj] : 0.f;
+    }
+    return;
+  }
   // 3. G[i][j] = sum_t a_{t-1}[i] ui_t[j]: A[m = i][k = t] from al16 rows t-1, B[k = t][n = j] = ui rows t
   {
     crf_f4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
@@ -424,6 +454,8 @@ __global__ __launch_bounds__(64) void crf_bwd_kernel(const float* __restrict__ e
   }
 }
 
+// GRAD = CRF_GRAD_MEAN: (*gout / B) sum_b partial[b];  CRF_GRAD_SENTENCE: sum_b -gout[b] partial[b] (the partials are d(-llh[b]))
+template <int GRAD>
 __global__ void crf_param_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ gout, int B, int C,
                                         float* __restrict__ dstart, float* __restrict__ dend, float* __restrict__ dtrans,
                                         int accumulate) {
@@ -431,8 +463,12 @@ __global__ void crf_param_reduce_kernel(const float* __restrict__ partial, const
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float s = 0.f;
-  for (int b = 0; b < B; ++b) s += partial[(long)b * n + i];
-  s *= (gout ? *gout : 1.f) / B;
+  if constexpr (GRAD == CRF_GRAD_SENTENCE) {
+    for (int b = 0; b < B; ++b) s -= gout[b] * partial[(long)b * n + i];
+  } else {
+    for (int b = 0; b < B; ++b) s += partial[(long)b * n + i];
+    s *= (gout ? *gout : 1.f) / B;
+  }
   float* d = i < C ? dstart + i : (i < 2 * C ? dend + (i - C) : dtrans + (i - 2 * C));
   if (accumulate) s += *d;
   *d = s;
@@ -790,13 +826,72 @@ int crf_allow_lds(K kernel, size_t bytes) {  // dynamic LDS beyond the 64 KB def
     return MTVAF_ERR_SHAPE;
   return MTVAF_OK;
 }
+bool crf_wide_shape(int S, int C) { return C > CMAX && C <= CRF_WIDE_CMAX && S <= CRF_WIDE_SMAX; }
+bool crf_bad_shape(int B, int S, int C) { return B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C)); }
+
+// C <= 16 workspace: alpha [B,S,16] | logZ [B] | llh [B] | parameter-gradient partials [B, 2C + C*C]
+struct Crf16Ws {
+  float *alpha, *logz, *llh, *partial;
+};
+Crf16Ws crf16_ws(void* ws, int B, int S) {
+  Crf16Ws w;
+  w.alpha = (float*)ws;
+  w.logz = w.alpha + (size_t)B * S * CMAX;
+  w.llh = w.logz + B;
+  w.partial = w.llh + B;
+  return w;
+}
+
+// the C <= 16 forward recursion: alpha into the workspace, logZ [B] and (GOLD) llh [B] where the caller wants them
+template <bool GOLD>
+int crf16_fwd(const float* em, const int64_t* tags, const uint8_t* mask, const float* start, const float* end,
+              const float* trans, float* alpha, float* logz, float* llh, int B, int S, int C, hipStream_t st) {
+  const size_t S16 = ((size_t)S + 15) & ~(size_t)15;
+  const size_t lds_f = (2 * (S16 + 1) * 16 + (size_t)S) * sizeof(float) + (size_t)S * sizeof(int) + (size_t)S;
+  if (int rc = crf_allow_lds(crf_fwd_kernel<GOLD>, lds_f)) return rc;  // S <= ~1100
+  hipLaunchKernelGGL(crf_fwd_kernel<GOLD>, dim3(B), dim3(64), lds_f, st, em, tags, mask, start, end, trans, alpha, logz, llh,
+                     S, C);
+  return MTVAF_OK;
+}
+
+// the C <= 16 backward recursion in one of its three forms (crf_bwd_kernel)
+template <int GRAD>
+int crf16_bwd(const float* gout, const float* em, const int64_t* tags, const uint8_t* mask, const float* end,
+              const float* trans, const float* alpha, float* dem, float* partial, int B, int S, int C, hipStream_t st) {
+  const size_t S16 = ((size_t)S + 15) & ~(size_t)15;
+  const size_t lds_b = (3 * S16 * 16 + CMAX * CMAX) * sizeof(float) + (size_t)S * sizeof(int) + (size_t)S;
+  if (int rc = crf_allow_lds(crf_bwd_kernel<GRAD>, lds_b)) return rc;  // S <= ~800
+  hipLaunchKernelGGL(crf_bwd_kernel<GRAD>, dim3(B), dim3(64), lds_b, st, em, tags, mask, end, trans, alpha, gout, dem,
+                     partial, B, S, C);
+  return MTVAF_OK;
+}
+
+// both paths' backward: the recursion kernel, then the reduction of the per-sentence parameter partials
+template <int GRAD>
+int crf_bwd(const float* gout, const float* em, const int64_t* tags, const uint8_t* mask, const float* end,
+            const float* trans, float* dem, float* dstart, float* dend, float* dtrans, int accumulate, int B, int S, int C,
+            void* workspace, hipStream_t st) {
+  const float* partial;
+  if (C > CMAX) {
+    const CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    if (int rc = crf_wide_bwd(GRAD, gout, em, tags, mask, end, trans, dem, w, B, S, C, st)) return rc;
+    partial = w.partial;
+  } else {
+    const Crf16Ws w = crf16_ws(workspace, B, S);
+    if (int rc = crf16_bwd<GRAD>(gout, em, tags, mask, end, trans, w.alpha, dem, w.partial, B, S, C, st)) return rc;
+    partial = w.partial;
+  }
+  const int n = 2 * C + C * C;
+  hipLaunchKernelGGL(crf_param_reduce_kernel<GRAD>, dim3((n + 255) / 256), dim3(256), 0, st, partial, gout, B, C, dstart,
+                     dend, dtrans, accumulate);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
 }  // namespace
 
 extern "C" {
 
-// C <= 16: alpha [B,S,16] | logZ [B] | llh [B] | parameter-gradient partials [B, 2C + C*C].
-// 16 < C <= 64 (S <= 512): the wide path's layout (crf_wide.h).  0 for a shape neither path takes.
-static bool crf_wide_shape(int S, int C) { return C > CMAX && C <= CRF_WIDE_CMAX && S <= CRF_WIDE_SMAX; }
+// C <= 16: Crf16Ws.  16 < C <= 64 (S <= 512): the wide path's layout (crf_wide.h).  0 for a shape neither path takes.
 size_t mtvaf_crf_workspace_bytes(int B, int S, int C) {
   if (C > CMAX) return crf_wide_shape(S, C) && B > 0 && S > 0 ? crf_wide_workspace_floats(B, S, C) * sizeof(float) : 0;
   return ((size_t)B * S * CMAX + (size_t)B * 2 + (size_t)B * (2 * C + C * C)) * sizeof(float);
@@ -806,23 +901,18 @@ size_t mtvaf_crf_workspace_bytes(int B, int S, int C) {
 int mtvaf_crf_nll_fwd(const float* emissions, const int64_t* tags, const uint8_t* mask, const float* start,
                       const float* end, const float* trans, float* loss, int B, int S, int C, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  const float* llh;
   if (C > CMAX) {
     const CrfWideWs w = crf_wide_ws(workspace, B, S, C);
     if (int rc = crf_wide_fwd(emissions, tags, mask, start, end, trans, w, B, S, C, st)) return rc;
-    hipLaunchKernelGGL(crf_loss_kernel, dim3(1), dim3(64), 0, st, w.llh, loss, B);
-    MTVAF_LAUNCH_CHECK();
-    return MTVAF_OK;
+    llh = w.llh;
+  } else {
+    const Crf16Ws w = crf16_ws(workspace, B, S);
+    if (int rc = crf16_fwd<true>(emissions, tags, mask, start, end, trans, w.alpha, w.logz, w.llh, B, S, C, st)) return rc;
+    llh = w.llh;
   }
-  float* alpha = (float*)workspace;
-  float* logz = alpha + (size_t)B * S * CMAX;
-  float* llh = logz + B;
-  const size_t S16 = ((size_t)S + 15) & ~(size_t)15;
-  const size_t lds_f = (2 * (S16 + 1) * 16 + (size_t)S) * sizeof(float) + (size_t)S * sizeof(int) + (size_t)S;
-  if (int rc = crf_allow_lds(crf_fwd_kernel, lds_f)) return rc;  // S <= ~1100
-  hipLaunchKernelGGL(crf_fwd_kernel, dim3(B), dim3(64), lds_f, st, emissions, tags, mask, start, end, trans, alpha, logz,
-                     llh, S, C);
   hipLaunchKernelGGL(crf_loss_kernel, dim3(1), dim3(64), 0, st, llh, loss, B);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -834,28 +924,62 @@ int mtvaf_crf_nll_bwd(const float* grad_out, const float* emissions, const int64
                       const float* start, const float* end, const float* trans, float* demissions, float* dstart,
                       float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  return crf_bwd<CRF_GRAD_MEAN>(grad_out, emissions, tags, mask, end, trans, demissions, dstart, dend, dtrans, accumulate, B,
+                                S, C, workspace, st);
+}
+
+// llh[b] = score(gold_b) - logZ_b, written by the forward kernel itself (no epilogue kernel).  The workspace keeps
+// alpha / logZ for mtvaf_crf_llh_bwd (same pointer), as mtvaf_crf_nll_fwd's does for mtvaf_crf_nll_bwd.
+int mtvaf_crf_llh_fwd(const float* emissions, const int64_t* tags, const uint8_t* mask, const float* start,
+                      const float* end, const float* trans, float* llh, int B, int S, int C, void* workspace,
+                      size_t workspace_bytes, hipStream_t st) {
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   if (C > CMAX) {
-    const CrfWideWs w = crf_wide_ws(workspace, B, S, C);
-    if (int rc = crf_wide_bwd(grad_out, emissions, tags, mask, end, trans, demissions, w, B, S, C, st)) return rc;
-    const int n = 2 * C + C * C;
-    hipLaunchKernelGGL(crf_param_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.partial, grad_out, B, C, dstart,
-                       dend, dtrans, accumulate);
-    MTVAF_LAUNCH_CHECK();
-    return MTVAF_OK;
+    CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    w.llh = llh;
+    if (int rc = crf_wide_fwd(emissions, tags, mask, start, end, trans, w, B, S, C, st)) return rc;
+  } else {
+    const Crf16Ws w = crf16_ws(workspace, B, S);
+    if (int rc = crf16_fwd<true>(emissions, tags, mask, start, end, trans, w.alpha, w.logz, llh, B, S, C, st)) return rc;
   }
-  float* alpha = (float*)workspace;
-  float* logz = alpha + (size_t)B * S * CMAX;
-  float* partial = logz + 2 * B;
-  const size_t S16 = ((size_t)S + 15) & ~(size_t)15;
-  const size_t lds_b = (3 * S16 * 16 + CMAX * CMAX) * sizeof(float) + (size_t)S * sizeof(int) + (size_t)S;
-  if (int rc = crf_allow_lds(crf_bwd_kernel, lds_b)) return rc;  // S <= ~800
-  hipLaunchKernelGGL(crf_bwd_kernel, dim3(B), dim3(64), lds_b, st, emissions, tags, mask, end, trans, alpha, grad_out,
-                     demissions, partial, B, S, C);
-  const int n = 2 * C + C * C;
-  hipLaunchKernelGGL(crf_param_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, partial, grad_out, B, C, dstart,
-                     dend, dtrans, accumulate);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+// grad_llh [B]: d(total)/d(llh[b]).  demissions[b] = grad_llh[b] (one-hot(gold) - marginal), exact zeros at masked steps;
+// the parameter gradients are sum_b grad_llh[b] d(llh[b]), overwritten or accumulated.
+int mtvaf_crf_llh_bwd(const float* grad_llh, const float* emissions, const int64_t* tags, const uint8_t* mask,
+                      const float* start, const float* end, const float* trans, float* demissions, float* dstart,
+                      float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
+                      size_t workspace_bytes, hipStream_t st) {
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  return crf_bwd<CRF_GRAD_SENTENCE>(grad_llh, emissions, tags, mask, end, trans, demissions, dstart, dend, dtrans,
+                                    accumulate, B, S, C, workspace, st);
+}
+
+// marg[b,t,j] = p(y_t = j | emissions_b) at unmasked steps, exact zeros at masked ones; logz [B] (nullable).  Two
+// launches: the forward recursion without the gold path, the backward recursion in its CRF_MARGINALS form.
+int mtvaf_crf_marginals(const float* emissions, const uint8_t* mask, const float* start, const float* end,
+                        const float* trans, float* marg, float* logz, int B, int S, int C, void* workspace,
+                        size_t workspace_bytes, hipStream_t st) {
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (workspace_bytes < mtvaf_crf_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
+  if (C > CMAX) {
+    CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    if (logz) w.logz = logz;
+    if (int rc = crf_wide_marginals(emissions, mask, start, end, trans, marg, w, B, S, C, st)) return rc;
+  } else {
+    const Crf16Ws w = crf16_ws(workspace, B, S);
+    if (int rc = crf16_fwd<false>(emissions, nullptr, mask, start, end, trans, w.alpha, logz ? logz : w.logz, nullptr, B, S,
+                                  C, st))
+      return rc;
+    if (int rc = crf16_bwd<CRF_MARGINALS>(nullptr, emissions, nullptr, mask, end, trans, w.alpha, marg, nullptr, B, S, C, st))
+      return rc;
+  }
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -863,7 +987,7 @@ int mtvaf_crf_nll_bwd(const float* grad_out, const float* emissions, const int64
 // tags_out [B,S] int32 (best path, -1 padded), lens_out [B] int32.
 int mtvaf_crf_viterbi(const float* emissions, const uint8_t* mask, const float* start, const float* end,
                       const float* trans, int32_t* tags_out, int32_t* lens_out, int B, int S, int C, hipStream_t st) {
-  if (B <= 0 || S <= 0 || C <= 0 || (C > CMAX && !crf_wide_shape(S, C))) return MTVAF_ERR_SHAPE;
+  if (crf_bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (C > CMAX) return crf_wide_viterbi(emissions, mask, start, end, trans, tags_out, lens_out, B, S, C, st);
   const size_t S8 = ((size_t)S + 7) >> 3;
   const size_t lds_v = ((size_t)S * C + 16) * sizeof(float) + S8 * 16 * sizeof(uint32_t) + (size_t)S * sizeof(int) + (size_t)S;

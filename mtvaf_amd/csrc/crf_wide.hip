@@ -100,8 +100,9 @@ __device__ __forceinline__ int mask_count(const uint8_t* mk, int S, int lane) {
 //     dot_t[j] = sum_i s_{t-1}[i] E[i][j],   s_t[j] = dot_t[j] x_t[j] r_{t-1},   log K_t = log K_{t-1} + tmax + mx_t - log r
 // with alpha_t = K_t s_t.  alpha_ws[t] = s_t (every t; carried over masked steps), sp_ws[t] = dot_t (the predicted
 // alpha the backward needs, on the same scale as alpha_ws[t-1]), mx_ws[t] = max_j emit_t[j].
+// GOLD = false (tag marginals): no tags are read, no gold-path score is formed, llh is not written.
 // ---------------------------------------------------------------------------------------------
-template <int CT>
+template <int CT, bool GOLD>
 __global__ __launch_bounds__(64) void crf_wide_fwd_kernel(const float* __restrict__ em, const int64_t* __restrict__ tags,
                                                          const uint8_t* __restrict__ mask, const float* __restrict__ start,
                                                          const float* __restrict__ end, const float* __restrict__ trans,
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(64) void crf_wide_fwd_kernel(const float* __restric
   const int b = blockIdx.x, j = threadIdx.x;
   const bool act = j < C;
   const float* emb = em + (long)b * S * C;
-  stage(em, tags, mask, b, S, C, j, mk, tg, mxs, mx_ws);
+  stage(em, tags, mask, b, S, C, j, mk, GOLD ? tg : nullptr, mxs, mx_ws);
   const float tmax = trans_max(trans, C, j);
   f32x2 w[CT / 2];  // column j of E = exp(trans - tmax), rows (2p, 2p+1) in w[p]
 #pragma unroll
@@ -172,18 +173,20 @@ __global__ __launch_bounds__(64) void crf_wide_fwd_kernel(const float* __restric
     cnt += mk[t] ? 1 : 0;
     if (t >= 1 && mk[t]) {
       lz += mxs[t] + tmax - __logf(rl[t]);
-      sc += trans[tg[t - 1] * C + tg[t]] + emb[(long)t * C + tg[t]];
+      if constexpr (GOLD) sc += trans[tg[t - 1] * C + tg[t]] + emb[(long)t * C + tg[t]];
     }
   }
   lz = wave_sum(lz);
-  sc = wave_sum(sc);
+  if constexpr (GOLD) {
+    sc = wave_sum(sc);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  }
   if (j == 0) {
     const float z = c0 + lz + __logf(fin) + em_;
-    sc += start[tg[0]] + emb[tg[0]] + end[tg[max(cnt - 1, 0)]];
+    if constexpr (GOLD) sc += start[tg[0]] + emb[tg[0]] + end[tg[max(cnt - 1, 0)]];
     logz[b] = z;
-    llh[b] = sc - z;
+    if constexpr (GOLD) llh[b] = sc - z;
   }
 }
 
@@ -194,8 +197,11 @@ __global__ __launch_bounds__(64) void crf_wide_fwd_kernel(const float* __restric
 //   goes to the workspace; then the summed edge marginals sum_t a_{t-1}[i] ui_t[j] = (A^T UI)[i][j] run on the matrix
 //   cores, 16 time steps at a time, the next block's operands loaded while the current one multiplies.
 // partial layout per sequence: [start C | end C | trans C*C] (crf.hip's crf_param_reduce_kernel sums them).
+// GRAD (crf_wide.h): CRF_GRAD_MEAN scales by *gout / B; CRF_GRAD_SENTENCE by -gout[b] (d(emissions) of sum_b gout[b] llh[b];
+// the partials take their weight in the reduction); CRF_MARGINALS writes the node marginals to dem and ends after the
+// serial part: no tags, no gold counts, no ui rows, no edge-marginal product, no partials.
 // ---------------------------------------------------------------------------------------------
-template <int CT>
+template <int CT, int GRAD>
 __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restrict__ em, const int64_t* __restrict__ tags,
                                                          const uint8_t* __restrict__ mask, const float* __restrict__ end,
                                                          const float* __restrict__ trans, const float* __restrict__ alpha_ws,
@@ -204,7 +210,8 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
                                                          float* __restrict__ dem, float* __restrict__ partial, int B, int S,
                                                          int C) {
   __shared__ __attribute__((aligned(16))) float bc[64];
-  __shared__ float gold[CT * CT];  // gold transition counts
+  constexpr bool MARG = GRAD == CRF_MARGINALS;
+  __shared__ float gold[MARG ? 1 : CT * CT];  // gold transition counts
   extern __shared__ __attribute__((aligned(16))) float crfw_lds[];
   float* mxs = crfw_lds;                              // [S]
   int* tg = reinterpret_cast<int*>(mxs + S);          // [S]
@@ -212,27 +219,30 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
   const int b = blockIdx.x, j = threadIdx.x;
   const bool act = j < C;
   const float* emb = em + (long)b * S * C;
-  stage(em, tags, mask, b, S, C, j, mk, tg, nullptr, nullptr);
+  stage(em, tags, mask, b, S, C, j, mk, MARG ? nullptr : tg, nullptr, nullptr);
   for (int t = j; t < S; t += 64) mxs[t] = mx_ws[(long)b * S + t];
-  for (int i = j; i < CT * CT; i += 64) gold[i] = 0.f;
+  if constexpr (!MARG)
+    for (int i = j; i < CT * CT; i += 64) gold[i] = 0.f;
   __syncthreads();
-  for (int t = 1 + j; t < S; t += 64)
-    if (mk[t]) atomicAdd(&gold[tg[t - 1] * CT + tg[t]], 1.f);  // (integer-valued sums: exact, order-independent)
-  const float g = (gout ? *gout : 1.f) / B;
+  if constexpr (!MARG)
+    for (int t = 1 + j; t < S; t += 64)
+      if (mk[t]) atomicAdd(&gold[tg[t - 1] * CT + tg[t]], 1.f);  // (integer-valued sums: exact, order-independent)
+  // (marginal - one-hot) below is d(-llh): the per-sentence weight enters negated
+  const float g = MARG ? 1.f : (GRAD == CRF_GRAD_SENTENCE ? -gout[b] : (gout ? *gout : 1.f) / B);
   const float tmax = trans_max(trans, C, j);
   f32x2 wr[CT / 2];  // row j of E, columns (2p, 2p+1) in wr[p]
 #pragma unroll
   for (int i = 0; i < CT; ++i) wr[i / 2][i % 2] = (act && i < C) ? __expf(trans[j * C + i] - tmax) : 0.f;
-  const int cnt = mask_count(mk, S, j);
-  const int last_tag = tg[max(cnt - 1, 0)];
+  const int cnt = MARG ? 0 : mask_count(mk, S, j);
+  const int last_tag = MARG ? 0 : tg[max(cnt - 1, 0)];
   const float* alb = alpha_ws + (long)b * S * CT;
   const float* spb = sp_ws + (long)b * S * CT;
   float* uib = ui_ws + (long)b * S * CT;
   float* deb = dem + (long)b * S * C;
   const float em_ = wave_max(act ? end[j] : NEG);
   float bt = act ? __expf(end[j] - em_) : 0.f;  // beta of the last position, any positive scale
-  float dend;
-  {
+  float dend = 0.f;
+  if constexpr (!MARG) {
     const float pe = act ? alb[(long)(S - 1) * CT + j] * bt : 0.f;
     dend = pe * __frcp_rn(wave_sum(pe)) - (j == last_tag ? 1.f : 0.f);
   }
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
       const bool onq = j < CHUNK && tq >= 1 && mk[tq] != 0;
       const unsigned long long mb = __ballot(onq);
       const float mxq = tq >= 1 ? mxs[tq] : 0.f;
-      const int tgq = tq >= 1 ? tg[tq] : -1;
+      const int tgq = (!MARG && tq >= 1) ? tg[tq] : -1;
       const int nq = min(CHUNK, hi);
 #pragma unroll
       for (int q = 0; q < CHUNK; ++q) {
@@ -271,10 +281,12 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
             const float rd = __builtin_amdgcn_rcpf(sum_u<CT>(sc[q] * u));
             const float dot = bcast_dot<CT>(bc, j, u, wr);
             ui = u * rd;
-            de = g * (sc[q] * ui - (j == lane_val(tgq, q) ? 1.f : 0.f));
+            if constexpr (MARG) de = sc[q] * ui;
+            else de = g * (sc[q] * ui - (j == lane_val(tgq, q) ? 1.f : 0.f));
             bt = dot * rd;
           }
-          if (j < CT) uib[(long)t * CT + j] = ui;
+          if constexpr (!MARG)
+            if (j < CT) uib[(long)t * CT + j] = ui;
           if (act) deb[(long)t * C + j] = de;
         }
       }
@@ -288,6 +300,10 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
   {
     const float p0 = act ? alb[j] * bt : 0.f;
     const float p0n = p0 * __frcp_rn(wave_sum(p0));
+    if constexpr (MARG) {
+      if (act) deb[j] = p0n;
+      return;
+    }
     float* pp = partial + (long)b * (2 * C + C * C);
     if (act) {
       const float oh = j == tg[0] ? 1.f : 0.f;
@@ -498,21 +514,41 @@ CrfWideWs crf_wide_ws(void* ws, int B, int S, int C) {
 int crf_wide_fwd(const float* em, const int64_t* tags, const uint8_t* mask, const float* start, const float* end,
                  const float* trans, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
   const size_t lds = (size_t)S * (2 * sizeof(float) + sizeof(int) + 1);
-#define L(CT) hipLaunchKernelGGL(crfw::crf_wide_fwd_kernel<CT>, dim3(B), dim3(64), lds, st, em, tags, mask, start, end, \
-                                 trans, w.alpha, w.sp, w.mx, w.logz, w.llh, S, C)
+#define L(CT) hipLaunchKernelGGL(HIP_KERNEL_NAME(crfw::crf_wide_fwd_kernel<CT, true>), dim3(B), dim3(64), lds, st, em, tags, \
+                                 mask, start, end, trans, w.alpha, w.sp, w.mx, w.logz, w.llh, S, C)
   CRFW_DISPATCH(C, L)
 #undef L
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 
-int crf_wide_bwd(const float* gout, const float* em, const int64_t* tags, const uint8_t* mask, const float* end,
-                 const float* trans, float* dem, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
+template <int GRAD>
+static void crf_wide_bwd_launch(const float* gout, const float* em, const int64_t* tags, const uint8_t* mask,
+                                const float* end, const float* trans, float* dem, const CrfWideWs& w, int B, int S, int C,
+                                hipStream_t st) {
   const size_t lds = (size_t)S * (sizeof(float) + sizeof(int) + 1);
-#define L(CT) hipLaunchKernelGGL(crfw::crf_wide_bwd_kernel<CT>, dim3(B), dim3(64), lds, st, em, tags, mask, end, trans, \
-                                 w.alpha, w.sp, w.mx, w.ui, gout, dem, w.partial, B, S, C)
+#define L(CT) hipLaunchKernelGGL(HIP_KERNEL_NAME(crfw::crf_wide_bwd_kernel<CT, GRAD>), dim3(B), dim3(64), lds, st, em, tags, \
+                                 mask, end, trans, w.alpha, w.sp, w.mx, w.ui, gout, dem, w.partial, B, S, C)
   CRFW_DISPATCH(C, L)
 #undef L
+}
+
+int crf_wide_bwd(int grad, const float* gout, const float* em, const int64_t* tags, const uint8_t* mask, const float* end,
+                 const float* trans, float* dem, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
+  if (grad == CRF_GRAD_SENTENCE) crf_wide_bwd_launch<CRF_GRAD_SENTENCE>(gout, em, tags, mask, end, trans, dem, w, B, S, C, st);
+  else crf_wide_bwd_launch<CRF_GRAD_MEAN>(gout, em, tags, mask, end, trans, dem, w, B, S, C, st);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+int crf_wide_marginals(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                       float* marg, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
+  const size_t lds = (size_t)S * (2 * sizeof(float) + sizeof(int) + 1);
+#define L(CT) hipLaunchKernelGGL(HIP_KERNEL_NAME(crfw::crf_wide_fwd_kernel<CT, false>), dim3(B), dim3(64), lds, st, em, \
+                                 nullptr, mask, start, end, trans, w.alpha, w.sp, w.mx, w.logz, nullptr, S, C)
+  CRFW_DISPATCH(C, L)
+#undef L
+  crf_wide_bwd_launch<CRF_MARGINALS>(nullptr, em, nullptr, mask, end, trans, marg, w, B, S, C, st);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

@@ -1229,6 +1229,30 @@ class CRFNLLFunction(torch.autograd.Function):
         return dem, ds, de, dt, None, None
 
 
+class CRFLLHFunction(torch.autograd.Function):
+    """llh [B] = log p(tags_b | emissions_b) per sentence (torchcrf's reduction='none').  The backward takes the [B]
+    upstream gradient as it is: one mtvaf_crf_llh_bwd call weights every sentence inside the kernels."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, tags, mask_u8):
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        ws, wsb = hip.crf_workspace(B, S, C, em.device)
+        llh = _empty(B, like=em)
+        hip.crf_llh_fwd(em, tags, mask_u8, start, end, trans, llh, ws, wsb)
+        ctx.stash = (em, start, end, trans, tags, mask_u8, ws, wsb)
+        return llh
+
+    @staticmethod
+    def backward(ctx, gout):
+        em, start, end, trans, tags, mask_u8, ws, wsb = ctx.stash
+        g = gout.contiguous().float()
+        dem = torch.empty_like(em)
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(trans)
+        hip.crf_llh_bwd(g, em, tags, mask_u8, start, end, trans, dem, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, None, None
+
+
 # -------------------------------------------------------------------------------------------------
 class PromptFunction(torch.autograd.Function):
     """enc [NI,B,L,4W] + packed projector weights -> pkv [NL,2,B,(NI*L)*(W/2)].

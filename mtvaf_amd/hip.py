@@ -87,6 +87,9 @@ _SIGS = {
     "mtvaf_crf_nll_fwd": (c_int, [P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_nll_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     "mtvaf_crf_viterbi": (c_int, [P, P, P, P, P, P, P, I, I, I, P]),
+    "mtvaf_crf_llh_fwd": (c_int, [P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_llh_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    "mtvaf_crf_marginals": (c_int, [P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_split_mean": (c_int, [P, P, L, I, P]),
     "mtvaf_gate_fwd": (c_int, [P, P, L, P]),
     "mtvaf_prompt_mix_fwd": (c_int, [P, P, P, I, I, I, I, I, P]),
@@ -653,6 +656,28 @@ def crf_nll_bwd(gout, em, tags, mask_u8, start, end, trans, dem, dstart, dend, d
     B, S, C = em.shape
     _ck(lib().mtvaf_crf_nll_bwd(_p(gout), _p(em), _p(tags), _p(mask_u8), _p(start), _p(end), _p(trans), _p(dem), _p(dstart),
                                 _p(dend), _p(dtrans), int(accumulate), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_nll_bwd")
+
+
+def crf_llh_fwd(em, tags, mask_u8, start, end, trans, llh, ws, wsb):
+    """llh [B] = score(gold) - logZ per sentence; the workspace keeps what crf_llh_bwd reads."""
+    B, S, C = em.shape
+    _ck(lib().mtvaf_crf_llh_fwd(_p(em), _p(tags), _p(mask_u8), _p(start), _p(end), _p(trans), _p(llh), B, S, C, _p(ws), wsb,
+                                _st()), "mtvaf_crf_llh_fwd")
+
+
+def crf_llh_bwd(grad_llh, em, tags, mask_u8, start, end, trans, dem, dstart, dend, dtrans, accumulate, ws, wsb):
+    """grad_llh [B]: the upstream gradient of every sentence's log-likelihood."""
+    B, S, C = em.shape
+    _ck(lib().mtvaf_crf_llh_bwd(_p(grad_llh), _p(em), _p(tags), _p(mask_u8), _p(start), _p(end), _p(trans), _p(dem),
+                                _p(dstart), _p(dend), _p(dtrans), int(accumulate), B, S, C, _p(ws), wsb, _st()),
+        "mtvaf_crf_llh_bwd")
+
+
+def crf_marginals(em, mask_u8, start, end, trans, marg, logz, ws, wsb):
+    """marg [B,S,C] posterior tag probabilities (zeros at masked steps); logz [B] or None."""
+    B, S, C = em.shape
+    _ck(lib().mtvaf_crf_marginals(_p(em), _p(mask_u8), _p(start), _p(end), _p(trans), _p(marg), _p(logz), B, S, C, _p(ws),
+                                  wsb, _st()), "mtvaf_crf_marginals")
 
 
 def crf_viterbi(em, mask_u8, start, end, trans, tags_out, lens_out):

@@ -30,6 +30,15 @@ def _arg(args, name, default=False):
     return getattr(args, name, default)
 
 
+def _crf_reduction(args):
+    """args.crf_reduction: how TVNetSAModel2 reduces the CRF log-likelihood into its loss (the loss stays -llh reduced).
+    'mean' (default, the reference's call) | 'token_mean' | 'sum'."""
+    reduction = _arg(args, "crf_reduction", "mean")
+    if reduction not in ("mean", "token_mean", "sum"):
+        raise ValueError(f"args.crf_reduction={reduction!r}: expected 'mean', 'token_mean' or 'sum'")
+    return reduction
+
+
 def _on_second_stream(fn, inputs, join=False):
     """Run the prompt generator (small, low-occupancy GEMMs and mixing kernels) on the engine's second stream so it
     overlaps the embeddings and the first QKV product; the encoder waits for the prefix right before its first
@@ -148,6 +157,7 @@ class TVNetSAModel2(nn.Module):
         # (engine.UNPAD) may leave zeros at masked positions.  TVNetSAModel's position softmax reads every position: no flag.
         self.bert.allow_unpad = True
         self.last_prefix_mass = None  # [L,B,NH,S] after a forward with args.output_prefix_mass
+        self.last_tag_marginals = None  # [B,S,num_labels] after a forward with args.output_tag_marginals
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -171,6 +181,7 @@ class TVNetSAModel2(nn.Module):
         self.crf = CRF(self.num_labels, batch_first=True)
         self.fc = nn.Linear(hidden, self.num_labels)
         self.dropout = nn.Dropout(0.1)
+        _crf_reduction(args)  # (a misspelt reduction is an error here, not at the first step)
         if _arg(args, "use_probe"):
             raise NotImplementedError("the structural probe (probes/) is off the hot path and its import chain is "
                                       "broken in the reference (models/bert_model.py:468-475)")
@@ -220,9 +231,17 @@ class TVNetSAModel2(nn.Module):
         else:
             logits = self.crf.decode_deferred(emissions, mask_u8)
             decoded = None
+        # args.output_tag_marginals fills self.last_tag_marginals [B,S,num_labels] -- posterior tag probabilities, zeros on
+        # padding -- from the marginals kernels; without the switch the step launches nothing for them.
+        self.last_tag_marginals = self.crf.marginals(emissions.detach(), mask_u8) \
+            if _arg(self.args, "output_tag_marginals") else None
         loss = None
         if labels is not None:
-            loss = self.crf.nll_mean(emissions, labels, mask=mask_u8)  # = -1 * crf(..., reduction='mean'), bert_model.py:521
+            reduction = _crf_reduction(self.args)
+            if reduction == "mean":
+                loss = self.crf.nll_mean(emissions, labels, mask=mask_u8)  # = -1 * crf(..., reduction='mean'), bert_model.py:521
+            else:
+                loss = -self.crf(emissions, labels, mask=mask_u8, reduction=reduction)
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
             if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
                 loss = loss + extra

@@ -1,7 +1,7 @@
 """Linear-chain CRF module with the public surface of ``torchcrf.CRF`` as the reference uses it
 (models/bert_model.py:464 ``CRF(num_labels, batch_first=True)``, :511 ``decode``, :521
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
-mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_viterbi.  Parameter names (``start_transitions``,
+mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi.  Parameter names (``start_transitions``,
 ``end_transitions``, ``transitions``) and the uniform(-0.1, 0.1) initialisation follow pytorch-crf.
 """
 from __future__ import annotations
@@ -125,17 +125,46 @@ class CRF(nn.Module):
             tags = tags.to(torch.long).contiguous()
         return emissions.float(), tags, mask
 
+    REDUCTIONS = ("none", "sum", "mean", "token_mean")
+
     def forward(self, emissions, tags, mask: Optional[torch.Tensor] = None, reduction: str = "sum"):
-        """Log-likelihood of ``tags`` (like torchcrf).  The fused kernel produces the batch-mean NLL, so
-        'mean' is exact and 'sum' is mean * B; 'none' / 'token_mean' are not on the MTVAF path."""
+        """Log-likelihood of ``tags`` with torchcrf's reductions.  'mean' and 'sum' come from the fused batch-mean NLL
+        kernels ('sum' is mean * B).  'none' returns the per-sentence log-likelihoods [B] from mtvaf_crf_llh_{fwd,bwd},
+        whose backward takes a per-sentence upstream gradient, so ``(w * crf(..., reduction='none')).sum()`` weights
+        sentences inside the kernels; 'token_mean' is ``llh.sum() / mask.sum()`` on top of it.  Any other string raises
+        ValueError."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
         emissions, tags, mask = self._prep(emissions, tags, mask)
+        if reduction in ("none", "token_mean"):
+            llh = engine.CRFLLHFunction.apply(emissions, self.start_transitions, self.end_transitions, self.transitions,
+                                              tags, mask)
+            if reduction == "none":
+                return llh
+            return llh.sum() / mask.to(llh.dtype).sum()
         nll_mean = engine.CRFNLLFunction.apply(emissions, self.start_transitions, self.end_transitions,
                                                self.transitions, tags, mask)
         if reduction == "mean":
             return -nll_mean
-        if reduction == "sum":
-            return -nll_mean * emissions.shape[0]
-        raise NotImplementedError(f"reduction={reduction!r} is not on the MTVAF path (the reference uses 'mean')")
+        return -nll_mean * emissions.shape[0]
+
+    @torch.no_grad()
+    def marginals(self, emissions, mask: Optional[torch.Tensor] = None, return_logz: bool = False):
+        """Posterior tag probabilities ``p(y_t = j | emissions)``: [B,S,C] (``batch_first``) or [S,B,C], exact zeros at
+        masked steps; with ``return_logz`` also the log-partition ``logZ`` [B].  Computed by mtvaf_crf_marginals (the
+        forward / backward recursions without gold path, edge marginals or parameter gradients).  Runs under
+        ``torch.no_grad()``: the result does not require grad and no gradient flows through it."""
+        emissions, _, mask = self._prep(emissions, None, mask)
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        ws, wsb = hip.crf_workspace(B, S, C, em.device)
+        marg = torch.empty_like(em)
+        logz = torch.empty(B, dtype=em.dtype, device=em.device) if return_logz else None
+        hip.crf_marginals(em, mask, self.start_transitions.data, self.end_transitions.data, self.transitions.data, marg,
+                          logz, ws, wsb)
+        if not self.batch_first:
+            marg = marg.transpose(0, 1)
+        return (marg, logz) if return_logz else marg
 
     def nll_mean(self, emissions, tags, mask: Optional[torch.Tensor] = None):
         """``-1 * self(emissions, tags, mask=mask, reduction='mean')`` (models/bert_model.py:521) as ONE autograd node: the
