@@ -310,6 +310,22 @@ int mtvaf_ce_fwd(const float* logits, const int64_t* labels, float* loss, float*
                  mtvaf_stream_t stream);
 int mtvaf_ce_bwd(const float* grad_out, const float* logits, const int64_t* labels, const float* ws2,
                  float* dlogits, int N, int C, mtvaf_stream_t stream);
+/* Candidate spans at eval / predict time: the eval branch of models/utils.py::span_annotate_candidates (:451-521) and
+ * the host round trip around it (modules/train.py:382-410) as one launch, no host read-back.  Start logit of (b,s) at
+ * logits[(b*S+s)*ld], end logit one element later (the binary_affine output, ld = 2).  word_index [B,S] int32: token
+ * -> original word, -1 outside the reference's token_to_orig_map; word_key [B,S] int32 or NULL: an id of the word's
+ * string (equal strings, equal ids); NULL = word_index (positional de-duplication).  Per sentence: the top
+ * min(n_best,S) start and end positions (logit descending, position ascending, masked positions included), their
+ * pairs in that order with both ends in the map, e >= s, e-s+1 <= max_len and (double)sl+(double)el >= threshold,
+ * ordered by key = that fp64 sum [- (e-s+1) with use_heuristics] descending, pair order ascending; walked greedily
+ * until 2*accepted >= n_best, skipping a pair whose word-key signature equals an accepted span's (nms = 1: that
+ * shares any word key with one).  span_starts / span_ends / label_masks [B,n_best] int64 and span_scores [B,n_best]
+ * fp32 (the fp64 sum rounded) are zero-padded, count [B] int32; every element is written.  1 <= S <= 512,
+ * 1 <= n_best <= 32.  Contract: finite logits; word_index rises by 0 or 1 along each run of in-map tokens. */
+int mtvaf_span_propose(const float* logits, int ld, const int* word_index, const int* word_key,
+                       int64_t* span_starts, int64_t* span_ends, int64_t* label_masks, float* span_scores, int* count,
+                       int B, int S, int n_best, int max_len, float threshold, int use_heuristics, int nms,
+                       mtvaf_stream_t stream);
 
 /* Cutoff augmentation on the embedding output (modules/augument.py:99-159): out = x * row_keep[b,s] * col_keep[b,:]
  * (either mask may be NULL); x/out [B,S,H] fp32, row_keep [B*S], col_keep [B,H].  Self-adjoint: the backward is the

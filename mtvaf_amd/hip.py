@@ -108,6 +108,7 @@ _SIGS = {
     "mtvaf_distant_ce_bwd": (c_int, [P, F, P, I, P, P, P, I, I, I, P]),
     "mtvaf_ce_fwd": (c_int, [P, P, P, P, I, I, P]),
     "mtvaf_ce_bwd": (c_int, [P, P, P, P, P, I, I, P]),
+    "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -734,6 +735,41 @@ def ce_fwd(logits, labels, loss, ws2):
 def ce_bwd(gout, logits, labels, ws2, dlogits):
     N, C = logits.shape
     _ck(lib().mtvaf_ce_bwd(_p(gout), _p(logits), _p(labels), _p(ws2), _p(dlogits), N, C, _st()), "mtvaf_ce_bwd")
+
+
+SPAN_PROPOSE_MAX_S, SPAN_PROPOSE_MAX_N = 512, 32
+
+
+def span_propose(logits, word_index, word_key=None, n_best=20, max_len=12, threshold=8.0, use_heuristics=True, nms=0):
+    """Candidate spans of every sentence (csrc/span_propose.hip), one launch and no host sync.  logits [B,S,>=2] fp32, start
+    and end logit of a token adjacent (any token stride: the binary_affine output or a slice of a wider tensor is read in
+    place); word_index [B,S] int32 (-1 outside the word map); word_key [B,S] int32 or None (= word_index).
+    -> span_starts, span_ends, label_masks [B,n_best] int64, span_scores [B,n_best] fp32, count [B] int32."""
+    if logits.dim() != 3 or logits.shape[2] < 2:
+        raise ValueError(f"span_propose: logits {tuple(logits.shape)}: expected [B, S, >=2]")
+    B, S = logits.shape[:2]
+    n_best = int(n_best)
+    if not 1 <= S <= SPAN_PROPOSE_MAX_S:
+        raise ValueError(f"span_propose: S={S} outside 1..{SPAN_PROPOSE_MAX_S}")
+    if not 1 <= n_best <= SPAN_PROPOSE_MAX_N:
+        raise ValueError(f"span_propose: n_best={n_best} outside 1..{SPAN_PROPOSE_MAX_N}")
+    if nms not in (0, 1):
+        raise ValueError(f"span_propose: nms={nms!r}: expected 0 (off) or 1 (shared word)")
+    if B < 1 or tuple(word_index.shape) != (B, S) or (word_key is not None and tuple(word_key.shape) != (B, S)):
+        raise ValueError("span_propose: word_index / word_key must be [B, S] of the logits")
+    ld = logits.stride(1)
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1 and ld >= 2 and logits.stride(0) == S * ld, \
+        (logits.dtype, logits.stride())
+    for t in (word_index, word_key):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous()), (t.dtype, t.stride())
+    dev = logits.device
+    starts, ends, masks = (torch.empty((B, n_best), dtype=torch.int64, device=dev) for _ in range(3))
+    scores = torch.empty((B, n_best), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    _ck(lib().mtvaf_span_propose(_p(logits), ld, _p(word_index), _p(word_key), _p(starts), _p(ends), _p(masks), _p(scores),
+                                 _p(count), B, S, n_best, int(max_len), float(threshold), int(bool(use_heuristics)), int(nms),
+                                 _st()), "mtvaf_span_propose")
+    return starts, ends, masks, scores, count
 
 
 def mask_mul(x, row_keep, col_keep, out):

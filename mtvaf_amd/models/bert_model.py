@@ -447,6 +447,62 @@ class TVNetSAModel(nn.Module):
         return reconstruct(ac_logits, span_starts), ac_logits
 
     # ------------------------------------------------------------------------------------------------
+    def propose_spans(self, start_logits, end_logits=None, attention_mask=None, token_to_word=None, word_key=None):
+        """Candidate spans for eval / predict, on the device and without a host sync: what the reference's trainer does on the
+        host between ``extraction`` and ``classification`` (modules/train.py:382-410 around the eval branch of
+        models/utils.py::span_annotate_candidates).  ``start_logits`` / ``end_logits`` [B,S] as ``extraction`` returns them
+        (two columns of one tensor: read in place), or the ``[B,S,2]`` extraction logits alone with ``end_logits=None``.
+        ``token_to_word`` [B,S]: token -> original word, -1 outside the word map (`mtvaf_amd.spans`); None: every token with
+        ``attention_mask`` 1 is its own word.  ``word_key`` [B,S]: ids of the words' strings; None: de-duplication by position.
+        Read from ``args`` with the reference's defaults: n_best_size 20, max_answer_length 12, logit_threshold 8.0,
+        use_heuristics True, use_nms False, filter_type 'f1'.
+        -> span_starts, span_ends, label_masks [B,n_best_size] int64, span_scores [B,n_best_size] fp32, count [B] int32."""
+        if end_logits is None:
+            ae = start_logits
+        elif (start_logits.dim() == 2 and start_logits.shape == end_logits.shape and start_logits.stride() == end_logits.stride()
+              and start_logits.stride(1) >= 2 and start_logits.stride(0) == start_logits.shape[1] * start_logits.stride(1)
+              and start_logits.untyped_storage().data_ptr() == end_logits.untyped_storage().data_ptr()
+              and end_logits.storage_offset() == start_logits.storage_offset() + 1):
+            ae = start_logits.as_strided((*start_logits.shape, 2), (*start_logits.stride(), 1))
+        else:
+            ae = torch.stack((start_logits, end_logits), dim=-1)
+        ae = ae.detach().float()
+        if token_to_word is None:
+            if attention_mask is None:
+                raise ValueError("propose_spans: give attention_mask or token_to_word")
+            pos = torch.arange(ae.shape[1], device=ae.device, dtype=torch.int32).expand(ae.shape[0], -1)
+            token_to_word = torch.where(attention_mask.to(ae.device) != 0, pos, torch.full_like(pos, -1))
+        filter_type = _arg(self.args, "filter_type", "f1")
+        if filter_type not in ("f1", "em"):
+            raise ValueError(f"args.filter_type={filter_type!r}: expected 'f1' or 'em'")
+        # 'em' drops later candidates of equal text: the de-duplication has done that already
+        nms = 1 if _arg(self.args, "use_nms", False) and filter_type == "f1" else 0
+        return engine.hip.span_propose(
+            ae, token_to_word.to(device=ae.device, dtype=torch.int32).contiguous(),
+            None if word_key is None else word_key.to(device=ae.device, dtype=torch.int32).contiguous(),
+            n_best=_arg(self.args, "n_best_size", 20), max_len=_arg(self.args, "max_answer_length", 12),
+            threshold=_arg(self.args, "logit_threshold", 8.0), use_heuristics=_arg(self.args, "use_heuristics", True), nms=nms)
+
+    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, token_to_word=None,
+                word_key=None):
+        """Inference end to end with no host sync: visual prompt -> extraction logits -> `propose_spans` -> span classifier.
+        -> dict: span_starts, span_ends, label_masks [B,n] int64, span_scores [B,n] fp32, logits [B,n,4] (polarity logits of
+        every slot; padding slots have label_masks 0), start_logits / end_logits [B,S] the proposal read."""
+        with torch.no_grad():
+            if _arg(self.args, "use_prefix"):
+                prefix_guids = self.get_visual_prompt(images, aux_imgs)
+                prefix_len = prefix_guids[0][0].shape[2]
+                prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
+                prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+            else:
+                prefix_guids, prompt_attention_mask = None, attention_mask
+            ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids)
+            span_starts, span_ends, label_masks, span_scores, _ = self.propose_spans(
+                ae_logits, None, attention_mask, token_to_word=token_to_word, word_key=word_key)
+            logits, _ = self.classification(span_starts, span_ends, sequence_output, attention_mask)
+        return {"span_starts": span_starts, "span_ends": span_ends, "label_masks": label_masks, "span_scores": span_scores,
+                "logits": logits, "start_logits": ae_logits[..., 0], "end_logits": ae_logits[..., 1]}
+
     _region_features = TVNetSAModel2._region_features
 
     def get_visual_prompt(self, images, aux_imgs):
