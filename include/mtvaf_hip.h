@@ -327,6 +327,21 @@ int mtvaf_span_propose(const float* logits, int ld, const int* word_index, const
                        int B, int S, int n_best, int max_len, float threshold, int use_heuristics, int nms,
                        mtvaf_stream_t stream);
 
+/* Entity-level score of decoded tags, the counting half: what modules/train.py:627-647 / :714-731 (y_true / y_pred on the
+ * host), modules/eval_metrics.py::get_chunks / evaluate / evaluate_each_class and seqeval's classification_report count,
+ * ADDED into a device counter by one launch with no host read-back.  pred [B,ldp] int32 (mtvaf_crf_viterbi's tags, -1
+ * beyond each length; ldp >= S), gold [B,S] int64, mask [B,S] u8.  Kept columns of a sentence: 1 .. S-1 while mask is 1
+ * (up to the first 0), minus those with gold_skip[gold] set ([C] u8); a label id outside [0,C) reads as 0.  The tagging
+ * scheme is the two tables start_tab / end_tab [(C+1)*(C+1)] u8 indexed [prev*(C+1)+cur], index C = sentence boundary:
+ * per side, over the kept labels l_j, a start at j iff start_tab[l_j-1][l_j], an end at j iff end_tab[l_j][l_j+1]; every
+ * end closes one chunk (type_of[l_j], b, j) with b the greatest start <= j of the sentence (none: the chunk is unopened,
+ * counted for its type, never correct).  type_of [C+1] int32 in [0,n_types).  counts [n_types*3+2] int64: per type
+ * predicted, gold, correct (both sides end at j with the same opened b and the same type), then tokens_equal, tokens_kept.
+ * Integer atomics only: bit-reproducible.  1 <= S <= 512, 1 <= C <= 64, 1 <= n_types <= C+1. */
+int mtvaf_entity_counts(const int* pred, int ldp, const int64_t* gold, const uint8_t* mask, const uint8_t* start_tab,
+                        const uint8_t* end_tab, const int* type_of, const uint8_t* gold_skip, int B, int S, int C,
+                        int n_types, int64_t* counts, mtvaf_stream_t stream);
+
 /* Cutoff augmentation on the embedding output (modules/augument.py:99-159): out = x * row_keep[b,s] * col_keep[b,:]
  * (either mask may be NULL); x/out [B,S,H] fp32, row_keep [B*S], col_keep [B,H].  Self-adjoint: the backward is the
  * same call on the gradient. */

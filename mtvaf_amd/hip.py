@@ -109,6 +109,7 @@ _SIGS = {
     "mtvaf_ce_fwd": (c_int, [P, P, P, P, I, I, P]),
     "mtvaf_ce_bwd": (c_int, [P, P, P, P, P, I, I, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
+    "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -770,6 +771,36 @@ def span_propose(logits, word_index, word_key=None, n_best=20, max_len=12, thres
                                  _p(count), B, S, n_best, int(max_len), float(threshold), int(bool(use_heuristics)), int(nms),
                                  _st()), "mtvaf_span_propose")
     return starts, ends, masks, scores, count
+
+
+ENTITY_MAX_S, ENTITY_MAX_C = 512, 64
+
+
+def entity_counts(pred, gold, mask_u8, start_tab, end_tab, type_of, gold_skip, n_types, counts):
+    """Adds one batch's entity and token counts into ``counts`` (csrc/entity.hip), one launch and no host sync.  pred [B,>=S]
+    int32 (``CRF.decode_packed``'s tags), gold [B,S] int64, mask_u8 [B,S] uint8; start_tab / end_tab [(C+1)^2] uint8, type_of
+    [C+1] int32, gold_skip [C] uint8; counts [n_types*3+2] int64: per type predicted, gold, correct, then tokens_equal,
+    tokens_kept."""
+    C = gold_skip.numel()
+    if gold.dim() != 2 or pred.dim() != 2:
+        raise ValueError(f"entity_counts: pred {tuple(pred.shape)}, gold {tuple(gold.shape)}: expected [B, >=S] and [B, S]")
+    B, S = gold.shape
+    if not 1 <= S <= ENTITY_MAX_S:
+        raise ValueError(f"entity_counts: S={S} outside 1..{ENTITY_MAX_S}")
+    if not 1 <= C <= ENTITY_MAX_C:
+        raise ValueError(f"entity_counts: C={C} outside 1..{ENTITY_MAX_C}")
+    if B < 1 or pred.shape[0] != B or pred.shape[1] < S or tuple(mask_u8.shape) != (B, S):
+        raise ValueError(f"entity_counts: pred {tuple(pred.shape)} / mask {tuple(mask_u8.shape)} do not fit gold [{B}, {S}]")
+    if (start_tab.numel(), end_tab.numel(), type_of.numel(), counts.numel()) != ((C + 1) ** 2, (C + 1) ** 2, C + 1, n_types * 3 + 2):
+        raise ValueError("entity_counts: tables / counter do not fit C and n_types")
+    ldp = pred.stride(0)
+    assert pred.dtype == torch.int32 and pred.stride(1) == 1 and ldp >= S, (pred.dtype, pred.stride())
+    assert gold.dtype == torch.int64 and gold.is_contiguous() and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert start_tab.dtype == end_tab.dtype == gold_skip.dtype == torch.uint8 and type_of.dtype == torch.int32
+    assert counts.dtype == torch.int64 and all(t.is_contiguous() for t in (start_tab, end_tab, type_of, gold_skip, counts))
+    _ck(lib().mtvaf_entity_counts(_p(pred), ldp, _p(gold), _p(mask_u8), _p(start_tab), _p(end_tab), _p(type_of), _p(gold_skip),
+                                  B, S, C, int(n_types), _p(counts), _st()), "mtvaf_entity_counts")
+    return counts
 
 
 def mask_mul(x, row_keep, col_keep, out):

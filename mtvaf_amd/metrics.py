@@ -49,3 +49,148 @@ def label_sequences(labels: torch.Tensor, attention_mask: torch.Tensor, logits: 
     y_true = [names[lab[r, 1:][keep[r]]].tolist() for r in range(B)]
     y_pred = [names[tags[r, 1:][keep[r]]].tolist() for r in range(B)]
     return y_true, y_pred
+
+
+# -------------------------------------------------------------------------------------------------
+# Entity-level score on the device (csrc/entity.hip): the lists above never leave the GPU
+# -------------------------------------------------------------------------------------------------
+SCHEMES = ("seqeval", "reference")
+_CHUNK_CLASSES = ("B", "I", "E", "S")
+
+
+def entity_tables(label_map: Dict[str, int], scheme: str = "seqeval", skip: Sequence[str] = ("X", "[SEP]")) -> dict:
+    """The tagging scheme as the tables `mtvaf_entity_counts` reads, filled from label NAMES.
+
+    Ids run 0 .. C-1 with C = max id + 1; the id -> name list is `label_sequences`': id 0 and holes read ``"PAD"``.  Index C is the
+    sentence boundary and behaves as ``'O'``.  ``start[p][c]`` / ``end[p][c]``: a chunk starts at a label c that follows p / ends
+    at a label p that c follows.
+
+    ``"reference"``: modules/eval_metrics.py::get_chunks / get_chunk_type.  O is the id ``label_map['O']`` alone; every other
+    name has class ``name.split('-')[0]`` and type ``name.split('-')[-1]``; start = c is not O and (p is O or the types differ or
+    class(c) == 'B'); end = p is not O and (c is O or the types differ or class(c) == 'B').
+
+    ``"seqeval"``: seqeval's default-mode get_entities on prefix tags, restated (the package is not a dependency): tag =
+    ``name[0]``, type = ``name[1:].split('-', 1)[-1] or '_'``; the predicates are the ones spelled out in DESIGN.md section 7.
+
+    -> dict(C, names, types, primary, start, end, type_of, gold_skip): ``types`` the type names in counter order, ``primary[t]``
+    whether a label of class B / I / E / S carries type t (the others are reported only when they have counts)."""
+    if scheme not in SCHEMES:
+        raise ValueError(f"scheme={scheme!r}: expected one of {SCHEMES}")
+    if "O" not in label_map:
+        raise ValueError("the label map has no 'O'")
+    if min(label_map.values()) < 0:
+        raise ValueError("negative label id")
+    id2 = {idx: name for name, idx in label_map.items()}
+    id2[0] = "PAD"
+    C = max(id2) + 1
+    names = [id2.get(i, "PAD") for i in range(C)]
+    if scheme == "reference":
+        o_id = label_map["O"]
+        outside = [i == o_id for i in range(C)] + [True]
+        klass = [n.split("-")[0] for n in names] + ["O"]
+        kind = ["O" if outside[i] else names[i].split("-")[-1] for i in range(C)] + ["O"]
+
+        def start(p, c):
+            return not outside[c] and (outside[p] or kind[p] != kind[c] or klass[c] == "B")
+
+        def end(p, c):
+            return not outside[p] and (outside[c] or kind[p] != kind[c] or klass[c] == "B")
+    else:
+        klass = [n[0] for n in names] + ["O"]
+        kind = [n[1:].split("-", 1)[-1] or "_" for n in names] + ["_"]
+        end_pairs = {("B", "B"), ("B", "S"), ("B", "O"), ("I", "B"), ("I", "S"), ("I", "O")}
+        start_pairs = {("E", "E"), ("E", "I"), ("S", "E"), ("S", "I"), ("O", "E"), ("O", "I")}
+
+        def start(p, c):
+            return (klass[c] in ("B", "S") or (klass[p], klass[c]) in start_pairs
+                    or (klass[c] not in ("O", ".") and kind[p] != kind[c]))
+
+        def end(p, c):
+            return (klass[p] in ("E", "S") or (klass[p], klass[c]) in end_pairs
+                    or (klass[p] not in ("O", ".") and kind[p] != kind[c]))
+    types: List[str] = []
+    for k in kind:
+        if k not in types:
+            types.append(k)
+    carried = {kind[i] for i in range(C) if klass[i] in _CHUNK_CLASSES and not (scheme == "reference" and outside[i])}
+    n = C + 1
+    return dict(C=C, names=names, types=types, primary=[t in carried for t in types],
+                start=np.array([[start(p, c) for c in range(n)] for p in range(n)], dtype=np.uint8),
+                end=np.array([[end(p, c) for c in range(n)] for p in range(n)], dtype=np.uint8),
+                type_of=np.array([types.index(k) for k in kind], dtype=np.int32),
+                gold_skip=np.array([names[i] in skip for i in range(C)], dtype=np.uint8))
+
+
+def _prf(correct: int, predicted: int, support: int) -> Tuple[float, float, float]:
+    p = correct / predicted if predicted else 0.0
+    r = correct / support if support else 0.0
+    return p, r, (2 * p * r / (p + r) if p + r else 0.0)
+
+
+class EntityScorer:
+    """Entity-level precision / recall / F1 of decoded tags, counted on the GPU.
+
+    ``update`` adds one batch into a small device counter (one `mtvaf_entity_counts` launch on the current stream, no host
+    sync); ``compute`` reads it once.  ``scheme="seqeval"`` counts what ``classification_report`` counts on the
+    `label_sequences` lists, ``"reference"`` what modules/eval_metrics.py::evaluate / evaluate_each_class count (see
+    `entity_tables`).  ``device=None``: the device of the first ``update``."""
+
+    def __init__(self, label_map: Dict[str, int], scheme: str = "seqeval", skip: Sequence[str] = ("X", "[SEP]"), device=None):
+        t = entity_tables(label_map, scheme, skip)
+        if t["C"] > 64:
+            raise ValueError(f"label ids up to {t['C'] - 1}: the counting kernel reads at most 64 labels (ids 0..63)")
+        self.scheme, self.types, self.primary, self.C = scheme, t["types"], t["primary"], t["C"]
+        self._tables = [torch.from_numpy(t[k]).reshape(-1) for k in ("start", "end", "type_of", "gold_skip")]
+        self.counts = torch.zeros(len(self.types) * 3 + 2, dtype=torch.int64)
+        self.device = None
+        if device is not None:
+            self._place(torch.device(device))
+
+    def _place(self, device):
+        self._tables = [x.to(device) for x in self._tables]
+        self.counts = self.counts.to(device)
+        self.device = device
+
+    def update(self, pred_tags: torch.Tensor, labels: torch.Tensor, attention_mask: torch.Tensor) -> None:
+        """pred_tags [B, >=S] int32 on the device as ``CRF.decode_packed`` returns them (-1 beyond each length), labels [B,S],
+        attention_mask [B,S] (uint8 is read in place; other dtypes cost a cast)."""
+        from . import hip
+        if self.device is None:
+            self._place(pred_tags.device)
+        mask = attention_mask if attention_mask.dtype == torch.uint8 else attention_mask.to(torch.uint8)
+        gold = labels if labels.dtype == torch.int64 else labels.to(torch.int64)
+        hip.entity_counts(pred_tags, gold.contiguous(), mask.contiguous(), *self._tables, len(self.types), self.counts)
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def all_reduce(self, group=None) -> None:
+        """Sums the counter over the process group (nothing without one)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        """One small device->host copy -> {type: {predicted, support, correct, precision, recall, f1}, ..., "micro": the same
+        over all chunks, "macro" / "weighted": {precision, recall, f1, support} over the listed types, "token_accuracy"}.
+        Types no B / I / E / S label carries are listed only with non-zero counts; x / 0 reads 0.0."""
+        c = self.counts.cpu().tolist()
+        out, rows = {}, []
+        for t, name in enumerate(self.types):
+            predicted, support, correct = c[3 * t:3 * t + 3]
+            if self.primary[t] or predicted or support or correct:
+                p, r, f = _prf(correct, predicted, support)
+                out[name] = dict(predicted=predicted, support=support, correct=correct, precision=p, recall=r, f1=f)
+                rows.append(out[name])
+        predicted, support, correct = (sum(c[k:3 * len(self.types):3]) for k in range(3))
+        p, r, f = _prf(correct, predicted, support)
+        result = dict(out)
+        result["micro"] = dict(predicted=predicted, support=support, correct=correct, precision=p, recall=r, f1=f)
+        n = len(rows)
+        result["macro"] = dict(support=support, **{k: (sum(x[k] for x in rows) / n if n else 0.0)
+                                                    for k in ("precision", "recall", "f1")})
+        result["weighted"] = dict(support=support, **{k: (sum(x[k] * x["support"] for x in rows) / support if support else 0.0)
+                                                       for k in ("precision", "recall", "f1")})
+        equal, kept = c[-2], c[-1]
+        result["token_accuracy"] = equal / kept if kept else 0.0
+        return result

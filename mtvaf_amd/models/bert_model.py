@@ -39,6 +39,16 @@ def _crf_reduction(args):
     return reduction
 
 
+def _entity_scorer(args, label_list):
+    """args.score_entities: True (the "seqeval" scheme) or a scheme name -> an `mtvaf_amd.metrics.EntityScorer` over the
+    trainer's label map (label_list enumerated from 1, MTVAF_training.py:369); unset / False -> None."""
+    want = _arg(args, "score_entities")
+    if not want:
+        return None
+    from ..metrics import EntityScorer
+    return EntityScorer({label: i for i, label in enumerate(label_list, 1)}, scheme="seqeval" if want is True else want)
+
+
 def _on_second_stream(fn, inputs, join=False):
     """Run the prompt generator (small, low-occupancy GEMMs and mixing kernels) on the engine's second stream so it
     overlaps the embeddings and the first QKV product; the encoder waits for the prefix right before its first
@@ -182,6 +192,9 @@ class TVNetSAModel2(nn.Module):
         self.fc = nn.Linear(hidden, self.num_labels)
         self.dropout = nn.Dropout(0.1)
         _crf_reduction(args)  # (a misspelt reduction is an error here, not at the first step)
+        # args.score_entities: every forward with labels adds its entity counts to model.entity_scorer on the device (one small
+        # launch behind the Viterbi kernel, on its tags); without the switch nothing is launched
+        self.entity_scorer = _entity_scorer(args, label_list)
         if _arg(args, "use_probe"):
             raise NotImplementedError("the structural probe (probes/) is off the hot path and its import chain is "
                                       "broken in the reference (models/bert_model.py:468-475)")
@@ -224,12 +237,17 @@ class TVNetSAModel2(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 logits = self.crf.decode_deferred(emissions.detach(), mask_u8)
+                if self.entity_scorer is not None and labels is not None:
+                    self.entity_scorer.update(logits.device_tags, labels, mask_u8)
+                    labels.record_stream(side)
                 decoded = torch.cuda.Event()
                 decoded.record(side)
             emissions.record_stream(side)
             mask_u8.record_stream(side)
         else:
             logits = self.crf.decode_deferred(emissions, mask_u8)
+            if self.entity_scorer is not None and labels is not None:
+                self.entity_scorer.update(logits.device_tags, labels, mask_u8)
             decoded = None
         # args.output_tag_marginals fills self.last_tag_marginals [B,S,num_labels] -- posterior tag probabilities, zeros on
         # padding -- from the marginals kernels; without the switch the step launches nothing for them.

@@ -26,6 +26,7 @@ class DeferredTags(list):
     def __init__(self, packed_host: torch.Tensor, event, S: int, release=None):
         super().__init__()
         self._packed, self._event, self._S, self._release = packed_host, event, S, release
+        self.device_tags = None  # decode_deferred: the [B, S] int32 device tensor of the same Viterbi launch (-1 beyond each length)
 
     def _fill(self):
         if self._packed is not None:
@@ -203,7 +204,9 @@ class CRF(nn.Module):
         ev = torch.cuda.Event()
         ev.record()
         pool = self._host_pool
-        return DeferredTags(host, ev, S, release=lambda: pool.append((buf, ev)) if len(pool) < 8 else None)
+        out = DeferredTags(host, ev, S, release=lambda: pool.append((buf, ev)) if len(pool) < 8 else None)
+        out.device_tags = tags  # for on-device consumers (mtvaf_amd.metrics.EntityScorer): no second launch, no copy
+        return out
 
     def decode(self, emissions, mask: Optional[torch.Tensor] = None) -> List[List[int]]:
         tags, lens = self.decode_packed(emissions, mask)
