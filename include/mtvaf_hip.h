@@ -342,6 +342,30 @@ int mtvaf_entity_counts(const int* pred, int ldp, const int64_t* gold, const uin
                         const uint8_t* end_tab, const int* type_of, const uint8_t* gold_skip, int B, int S, int C,
                         int n_types, int64_t* counts, mtvaf_stream_t stream);
 
+/* Tagger inference, the emitting half: the entities of decoded tags with the CRF posterior of each decoded segment.  It
+ * complements the reference's decode (models/bert_model.py:511) and its host chunker (modules/eval_metrics.py::get_chunks).
+ * One launch, no host read-back, no allocation, no workspace; safe under stream capture.
+ * emissions [B,S,C] fp32; mask [B,S] u8, a PREFIX mask with mask[:,0] == 1 (ones, then zeros; L_b = the number of leading
+ * ones; masks with holes are outside the contract: everything behind the first 0 is ignored).  tags [B,ldt] int32, ldt >= S,
+ * as mtvaf_crf_viterbi writes them: only columns < L_b are read, an id outside [0,C) reads as 0.  keep [B,S] u8 names the
+ * columns that take part in chunking (only columns < L_b count); NULL = columns 1 .. L_b-1.  start_tab / end_tab / type_of:
+ * layout and meaning of mtvaf_entity_counts, index C = sentence boundary.  Over the kept labels l_j: a start at j iff
+ * start_tab[l_j-1][l_j], an end at j iff end_tab[l_j][l_j+1]; every end with a start b <= j in the sentence closes one
+ * chunk (type_of[l_j], b, j), b the greatest such start; an end without a start is dropped (neither emitted nor counted).
+ * Per chunk, over ALL columns b..e (kept or not), each fixed to its decoded tag t_k:
+ *   log_conf = alpha_b(t_b) + sum_{k=b+1..e} (trans[t_k-1][t_k] + em_k[t_k]) + beta_e(t_e) - logZ
+ * with alpha / beta / logZ of the unconstrained chain over columns 0 .. L_b-1 (start and end included): the log posterior
+ * of the decoded segment, <= 0 up to rounding, always finite (finite inputs).
+ * ents [B,max_entities,3] int32 = (start column, end column, type), unused slots -1; log_conf [B,max_entities] fp32,
+ * unused slots 0; count [B] int32 = chunks found, may exceed max_entities (then the first max_entities by end column are
+ * stored).  Chunks are ordered by end column, ascending; every output element is written on every call.
+ * 1 <= S <= 512, 1 <= C <= 64, ldt >= S (MTVAF_ERR_SHAPE); 1 <= n_types <= C+1, 1 <= max_entities <= 64 (MTVAF_ERR_ARG):
+ * checked before any launch. */
+int mtvaf_crf_entities(const float* emissions, const uint8_t* mask, const int32_t* tags, int ldt, const uint8_t* keep,
+                       const float* start, const float* end, const float* trans, const uint8_t* start_tab,
+                       const uint8_t* end_tab, const int* type_of, int n_types, int32_t* ents, float* log_conf,
+                       int32_t* count, int B, int S, int C, int max_entities, mtvaf_stream_t stream);
+
 /* Cutoff augmentation on the embedding output (modules/augument.py:99-159): out = x * row_keep[b,s] * col_keep[b,:]
  * (either mask may be NULL); x/out [B,S,H] fp32, row_keep [B*S], col_keep [B,H].  Self-adjoint: the backward is the
  * same call on the gradient. */

@@ -18,6 +18,7 @@
 // highest / lowest-set-bit searches over those words.  Counts go through LDS integer atomics per block and leave as one 64-bit
 // global atomic per block and non-zero counter: integer sums commute, so the counter is bit-reproducible.
 #include "common.h"
+#include "entity_bits.h"
 
 namespace mtvaf {
 
@@ -28,29 +29,6 @@ constexpr int ENT_WAVES = 4;                       // sentences in flight per bl
 constexpr int ENT_MAX_T = ENT_MAX_C + 1;           // type_of has C + 1 entries: no more types than that
 constexpr int ENT_MAX_CNT = ENT_MAX_T * 3 + 2;
 enum { ENT_KEEP = 0, ENT_START = 1, ENT_END = 3, ENT_SETS = 5 };  // bit sets of a sentence: keep, start[2], end[2]
-
-// greatest set bit of `bits` strictly below column c (le: at or below), or -1
-__device__ __forceinline__ int ent_prev(const uint64_t* bits, int c, bool le) {
-  int w = c >> 6;
-  const int b = c & 63;
-  uint64_t m = bits[w] & (le ? (2ull << b) - 1 : (1ull << b) - 1);  // b == 63: 2 << 63 wraps to 0, minus 1 = all ones
-  for (;;) {
-    if (m) return 64 * w + 63 - __clzll((long long)m);
-    if (--w < 0) return -1;
-    m = bits[w];
-  }
-}
-// lowest set bit strictly above column c among the first W words, or -1
-__device__ __forceinline__ int ent_next(const uint64_t* bits, int c, int W) {
-  int w = c >> 6;
-  const int b = c & 63;
-  uint64_t m = bits[w] & ~((2ull << b) - 1);
-  for (;;) {
-    if (m) return 64 * w + __ffsll((long long)m) - 1;
-    if (++w >= W) return -1;
-    m = bits[w];
-  }
-}
 
 __global__ __launch_bounds__(64 * ENT_WAVES) void entity_counts_kernel(
     const int* __restrict__ pred, int ldp, const int64_t* __restrict__ gold, const uint8_t* __restrict__ mask,

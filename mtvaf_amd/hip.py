@@ -110,6 +110,7 @@ _SIGS = {
     "mtvaf_ce_bwd": (c_int, [P, P, P, P, P, I, I, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
+    "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -801,6 +802,56 @@ def entity_counts(pred, gold, mask_u8, start_tab, end_tab, type_of, gold_skip, n
     _ck(lib().mtvaf_entity_counts(_p(pred), ldp, _p(gold), _p(mask_u8), _p(start_tab), _p(end_tab), _p(type_of), _p(gold_skip),
                                   B, S, C, int(n_types), _p(counts), _st()), "mtvaf_entity_counts")
     return counts
+
+
+CRF_ENTITIES_MAX_E = 64
+
+
+def crf_entities(em, mask_u8, tags, keep, start, end, trans, start_tab, end_tab, type_of, n_types, max_entities=32, out=None):
+    """Entities of decoded tags with the CRF posterior of each decoded segment (csrc/crf_entities.hip), one launch and no host
+    sync.  em [B,S,C] fp32, mask_u8 [B,S] uint8 (a prefix mask), tags [B,>=S] int32 (``CRF.decode_packed``'s), keep [B,S] uint8
+    or None (= columns 1 .. L-1); start / end [C], trans [C,C] fp32; start_tab / end_tab [(C+1)^2] uint8, type_of [C+1] int32.
+    -> ents [B,max_entities,3] int32 (start column, end column, type; -1 in unused slots), log_conf [B,max_entities] fp32 (0 in
+    unused slots), count [B] int32 (may exceed max_entities).  ``out``: that triple, to be overwritten."""
+    if em.dim() != 3 or tags.dim() != 2:
+        raise ValueError(f"crf_entities: emissions {tuple(em.shape)}, tags {tuple(tags.shape)}: expected [B, S, C] and [B, >=S]")
+    B, S, C = em.shape
+    max_entities, n_types = int(max_entities), int(n_types)
+    if not 1 <= S <= ENTITY_MAX_S:
+        raise ValueError(f"crf_entities: S={S} outside 1..{ENTITY_MAX_S}")
+    if not 1 <= C <= ENTITY_MAX_C:
+        raise ValueError(f"crf_entities: C={C} outside 1..{ENTITY_MAX_C}")
+    if not 1 <= max_entities <= CRF_ENTITIES_MAX_E:
+        raise ValueError(f"crf_entities: max_entities={max_entities} outside 1..{CRF_ENTITIES_MAX_E}")
+    if not 1 <= n_types <= C + 1:
+        raise ValueError(f"crf_entities: n_types={n_types} outside 1..{C + 1}")
+    if B < 1 or tags.shape[0] != B or tags.shape[1] < S or tuple(mask_u8.shape) != (B, S) or \
+            (keep is not None and tuple(keep.shape) != (B, S)):
+        raise ValueError(f"crf_entities: tags {tuple(tags.shape)} / mask {tuple(mask_u8.shape)} / keep do not fit emissions "
+                         f"[{B}, {S}, {C}]")
+    if (start.numel(), end.numel(), trans.numel(), start_tab.numel(), end_tab.numel(), type_of.numel()) != \
+            (C, C, C * C, (C + 1) ** 2, (C + 1) ** 2, C + 1):
+        raise ValueError("crf_entities: CRF parameters / tables do not fit C")
+    ldt = tags.stride(0)
+    if tags.stride(1) != 1 or ldt < S:
+        raise ValueError(f"crf_entities: tags strides {tags.stride()}: expected unit columns and a row stride >= S")
+    _f32(em, start, end, trans)
+    assert tags.dtype == torch.int32 and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert keep is None or (keep.dtype == torch.uint8 and keep.is_contiguous())
+    assert start_tab.dtype == end_tab.dtype == torch.uint8 and type_of.dtype == torch.int32
+    assert all(t.is_contiguous() for t in (start_tab, end_tab, type_of))
+    if out is None:
+        out = (torch.empty((B, max_entities, 3), dtype=torch.int32, device=em.device),
+               torch.empty((B, max_entities), dtype=torch.float32, device=em.device),
+               torch.empty(B, dtype=torch.int32, device=em.device))
+    ents, log_conf, count = out
+    assert tuple(ents.shape) == (B, max_entities, 3) and tuple(log_conf.shape) == (B, max_entities) and count.numel() == B
+    assert ents.dtype == count.dtype == torch.int32 and log_conf.dtype == torch.float32
+    assert ents.is_contiguous() and log_conf.is_contiguous() and count.is_contiguous()
+    _ck(lib().mtvaf_crf_entities(_p(em), _p(mask_u8), _p(tags), ldt, _p(keep), _p(start), _p(end), _p(trans), _p(start_tab),
+                                 _p(end_tab), _p(type_of), n_types, _p(ents), _p(log_conf), _p(count), B, S, C, max_entities,
+                                 _st()), "mtvaf_crf_entities")
+    return ents, log_conf, count
 
 
 def mask_mul(x, row_keep, col_keep, out):

@@ -121,6 +121,43 @@ def entity_tables(label_map: Dict[str, int], scheme: str = "seqeval", skip: Sequ
                 gold_skip=np.array([names[i] in skip for i in range(C)], dtype=np.uint8))
 
 
+def structural_labels(label_map: Dict[str, int]) -> tuple:
+    """The label names that are neither ``"O"`` nor of the form ``<class>-<type>``, plus ``"PAD"`` (first), in id order: for the
+    reference's list ``("PAD", "X", "[CLS]", "[SEP]")``.  `TVNetSAModel2.predict` leaves the columns whose PREDICTED label is one
+    of these out of the chunking (at inference there is no gold label to skip by)."""
+    def chunked(name):
+        klass, sep, kind = name.partition("-")
+        return bool(klass and sep and kind)
+    rest = [n for n, _ in sorted(label_map.items(), key=lambda kv: kv[1]) if n not in ("O", "PAD") and not chunked(n)]
+    return ("PAD", *rest)
+
+
+def entity_device_tables(tables: dict, device) -> dict:
+    """The tables of `entity_tables` as `mtvaf_crf_entities` reads them, on ``device``: start / end [(C+1)^2] uint8, type_of
+    [C+1] int32, plus n_types, types, names and C.  A dict that already holds tensors is returned as it is."""
+    if torch.is_tensor(tables["start"]):
+        return tables
+    out = {k: torch.from_numpy(np.ascontiguousarray(tables[k])).reshape(-1).to(device) for k in ("start", "end", "type_of")}
+    out.update(n_types=len(tables["types"]), types=list(tables["types"]), names=list(tables["names"]), C=tables["C"])
+    return out
+
+
+def entities_to_lists(result: dict, types: Sequence[str]) -> List[List[dict]]:
+    """The dict of `CRF.entities` / `TVNetSAModel2.predict` -> per sentence a list of ``{"start", "end", "type", "confidence"}``
+    (token columns, inclusive end; ``types`` names the type indices), ordered by end column: at most ``max_entities`` per sentence.
+    ONE device->host copy -- the only part of the inference path that waits for the GPU."""
+    ents, conf, count = result["entities"], result["confidence"], result["count"]
+    B, E = conf.shape
+    packed = torch.cat([ents.reshape(B, E * 3).double(), conf.double(), count.reshape(B, 1).double()], dim=1).cpu().numpy()
+    out = []
+    for row in packed:
+        n = min(int(row[-1]), E)
+        e, c = row[:E * 3].reshape(E, 3).astype(np.int64), row[E * 3:E * 4]
+        out.append([{"start": int(e[k, 0]), "end": int(e[k, 1]), "type": types[int(e[k, 2])], "confidence": float(c[k])}
+                    for k in range(n)])
+    return out
+
+
 def _prf(correct: int, predicted: int, support: int) -> Tuple[float, float, float]:
     p = correct / predicted if predicted else 0.0
     r = correct / support if support else 0.0

@@ -195,6 +195,8 @@ class TVNetSAModel2(nn.Module):
         # args.score_entities: every forward with labels adds its entity counts to model.entity_scorer on the device (one small
         # launch behind the Viterbi kernel, on its tags); without the switch nothing is launched
         self.entity_scorer = _entity_scorer(args, label_list)
+        self.label_list = list(label_list)
+        self._predict_tables = None  # (device, scheme) -> the scheme tables of `predict`, built at its first call
         if _arg(args, "use_probe"):
             raise NotImplementedError("the structural probe (probes/) is off the hot path and its import chain is "
                                       "broken in the reference (models/bert_model.py:468-475)")
@@ -270,6 +272,64 @@ class TVNetSAModel2(nn.Module):
         return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
 
     # ------------------------------------------------------------------------------------------------
+    def _entity_tables(self, device):
+        """The tagging scheme of `predict` on ``device`` (args.entity_scheme, default "seqeval") over the trainer's label map
+        (label_list enumerated from 1, MTVAF_training.py:369), plus the lookup of the structural predicted labels: built once."""
+        scheme = _arg(self.args, "entity_scheme", "seqeval")
+        key = (torch.device(device), scheme)
+        if self._predict_tables is None or self._predict_tables[0] != key:
+            from ..metrics import entity_device_tables, entity_tables, structural_labels
+            label_map = {label: i for i, label in enumerate(self.label_list, 1)}
+            t = entity_device_tables(entity_tables(label_map, scheme), device)
+            structural = structural_labels(label_map)
+            t["structural"] = torch.tensor([n in structural for n in t["names"]], dtype=torch.bool, device=device)
+            self._predict_tables = (key, t)
+        return self._predict_tables[1]
+
+    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None):
+        """Inference end to end with no host sync, in eval mode whatever mode the module is in: visual prompt -> encoder -> fc ->
+        Viterbi -> `CRF.entities`.  Chunked columns: the run of attention_mask from column 1, minus the columns whose PREDICTED
+        label is structural (`mtvaf_amd.metrics.structural_labels`: PAD, X, [CLS], [SEP]), and only those of ``word_mask``
+        [B,S] when it is given (e.g. first sub-tokens).  args.entity_scheme ("seqeval" | "reference"), args.max_entities (32).
+        -> the dict of `CRF.entities` (tags, lengths, entities, log_confidence, confidence, count) plus ``types``, the type
+        names the entities' type indices refer to; `mtvaf_amd.metrics.entities_to_lists` turns it into Python lists."""
+        # (an eval pass still reserves dropout offsets: the counter is put back, so a training run draws the same masks with or
+        # without predictions in between)
+        was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
+        self.eval()
+        try:
+            with torch.no_grad():
+                if _arg(self.args, "use_prefix"):
+                    prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
+                    prefix_len = prefix_guids[0][0].shape[2]
+                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
+                                             dtype=attention_mask.dtype)
+                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                else:
+                    prefix_guids, prompt_attention_mask = None, attention_mask
+                self.bert.encoder.output_prefix_mass = False
+                bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
+                                        past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
+                                        return_dict=True)
+                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                mask_u8 = attention_mask.to(torch.uint8)
+                tags, _ = self.crf.decode_packed(emissions, mask_u8)
+                t = self._entity_tables(emissions.device)
+                keep = torch.zeros_like(mask_u8, dtype=torch.bool)
+                keep[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0
+                keep &= ~t["structural"][tags.clamp(0, t["C"] - 1).long()]
+                if word_mask is not None:
+                    keep &= word_mask.to(keep.device) != 0
+                out = self.crf.entities(emissions, mask_u8, t, tags=tags, keep=keep,
+                                        max_entities=_arg(self.args, "max_entities", 32))
+        finally:
+            self.bert.encoder.output_prefix_mass = mass
+            engine.RNG.offset = offset
+            self.train(was_training)
+        out["types"] = t["types"]
+        return out
+
+    # ------------------------------------------------------------------------------------------------
     def _region_features(self, images, aux_imgs):
         """-> (feats [B,4,F], [aux feats [B,4,F]]).  Accepts raw images (through the frozen ResNet,
         bert_model.py:536-539) or pre-extracted pyramid features [B,F,2,2] / [B,4,F] (aux: [B,n,...])."""
@@ -289,9 +349,10 @@ class TVNetSAModel2(nn.Module):
             aux = [aux_imgs[:, i].reshape(bsz, L, -1).float() for i in range(aux_imgs.shape[1])]
         return feats, aux
 
-    def get_visual_prompt(self, images, aux_imgs, imagelabel):
+    def get_visual_prompt(self, images, aux_imgs, imagelabel, vao=True):
         """reference: models/bert_model.py:534-588.  Returns (list of num_layers (K, V) [B,NH,P,64],
-        img_tag_loss, [aux_img_tag_loss])."""
+        img_tag_loss, [aux_img_tag_loss]).  ``vao=False`` (`predict`: there are no image labels at inference) leaves the VAO
+        losses of args.vao out."""
         feats, aux = self._region_features(images, aux_imgs)
         bsz, L, Fd = feats.shape
         cfg = self.bert.config
@@ -304,7 +365,7 @@ class TVNetSAModel2(nn.Module):
 
         img_tag_loss = 0
         aux_img_tag_loss = []
-        if _arg(self.args, "vao"):
+        if _arg(self.args, "vao") and vao:
             means = engine.MeanLFunction.apply(enc.view(NI * bsz, L, 8 * hidden)).view(NI, bsz, 8 * hidden)
             target = imagelabel.to(means.device)
             heads = [self.img_classifier] + list(self.aux_img_classifier)

@@ -186,6 +186,40 @@ class CRF(nn.Module):
                         lens)
         return tags, lens
 
+    @torch.no_grad()
+    def entities(self, emissions, mask, tables, tags=None, keep=None, max_entities: int = 32) -> dict:
+        """The entities of decoded tags with the posterior of each decoded segment (mtvaf_crf_entities); no host sync.
+
+        ``mask`` is a prefix mask (ones, then zeros); ``tables`` the dict of ``mtvaf_amd.metrics.entity_tables`` or the device
+        tensors ``entity_device_tables`` made of it; ``tags`` [B,>=S] int32 as ``decode_packed`` returns them (None: decoded
+        here); ``keep`` [B,S] the columns that take part in chunking (None: columns 1 .. L-1).  ``tags``, ``keep`` and every
+        result are batch-first; emissions and mask follow ``batch_first`` as everywhere else.
+        -> dict: tags [B,S] int32, lengths [B] int32, entities [B,E,3] int32 (start column, end column, type index; -1 in
+        unused slots), log_confidence [B,E] = log p(y_b..y_e = decoded tags | x), confidence [B,E] = its exp (0 in unused
+        slots), count [B] int32 (may exceed E = max_entities: the first E chunks by end column are stored)."""
+        from ..metrics import entity_device_tables
+        emissions, _, mask = self._prep(emissions, None, mask)
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        t = entity_device_tables(tables, em.device)
+        if tags is None:  # (decode_packed on the prepared tensors)
+            tags = torch.empty(B, S, dtype=torch.int32, device=em.device)
+            lengths = torch.empty(B, dtype=torch.int32, device=em.device)
+            hip.crf_viterbi(em, mask, self.start_transitions.data, self.end_transitions.data, self.transitions.data, tags,
+                            lengths)
+        else:
+            lengths = mask.sum(dim=1, dtype=torch.int32)
+            if tags.dtype != torch.int32:
+                tags = tags.to(torch.int32)
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        ents, log_conf, count = hip.crf_entities(em, mask, tags, keep, self.start_transitions.data, self.end_transitions.data,
+                                                 self.transitions.data, t["start"], t["end"], t["type_of"], t["n_types"],
+                                                 max_entities)
+        conf = torch.where(ents[..., 0] >= 0, torch.exp(log_conf), torch.zeros_like(log_conf))
+        return {"tags": tags[:, :S], "lengths": lengths, "entities": ents, "log_confidence": log_conf, "confidence": conf,
+                "count": count}
+
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
         tags, lens = self.decode_packed(emissions, mask)
