@@ -310,6 +310,25 @@ int mtvaf_ce_fwd(const float* logits, const int64_t* labels, float* loss, float*
                  mtvaf_stream_t stream);
 int mtvaf_ce_bwd(const float* grad_out, const float* logits, const int64_t* labels, const float* ws2,
                  float* dlogits, int N, int C, mtvaf_stream_t stream);
+/* Cutoff consistency term of the span model (modules/train.py:523-538, cal_cut_loss / js_div): x, y [B,M,C] fp32
+ * contiguous, the polarity logits of the plain and of the cut pass.  The softmax runs over axis 1, the M candidate slots,
+ * separately for every (b,c) column -- the reference's dim=1 on [B,M,4].  With p = softmax_m(x), q = softmax_m(y),
+ * mbar = (p+q)/2:
+ *   loss[0] = scale / (2B) * sum_{b,m,c} mbar (2 log mbar - log p - log q)
+ * which is the value of js_div: (KL(mbar||p) + KL(mbar||q)) / 2 under kl_div's 'batchmean'.  The KLs run FROM mbar, so
+ * this is not the textbook Jensen-Shannon divergence: it is >= 0 and unbounded.  The reference's +1e-10 on the logits
+ * is dropped (softmax is shift-invariant).  Evaluated in log space with expf / logf / log1pf, so probabilities that
+ * underflow give finite values and gradients where the reference's fp32 form gives NaN.
+ * mask [B,M] u8 or NULL (an extension; NULL = the reference: padding slots take part): slots with mask 0 are left out of
+ * both softmaxes and of the sum, their dx / dy entries are exact 0; a sentence without a live slot adds 0; the divisor
+ * stays B.  row_ws [B] is scratch.  The backward recomputes everything from x, y and mask (nothing is kept from the
+ * forward): dx, dy [B,M,C] = *grad_out (device) times the gradient of loss[0], through p, q and mbar, every element
+ * written.  No floating-point atomics: the same inputs give the same bits.  B >= 1, 1 <= M <= 1024, 1 <= C <= 16
+ * (MTVAF_ERR_SHAPE, checked before any launch). */
+int mtvaf_js_consistency_fwd(const float* x, const float* y, const uint8_t* mask, float* loss, float* row_ws, int B,
+                             int M, int C, float scale, mtvaf_stream_t stream);
+int mtvaf_js_consistency_bwd(const float* grad_out, float scale, const float* x, const float* y, const uint8_t* mask,
+                             float* dx, float* dy, int B, int M, int C, mtvaf_stream_t stream);
 /* Candidate spans at eval / predict time: the eval branch of models/utils.py::span_annotate_candidates (:451-521) and
  * the host round trip around it (modules/train.py:382-410) as one launch, no host read-back.  Start logit of (b,s) at
  * logits[(b*S+s)*ld], end logit one element later (the binary_affine output, ld = 2).  word_index [B,S] int32: token

@@ -5,6 +5,7 @@
 //   * span_pool_bwd   two deterministic passes (per span, then per token) -- no float atomics
 //   * distant_ce      distant_cross_entropy (:181-190), forward and backward
 //   * ce              nn.CrossEntropyLoss (mean, ignore_index = -100) on the [N*M, C] polarity logits (:288, :302)
+//   * js_consistency  the cutoff consistency term between the plain and the cut pass (modules/train.py:523-538)
 //
 // The reference sizes JR (= widest span of the batch) and the flattened token list on the host (torch.max(...)
 // .item(), nonzero()); here both live in a small device-side `meta` block so the step has no host sync.
@@ -334,6 +335,179 @@ __global__ __launch_bounds__(256) void mask_mul_kernel(const float* __restrict__
   }
 }
 
+// Cutoff consistency term (modules/train.py:523-538, cal_cut_loss / js_div) on the [B,M,C] polarity logits of the plain
+// (x) and the cut (y) pass.  Softmax over the M slots of every (b, c) column; with p, q the two softmaxes, d = log p -
+// log q and mbar = (p + q) / 2 the summand mbar (2 log mbar - log p - log q) is  mbar * t,  t = 2 log cosh(d / 2) >= 0,
+// so everything is a function of log p and log q: no probability is ever the argument of a log, and an underflowing
+// one gives 0, not NaN.  One work-group per sentence: thread (r, c) = (tid / C, tid % C) walks slots r, r + R, ... of
+// column c (its M*C floats are read contiguously), the R partials of a column meet in an LDS tree of fixed shape.
+constexpr int JS_THREADS = 256;
+constexpr float JS_LN2 = 0.69314718055994531f;
+
+struct JsTerm {
+  float p, q, t, pmq, mbar;  // pmq = p - q
+};
+
+// lp = log p, lq = log q
+__device__ __forceinline__ JsTerm js_term(float lp, float lq) {
+  const float d = lp - lq, a = fabsf(d), hi = fmaxf(lp, lq);
+  const float w = log1pf(expf(-a)) - JS_LN2;             // log mbar - hi, in [-ln 2, 0]
+  const float e_hi = expf(hi), e_lo = expf(fminf(lp, lq));
+  JsTerm r;
+  r.p = d > 0.f ? e_hi : e_lo;
+  r.q = d > 0.f ? e_lo : e_hi;
+  r.pmq = (d > 0.f ? -e_hi : e_hi) * expm1f(-a);
+  r.mbar = expf(hi + w);
+  if (a < 0.5f) {  // |d| + 2 w cancels to ~d^2/4 here: 2 log cosh u by its series, u = d/2 (next term < 1e-10 relative)
+    const float u2 = 0.25f * d * d;
+    r.t = u2 * (1.f + u2 * (-1.f / 6.f + u2 * (2.f / 45.f + u2 * (-17.f / 1260.f + u2 * (62.f / 14175.f)))));
+  } else {
+    r.t = a + 2.f * w;
+  }
+  return r;
+}
+
+// Per-sentence state of both softmaxes, shared by the forward and the backward kernel.
+struct JsColumn {
+  float mx, my, lsx, lsy;  // column max and log sum exp(. - max) of x and y over the live slots
+  // log p and log q of one slot; the maximum and the log-sum are subtracted one after the other so that a probability
+  // near 1 keeps its relative precision whatever the magnitude of the logits
+  __device__ __forceinline__ void logs(float xv, float yv, float& lp, float& lq) const {
+    lp = (xv - mx) - lsx;
+    lq = (yv - my) - lsy;
+  }
+};
+
+// Combine (a, b) over the R row groups of every column, in a fixed tree; every thread gets its column's pair back.
+template <bool IS_MAX>
+__device__ __forceinline__ void js_col_reduce(float& a, float& b, float (*red)[JS_THREADS], int tid, int r, int c, int C,
+                                              int R, bool act) {
+  __syncthreads();  // the previous round's reads of `red` are over
+  if (act) {
+    red[0][tid] = a;
+    red[1][tid] = b;
+  }
+  __syncthreads();
+  int s = 1;
+  while (s < R) s <<= 1;
+  for (s >>= 1; s > 0; s >>= 1) {
+    if (act && r < s && r + s < R) {
+      const float a2 = red[0][tid + s * C], b2 = red[1][tid + s * C];
+      red[0][tid] = IS_MAX ? fmaxf(red[0][tid], a2) : red[0][tid] + a2;
+      red[1][tid] = IS_MAX ? fmaxf(red[1][tid], b2) : red[1][tid] + b2;
+    }
+    __syncthreads();
+  }
+  if (act) {
+    a = red[0][c];
+    b = red[1][c];
+  }
+}
+
+__device__ __forceinline__ JsColumn js_column(const float* __restrict__ xb, const float* __restrict__ yb,
+                                              const uint8_t* __restrict__ mb, float (*red)[JS_THREADS], int tid, int r, int c,
+                                              int M, int C, int R, bool act) {
+  JsColumn k;
+  k.mx = k.my = -3.0e38f;
+  if (act)
+    for (int m = r; m < M; m += R)
+      if (!mb || mb[m]) {
+        k.mx = fmaxf(k.mx, xb[m * C + c]);
+        k.my = fmaxf(k.my, yb[m * C + c]);
+      }
+  js_col_reduce<true>(k.mx, k.my, red, tid, r, c, C, R, act);
+  float sx = 0.f, sy = 0.f;
+  if (act)
+    for (int m = r; m < M; m += R)
+      if (!mb || mb[m]) {
+        sx += expf(xb[m * C + c] - k.mx);
+        sy += expf(yb[m * C + c] - k.my);
+      }
+  js_col_reduce<false>(sx, sy, red, tid, r, c, C, R, act);
+  k.lsx = logf(sx);  // a column without a live slot: -inf, and no slot ever reads it
+  k.lsy = logf(sy);
+  return k;
+}
+
+// row_ws[b] = sum_{m,c} mbar t over the live slots of sentence b
+__global__ __launch_bounds__(JS_THREADS) void js_consistency_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                                       const uint8_t* __restrict__ mask,
+                                                                       float* __restrict__ row_ws, int M, int C, int R) {
+  __shared__ float red[2][JS_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x, r = tid / C, c = tid % C;
+  const bool act = r < R;
+  const float* xb = x + (long)b * M * C;
+  const float* yb = y + (long)b * M * C;
+  const uint8_t* mb = mask ? mask + (long)b * M : nullptr;
+  const JsColumn k = js_column(xb, yb, mb, red, tid, r, c, M, C, R, act);
+  float f = 0.f, unused = 0.f;
+  if (act)
+    for (int m = r; m < M; m += R)
+      if (!mb || mb[m]) {
+        float lp, lq;
+        k.logs(xb[m * C + c], yb[m * C + c], lp, lq);
+        const JsTerm e = js_term(lp, lq);
+        f += e.mbar * e.t;
+      }
+  js_col_reduce<false>(f, unused, red, tid, r, c, C, R, act);
+  if (tid == 0) {
+    float tot = 0.f;
+    for (int cc = 0; cc < C; ++cc) tot += red[0][cc];
+    row_ws[b] = tot;
+  }
+}
+
+// loss = scale / (2 B) * sum_b row_ws[b]
+__global__ __launch_bounds__(64) void js_consistency_finish_kernel(const float* __restrict__ row_ws, float* __restrict__ loss,
+                                                                  int B, float scale) {
+  float s = 0.f;
+  for (int b = threadIdx.x; b < B; b += 64) s += row_ws[b];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) *loss = scale * s / (2.f * B);
+}
+
+// With Sp = sum_m p t and Sq = sum_m q t of the column:  dx = g (p (t - Sp) + (p - q)),  dy = g (q (t - Sq) - (p - q)),
+// g = grad_out * scale / (4 B)  (the derivative through p, q and mbar; sum_m (p - mbar) = 0 removes the other terms).
+__global__ __launch_bounds__(JS_THREADS) void js_consistency_bwd_kernel(const float* __restrict__ gout, float scale,
+                                                                       const float* __restrict__ x, const float* __restrict__ y,
+                                                                       const uint8_t* __restrict__ mask, float* __restrict__ dx,
+                                                                       float* __restrict__ dy, int B, int M, int C, int R) {
+  __shared__ float red[2][JS_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x, r = tid / C, c = tid % C;
+  const bool act = r < R;
+  const float* xb = x + (long)b * M * C;
+  const float* yb = y + (long)b * M * C;
+  float* dxb = dx + (long)b * M * C;
+  float* dyb = dy + (long)b * M * C;
+  const uint8_t* mb = mask ? mask + (long)b * M : nullptr;
+  const JsColumn k = js_column(xb, yb, mb, red, tid, r, c, M, C, R, act);
+  float sp = 0.f, sq = 0.f;
+  if (act)
+    for (int m = r; m < M; m += R)
+      if (!mb || mb[m]) {
+        float lp, lq;
+        k.logs(xb[m * C + c], yb[m * C + c], lp, lq);
+        const JsTerm e = js_term(lp, lq);
+        sp += e.p * e.t;
+        sq += e.q * e.t;
+      }
+  js_col_reduce<false>(sp, sq, red, tid, r, c, C, R, act);
+  if (!act) return;  // no barrier below
+  const float g = *gout * scale / (4.f * B);
+  for (int m = r; m < M; m += R) {
+    float vx = 0.f, vy = 0.f;
+    if (!mb || mb[m]) {
+      float lp, lq;
+      k.logs(xb[m * C + c], yb[m * C + c], lp, lq);
+      const JsTerm e = js_term(lp, lq);
+      vx = g * (e.p * (e.t - sp) + e.pmq);
+      vy = g * (e.q * (e.t - sq) - e.pmq);
+    }
+    dxb[m * C + c] = vx;
+    dyb[m * C + c] = vy;
+  }
+}
+
 }  // namespace mtvaf
 
 using namespace mtvaf;
@@ -433,6 +607,28 @@ int mtvaf_ce_bwd(const float* grad_out, const float* logits, const int64_t* labe
                  int C, hipStream_t st) {
   if (N <= 0 || C <= 0 || C > 64) return MTVAF_ERR_SHAPE;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, st, grad_out, logits, labels, ws2, dlogits, N, C);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static bool js_shape_ok(int B, int M, int C) { return B >= 1 && M >= 1 && M <= 1024 && C >= 1 && C <= 16; }
+
+int mtvaf_js_consistency_fwd(const float* x, const float* y, const uint8_t* mask, float* loss, float* row_ws, int B, int M,
+                             int C, float scale, hipStream_t st) {
+  if (!js_shape_ok(B, M, C)) return MTVAF_ERR_SHAPE;
+  const int R = std::min(JS_THREADS / C, M);
+  hipLaunchKernelGGL(js_consistency_fwd_kernel, dim3(B), dim3(JS_THREADS), 0, st, x, y, mask, row_ws, M, C, R);
+  hipLaunchKernelGGL(js_consistency_finish_kernel, dim3(1), dim3(64), 0, st, row_ws, loss, B, scale);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+int mtvaf_js_consistency_bwd(const float* grad_out, float scale, const float* x, const float* y, const uint8_t* mask,
+                             float* dx, float* dy, int B, int M, int C, hipStream_t st) {
+  if (!js_shape_ok(B, M, C)) return MTVAF_ERR_SHAPE;
+  const int R = std::min(JS_THREADS / C, M);
+  hipLaunchKernelGGL(js_consistency_bwd_kernel, dim3(B), dim3(JS_THREADS), 0, st, grad_out, scale, x, y, mask, dx, dy, B, M,
+                     C, R);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

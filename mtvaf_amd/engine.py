@@ -1431,6 +1431,32 @@ class CrossEntropyFunction(torch.autograd.Function):
         return dz, None
 
 
+class JSConsistencyFunction(torch.autograd.Function):
+    """The cutoff consistency term of modules/train.py:523-538 (cal_cut_loss / js_div) between the polarity logits of the
+    plain and of the cut pass, both [B,M,C]: scale * js_div(softmax(logits, 1), softmax(cutoff_logits, 1)) -> 0-dim tensor.
+    ``mask`` [B,M] (optional, an extension): slots with 0 leave both softmaxes and the sum.  Gradients to both logit
+    tensors, recomputed from the inputs (include/mtvaf_hip.h, mtvaf_js_consistency_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, cutoff_logits, mask=None, scale=1.0):
+        if logits.dim() != 3 or logits.shape != cutoff_logits.shape:
+            raise ValueError(f"JSConsistencyFunction: logits {tuple(logits.shape)} and cutoff_logits "
+                             f"{tuple(cutoff_logits.shape)} must be the same [B,M,C]")
+        x, y = logits.contiguous().float(), cutoff_logits.contiguous().float()
+        m8 = None if mask is None else mask.ne(0).contiguous().view(torch.uint8)
+        loss, row = _empty(1, like=x), _empty(x.shape[0], like=x)
+        hip.js_consistency_fwd(x, y, m8, loss, row, scale)
+        ctx.stash = (x, y, m8, float(scale), logits.dtype, cutoff_logits.dtype)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, y, m8, scale, tx, ty = ctx.stash
+        dx, dy = torch.empty_like(x), torch.empty_like(y)
+        hip.js_consistency_bwd(gout.contiguous().view(1).float(), scale, x, y, m8, dx, dy)
+        return dx.to(tx), dy.to(ty), None, None
+
+
 class MaskMulFunction(torch.autograd.Function):
     """Cutoff augmentation apply (modules/augument.py:99-159): x * row_keep[b,s] * col_keep[b,:]."""
 

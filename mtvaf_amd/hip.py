@@ -108,6 +108,8 @@ _SIGS = {
     "mtvaf_distant_ce_bwd": (c_int, [P, F, P, I, P, P, P, I, I, I, P]),
     "mtvaf_ce_fwd": (c_int, [P, P, P, P, I, I, P]),
     "mtvaf_ce_bwd": (c_int, [P, P, P, P, P, I, I, P]),
+    "mtvaf_js_consistency_fwd": (c_int, [P, P, P, P, P, I, I, I, F, P]),
+    "mtvaf_js_consistency_bwd": (c_int, [P, F, P, P, P, P, P, I, I, I, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
@@ -737,6 +739,25 @@ def ce_fwd(logits, labels, loss, ws2):
 def ce_bwd(gout, logits, labels, ws2, dlogits):
     N, C = logits.shape
     _ck(lib().mtvaf_ce_bwd(_p(gout), _p(logits), _p(labels), _p(ws2), _p(dlogits), N, C, _st()), "mtvaf_ce_bwd")
+
+
+def js_consistency_fwd(x, y, mask_u8, loss, row_ws, scale):
+    """x, y [B,M,C] fp32 contiguous, mask_u8 [B,M] or None; loss [1] written, row_ws [B] scratch."""
+    _f32(x, y, loss, row_ws)
+    B, M, C = x.shape
+    assert y.shape == x.shape and row_ws.numel() >= B and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and
+           tuple(mask_u8.shape) == (B, M) and mask_u8.is_contiguous())), (x.shape, y.shape, row_ws.shape)
+    _ck(lib().mtvaf_js_consistency_fwd(_p(x), _p(y), _p(mask_u8), _p(loss), _p(row_ws), B, M, C, float(scale), _st()),
+        "mtvaf_js_consistency_fwd")
+
+
+def js_consistency_bwd(gout, scale, x, y, mask_u8, dx, dy):
+    _f32(gout, x, y, dx, dy)
+    B, M, C = x.shape
+    assert y.shape == x.shape == dx.shape == dy.shape and (mask_u8 is None or (mask_u8.dtype == torch.uint8 and
+           tuple(mask_u8.shape) == (B, M) and mask_u8.is_contiguous())), (x.shape, y.shape, dx.shape, dy.shape)
+    _ck(lib().mtvaf_js_consistency_bwd(_p(gout), float(scale), _p(x), _p(y), _p(mask_u8), _p(dx), _p(dy), B, M, C, _st()),
+        "mtvaf_js_consistency_bwd")
 
 
 SPAN_PROPOSE_MAX_S, SPAN_PROPOSE_MAX_N = 512, 32

@@ -420,7 +420,8 @@ class TVNetSAModel(nn.Module):
     ``get_span_representation`` (:160-165); here they stay in a device-side index block
     (``mtvaf_span_index``), so a training step of this model has no host sync either.
 
-    ``augument=True`` runs the cutoff augmentation of ``modules/augument.py`` (``mtvaf_amd.modules.augument``).
+    ``augument=True`` runs the cutoff augmentation of ``modules/augument.py`` (``mtvaf_amd.modules.augument``);
+    ``forward_with_cutoff`` is the trainer's whole ``do_aug`` step (plain pass + cut pass + consistency term) in one call.
     Not built (out of scope): the GCN branches (``gcn_layer_number`` / ``num_layers`` > 0,
     whose modules are missing from the reference checkout) and the structural probe."""
 
@@ -470,15 +471,68 @@ class TVNetSAModel(nn.Module):
                 images=None, aux_imgs=None, valid_ids=None, adjacency_matrix=None, output_attention=False,
                 augument=False, labels=None, adj_matrix=None, src_mask=None, aspect_mask=None, polaritys=None):
         """reference: models/bert_model.py:246-321 (use_probe / GCN branches excluded)."""
-        bsz = input_ids.size(0)
-        if _arg(self.args, "use_prefix"):
+        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True)
+        loss, logits = self._loss_pass(prefix_guids, prompt_attention_mask, input_ids, attention_mask, token_type_ids,
+                                       start_positions, end_positions, span_starts, span_ends, polarity_labels,
+                                       label_masks, augument)
+        return TokenClassifierOutput(loss=loss, logits=logits)
+
+    def forward_with_cutoff(self, input_ids=None, attention_mask=None, token_type_ids=None, start_positions=None,
+                            end_positions=None, span_starts=None, span_ends=None, polarity_labels=None, label_masks=None,
+                            images=None, aux_imgs=None, valid_ids=None, adjacency_matrix=None, output_attention=False,
+                            labels=None, adj_matrix=None, src_mask=None, aspect_mask=None, polaritys=None,
+                            return_parts=False):
+        """One training step's loss with the cutoff augmentation on -- what ``SATrainer._step`` does when ``mode ==
+        "train" and args.do_aug`` (modules/train.py:412-455 with cal_cut_loss / js_div, :523-538): a plain pass, a cut
+        pass (``args.aug_type`` / ``args.aug_cutoff_ratio``) and
+
+            loss + aug_ce_loss * cutoff_loss + aug_js_loss * js_div(softmax(logits, 1), softmax(cutoff_logits, 1))
+
+        ``args.aug_ce_loss`` / ``args.aug_js_loss`` default to 1.0 (MTVAF_training.py:245-246); a weight <= 0 drops its
+        term and with both <= 0 the cut pass is not run.  ``args.aug_js_masked`` (new, default False): ``label_masks``
+        keeps the padding slots out of the consistency term; False is the reference, where they take part.
+        The visual prompt is computed once and serves both passes (``get_visual_prompt`` has no randomness, so this
+        equals the reference's two computations; autograd sums the two prefix gradients in front of one backward of the
+        generator).  In train mode the two passes draw independent dropout masks, as two ``forward`` calls do.
+        -> ``TokenClassifierOutput(loss=combined, logits=plain logits)``; with ``return_parts`` also a dict: ``loss``
+        (plain), ``cutoff_loss``, ``js`` (unweighted, detached), ``cutoff_logits`` -- None where a term was not computed."""
+        w_ce, w_js = _arg(self.args, "aug_ce_loss", 1.0), _arg(self.args, "aug_js_loss", 1.0)
+        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True)
+        batch = (prompt_attention_mask, input_ids, attention_mask, token_type_ids, start_positions, end_positions,
+                 span_starts, span_ends, polarity_labels, label_masks)
+        loss, logits = self._loss_pass(prefix_guids, *batch, False)
+        parts = {"loss": loss, "cutoff_loss": None, "js": None, "cutoff_logits": None}
+        combined = loss
+        if w_ce > 0 or w_js > 0:
+            cutoff_loss, cutoff_logits = self._loss_pass(prefix_guids, *batch, True)
+            parts.update(cutoff_loss=cutoff_loss, cutoff_logits=cutoff_logits)
+            if w_ce > 0:
+                combined = combined + w_ce * cutoff_loss
+            if w_js > 0:
+                mask = label_masks if _arg(self.args, "aug_js_masked") else None
+                js = engine.JSConsistencyFunction.apply(logits, cutoff_logits, mask, float(w_js))  # the weight rides in the kernel
+                combined = combined + js
+                if return_parts:
+                    parts["js"] = js.detach() / float(w_js)
+        out = TokenClassifierOutput(loss=combined, logits=logits)
+        return (out, parts) if return_parts else out
+
+    def _prompt_prologue(self, input_ids, attention_mask, images, aux_imgs, second_stream):
+        """-> (prefix_guids, prompt_attention_mask): the visual prompt and the attention mask extended over its slots
+        (:262-271); (None, attention_mask) without ``use_prefix``."""
+        if not _arg(self.args, "use_prefix"):
+            return None, attention_mask
+        if second_stream:
             prefix_guids = _on_second_stream(lambda: self.get_visual_prompt(images, aux_imgs), (images, aux_imgs))
-            prefix_len = prefix_guids[0][0].shape[2]
-            prefix_mask = torch.ones((bsz, prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
-            prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
         else:
-            prefix_guids = None
-            prompt_attention_mask = attention_mask
+            prefix_guids = self.get_visual_prompt(images, aux_imgs)
+        prefix_len = prefix_guids[0][0].shape[2]
+        prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
+        return prefix_guids, torch.cat((prefix_mask, attention_mask), dim=1)
+
+    def _loss_pass(self, prefix_guids, prompt_attention_mask, input_ids, attention_mask, token_type_ids, start_positions,
+                   end_positions, span_starts, span_ends, polarity_labels, label_masks, augument):
+        """Encoder + both heads + the loss of :298-303 for one (plain or cut) pass -> (loss, logits [B,M,4])."""
         ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids,
                                                    augument)
         logits, ac_logits = self.classification(attention_mask=attention_mask, span_starts=span_starts,
@@ -489,7 +543,7 @@ class TVNetSAModel(nn.Module):
         ae_loss = engine.DistantCEPairFunction.apply(ae_logits, start_positions, end_positions)
         ac_loss = engine.CrossEntropyFunction.apply(ac_logits, flat_polarity_labels)
         ac_loss = torch.sum(flat_label_masks * ac_loss) / flat_label_masks.sum()  # :303, the reference's scalar quirk
-        return TokenClassifierOutput(loss=ae_loss + ac_loss, logits=logits)
+        return ae_loss + ac_loss, logits
 
     def _extract(self, prompt_attention_mask, input_ids, prefix_guids, token_type_ids, augument=False):
         if augument:
@@ -568,13 +622,7 @@ class TVNetSAModel(nn.Module):
         -> dict: span_starts, span_ends, label_masks [B,n] int64, span_scores [B,n] fp32, logits [B,n,4] (polarity logits of
         every slot; padding slots have label_masks 0), start_logits / end_logits [B,S] the proposal read."""
         with torch.no_grad():
-            if _arg(self.args, "use_prefix"):
-                prefix_guids = self.get_visual_prompt(images, aux_imgs)
-                prefix_len = prefix_guids[0][0].shape[2]
-                prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
-                prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
-            else:
-                prefix_guids, prompt_attention_mask = None, attention_mask
+            prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, False)
             ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids)
             span_starts, span_ends, label_masks, span_scores, _ = self.propose_spans(
                 ae_logits, None, attention_mask, token_to_word=token_to_word, word_key=word_key)
