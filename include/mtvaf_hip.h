@@ -361,6 +361,32 @@ int mtvaf_entity_counts(const int* pred, int ldp, const int64_t* gold, const uin
                         const uint8_t* end_tab, const int* type_of, const uint8_t* gold_skip, int B, int S, int C,
                         int n_types, int64_t* counts, mtvaf_stream_t stream);
 
+/* Aspect-level score of the span model's predictions, the counting of modules/eval_metrics.py::eval_absa (:80-124) without
+ * the per-sentence host copies of modules/train.py:200-209: common / retrieved / relevant per polarity class, ADDED into a
+ * device counter by one launch with no host read-back.  Integers only, apart from one arg-max over fp32.
+ * span_starts / span_ends / label_masks [B,N] int64 as mtvaf_span_propose writes them, logits [B,N,K] fp32 (the polarity
+ * logits of every slot); gold_starts / gold_ends / gold_class / gold_masks [B,G] int64 (the feature's start_indexes,
+ * end_indexes, polarity_labels, label_masks: models/utils.py:304-335); word_index [B,S] int32, -1 outside the word map;
+ * word_key [B,S] int32 or NULL (= word_index), both as for mtvaf_span_propose.
+ * A span (s, e) is valid iff 0 <= s <= e < S, word_index[s] >= 0 and word_index[e] >= 0.  Its signature is word_key[t]
+ * wherever word_index[t] differs from the previous in-map token of the span (what mtvaf_span_propose de-duplicates by).
+ * A predicted slot exists iff label_masks != 0, a gold slot iff gold_masks != 0.  The predicted class is the lowest k
+ * whose logit no other logit exceeds (finite logits; NaN unspecified).  Every existing predicted slot adds 1 to
+ * retrieved[class], valid or not; every existing gold slot adds 1 to relevant[gold_class], or to relevant_other when its
+ * class is outside [0,K).  A valid predicted slot hits iff some valid gold slot of the sentence has an equal signature
+ * and an equal class; a hit adds 1 to common[class], however many gold slots match.  An invalid slot of either side
+ * never takes part in a match (an invalid gold slot is a term the feature truncated: eval_absa counts it in relevant).
+ * counts [3K+2] int64: per class retrieved, relevant, common, then relevant_other, sentences (+B per call).  64-bit
+ * integer atomics, one per block and non-zero counter: bit-reproducible.
+ * pred_class [B,N] int32 or NULL: the class of every slot, -1 on a slot that does not exist; matched_gold [B,N] int32 or
+ * NULL: the lowest matching gold slot, -1 without a hit.  Every element of a non-NULL output is written.
+ * B >= 1, 1 <= S <= 512, 1 <= N <= 32, 1 <= G <= 32, 2 <= K <= 8 (MTVAF_ERR_SHAPE, checked before any launch). */
+int mtvaf_span_counts(const int64_t* span_starts, const int64_t* span_ends, const int64_t* label_masks,
+                      const float* logits, const int64_t* gold_starts, const int64_t* gold_ends,
+                      const int64_t* gold_class, const int64_t* gold_masks, const int* word_index, const int* word_key,
+                      int B, int S, int N, int G, int K, int64_t* counts, int* pred_class, int* matched_gold,
+                      mtvaf_stream_t stream);
+
 /* Tagger inference, the emitting half: the entities of decoded tags with the CRF posterior of each decoded segment.  It
  * complements the reference's decode (models/bert_model.py:511) and its host chunker (modules/eval_metrics.py::get_chunks).
  * One launch, no host read-back, no allocation, no workspace; safe under stream capture.

@@ -15,6 +15,7 @@
 // every accepted span precedes the pairs it drops in the order, so the accepted list is the same.  No atomics; deterministic.
 // Contract: finite logits; word_index rises by 0 or 1 along each run of in-map tokens.
 #include "common.h"
+#include "span_signature.h"  // same_signature
 #include <limits.h>
 
 namespace mtvaf {
@@ -52,20 +53,6 @@ __device__ __forceinline__ void top_positions(const float (&v)[PROP_LCH], int S,
     if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
     idx_out[r] = bi;
     val_out[r] = bv;
-  }
-}
-
-// word-key signature equality of the spans [s1,e1] and [s2,e2]: the keys at every change of word_index among the in-map tokens
-__device__ __forceinline__ bool same_signature(const int* wi, const int* wk, int s1, int e1, int s2, int e2) {
-  int t1 = s1, t2 = s2, p1 = -1, p2 = -1;
-  for (;;) {
-    while (t1 <= e1 && (wi[t1] < 0 || wi[t1] == p1)) ++t1;
-    while (t2 <= e2 && (wi[t2] < 0 || wi[t2] == p2)) ++t2;
-    const bool d1 = t1 > e1, d2 = t2 > e2;
-    if (d1 || d2) return d1 && d2;
-    if (wk[t1] != wk[t2]) return false;
-    p1 = wi[t1++];
-    p2 = wi[t2++];
   }
 }
 

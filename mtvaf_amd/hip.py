@@ -112,6 +112,7 @@ _SIGS = {
     "mtvaf_js_consistency_bwd": (c_int, [P, F, P, P, P, P, P, I, I, I, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
+    "mtvaf_span_counts": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
@@ -822,6 +823,45 @@ def entity_counts(pred, gold, mask_u8, start_tab, end_tab, type_of, gold_skip, n
     assert counts.dtype == torch.int64 and all(t.is_contiguous() for t in (start_tab, end_tab, type_of, gold_skip, counts))
     _ck(lib().mtvaf_entity_counts(_p(pred), ldp, _p(gold), _p(mask_u8), _p(start_tab), _p(end_tab), _p(type_of), _p(gold_skip),
                                   B, S, C, int(n_types), _p(counts), _st()), "mtvaf_entity_counts")
+    return counts
+
+
+SPAN_COUNTS_MAX_S, SPAN_COUNTS_MAX_N, SPAN_COUNTS_MAX_G, SPAN_COUNTS_MIN_K, SPAN_COUNTS_MAX_K = 512, 32, 32, 2, 8
+
+
+def span_counts(span_starts, span_ends, label_masks, logits, gold_starts, gold_ends, gold_class, gold_masks, word_index,
+                word_key, counts, pred_class=None, matched_gold=None):
+    """Adds one batch's aspect counts into ``counts`` (csrc/span_score.hip), one launch and no host sync.  span_starts /
+    span_ends / label_masks [B,N] int64 (``span_propose``'s), logits [B,N,K] fp32; gold_starts / gold_ends / gold_class /
+    gold_masks [B,G] int64; word_index [B,S] int32 (-1 outside the word map), word_key [B,S] int32 or None (= word_index);
+    counts [3K+2] int64: per class retrieved, relevant, common, then relevant_other, sentences.  pred_class / matched_gold
+    [B,N] int32 or None: written when given."""
+    if logits.dim() != 3 or word_index.dim() != 2 or gold_starts.dim() != 2:
+        raise ValueError(f"span_counts: logits {tuple(logits.shape)}, gold {tuple(gold_starts.shape)}, word_index "
+                         f"{tuple(word_index.shape)}: expected [B, N, K], [B, G] and [B, S]")
+    B, N, K = logits.shape
+    G, S = gold_starts.shape[1], word_index.shape[1]
+    if not 1 <= S <= SPAN_COUNTS_MAX_S:
+        raise ValueError(f"span_counts: S={S} outside 1..{SPAN_COUNTS_MAX_S}")
+    if not 1 <= N <= SPAN_COUNTS_MAX_N:
+        raise ValueError(f"span_counts: N={N} outside 1..{SPAN_COUNTS_MAX_N}")
+    if not 1 <= G <= SPAN_COUNTS_MAX_G:
+        raise ValueError(f"span_counts: G={G} outside 1..{SPAN_COUNTS_MAX_G}")
+    if not SPAN_COUNTS_MIN_K <= K <= SPAN_COUNTS_MAX_K:
+        raise ValueError(f"span_counts: K={K} outside {SPAN_COUNTS_MIN_K}..{SPAN_COUNTS_MAX_K}")
+    pred, gold = (span_starts, span_ends, label_masks), (gold_starts, gold_ends, gold_class, gold_masks)
+    outs = [t for t in (pred_class, matched_gold) if t is not None]
+    if B < 1 or any(tuple(t.shape) != (B, N) for t in (*pred, *outs)) or any(tuple(t.shape) != (B, G) for t in gold) or \
+            tuple(word_index.shape) != (B, S) or (word_key is not None and tuple(word_key.shape) != (B, S)):
+        raise ValueError(f"span_counts: spans / gold / word maps do not fit logits [{B}, {N}, {K}], G={G}, S={S}")
+    if counts.numel() != 3 * K + 2:
+        raise ValueError(f"span_counts: counter of {counts.numel()} elements, expected 3 * K + 2 = {3 * K + 2}")
+    assert logits.dtype == torch.float32 and logits.is_contiguous(), (logits.dtype, logits.stride())
+    assert all(t.dtype == torch.int64 and t.is_contiguous() for t in (*pred, *gold, counts))
+    assert all(t is None or (t.dtype == torch.int32 and t.is_contiguous()) for t in (word_index, word_key, *outs))
+    _ck(lib().mtvaf_span_counts(_p(span_starts), _p(span_ends), _p(label_masks), _p(logits), _p(gold_starts), _p(gold_ends),
+                                _p(gold_class), _p(gold_masks), _p(word_index), _p(word_key), B, S, N, G, K, _p(counts),
+                                _p(pred_class), _p(matched_gold), _st()), "mtvaf_span_counts")
     return counts
 
 

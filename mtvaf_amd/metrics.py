@@ -231,3 +231,87 @@ class EntityScorer:
         equal, kept = c[-2], c[-1]
         result["token_accuracy"] = equal / kept if kept else 0.0
         return result
+
+
+# -------------------------------------------------------------------------------------------------
+# Aspect-level score of the span model on the device (csrc/span_score.hip): eval_absa's counts
+# -------------------------------------------------------------------------------------------------
+SPAN_CLASSES = ("other", "neutral", "positive", "negative")  # models/utils.py:17 id_to_label, the classifier's four outputs
+
+
+class SpanScorer:
+    """Precision / recall / F1 of `TVNetSAModel.predict`'s aspect terms against the gold terms, counted on the GPU: what
+    modules/eval_metrics.py::eval_absa counts after the trainer's per-sentence host copies (modules/train.py:200-209).
+
+    ``update`` adds one batch into a small device counter (one `mtvaf_span_counts` launch on the current stream, no host
+    sync); ``compute`` reads it once.  ``classes`` names the class ids; ``len(classes)`` must equal the K of the logits.
+    Terms are compared by word-key signature and class (include/mtvaf_hip.h), not by normalised text.  ``device=None``: the
+    device of the first ``update``."""
+
+    def __init__(self, classes: Sequence[str] = SPAN_CLASSES, device=None):
+        self.classes = tuple(classes)
+        if not 2 <= len(self.classes) <= 8:
+            raise ValueError(f"{len(self.classes)} classes: the counting kernel reads 2 to 8")
+        self.counts = torch.zeros(3 * len(self.classes) + 2, dtype=torch.int64)
+        self.device = None
+        if device is not None:
+            self._place(torch.device(device))
+
+    def _place(self, device):
+        self.counts = self.counts.to(device)
+        self.device = device
+
+    def update(self, pred: dict, gold_starts, gold_ends, gold_class, gold_masks, word_index, word_key=None, return_slots=False):
+        """pred: the dict of `TVNetSAModel.predict` (span_starts, span_ends, label_masks [B,N], logits [B,N,K]); gold_* [B,G]:
+        the feature's start_indexes, end_indexes, polarity_labels, label_masks; word_index [B,S] token -> word (-1 outside the
+        word map), word_key [B,S] or None (= word_index).  int64 / int32 / fp32 contiguous tensors are read in place, others
+        cost a cast.  -> None, or with ``return_slots`` (pred_class, matched_gold) [B,N] int32: the class of every slot (-1:
+        no such slot) and the lowest gold slot it matches (-1: none)."""
+        from . import hip
+        logits = pred["logits"]
+        if logits.dim() != 3 or logits.shape[2] != len(self.classes):
+            raise ValueError(f"logits {tuple(logits.shape)}: expected [B, N, {len(self.classes)}] for classes {self.classes}")
+        dev = logits.device
+        if self.device is None:
+            self._place(dev)
+
+        def as_(t, dtype):
+            return t.detach().to(device=dev, dtype=dtype).contiguous()
+        spans = [as_(pred[k], torch.int64) for k in ("span_starts", "span_ends", "label_masks")]
+        gold = [as_(t, torch.int64) for t in (gold_starts, gold_ends, gold_class, gold_masks)]
+        slots = [torch.empty(logits.shape[:2], dtype=torch.int32, device=dev) for _ in range(2)] if return_slots else [None, None]
+        hip.span_counts(*spans, as_(logits, torch.float32), *gold, as_(word_index, torch.int32),
+                        None if word_key is None else as_(word_key, torch.int32), self.counts, *slots)
+        return tuple(slots) if return_slots else None
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def all_reduce(self, group=None) -> None:
+        """Sums the counter over the process group (nothing without one)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        """One small device->host copy -> {class: {retrieved, relevant, common, precision, recall, f1}, ..., "micro": eval_absa's
+        {p, r, f1, common, retrieved, relevant} over all terms (``relevant`` includes the gold terms of a class outside the
+        list), "macro": {precision, recall, f1} over the classes with a non-zero count, "sentences"}.  x / 0 reads 0.0
+        (eval_absa divides by ``relevant`` unguarded: it raises on a set without gold terms)."""
+        c = self.counts.cpu().tolist()
+        K = len(self.classes)
+        out, rows = {}, []
+        for k, name in enumerate(self.classes):
+            retrieved, relevant, common = c[3 * k:3 * k + 3]
+            p, r, f = _prf(common, retrieved, relevant)
+            out[name] = dict(retrieved=retrieved, relevant=relevant, common=common, precision=p, recall=r, f1=f)
+            if retrieved or relevant or common:
+                rows.append(out[name])
+        retrieved, relevant, common = (sum(c[j:3 * K:3]) for j in range(3))
+        relevant += c[3 * K]
+        p, r, f = _prf(common, retrieved, relevant)
+        out["micro"] = dict(p=p, r=r, f1=f, common=common, retrieved=retrieved, relevant=relevant)
+        n = len(rows)
+        out["macro"] = {k: (sum(x[k] for x in rows) / n if n else 0.0) for k in ("precision", "recall", "f1")}
+        out["sentences"] = c[3 * K + 1]
+        return out

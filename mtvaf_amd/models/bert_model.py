@@ -49,6 +49,22 @@ def _entity_scorer(args, label_list):
     return EntityScorer({label: i for i, label in enumerate(label_list, 1)}, scheme="seqeval" if want is True else want)
 
 
+def _span_scorer(args):
+    """args.score_spans: True (the reference's class names) or a sequence of four class names -> an
+    `mtvaf_amd.metrics.SpanScorer` over the span classifier's four outputs; unset / False -> None."""
+    want = _arg(args, "score_spans")
+    if not want:
+        return None
+    from ..metrics import SpanScorer
+    return SpanScorer() if want is True else SpanScorer(classes=want)
+
+
+def _mask_word_map(attention_mask, device):
+    """The word map without a tokenizer's: every token with ``attention_mask`` 1 is its own word, the others are outside."""
+    pos = torch.arange(attention_mask.shape[1], device=device, dtype=torch.int32).expand(attention_mask.shape[0], -1)
+    return torch.where(attention_mask.to(device) != 0, pos, torch.full_like(pos, -1))
+
+
 def _on_second_stream(fn, inputs, join=False):
     """Run the prompt generator (small, low-occupancy GEMMs and mixing kernels) on the engine's second stream so it
     overlaps the embeddings and the first QKV product; the encoder waits for the prefix right before its first
@@ -458,6 +474,8 @@ class TVNetSAModel(nn.Module):
             self._packed_proj: Optional[_PackedLinears] = None
         self.fc = nn.Linear(hidden, self.num_labels)  # unused by forward, kept: it is in the reference's state_dict
         self.dropout = nn.Dropout(0.1)
+        # args.score_spans: `predict` with gold terms adds its aspect counts to model.span_scorer on the device
+        self.span_scorer = _span_scorer(args)
         if _arg(args, "gcn_layer_number", 0) > 0 or _arg(args, "num_layers", 0) > 0:
             raise NotImplementedError("the GCN branches are outside the accelerated path (their modules are not in "
                                       "the reference checkout either: models/bert_model.py:233-237)")
@@ -603,8 +621,7 @@ class TVNetSAModel(nn.Module):
         if token_to_word is None:
             if attention_mask is None:
                 raise ValueError("propose_spans: give attention_mask or token_to_word")
-            pos = torch.arange(ae.shape[1], device=ae.device, dtype=torch.int32).expand(ae.shape[0], -1)
-            token_to_word = torch.where(attention_mask.to(ae.device) != 0, pos, torch.full_like(pos, -1))
+            token_to_word = _mask_word_map(attention_mask, ae.device)
         filter_type = _arg(self.args, "filter_type", "f1")
         if filter_type not in ("f1", "em"):
             raise ValueError(f"args.filter_type={filter_type!r}: expected 'f1' or 'em'")
@@ -617,18 +634,28 @@ class TVNetSAModel(nn.Module):
             threshold=_arg(self.args, "logit_threshold", 8.0), use_heuristics=_arg(self.args, "use_heuristics", True), nms=nms)
 
     def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, token_to_word=None,
-                word_key=None):
+                word_key=None, gold=None):
         """Inference end to end with no host sync: visual prompt -> extraction logits -> `propose_spans` -> span classifier.
         -> dict: span_starts, span_ends, label_masks [B,n] int64, span_scores [B,n] fp32, logits [B,n,4] (polarity logits of
-        every slot; padding slots have label_masks 0), start_logits / end_logits [B,S] the proposal read."""
+        every slot; padding slots have label_masks 0), start_logits / end_logits [B,S] the proposal read.
+        ``gold``: dict ``starts, ends, classes, masks`` [B,G], the feature's start_indexes, end_indexes, polarity_labels and
+        label_masks.  With ``args.score_spans`` the call then adds the batch's aspect counts to ``self.span_scorer`` (one more
+        launch on the same stream, on the word map the proposal read) and the dict also holds pred_class, matched_gold [B,n]
+        int32 (`SpanScorer.update`).  Without ``gold`` or without the switch nothing more is launched."""
         with torch.no_grad():
             prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, False)
             ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids)
+            if gold is not None and self.span_scorer is not None and token_to_word is None:
+                token_to_word = _mask_word_map(attention_mask, ae_logits.device)  # one map for proposal and score
             span_starts, span_ends, label_masks, span_scores, _ = self.propose_spans(
                 ae_logits, None, attention_mask, token_to_word=token_to_word, word_key=word_key)
             logits, _ = self.classification(span_starts, span_ends, sequence_output, attention_mask)
-        return {"span_starts": span_starts, "span_ends": span_ends, "label_masks": label_masks, "span_scores": span_scores,
-                "logits": logits, "start_logits": ae_logits[..., 0], "end_logits": ae_logits[..., 1]}
+        out = {"span_starts": span_starts, "span_ends": span_ends, "label_masks": label_masks, "span_scores": span_scores,
+               "logits": logits, "start_logits": ae_logits[..., 0], "end_logits": ae_logits[..., 1]}
+        if gold is not None and self.span_scorer is not None:
+            out["pred_class"], out["matched_gold"] = self.span_scorer.update(
+                out, gold["starts"], gold["ends"], gold["classes"], gold["masks"], token_to_word, word_key, return_slots=True)
+        return out
 
     _region_features = TVNetSAModel2._region_features
 
