@@ -256,6 +256,21 @@ int mtvaf_crf_marginals(const float* emissions, const uint8_t* mask, const float
                         const float* trans, float* marg, float* logz, int B, int S, int C, void* workspace,
                         size_t workspace_bytes, mtvaf_stream_t stream);
 
+/* n-best Viterbi: the K best tag sequences of every sentence, 1 <= K <= 8, 1 <= C <= 64, 1 <= S <= 512 (anything else:
+ * MTVAF_ERR_SHAPE before any launch, and the workspace query returns 0; a workspace below the query: MTVAF_ERR_WORKSPACE).
+ * mask is a prefix mask with mask[:,0] == 1: len_b = its leading ones, end[] is added at step len_b - 1.
+ *   tags_out    int32 [B,K,S]: row k the k-th best path in columns < len_b, -1 behind it
+ *   scores_out  [B,K] unnormalised path scores (the terms of llh_fwd's gold-path score), non-increasing in k
+ *   logprob_out [B,K] = score - logZ_b, logZ by the forward recursion of mtvaf_crf_marginals; NULL: not computed, no forward launch
+ *   n_paths_out int32 [B] = min(K, C^len_b); ranks >= n_paths: tags -1, score and log-probability -inf.
+ * Equal scores: the lower previous tag first, then the lower previous rank; at the end the lower last tag, then the lower rank
+ * (rank 0 follows mtvaf_crf_viterbi's rule).  workspace bytes: round256(2 B S K C) back-pointers + round256(4 B) logZ +
+ * mtvaf_crf_workspace_bytes(B, S, C).  No host sync, no allocation; safe under stream capture. */
+size_t mtvaf_crf_nbest_workspace_bytes(int B, int S, int C, int K);
+int mtvaf_crf_nbest(const float* emissions, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                    int K, int32_t* tags_out, float* scores_out, float* logprob_out, int32_t* n_paths_out, int B, int S,
+                    int C, void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+
 /* ---- visual prompt generator + VAO loss ----------------------------------------------------------------------
  * replaces TVNetSAModel2.get_visual_prompt's split-mean / gates / gated sums / cat / reshape
  * (bert_model.py:544-545, 566-585) and the KLDiv(batchmean) ANP loss (:549-563).

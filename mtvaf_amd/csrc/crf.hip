@@ -13,6 +13,7 @@
 //   * whatever is not part of the serial chain is a small GEMM over all time steps on the matrix cores
 //     (v_mfma_f32_16x16x4_f32): the predicted alphas of the backward pass and the summed edge marginals.
 #include "common.h"
+#include "crf.h"
 #include "crf_wide.h"
 
 namespace mtvaf {
@@ -889,6 +890,19 @@ int crf_bwd(const float* gout, const float* em, const int64_t* tags, const uint8
 }
 }  // namespace
 
+int mtvaf::crf_logz(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                    float* logz, int B, int S, int C, void* workspace, hipStream_t st) {
+  if (C > CMAX) {
+    CrfWideWs w = crf_wide_ws(workspace, B, S, C);
+    w.logz = logz;
+    return crf_wide_logz(em, mask, start, end, trans, w, B, S, C, st);
+  }
+  const Crf16Ws w = crf16_ws(workspace, B, S);
+  if (int rc = crf16_fwd<false>(em, nullptr, mask, start, end, trans, w.alpha, logz, nullptr, B, S, C, st)) return rc;
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
 extern "C" {
 
 // C <= 16: Crf16Ws.  16 < C <= 64 (S <= 512): the wide path's layout (crf_wide.h).  0 for a shape neither path takes.
@@ -974,9 +988,7 @@ int mtvaf_crf_marginals(const float* emissions, const uint8_t* mask, const float
     if (int rc = crf_wide_marginals(emissions, mask, start, end, trans, marg, w, B, S, C, st)) return rc;
   } else {
     const Crf16Ws w = crf16_ws(workspace, B, S);
-    if (int rc = crf16_fwd<false>(emissions, nullptr, mask, start, end, trans, w.alpha, logz ? logz : w.logz, nullptr, B, S,
-                                  C, st))
-      return rc;
+    if (int rc = crf_logz(emissions, mask, start, end, trans, logz ? logz : w.logz, B, S, C, workspace, st)) return rc;
     if (int rc = crf16_bwd<CRF_MARGINALS>(nullptr, emissions, nullptr, mask, end, trans, w.alpha, marg, nullptr, B, S, C, st))
       return rc;
   }

@@ -23,13 +23,15 @@ struct CrfWideWs {
 size_t crf_wide_workspace_floats(int B, int S, int C);
 CrfWideWs crf_wide_ws(void* ws, int B, int S, int C);
 
-// each launches one kernel (one wave per sentence) on `st`; crf_wide_marginals two (forward without the gold path, then
-// the CRF_MARGINALS backward, which writes marg [B,S,C]).  grad: CRF_GRAD_MEAN (gout a scalar or NULL) or CRF_GRAD_SENTENCE
-// (gout [B]).
+// each launches one kernel (one wave per sentence) on `st`; crf_wide_marginals two (crf_wide_logz: the forward without the
+// gold path, w.logz [B] its result; then the CRF_MARGINALS backward, which writes marg [B,S,C]).  grad: CRF_GRAD_MEAN (gout a
+// scalar or NULL) or CRF_GRAD_SENTENCE (gout [B]).
 int crf_wide_fwd(const float* em, const int64_t* tags, const uint8_t* mask, const float* start, const float* end,
                  const float* trans, const CrfWideWs& w, int B, int S, int C, hipStream_t st);
 int crf_wide_bwd(int grad, const float* gout, const float* em, const int64_t* tags, const uint8_t* mask, const float* end,
                  const float* trans, float* dem, const CrfWideWs& w, int B, int S, int C, hipStream_t st);
+int crf_wide_logz(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                  const CrfWideWs& w, int B, int S, int C, hipStream_t st);
 int crf_wide_marginals(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
                        float* marg, const CrfWideWs& w, int B, int S, int C, hipStream_t st);
 int crf_wide_viterbi(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,

@@ -541,13 +541,20 @@ int crf_wide_bwd(int grad, const float* gout, const float* em, const int64_t* ta
   return MTVAF_OK;
 }
 
-int crf_wide_marginals(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
-                       float* marg, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
+int crf_wide_logz(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                  const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
   const size_t lds = (size_t)S * (2 * sizeof(float) + sizeof(int) + 1);
 #define L(CT) hipLaunchKernelGGL(HIP_KERNEL_NAME(crfw::crf_wide_fwd_kernel<CT, false>), dim3(B), dim3(64), lds, st, em, \
                                  nullptr, mask, start, end, trans, w.alpha, w.sp, w.mx, w.logz, nullptr, S, C)
   CRFW_DISPATCH(C, L)
 #undef L
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+int crf_wide_marginals(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                       float* marg, const CrfWideWs& w, int B, int S, int C, hipStream_t st) {
+  if (int rc = crf_wide_logz(em, mask, start, end, trans, w, B, S, C, st)) return rc;
   crf_wide_bwd_launch<CRF_MARGINALS>(nullptr, em, nullptr, mask, end, trans, marg, w, B, S, C, st);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;

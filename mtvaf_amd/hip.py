@@ -113,6 +113,8 @@ _SIGS = {
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_span_counts": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
+    "mtvaf_crf_nbest_workspace_bytes": (SZ, [I, I, I, I]),
+    "mtvaf_crf_nbest": (c_int, [P, P, P, P, P, I, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
@@ -913,6 +915,48 @@ def crf_entities(em, mask_u8, tags, keep, start, end, trans, start_tab, end_tab,
                                  _p(end_tab), _p(type_of), n_types, _p(ents), _p(log_conf), _p(count), B, S, C, max_entities,
                                  _st()), "mtvaf_crf_entities")
     return ents, log_conf, count
+
+
+CRF_NBEST_MAX_K = 8
+
+
+def crf_nbest(em, mask_u8, start, end, trans, nbest, return_logprob=True, out=None):
+    """The ``nbest`` best tag sequences of every sentence (csrc/crf_nbest.hip); no host sync.  em [B,S,C] fp32, mask_u8 [B,S]
+    uint8 (a prefix mask with mask[:,0] == 1), start / end [C], trans [C,C] fp32.
+    -> tags [B,K,S] int32 (row k the k-th best path, -1 behind the sentence), scores [B,K] fp32 (unnormalised, non-increasing),
+    logprob [B,K] fp32 = score - logZ (None without ``return_logprob``: the forward recursion is then not launched), n_paths [B]
+    int32 = min(K, C^len); ranks >= n_paths hold -1 / -inf / -inf.  ``out``: that quadruple, to be overwritten."""
+    if em.dim() != 3:
+        raise ValueError(f"crf_nbest: emissions {tuple(em.shape)}: expected [B, S, C]")
+    B, S, C = em.shape
+    K = int(nbest)
+    if not 1 <= K <= CRF_NBEST_MAX_K:
+        raise ValueError(f"crf_nbest: nbest={K} outside 1..{CRF_NBEST_MAX_K}")
+    if not 1 <= S <= ENTITY_MAX_S:
+        raise ValueError(f"crf_nbest: S={S} outside 1..{ENTITY_MAX_S}")
+    if not 1 <= C <= ENTITY_MAX_C:
+        raise ValueError(f"crf_nbest: C={C} outside 1..{ENTITY_MAX_C}")
+    if B < 1 or tuple(mask_u8.shape) != (B, S):
+        raise ValueError(f"crf_nbest: mask {tuple(mask_u8.shape)} does not fit emissions [{B}, {S}, {C}]")
+    if (start.numel(), end.numel(), trans.numel()) != (C, C, C * C):
+        raise ValueError("crf_nbest: CRF parameters do not fit C")
+    _f32(em, start, end, trans)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    if out is None:
+        out = (torch.empty((B, K, S), dtype=torch.int32, device=em.device),
+               torch.empty((B, K), dtype=torch.float32, device=em.device),
+               torch.empty((B, K), dtype=torch.float32, device=em.device) if return_logprob else None,
+               torch.empty(B, dtype=torch.int32, device=em.device))
+    tags, scores, logprob, n_paths = out
+    assert tuple(tags.shape) == (B, K, S) and tuple(scores.shape) == (B, K) and n_paths.numel() == B
+    assert tags.dtype == n_paths.dtype == torch.int32 and scores.dtype == torch.float32
+    assert tags.is_contiguous() and scores.is_contiguous() and n_paths.is_contiguous()
+    assert logprob is None or (tuple(logprob.shape) == (B, K) and logprob.dtype == torch.float32 and logprob.is_contiguous())
+    wsb = lib().mtvaf_crf_nbest_workspace_bytes(B, S, C, K)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=em.device)
+    _ck(lib().mtvaf_crf_nbest(_p(em), _p(mask_u8), _p(start), _p(end), _p(trans), K, _p(tags), _p(scores), _p(logprob),
+                              _p(n_paths), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_nbest")
+    return tags, scores, logprob, n_paths
 
 
 def mask_mul(x, row_keep, col_keep, out):

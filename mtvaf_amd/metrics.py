@@ -158,6 +158,25 @@ def entities_to_lists(result: dict, types: Sequence[str]) -> List[List[dict]]:
     return out
 
 
+def nbest_to_lists(result: dict) -> List[List[Tuple[List[int], float, float]]]:
+    """The dict of `CRF.decode_nbest` -> per sentence its ``n_paths`` hypotheses, best first, as ``(tags, score, prob)``:
+    the tag list without padding, the unnormalised path score and ``exp(logprob)`` (None if the log-probabilities were not asked
+    for).  ONE device->host copy."""
+    tags, scores, logprob, n_paths = result["tags"], result["scores"], result["logprob"], result["n_paths"]
+    B, K, S = tags.shape
+    cols = [tags.reshape(B, K * S).double(), scores.double(), n_paths.reshape(B, 1).double()]
+    if logprob is not None:
+        cols.append(logprob.double())
+    packed = torch.cat(cols, dim=1).cpu().numpy()
+    out = []
+    for row in packed:
+        t, sc, n = row[:K * S].reshape(K, S).astype(np.int64), row[K * S:K * S + K], int(row[K * S + K])
+        lp = row[K * S + K + 1:] if logprob is not None else None
+        out.append([(t[k][t[k] >= 0].tolist(), float(sc[k]), float(np.exp(lp[k])) if lp is not None else None)
+                    for k in range(n)])
+    return out
+
+
 def _prf(correct: int, predicted: int, support: int) -> Tuple[float, float, float]:
     p = correct / predicted if predicted else 0.0
     r = correct / support if support else 0.0

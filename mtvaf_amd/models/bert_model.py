@@ -345,6 +345,56 @@ class TVNetSAModel2(nn.Module):
         out["types"] = t["types"]
         return out
 
+    def predict_nbest(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, nbest=None):
+        """`predict` with the ``nbest`` best tag sequences of every sentence instead of the best one (args.nbest, default 4; 1..8):
+        the same prologue (visual prompt -> encoder -> fc, eval mode, no host sync, dropout counter put back), then
+        `CRF.decode_nbest`, then every hypothesis through `CRF.entities` as one batch of B * K rows against the repeated emissions
+        -- each hypothesis gets its entities and their posterior confidence in `predict`'s format and by `predict`'s column rule.
+        -> dict: tags [B,K,S], scores / logprob [B,K], n_paths [B] (`CRF.decode_nbest`); lengths / count [B,K], entities
+        [B,K,E,3], log_confidence / confidence [B,K,E] (`CRF.entities`), ``types``.  Hypothesis 0 is `predict`'s answer; ranks >=
+        n_paths have no entities."""
+        K = int(_arg(self.args, "nbest", 4) if nbest is None else nbest)
+        # (the prologue is `predict`'s, restated: that method is left as it is)
+        was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
+        self.eval()
+        try:
+            with torch.no_grad():
+                if _arg(self.args, "use_prefix"):
+                    prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
+                    prefix_len = prefix_guids[0][0].shape[2]
+                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
+                                             dtype=attention_mask.dtype)
+                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                else:
+                    prefix_guids, prompt_attention_mask = None, attention_mask
+                self.bert.encoder.output_prefix_mass = False
+                bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
+                                        past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
+                                        return_dict=True)
+                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                mask_u8 = attention_mask.to(torch.uint8)
+                out = self.crf.decode_nbest(emissions, mask_u8, nbest=K)
+                B, _, S = out["tags"].shape
+                tags = out["tags"].view(B * K, S)
+                t = self._entity_tables(emissions.device)
+                keep = torch.zeros_like(mask_u8, dtype=torch.bool)
+                keep[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0
+                if word_mask is not None:
+                    keep &= word_mask.to(keep.device) != 0
+                keep = keep.repeat_interleave(K, dim=0) & ~t["structural"][tags.clamp(0, t["C"] - 1).long()]
+                exists = torch.arange(K, device=keep.device)[None, :] < out["n_paths"][:, None]
+                keep &= exists.reshape(B * K, 1)  # a rank without a path chunks nothing
+                ent = self.crf.entities(emissions.repeat_interleave(K, dim=0), mask_u8.repeat_interleave(K, dim=0), t, tags=tags,
+                                        keep=keep, max_entities=_arg(self.args, "max_entities", 32))
+        finally:
+            self.bert.encoder.output_prefix_mass = mass
+            engine.RNG.offset = offset
+            self.train(was_training)
+        for k in ("lengths", "entities", "log_confidence", "confidence", "count"):
+            out[k] = ent[k].view(B, K, *ent[k].shape[1:])
+        out["types"] = t["types"]
+        return out
+
     # ------------------------------------------------------------------------------------------------
     def _region_features(self, images, aux_imgs):
         """-> (feats [B,4,F], [aux feats [B,4,F]]).  Accepts raw images (through the frozen ResNet,

@@ -1,7 +1,7 @@
 """Linear-chain CRF module with the public surface of ``torchcrf.CRF`` as the reference uses it
 (models/bert_model.py:464 ``CRF(num_labels, batch_first=True)``, :511 ``decode``, :521
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
-mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi.  Parameter names (``start_transitions``,
+mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest.  Parameter names (``start_transitions``,
 ``end_transitions``, ``transitions``) and the uniform(-0.1, 0.1) initialisation follow pytorch-crf.
 """
 from __future__ import annotations
@@ -185,6 +185,20 @@ class CRF(nn.Module):
         hip.crf_viterbi(em, mask, self.start_transitions.data, self.end_transitions.data, self.transitions.data, tags,
                         lens)
         return tags, lens
+
+    @torch.no_grad()
+    def decode_nbest(self, emissions, mask: Optional[torch.Tensor] = None, nbest: int = 4, return_logprob: bool = True) -> dict:
+        """The ``nbest`` (1..8) best tag sequences of every sentence on the device (mtvaf_crf_nbest); no host sync, nothing copied.
+
+        ``mask`` is a prefix mask (ones, then zeros); emissions and mask follow ``batch_first``, every result is batch-first.
+        -> dict: tags [B,K,S] int32 (row k the k-th best path, -1 behind the sentence), scores [B,K] (unnormalised path scores,
+        non-increasing), logprob [B,K] = score - logZ (None without ``return_logprob``), n_paths [B] int32 = min(K, C^length):
+        ranks >= n_paths hold tags -1, score -inf and logprob -inf.  Equal scores: the lower previous tag first, then the lower
+        previous rank, so row 0 is ``decode_packed``'s path.  `mtvaf_amd.metrics.nbest_to_lists` turns it into Python lists."""
+        emissions, _, mask = self._prep(emissions, None, mask)
+        tags, scores, logprob, n_paths = hip.crf_nbest(emissions.contiguous(), mask, self.start_transitions.data,
+                                                       self.end_transitions.data, self.transitions.data, nbest, return_logprob)
+        return {"tags": tags, "scores": scores, "logprob": logprob, "n_paths": n_paths}
 
     @torch.no_grad()
     def entities(self, emissions, mask, tables, tags=None, keep=None, max_entities: int = 32) -> dict:
