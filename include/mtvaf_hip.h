@@ -271,6 +271,41 @@ int mtvaf_crf_nbest(const float* emissions, const uint8_t* mask, const float* st
                     int K, int32_t* tags_out, float* scores_out, float* logprob_out, int32_t* n_paths_out, int B, int S,
                     int C, void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
 
+/* per-token tag constraints (csrc/crf_lattice.hip): likelihood, posteriors and decoding over the paths a per-position tag
+ * set allows.  allowed int64 [B,S], read as an unsigned word: bit j set = tag j may be taken at that column.  The effective
+ * set is A[b,t] = allowed[b,t] & (2^C - 1), and the full set where that is empty (0 = no constraint, bits >= C ignored), so
+ * every input has a finite answer and nothing is checked on the host.  1 <= C <= 64, 1 <= S <= 512 (anything else:
+ * MTVAF_ERR_SHAPE before any launch, and the workspace query returns 0; a workspace below the query: MTVAF_ERR_WORKSPACE).
+ * mask is a prefix mask with mask[:,0] == 1: len_b = its leading ones, columns at or beyond len_b are never read, end[]
+ * enters at column len_b - 1.  score(y) is llh_fwd's path score; logZ_A[b] = log sum_{y: y_t in A[b,t]} exp score(y).
+ *   lattice_fwd        pllh[b] = logZ_A[b] - logZ[b] <= 0; logz_a [B] and logz [B] may be NULL; leaves in the workspace what
+ *                      lattice_bwd reads.
+ *   lattice_bwd        gradients of sum_b grad[b] pllh[b]: demissions[b,t,:] = grad[b] (muA - mu) at unmasked columns, exact
+ *                      zeros at masked ones; dstart/dend/dtrans from the two sets of node and edge marginals, overwritten
+ *                      or accumulated as by llh_bwd.
+ *   lattice_marginals  marg[b,t,j] = muA, the posterior under the constraint: exact zeros at disallowed tags and masked
+ *                      columns; logz_a [B] may be NULL.  Overwrites the workspace of a preceding lattice_fwd.
+ *   lattice_viterbi    tags_out int32 [B,S] the best allowed path (-1 behind len_b), lens_out int32 [B] = len_b, score_out [B]
+ *                      (may be NULL) its unnormalised score.  Ties: the lowest allowed previous tag, at the end the lowest
+ *                      allowed last tag; mtvaf_crf_viterbi's order of additions, so full sets give its output bit for bit.
+ * A sentence whose effective sets are all full has pllh[b] == +0.0 and contributes exact zeros to every gradient.  The
+ * constrained chain takes its per-step maximum over the allowed tags only: finite inputs give finite results however far
+ * the allowed emissions lie below the others.  No host sync, no allocation; safe under single-stream capture. */
+size_t mtvaf_crf_lattice_workspace_bytes(int B, int S, int C);
+int mtvaf_crf_lattice_fwd(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
+                          const float* end, const float* trans, float* pllh, float* logz_a, float* logz, int B, int S,
+                          int C, void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_lattice_bwd(const float* grad, const float* emissions, const int64_t* allowed, const uint8_t* mask,
+                          const float* start, const float* end, const float* trans, float* demissions, float* dstart,
+                          float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
+                          size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_lattice_marginals(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
+                                const float* end, const float* trans, float* marg, float* logz_a, int B, int S, int C,
+                                void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_lattice_viterbi(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
+                              const float* end, const float* trans, int32_t* tags_out, int32_t* lens_out, float* score_out,
+                              int B, int S, int C, mtvaf_stream_t stream);
+
 /* ---- visual prompt generator + VAO loss ----------------------------------------------------------------------
  * replaces TVNetSAModel2.get_visual_prompt's split-mean / gates / gated sums / cat / reshape
  * (bert_model.py:544-545, 566-585) and the KLDiv(batchmean) ANP loss (:549-563).

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 # The flags are part of every object's stamp, so a variant can never be mistaken for the product build.
 LIBDIR = os.environ.get("MTVAF_LIBDIR") or os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmtvaf_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16x.hip", "gemm_bf16p.hip", "gemm_f32x3.hip", "gemm_f32p.hip", "gemm_f32pw.hip", "attention.hip", "attention_f32s.hip", "attention_bf16.hip", "rowops.hip", "crf.hip", "crf_wide.hip", "crf_entities.hip", "crf_nbest.hip", "prompt.hip", "span.hip", "span_propose.hip", "span_score.hip", "entity.hip", "optim.hip", "executor.hip", "runtime.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16x.hip", "gemm_bf16p.hip", "gemm_f32x3.hip", "gemm_f32p.hip", "gemm_f32pw.hip", "attention.hip", "attention_f32s.hip", "attention_bf16.hip", "rowops.hip", "crf.hip", "crf_wide.hip", "crf_entities.hip", "crf_nbest.hip", "crf_lattice.hip", "prompt.hip", "span.hip", "span_propose.hip", "span_score.hip", "entity.hip", "optim.hip", "executor.hip", "runtime.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"] + os.environ.get("MTVAF_EXTRA_FLAGS", "").split()
 # The attention kernels read their MFMA results with VALU code every 16 products (softmax, dS): keeping the
 # accumulators in architectural VGPRs saves ~200 v_accvgpr moves per key tile (gfx950 has one unified file).
@@ -27,7 +27,11 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_f32s.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # the operand split writes its residuals as scalar subtractions: the SLP vectoriser would pair them into
                # v_pk_add_f32, which issues slower beside MFMAs (csrc/gemm_f32x3.hip, resid2)
-               "gemm_f32x3.hip": ["-fno-slp-vectorize"]}
+               "gemm_f32x3.hip": ["-fno-slp-vectorize"],
+               # exact zeros for unconstrained sentences: the two chains' results are subtracted before they are scaled, and no
+               # backend may fuse such a difference into the product that feeds it (csrc/crf_lattice.hip; the file's pragma
+               # alone leaves the code generator's global fusion mode at "fast")
+               "crf_lattice.hip": ["-ffp-contract=off"]}
 
 
 def _headers_digest() -> bytes:

@@ -1253,6 +1253,32 @@ class CRFLLHFunction(torch.autograd.Function):
         return dem, ds, de, dt, None, None
 
 
+class CRFLatticeFunction(torch.autograd.Function):
+    """(pllh, logz_a, logz), each [B]: pllh[b] = logZ_A[b] - logZ[b], the log-probability of the paths the tag sets ``allowed``
+    [B,S] int64 permit (mtvaf_crf_lattice_fwd).  Only pllh carries a gradient: one mtvaf_crf_lattice_bwd call takes its [B]
+    upstream gradient as it is; logz_a and logz are returned for inspection and marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, allowed, mask_u8):
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        ws, wsb = hip.crf_lattice_workspace(B, S, C, em.device)
+        pllh, logz_a, logz = _empty(B, like=em), _empty(B, like=em), _empty(B, like=em)
+        hip.crf_lattice_fwd(em, allowed, mask_u8, start, end, trans, pllh, logz_a, logz, ws, wsb)
+        ctx.stash = (em, start, end, trans, allowed, mask_u8, ws, wsb)
+        ctx.mark_non_differentiable(logz_a, logz)
+        return pllh, logz_a, logz
+
+    @staticmethod
+    def backward(ctx, gout, _ga, _gz):
+        em, start, end, trans, allowed, mask_u8, ws, wsb = ctx.stash
+        g = gout.contiguous().float()
+        dem = torch.empty_like(em)
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(trans)
+        hip.crf_lattice_bwd(g, em, allowed, mask_u8, start, end, trans, dem, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, None, None
+
+
 # -------------------------------------------------------------------------------------------------
 class PromptFunction(torch.autograd.Function):
     """enc [NI,B,L,4W] + packed projector weights -> pkv [NL,2,B,(NI*L)*(W/2)].

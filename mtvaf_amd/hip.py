@@ -116,6 +116,11 @@ _SIGS = {
     "mtvaf_crf_nbest_workspace_bytes": (SZ, [I, I, I, I]),
     "mtvaf_crf_nbest": (c_int, [P, P, P, P, P, I, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
+    "mtvaf_crf_lattice_workspace_bytes": (SZ, [I, I, I]),
+    "mtvaf_crf_lattice_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_lattice_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    "mtvaf_crf_lattice_marginals": (c_int, [P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_lattice_viterbi": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -957,6 +962,67 @@ def crf_nbest(em, mask_u8, start, end, trans, nbest, return_logprob=True, out=No
     _ck(lib().mtvaf_crf_nbest(_p(em), _p(mask_u8), _p(start), _p(end), _p(trans), K, _p(tags), _p(scores), _p(logprob),
                               _p(n_paths), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_nbest")
     return tags, scores, logprob, n_paths
+
+
+# ---- per-token tag constraints (csrc/crf_lattice.hip) -------------------------------------------------------------
+CRF_LATTICE_MAX_S = 512
+CRF_LATTICE_MAX_C = 64
+
+
+def crf_lattice_check(em, allowed, mask_u8=None, who="crf_lattice"):
+    """Argument checks shared by the lattice entry points (host-side: shapes and dtypes only, nothing is read).  em [B,S,C]
+    fp32, allowed [B,S] int64 (bit j of a word = tag j allowed; 0 = no constraint), mask_u8 [B,S] uint8."""
+    if em.dim() != 3:
+        raise ValueError(f"{who}: emissions {tuple(em.shape)}: expected [B, S, C]")
+    B, S, C = em.shape
+    if not 1 <= C <= CRF_LATTICE_MAX_C:
+        raise ValueError(f"{who}: C={C} outside 1..{CRF_LATTICE_MAX_C}")
+    if not 1 <= S <= CRF_LATTICE_MAX_S:
+        raise ValueError(f"{who}: S={S} outside 1..{CRF_LATTICE_MAX_S}")
+    if B < 1:
+        raise ValueError(f"{who}: empty batch")
+    if not isinstance(allowed, torch.Tensor) or allowed.dtype != torch.int64:
+        raise ValueError(f"{who}: allowed must be an int64 tensor of tag-set words, got "
+                         f"{getattr(allowed, 'dtype', type(allowed).__name__)}")
+    if tuple(allowed.shape) != (B, S):
+        raise ValueError(f"{who}: allowed {tuple(allowed.shape)} does not fit emissions [{B}, {S}, {C}]")
+    if mask_u8 is not None and tuple(mask_u8.shape) != (B, S):
+        raise ValueError(f"{who}: mask {tuple(mask_u8.shape)} does not fit emissions [{B}, {S}, {C}]")
+    return B, S, C
+
+
+def crf_lattice_workspace(B, S, C, device):
+    n = lib().mtvaf_crf_lattice_workspace_bytes(B, S, C)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def crf_lattice_fwd(em, allowed, mask_u8, start, end, trans, pllh, logz_a, logz, ws, wsb):
+    """pllh [B] = logZ_A - logZ; logz_a / logz [B] or None; the workspace keeps what crf_lattice_bwd reads."""
+    B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_fwd")
+    _ck(lib().mtvaf_crf_lattice_fwd(_p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(pllh), _p(logz_a),
+                                    _p(logz), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_lattice_fwd")
+
+
+def crf_lattice_bwd(grad, em, allowed, mask_u8, start, end, trans, dem, dstart, dend, dtrans, accumulate, ws, wsb):
+    """grad [B]: the upstream gradient of every sentence's pllh."""
+    B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_bwd")
+    _ck(lib().mtvaf_crf_lattice_bwd(_p(grad), _p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(dem),
+                                    _p(dstart), _p(dend), _p(dtrans), int(accumulate), B, S, C, _p(ws), wsb, _st()),
+        "mtvaf_crf_lattice_bwd")
+
+
+def crf_lattice_marginals(em, allowed, mask_u8, start, end, trans, marg, logz_a, ws, wsb):
+    """marg [B,S,C] posteriors under the constraint (zeros at disallowed tags and masked columns); logz_a [B] or None."""
+    B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_marginals")
+    _ck(lib().mtvaf_crf_lattice_marginals(_p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(marg),
+                                          _p(logz_a), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_lattice_marginals")
+
+
+def crf_lattice_viterbi(em, allowed, mask_u8, start, end, trans, tags_out, lens_out, score_out=None):
+    """tags_out [B,S] int32 the best allowed path (-1 behind the sentence), lens_out [B] int32, score_out [B] fp32 or None."""
+    B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_viterbi")
+    _ck(lib().mtvaf_crf_lattice_viterbi(_p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(tags_out),
+                                        _p(lens_out), _p(score_out), B, S, C, _st()), "mtvaf_crf_lattice_viterbi")
 
 
 def mask_mul(x, row_keep, col_keep, out):

@@ -219,8 +219,11 @@ class TVNetSAModel2(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
-                images=None, aux_imgs=None):
-        """reference: models/bert_model.py:480-532"""
+                images=None, aux_imgs=None, allowed_tags=None):
+        """reference: models/bert_model.py:480-532.  ``allowed_tags`` int64 [B,S] (`mtvaf_amd.constraints`: per-column tag sets of a
+        partly annotated batch), given with ``labels=None``: the loss is ``-CRF.partial_llh`` -- the marginal likelihood of the
+        paths the sets permit -- with args.crf_reduction, plus the same ``alpha * img_tag_loss`` term.  Without it the method runs
+        the code it always ran."""
         bsz = input_ids.size(0)
         img_tag_loss = 0
         if _arg(self.args, "use_prefix"):
@@ -281,6 +284,11 @@ class TVNetSAModel2(nn.Module):
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
             if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
                 loss = loss + extra
+        elif allowed_tags is not None:
+            loss = -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=_crf_reduction(self.args))
+            extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
+            if torch.is_tensor(extra) or extra != 0:
+                loss = loss + extra
         if decoded is not None:
             # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
             # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)
@@ -330,6 +338,53 @@ class TVNetSAModel2(nn.Module):
                 emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 tags, _ = self.crf.decode_packed(emissions, mask_u8)
+                t = self._entity_tables(emissions.device)
+                keep = torch.zeros_like(mask_u8, dtype=torch.bool)
+                keep[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0
+                keep &= ~t["structural"][tags.clamp(0, t["C"] - 1).long()]
+                if word_mask is not None:
+                    keep &= word_mask.to(keep.device) != 0
+                out = self.crf.entities(emissions, mask_u8, t, tags=tags, keep=keep,
+                                        max_entities=_arg(self.args, "max_entities", 32))
+        finally:
+            self.bert.encoder.output_prefix_mass = mass
+            engine.RNG.offset = offset
+            self.train(was_training)
+        out["types"] = t["types"]
+        return out
+
+    def predict_constrained(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
+                            allowed=None):
+        """`predict` with the decoder searching only among the tag sequences that the input's layout permits, instead of decoding
+        freely and dropping the columns whose predicted label is structural afterwards: the same prologue (visual prompt ->
+        encoder -> fc, eval mode, no host sync, dropout counter put back), then `CRF.decode_constrained` over ``allowed`` int64
+        [B,S] (`mtvaf_amd.constraints`; None: `structural_sets` of the trainer's label map, the attention mask and ``word_mask``
+        -- [CLS] / [SEP] at the ends, X on the columns outside ``word_mask``, no structural tag on a word column), then
+        `CRF.entities` on those tags by `predict`'s column rule.  -> `predict`'s dict.  The reported confidence stays the
+        posterior of the decoded segment under the UNCONSTRAINED chain, p(y_b..y_e | x), not conditioned on the sets."""
+        # (the prologue is `predict`'s, restated: that method is left as it is)
+        was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
+        self.eval()
+        try:
+            with torch.no_grad():
+                if _arg(self.args, "use_prefix"):
+                    prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
+                    prefix_len = prefix_guids[0][0].shape[2]
+                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
+                                             dtype=attention_mask.dtype)
+                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                else:
+                    prefix_guids, prompt_attention_mask = None, attention_mask
+                self.bert.encoder.output_prefix_mass = False
+                bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
+                                        past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
+                                        return_dict=True)
+                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                mask_u8 = attention_mask.to(torch.uint8)
+                if allowed is None:
+                    from ..constraints import structural_sets
+                    allowed = structural_sets({label: i for i, label in enumerate(self.label_list, 1)}, attention_mask, word_mask)
+                tags, _ = self.crf.decode_constrained(emissions, allowed.to(emissions.device), mask_u8)
                 t = self._entity_tables(emissions.device)
                 keep = torch.zeros_like(mask_u8, dtype=torch.bool)
                 keep[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0

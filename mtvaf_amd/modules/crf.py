@@ -1,7 +1,8 @@
 """Linear-chain CRF module with the public surface of ``torchcrf.CRF`` as the reference uses it
 (models/bert_model.py:464 ``CRF(num_labels, batch_first=True)``, :511 ``decode``, :521
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
-mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest.  Parameter names (``start_transitions``,
+mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest, and over per-position
+tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``constrained_marginals``, ``decode_constrained``).  Parameter names (``start_transitions``,
 ``end_transitions``, ``transitions``) and the uniform(-0.1, 0.1) initialisation follow pytorch-crf.
 """
 from __future__ import annotations
@@ -233,6 +234,75 @@ class CRF(nn.Module):
         conf = torch.where(ents[..., 0] >= 0, torch.exp(log_conf), torch.zeros_like(log_conf))
         return {"tags": tags[:, :S], "lengths": lengths, "entities": ents, "log_confidence": log_conf, "confidence": conf,
                 "count": count}
+
+    # ---- per-token tag constraints (csrc/crf_lattice.hip) ----
+    def _prep_allowed(self, emissions, allowed, mask, who):
+        """``_prep`` plus the tag-set words: ``allowed`` follows ``batch_first`` like the mask and must be int64 [B,S]."""
+        if not isinstance(allowed, torch.Tensor) or allowed.dtype != torch.int64:
+            raise ValueError(f"{who}: allowed must be an int64 tensor of tag-set words (bit j = tag j allowed), got "
+                             f"{getattr(allowed, 'dtype', type(allowed).__name__)}")
+        if allowed.dim() != 2:
+            raise ValueError(f"{who}: allowed {tuple(allowed.shape)}: expected two dimensions")
+        emissions, _, mask = self._prep(emissions, None, mask)
+        if not self.batch_first:
+            allowed = allowed.transpose(0, 1)
+        hip.crf_lattice_check(emissions, allowed, mask, who)
+        return emissions.contiguous(), allowed.contiguous(), mask
+
+    def partial_llh(self, emissions, allowed, mask: Optional[torch.Tensor] = None, reduction: str = "none",
+                    return_parts: bool = False):
+        """Log-probability of the paths that the per-position tag sets permit: ``pllh[b] = logZ_A[b] - logZ[b] <= 0``, the
+        marginal likelihood of a partly annotated sentence (mtvaf_crf_lattice_{fwd,bwd}).
+
+        ``allowed`` int64 [B,S] (``batch_first``) or [S,B]: bit ``j`` of a word set = tag ``j`` may be taken at that column; a
+        word without any of the low ``num_tags`` bits means "no constraint" and higher bits are ignored
+        (``mtvaf_amd.constraints`` builds such words on the device).  ``mask`` is a prefix mask.  A sentence whose sets are
+        all full has ``pllh == 0.0`` exactly and contributes exact zeros to every gradient.  Reductions as ``forward``:
+        'none' [B], 'sum', 'mean' (over sentences), 'token_mean' (sum / mask.sum()).  ``return_parts``: also ``logz_a`` [B] and
+        ``logz`` [B], which carry no gradient."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        em, allowed, mask = self._prep_allowed(emissions, allowed, mask, "CRF.partial_llh")
+        pllh, logz_a, logz = engine.CRFLatticeFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions,
+                                                             allowed, mask)
+        if reduction == "sum":
+            pllh = pllh.sum()
+        elif reduction == "mean":
+            pllh = pllh.mean()
+        elif reduction == "token_mean":
+            pllh = pllh.sum() / mask.to(pllh.dtype).sum()
+        return (pllh, logz_a, logz) if return_parts else pllh
+
+    @torch.no_grad()
+    def constrained_marginals(self, emissions, allowed, mask: Optional[torch.Tensor] = None, return_logz: bool = False):
+        """Posterior tag probabilities given that the path stays inside the tag sets: ``p(y_t = j | emissions, y in allowed)``,
+        [B,S,C] (``batch_first``) or [S,B,C]; exact zeros at disallowed tags and masked columns.  ``return_logz``: also
+        ``logz_a`` [B].  ``allowed`` and ``mask`` as for ``partial_llh``.  mtvaf_crf_lattice_marginals; no gradient."""
+        em, allowed, mask = self._prep_allowed(emissions, allowed, mask, "CRF.constrained_marginals")
+        B, S, C = em.shape
+        ws, wsb = hip.crf_lattice_workspace(B, S, C, em.device)
+        marg = torch.empty_like(em)
+        logz_a = torch.empty(B, dtype=em.dtype, device=em.device) if return_logz else None
+        hip.crf_lattice_marginals(em, allowed, mask, self.start_transitions.data, self.end_transitions.data,
+                                  self.transitions.data, marg, logz_a, ws, wsb)
+        if not self.batch_first:
+            marg = marg.transpose(0, 1)
+        return (marg, logz_a) if return_logz else marg
+
+    @torch.no_grad()
+    def decode_constrained(self, emissions, allowed, mask: Optional[torch.Tensor] = None, return_score: bool = False):
+        """Viterbi among the paths the tag sets permit -> (tags int32 [B,S] padded with -1, lengths int32 [B]) on the device
+        like ``decode_packed``, with ``return_score`` also the unnormalised score [B] of each path; no host sync.  Equal scores:
+        the lowest allowed previous tag, at the end the lowest allowed last tag; with full sets the result is ``decode_packed``'s.
+        ``allowed`` and ``mask`` as for ``partial_llh``.  mtvaf_crf_lattice_viterbi."""
+        em, allowed, mask = self._prep_allowed(emissions, allowed, mask, "CRF.decode_constrained")
+        B, S, _ = em.shape
+        tags = torch.empty(B, S, dtype=torch.int32, device=em.device)
+        lens = torch.empty(B, dtype=torch.int32, device=em.device)
+        score = torch.empty(B, dtype=em.dtype, device=em.device) if return_score else None
+        hip.crf_lattice_viterbi(em, allowed, mask, self.start_transitions.data, self.end_transitions.data,
+                                self.transitions.data, tags, lens, score)
+        return (tags, lens, score) if return_score else (tags, lens)
 
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
