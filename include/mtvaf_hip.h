@@ -461,6 +461,30 @@ int mtvaf_crf_entities(const float* emissions, const uint8_t* mask, const int32_
                        const uint8_t* end_tab, const int* type_of, int n_types, int32_t* ents, float* log_conf,
                        int32_t* count, int B, int S, int C, int max_entities, mtvaf_stream_t stream);
 
+/* Tagger inference: the posterior of every chunk EVENT -- for every span of kept columns and every type, the probability that
+ * the chunker above (the reference's modules/eval_metrics.py::get_chunks on the tags of its decode, models/bert_model.py:511)
+ * emits exactly that chunk -- under the chain over columns 0 .. L_b-1 restricted to the per-column tag sets of
+ * mtvaf_crf_lattice_* (allowed int64 [B,S], 0 = the full set, bits >= C ignored; NULL = no constraint), start and end included.
+ * One launch, no host read-back, no atomics, no allocation; safe under stream capture.
+ * emissions, mask (a prefix mask; L_b = its leading ones), keep, start_tab / end_tab / type_of: as mtvaf_crf_entities reads them.
+ * Kept columns k_0 < .. < k_n-1.  A non-kept column strictly between two kept columns must carry a singleton set; elsewhere
+ * the kernel takes the LOWEST tag of its set there, for every quantity it computes (outside the contract).  Event (i, w, T),
+ * b = k_i, e = k_i+w, 0 <= w < max_width, labels l_j of the kept columns with the boundary C on both sides:
+ *   start_tab[l_i-1][l_i], no start_tab[l_j-1][l_j] for i < j <= i+w, end_tab[l_i+w][l_i+w+1], type_of[l_i+w] = T.
+ * An end strictly inside the span does not exclude the event (the chunker emits both chunks then).
+ * log_post [B,S,max_width,n_types] fp32, indexed by the start COLUMN b and the width w in kept columns: the log probability
+ * of the event, -inf where it is impossible or undefined (b not kept, b >= L_b, the span runs past the last kept column).
+ * logz_a [B] = log Z_A (0 for an empty sentence).  Every element of both is written on every call.
+ * workspace: mtvaf_crf_chunk_posteriors_workspace_bytes(B, S, C) bytes (MTVAF_ERR_WORKSPACE if NULL or short).
+ * 1 <= S <= 512, 1 <= C <= 64 (MTVAF_ERR_SHAPE); 1 <= n_types <= 64, 1 <= max_width <= 16 (MTVAF_ERR_ARG): checked before
+ * the launch. */
+size_t mtvaf_crf_chunk_posteriors_workspace_bytes(int B, int S, int C);
+int mtvaf_crf_chunk_posteriors(const float* emissions, const int64_t* allowed, const uint8_t* mask, const uint8_t* keep,
+                               const float* start, const float* end, const float* trans, const uint8_t* start_tab,
+                               const uint8_t* end_tab, const int* type_of, int n_types, int max_width, float* log_post,
+                               float* logz_a, int B, int S, int C, void* workspace, size_t workspace_bytes,
+                               mtvaf_stream_t stream);
+
 /* Cutoff augmentation on the embedding output (modules/augument.py:99-159): out = x * row_keep[b,s] * col_keep[b,:]
  * (either mask may be NULL); x/out [B,S,H] fp32, row_keep [B*S], col_keep [B,H].  Self-adjoint: the backward is the
  * same call on the gradient. */

@@ -116,6 +116,8 @@ _SIGS = {
     "mtvaf_crf_nbest_workspace_bytes": (SZ, [I, I, I, I]),
     "mtvaf_crf_nbest": (c_int, [P, P, P, P, P, I, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
+    "mtvaf_crf_chunk_posteriors_workspace_bytes": (SZ, [I, I, I]),
+    "mtvaf_crf_chunk_posteriors": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_lattice_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_lattice_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_lattice_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
@@ -1023,6 +1025,57 @@ def crf_lattice_viterbi(em, allowed, mask_u8, start, end, trans, tags_out, lens_
     B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_viterbi")
     _ck(lib().mtvaf_crf_lattice_viterbi(_p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(tags_out),
                                         _p(lens_out), _p(score_out), B, S, C, _st()), "mtvaf_crf_lattice_viterbi")
+
+
+CRF_CHUNKS_MAX_W = 16
+CRF_CHUNKS_MAX_TYPES = 64
+
+
+def crf_chunk_posteriors(em, allowed, mask_u8, keep, start, end, trans, start_tab, end_tab, type_of, n_types, max_width=8,
+                         out=None):
+    """Chunk-event log posteriors of every span of kept columns and every type (csrc/crf_chunks.hip), one launch and no host
+    sync.  em [B,S,C] fp32, allowed [B,S] int64 set words or None (no constraint), mask_u8 [B,S] uint8 (a prefix mask), keep
+    [B,S] uint8 or None (= columns 1 .. L-1); the CRF parameters and the scheme tables as `crf_entities` takes them.
+    -> log_post [B,S,max_width,n_types] fp32 (start column, width in kept columns, type; -inf where the event is impossible or
+    undefined), logz_a [B] fp32.  ``out``: that pair, to be overwritten."""
+    if em.dim() != 3:
+        raise ValueError(f"crf_chunk_posteriors: emissions {tuple(em.shape)}: expected [B, S, C]")
+    B, S, C = em.shape
+    W, n_types = int(max_width), int(n_types)
+    if not 1 <= S <= CRF_LATTICE_MAX_S:
+        raise ValueError(f"crf_chunk_posteriors: S={S} outside 1..{CRF_LATTICE_MAX_S}")
+    if not 1 <= C <= CRF_LATTICE_MAX_C:
+        raise ValueError(f"crf_chunk_posteriors: C={C} outside 1..{CRF_LATTICE_MAX_C}")
+    if not 1 <= W <= CRF_CHUNKS_MAX_W:
+        raise ValueError(f"crf_chunk_posteriors: max_width={W} outside 1..{CRF_CHUNKS_MAX_W}")
+    if not 1 <= n_types <= CRF_CHUNKS_MAX_TYPES:
+        raise ValueError(f"crf_chunk_posteriors: n_types={n_types} outside 1..{CRF_CHUNKS_MAX_TYPES}")
+    if B < 1 or tuple(mask_u8.shape) != (B, S) or (keep is not None and tuple(keep.shape) != (B, S)) or \
+            (allowed is not None and tuple(allowed.shape) != (B, S)):
+        raise ValueError(f"crf_chunk_posteriors: mask {tuple(mask_u8.shape)} / keep / allowed do not fit emissions [{B}, {S}, {C}]")
+    if (start.numel(), end.numel(), trans.numel(), start_tab.numel(), end_tab.numel(), type_of.numel()) != \
+            (C, C, C * C, (C + 1) ** 2, (C + 1) ** 2, C + 1):
+        raise ValueError("crf_chunk_posteriors: CRF parameters / tables do not fit C")
+    if allowed is not None and allowed.dtype != torch.int64:
+        raise ValueError(f"crf_chunk_posteriors: allowed must be an int64 tensor of tag-set words, got {allowed.dtype}")
+    _f32(em, start, end, trans)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert keep is None or (keep.dtype == torch.uint8 and keep.is_contiguous())
+    assert allowed is None or allowed.is_contiguous()
+    assert start_tab.dtype == end_tab.dtype == torch.uint8 and type_of.dtype == torch.int32
+    assert all(t.is_contiguous() for t in (start_tab, end_tab, type_of))
+    if out is None:
+        out = (torch.empty((B, S, W, n_types), dtype=torch.float32, device=em.device),
+               torch.empty(B, dtype=torch.float32, device=em.device))
+    log_post, logz_a = out
+    assert tuple(log_post.shape) == (B, S, W, n_types) and logz_a.numel() == B
+    _f32(log_post, logz_a)
+    wsb = lib().mtvaf_crf_chunk_posteriors_workspace_bytes(B, S, C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=em.device)
+    _ck(lib().mtvaf_crf_chunk_posteriors(_p(em), _p(allowed), _p(mask_u8), _p(keep), _p(start), _p(end), _p(trans),
+                                         _p(start_tab), _p(end_tab), _p(type_of), n_types, W, _p(log_post), _p(logz_a), B, S,
+                                         C, _p(ws), wsb, _st()), "mtvaf_crf_chunk_posteriors")
+    return log_post, logz_a
 
 
 def mask_mul(x, row_keep, col_keep, out):

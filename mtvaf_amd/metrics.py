@@ -158,6 +158,31 @@ def entities_to_lists(result: dict, types: Sequence[str]) -> List[List[dict]]:
     return out
 
 
+def posteriors_to_lists(result: dict) -> List[dict]:
+    """The dict of `TVNetSAModel2.predict_posteriors` -> per sentence ``{"decoded": [...], "selected": [...]}``: the decoded
+    entities as `entities_to_lists` gives them plus ``"chunk_confidence"`` (the posterior of the chunk event, 0.0 for an entity
+    wider than the computed widths), and the spans above the threshold as ``{"start", "end", "type", "confidence"}``, both ordered
+    by end column.  ONE device->host copy."""
+    types, dec, sel = result["types"], result["decoded"], result["selected"]
+    B, E = dec["confidence"].shape
+    Es = sel["confidence"].shape[1]
+    cols = [dec["entities"].reshape(B, E * 3).double(), dec["confidence"].double(), torch.exp(dec["chunk_log_conf"]).double(),
+            dec["count"].reshape(B, 1).double(), sel["entities"].reshape(B, Es * 3).double(), sel["confidence"].double(),
+            sel["count"].reshape(B, 1).double()]
+    packed = torch.cat(cols, dim=1).cpu().numpy()
+    out = []
+    for row in packed:
+        e, c, cc, n, rest = row[:E * 3].reshape(E, 3).astype(np.int64), row[E * 3:E * 4], row[E * 4:E * 5], int(row[E * 5]), \
+            row[E * 5 + 1:]
+        se, sc, sn = rest[:Es * 3].reshape(Es, 3).astype(np.int64), rest[Es * 3:Es * 4], int(rest[Es * 4])
+        out.append({
+            "decoded": [{"start": int(e[k, 0]), "end": int(e[k, 1]), "type": types[int(e[k, 2])], "confidence": float(c[k]),
+                         "chunk_confidence": float(cc[k])} for k in range(min(n, E))],
+            "selected": [{"start": int(se[k, 0]), "end": int(se[k, 1]), "type": types[int(se[k, 2])], "confidence": float(sc[k])}
+                         for k in range(min(sn, Es))]})
+    return out
+
+
 def nbest_to_lists(result: dict) -> List[List[Tuple[List[int], float, float]]]:
     """The dict of `CRF.decode_nbest` -> per sentence its ``n_paths`` hypotheses, best first, as ``(tags, score, prob)``:
     the tag list without padding, the unnormalised path score and ``exp(logprob)`` (None if the log-probabilities were not asked

@@ -400,6 +400,70 @@ class TVNetSAModel2(nn.Module):
         out["types"] = t["types"]
         return out
 
+    def predict_posteriors(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
+                           threshold=0.5):
+        """`predict_constrained` plus the posterior of every chunk EVENT (`CRF.chunk_posteriors`): the same prologue and the same
+        layout sets (`structural_sets` of the trainer's label map, the attention mask and ``word_mask``), the posteriors
+        conditional on them.  Kept columns: the word columns between [CLS] and [SEP] (columns 1 .. L-2, and only those of
+        ``word_mask`` when it is given) -- the columns `predict_constrained` chunks.  args.max_entity_width (8): the widest span,
+        in kept columns, 1..16.  No host sync.
+        -> dict: ``decoded`` = `predict_constrained`'s dict, unchanged, plus ``chunk_log_conf`` [B,E], the log probability that
+        the decoded entity is a chunk of the answer (0 in unused slots, -inf for an entity wider than max_entity_width);
+        ``log_post`` [B,S,W,n_types] and ``logz_a`` [B] of `CRF.chunk_posteriors`; ``keep`` [B,S]; ``selected`` = the spans whose
+        posterior is >= ``threshold`` in `predict`'s entities / log_confidence / confidence / count format, ordered by end column,
+        then start (`CRF.chunks_above`; args.max_entities); ``types``.  Two overlapping chunks exclude each other, so with
+        ``threshold > 0.5`` the selected spans of a sentence cannot overlap.  `mtvaf_amd.metrics.posteriors_to_lists` makes
+        Python lists of it."""
+        # (the prologue is `predict`'s, restated: that method is left as it is)
+        was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
+        self.eval()
+        try:
+            with torch.no_grad():
+                if _arg(self.args, "use_prefix"):
+                    prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
+                    prefix_len = prefix_guids[0][0].shape[2]
+                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
+                                             dtype=attention_mask.dtype)
+                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                else:
+                    prefix_guids, prompt_attention_mask = None, attention_mask
+                self.bert.encoder.output_prefix_mass = False
+                bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
+                                        past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
+                                        return_dict=True)
+                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                mask_u8 = attention_mask.to(torch.uint8)
+                from ..constraints import structural_sets
+                allowed = structural_sets({label: i for i, label in enumerate(self.label_list, 1)}, attention_mask,
+                                          word_mask).to(emissions.device)
+                tags, _ = self.crf.decode_constrained(emissions, allowed, mask_u8)
+                t = self._entity_tables(emissions.device)
+                run = torch.zeros_like(mask_u8, dtype=torch.bool)
+                run[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0
+                keep = run & ~t["structural"][tags.clamp(0, t["C"] - 1).long()]
+                if word_mask is not None:
+                    keep &= word_mask.to(keep.device) != 0
+                decoded = self.crf.entities(emissions, mask_u8, t, tags=tags, keep=keep,
+                                            max_entities=_arg(self.args, "max_entities", 32))
+                # the word columns between [CLS] and [SEP], whatever was decoded there: the same columns, since the sets leave no
+                # structural tag on a word column and nothing else on the others
+                lens = torch.cumprod(mask_u8.long(), dim=1).sum(dim=1, keepdim=True)
+                col = torch.arange(mask_u8.shape[1], device=mask_u8.device)[None, :]
+                keep_w = (col >= 1) & (col < lens - 1)
+                if word_mask is not None:
+                    keep_w &= word_mask.to(keep_w.device) != 0
+                log_post, logz_a = self.crf.chunk_posteriors(emissions, mask_u8, t, keep=keep_w, allowed=allowed,
+                                                             max_width=_arg(self.args, "max_entity_width", 8))
+                decoded["chunk_log_conf"] = self.crf.entity_chunk_confidence(decoded["entities"], log_post, keep_w)
+                selected = self.crf.chunks_above(log_post, keep_w, threshold, _arg(self.args, "max_entities", 32))
+        finally:
+            self.bert.encoder.output_prefix_mass = mass
+            engine.RNG.offset = offset
+            self.train(was_training)
+        decoded["types"] = t["types"]
+        return {"decoded": decoded, "log_post": log_post, "logz_a": logz_a, "keep": keep_w, "selected": selected,
+                "types": t["types"]}
+
     def predict_nbest(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, nbest=None):
         """`predict` with the ``nbest`` best tag sequences of every sentence instead of the best one (args.nbest, default 4; 1..8):
         the same prologue (visual prompt -> encoder -> fc, eval mode, no host sync, dropout counter put back), then

@@ -7,6 +7,7 @@ tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``co
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional
 
 import torch
@@ -234,6 +235,98 @@ class CRF(nn.Module):
         conf = torch.where(ents[..., 0] >= 0, torch.exp(log_conf), torch.zeros_like(log_conf))
         return {"tags": tags[:, :S], "lengths": lengths, "entities": ents, "log_confidence": log_conf, "confidence": conf,
                 "count": count}
+
+    @torch.no_grad()
+    def chunk_posteriors(self, emissions, mask, tables, keep=None, allowed=None, max_width: int = 8, check: bool = False):
+        """The posterior of every chunk EVENT (mtvaf_crf_chunk_posteriors): for every span of kept columns and every type, the
+        probability that the chunker of ``entities`` emits exactly that chunk -- a start at its first column, no start after
+        it, an end at its last column, that type -- under the chain restricted to the tag sets ``allowed``.  No host sync.
+
+        ``mask`` / ``tables`` / ``keep`` as for ``entities`` (``keep`` None: columns 1 .. L-1); ``allowed`` int64 [B,S] set words
+        as for ``partial_llh`` (None: no constraint) -- the posteriors are conditional on them.  ``keep`` and ``allowed`` are
+        batch-first like every result.  A non-kept column strictly between two kept columns must carry a singleton set (the X of
+        a sub-word piece under `mtvaf_amd.constraints.structural_sets`); where it does not, the kernel takes the lowest tag of
+        its set, which is outside the contract -- ``check=True`` verifies it on the host (one sync) and raises ValueError.
+        -> (log_post [B,S,max_width,n_types], logz_a [B]): ``log_post[s, b, w, T]`` for the span of ``w + 1`` kept columns that
+        starts at column ``b``; -inf where the event is impossible or undefined (``b`` not kept or behind the sentence, the span
+        past the last kept column).  ``max_width`` 1..16.  Ends strictly inside a span do not exclude it, as in the chunker."""
+        from ..metrics import entity_device_tables
+        emissions, _, mask = self._prep(emissions, None, mask)
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        t = entity_device_tables(tables, em.device)
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        if allowed is not None:
+            hip.crf_lattice_check(em, allowed, mask, "CRF.chunk_posteriors")
+            allowed = allowed.contiguous()
+        if check:
+            on = torch.cumprod(mask.long(), dim=1).bool()
+            kp = (keep.bool() if keep is not None else torch.arange(S, device=em.device)[None, :] >= 1) & on
+            inner = ~kp & on & (torch.cumsum(kp.long(), dim=1) > 0) & (torch.flip(torch.cumsum(torch.flip(kp.long(), [1]), 1), [1]) > 0)
+            bits = torch.ones(B, S, C, dtype=torch.bool, device=em.device) if allowed is None else \
+                ((allowed[..., None] >> torch.arange(C, device=em.device)) & 1).bool()
+            size = bits.sum(-1)
+            size = torch.where(size == 0, torch.full_like(size, C), size)
+            if bool((inner & (size != 1)).any()):
+                raise ValueError("CRF.chunk_posteriors: a non-kept column between two kept columns carries a set of more than one tag")
+        return hip.crf_chunk_posteriors(em, allowed, mask, keep, self.start_transitions.data, self.end_transitions.data,
+                                        self.transitions.data, t["start"], t["end"], t["type_of"], t["n_types"], max_width)
+
+    @staticmethod
+    def entity_chunk_confidence(ents, log_post, keep):
+        """The chunk-event log posterior of given entities, gathered from ``chunk_posteriors``' ``log_post`` [B,S,W,n_types]:
+        ``ents`` [B,E,3] as ``entities`` returns them (start column, end column, type; -1 in unused slots), ``keep`` [B,S] the
+        kept columns of that call.  The width of an entity is the number of kept columns in (start, end], from a cumulative sum.
+        Pure torch on the tensors' device, no sync.  -> [B,E]: 0 in unused slots, -inf for an entity wider than ``W`` kept
+        columns (its event was not computed)."""
+        B, S, W, _ = log_post.shape
+        b, e, ty = (ents[..., k].long() for k in range(3))
+        used = b >= 0
+        b, e, ty = b.clamp(0, S - 1), e.clamp(0, S - 1), ty.clamp(min=0)
+        cum = torch.cumsum((keep != 0).long(), dim=1)
+        w = torch.gather(cum, 1, e) - torch.gather(cum, 1, b)
+        flat = log_post.reshape(B, -1)
+        got = torch.gather(flat, 1, (b * W + w.clamp(0, W - 1)) * log_post.shape[3] + ty)
+        got = torch.where((w >= 0) & (w < W), got, torch.full_like(got, float("-inf")))
+        return torch.where(used, got, torch.zeros_like(got))
+
+    @staticmethod
+    def chunks_above(log_post, keep, threshold: float = 0.5, max_entities: int = 32) -> dict:
+        """The spans of ``chunk_posteriors``' ``log_post`` [B,S,W,n_types] whose posterior is ``>= threshold``, in ``entities``'
+        format: entities [B,E,3] int32 (start column, end column, type; -1 in unused slots), log_confidence / confidence [B,E]
+        (0 in unused slots), count [B] int32 (may exceed E = max_entities: the first E are stored), ordered by end column, then
+        start column, then type.  ``keep`` [B,S]: the kept columns of that call.  Torch ops on the tensors' device, no sync.
+        Two different chunks that overlap exclude each other (the later one needs a start inside the earlier one, or they share
+        their start and differ in where the first end falls), so with ``threshold > 0.5`` the selection of a sentence cannot
+        overlap."""
+        if not 0.0 < threshold <= 1.0:
+            raise ValueError(f"CRF.chunks_above: threshold={threshold} outside (0, 1]")
+        B, S, W, T = log_post.shape
+        E, dev = int(max_entities), log_post.device
+        kp = keep != 0
+        order = torch.cumsum(kp.long(), dim=1) - 1                                  # ordinal of a kept column
+        col_of = torch.zeros(B, S + W, dtype=torch.long, device=dev)                # column of an ordinal
+        col_of.scatter_(1, torch.where(kp, order, torch.full_like(order, S + W - 1)), torch.arange(S, device=dev).expand(B, S))
+        last = (order.clamp(min=0)[:, :, None] + torch.arange(W, device=dev)[None, None, :]).reshape(B, S * W)
+        e = torch.gather(col_of, 1, last).reshape(B, S, W, 1).expand(B, S, W, T)
+        b = torch.arange(S, device=dev).reshape(1, S, 1, 1).expand(B, S, W, T)
+        ty = torch.arange(T, device=dev).reshape(1, 1, 1, T).expand(B, S, W, T)
+        sel = log_post >= math.log(threshold)
+        key = torch.where(sel, (e * S + b) * T + ty, torch.full_like(e, S * S * T)).reshape(B, -1)
+        n = min(E, key.shape[1])
+        key, idx = torch.sort(key, dim=1, stable=True)
+        key, idx = key[:, :n], idx[:, :n]
+        used = key < S * S * T
+        ents = torch.stack([key // T // S, key // T % S, key % T], dim=-1)[..., [1, 0, 2]]
+        ents = torch.where(used[..., None], ents, torch.full_like(ents, -1)).to(torch.int32)
+        lc = torch.where(used, torch.gather(log_post.reshape(B, -1), 1, idx), torch.zeros((), device=dev))
+        conf = torch.where(used, torch.exp(lc), torch.zeros_like(lc))
+        if n < E:
+            pad = E - n
+            ents = torch.cat([ents, torch.full((B, pad, 3), -1, dtype=torch.int32, device=dev)], dim=1)
+            lc, conf = (torch.cat([x, torch.zeros(B, pad, device=dev)], dim=1) for x in (lc, conf))
+        return {"entities": ents, "log_confidence": lc, "confidence": conf, "count": sel.reshape(B, -1).sum(1).to(torch.int32)}
 
     # ---- per-token tag constraints (csrc/crf_lattice.hip) ----
     def _prep_allowed(self, emissions, allowed, mask, who):
