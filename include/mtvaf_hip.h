@@ -306,6 +306,34 @@ int mtvaf_crf_lattice_viterbi(const float* emissions, const int64_t* allowed, co
                               const float* end, const float* trans, int32_t* tags_out, int32_t* lens_out, float* score_out,
                               int B, int S, int C, mtvaf_stream_t stream);
 
+/* expected cost (risk) under the chain's posterior and its gradients (csrc/crf_risk.hip) -- the losses that need the gradient
+ * of a posterior expectation, which the reference's CRF (models/bert_model.py:464, :521: log-likelihood only) cannot train:
+ * expected Hamming / cost-sensitive risk, distillation on marginals, and the vector-Jacobian product of the node marginals.
+ * cost fp32 [B,S,C], additive over columns: risk[b] = E_{y ~ p(.|x_b)} sum_{t < len_b} cost[b,t,y_t].  1 <= C <= 64,
+ * 1 <= S <= 512 (anything else: MTVAF_ERR_SHAPE before any launch, and the workspace query returns 0; a workspace below the
+ * query: MTVAF_ERR_WORKSPACE).  mask is a prefix mask with mask[:,0] == 1: len_b = its leading ones; emissions and cost at or
+ * beyond len_b are never read (they may hold NaN), end[] enters at column len_b - 1.
+ *   risk_fwd  risk [B]; logz [B] (the log-partition) and marg [B,S,C] (the node marginals m_t(c), zeros at masked columns) may
+ *             be NULL; one launch, two with marg.  Leaves in the workspace what risk_bwd reads.
+ *   risk_bwd  gradients of sum_b grad[b] risk[b] after a risk_fwd on the same inputs and workspace:
+ *             demissions[b,t,c] = grad[b] m_t(c) (E[cost | y_t = c] - risk[b]), dcost[b,t,c] = grad[b] m_t(c) (dcost may be NULL),
+ *             exact zeros at masked columns; dstart / dend / dtrans from the same covariances on the edge marginals, reduced
+ *             over sentences in a fixed order, overwritten or accumulated as by llh_bwd.  Two launches.
+ * The recursions are re-centred at every step (the conditional expectations never grow with the length), so the float32
+ * error of a gradient does not grow with len |cost|.  sum_c demissions[b,t,c] = 0 up to rounding; a constant added to
+ * cost[b,t,:] moves risk[b] by it and no gradient.  Exact zeros, all written as +0.0 whatever the sign of grad[b]: cost == 0 on
+ * the live columns gives risk == 0 and zero gradients; grad[b] == 0 gives zeros for that sentence.  The vector-Jacobian product of the marginals with a cotangent V
+ * [B,S,C] is risk_fwd + risk_bwd with cost = V and grad = 1.  Results are bit-reproducible.  No host sync, no allocation,
+ * no atomics; safe under single-stream capture. */
+size_t mtvaf_crf_risk_workspace_bytes(int B, int S, int C);
+int mtvaf_crf_risk_fwd(const float* emissions, const float* cost, const uint8_t* mask, const float* start, const float* end,
+                       const float* trans, float* risk, float* logz, float* marg, int B, int S, int C, void* workspace,
+                       size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_risk_bwd(const float* grad, const float* emissions, const float* cost, const uint8_t* mask, const float* start,
+                       const float* end, const float* trans, float* demissions, float* dcost, float* dstart, float* dend,
+                       float* dtrans, int accumulate, int B, int S, int C, void* workspace, size_t workspace_bytes,
+                       mtvaf_stream_t stream);
+
 /* ---- visual prompt generator + VAO loss ----------------------------------------------------------------------
  * replaces TVNetSAModel2.get_visual_prompt's split-mean / gates / gated sums / cat / reshape
  * (bert_model.py:544-545, 566-585) and the KLDiv(batchmean) ANP loss (:549-563).

@@ -1279,6 +1279,63 @@ class CRFLatticeFunction(torch.autograd.Function):
         return dem, ds, de, dt, None, None
 
 
+class CRFRiskFunction(torch.autograd.Function):
+    """risk [B] = E_{y ~ p(.|emissions_b)} sum_t cost[b,t,y_t], the expected value of a column-additive cost under the chain's
+    posterior (mtvaf_crf_risk_fwd).  The backward is one mtvaf_crf_risk_bwd call on the [B] upstream gradient: gradients to the
+    emissions and the three chain parameters, and to ``cost`` (the node marginals times the upstream gradient) only where it
+    requires one."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, cost, mask_u8):
+        B, S, C = emissions.shape
+        em, cst = emissions.contiguous(), cost.contiguous()
+        ws, wsb = hip.crf_risk_workspace(B, S, C, em.device)
+        risk = _empty(B, like=em)
+        hip.crf_risk_fwd(em, cst, mask_u8, start, end, trans, risk, None, None, ws, wsb)
+        ctx.stash = (em, start, end, trans, cst, mask_u8, ws, wsb)
+        return risk
+
+    @staticmethod
+    def backward(ctx, gout):
+        em, start, end, trans, cst, mask_u8, ws, wsb = ctx.stash
+        g = gout.contiguous().float()
+        dem = torch.empty_like(em)
+        dcost = torch.empty_like(cst) if ctx.needs_input_grad[4] else None
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(trans)
+        hip.crf_risk_bwd(g, em, cst, mask_u8, start, end, trans, dem, dcost, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, dcost, None
+
+
+class CRFMarginalsFunction(torch.autograd.Function):
+    """marg [B,S,C] = the node marginals p(y_t = c | emissions_b), the values of mtvaf_crf_marginals (``CRF.marginals``), with a
+    gradient.  The vector-Jacobian product of the marginals with a cotangent V is the gradient of the expected cost sum_t
+    sum_c m_t(c) V[t,c] at fixed V, so the backward is one mtvaf_crf_risk_fwd + mtvaf_crf_risk_bwd with cost := V and an
+    upstream gradient of 1 (masked columns of V are never read by the kernels, so they need no zeroing)."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, mask_u8):
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        ws, wsb = hip.crf_workspace(B, S, C, em.device)
+        marg = torch.empty_like(em)
+        hip.crf_marginals(em, mask_u8, start, end, trans, marg, None, ws, wsb)
+        ctx.stash = (em, start, end, trans, mask_u8)
+        return marg
+
+    @staticmethod
+    def backward(ctx, gmarg):
+        em, start, end, trans, mask_u8 = ctx.stash
+        B, S, C = em.shape
+        v = gmarg.contiguous().float()
+        ws, wsb = hip.crf_risk_workspace(B, S, C, em.device)
+        risk, one = _empty(B, like=em), torch.ones(B, dtype=em.dtype, device=em.device)
+        hip.crf_risk_fwd(em, v, mask_u8, start, end, trans, risk, None, None, ws, wsb)
+        dem = torch.empty_like(em)
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(trans)
+        hip.crf_risk_bwd(one, em, v, mask_u8, start, end, trans, dem, None, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, None
+
+
 # -------------------------------------------------------------------------------------------------
 class PromptFunction(torch.autograd.Function):
     """enc [NI,B,L,4W] + packed projector weights -> pkv [NL,2,B,(NI*L)*(W/2)].

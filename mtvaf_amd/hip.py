@@ -123,6 +123,9 @@ _SIGS = {
     "mtvaf_crf_lattice_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     "mtvaf_crf_lattice_marginals": (c_int, [P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_lattice_viterbi": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "mtvaf_crf_risk_workspace_bytes": (SZ, [I, I, I]),
+    "mtvaf_crf_risk_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_risk_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -1025,6 +1028,61 @@ def crf_lattice_viterbi(em, allowed, mask_u8, start, end, trans, tags_out, lens_
     B, S, C = crf_lattice_check(em, allowed, mask_u8, "crf_lattice_viterbi")
     _ck(lib().mtvaf_crf_lattice_viterbi(_p(em), _p(allowed), _p(mask_u8), _p(start), _p(end), _p(trans), _p(tags_out),
                                         _p(lens_out), _p(score_out), B, S, C, _st()), "mtvaf_crf_lattice_viterbi")
+
+
+# ---- expected cost under the posterior (csrc/crf_risk.hip) ----------------------------------------------------------
+def crf_risk_check(em, cost=None, mask_u8=None, who="crf_risk"):
+    """Argument checks shared by the risk entry points (host-side: shapes, dtypes and devices only, nothing is read).  em
+    [B,S,C] fp32 on the GPU, cost (None: a call without one) floating-point [B,S,C] on the same device, mask_u8 [B,S] uint8."""
+    if em.dim() != 3:
+        raise ValueError(f"{who}: emissions {tuple(em.shape)}: expected [B, S, C]")
+    B, S, C = em.shape
+    if not 1 <= C <= CRF_LATTICE_MAX_C:
+        raise ValueError(f"{who}: C={C} outside 1..{CRF_LATTICE_MAX_C}")
+    if not 1 <= S <= CRF_LATTICE_MAX_S:
+        raise ValueError(f"{who}: S={S} outside 1..{CRF_LATTICE_MAX_S}")
+    if B < 1:
+        raise ValueError(f"{who}: empty batch")
+    if cost is not None:
+        if not isinstance(cost, torch.Tensor) or not cost.dtype.is_floating_point:
+            raise ValueError(f"{who}: cost must be a floating-point tensor, got {getattr(cost, 'dtype', type(cost).__name__)}")
+        if tuple(cost.shape) != (B, S, C):
+            raise ValueError(f"{who}: cost {tuple(cost.shape)} does not fit emissions [{B}, {S}, {C}]")
+    if mask_u8 is not None and tuple(mask_u8.shape) != (B, S):
+        raise ValueError(f"{who}: mask {tuple(mask_u8.shape)} does not fit emissions [{B}, {S}, {C}]")
+    if not em.is_cuda or (cost is not None and not cost.is_cuda):
+        raise RuntimeError(f"{who}: emissions on {em.device}" + ("" if cost is None else f", cost on {cost.device}") +
+                           ": the CRF kernels run on the GPU and there is no CPU fallback")
+    if cost is not None and cost.device != em.device:
+        raise ValueError(f"{who}: cost on {cost.device}, emissions on {em.device}")
+    return B, S, C
+
+
+def crf_risk_workspace(B, S, C, device):
+    n = lib().mtvaf_crf_risk_workspace_bytes(B, S, C)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def crf_risk_fwd(em, cost, mask_u8, start, end, trans, risk, logz, marg, ws, wsb):
+    """risk [B] = the expected cost; logz [B] / marg [B,S,C] or None; the workspace keeps what crf_risk_bwd reads."""
+    B, S, C = crf_risk_check(em, cost, mask_u8, "crf_risk_fwd")
+    _f32(em, cost, start, end, trans, risk)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert marg is None or (tuple(marg.shape) == (B, S, C) and marg.dtype == torch.float32 and marg.is_contiguous())
+    _ck(lib().mtvaf_crf_risk_fwd(_p(em), _p(cost), _p(mask_u8), _p(start), _p(end), _p(trans), _p(risk), _p(logz), _p(marg),
+                                 B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_risk_fwd")
+
+
+def crf_risk_bwd(grad, em, cost, mask_u8, start, end, trans, dem, dcost, dstart, dend, dtrans, accumulate, ws, wsb):
+    """grad [B]: the upstream gradient of every sentence's risk; dcost [B,S,C] or None."""
+    B, S, C = crf_risk_check(em, cost, mask_u8, "crf_risk_bwd")
+    _f32(grad, em, cost, start, end, trans, dem, dstart, dend, dtrans)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and grad.numel() == B
+    assert tuple(dem.shape) == (B, S, C) and dem.is_contiguous()
+    assert dcost is None or (tuple(dcost.shape) == (B, S, C) and dcost.dtype == torch.float32 and dcost.is_contiguous())
+    _ck(lib().mtvaf_crf_risk_bwd(_p(grad), _p(em), _p(cost), _p(mask_u8), _p(start), _p(end), _p(trans), _p(dem), _p(dcost),
+                                 _p(dstart), _p(dend), _p(dtrans), int(accumulate), B, S, C, _p(ws), wsb, _st()),
+        "mtvaf_crf_risk_bwd")
 
 
 CRF_CHUNKS_MAX_W = 16

@@ -184,6 +184,7 @@ class TVNetSAModel2(nn.Module):
         self.bert.allow_unpad = True
         self.last_prefix_mass = None  # [L,B,NH,S] after a forward with args.output_prefix_mass
         self.last_tag_marginals = None  # [B,S,num_labels] after a forward with args.output_tag_marginals
+        self.last_crf_risk = None  # detached device scalar after a forward with labels and args.crf_risk_weight > 0
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -275,6 +276,7 @@ class TVNetSAModel2(nn.Module):
         self.last_tag_marginals = self.crf.marginals(emissions.detach(), mask_u8) \
             if _arg(self.args, "output_tag_marginals") else None
         loss = None
+        self.last_crf_risk = None
         if labels is not None:
             reduction = _crf_reduction(self.args)
             if reduction == "mean":
@@ -284,6 +286,13 @@ class TVNetSAModel2(nn.Module):
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
             if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
                 loss = loss + extra
+            # args.crf_risk_weight > 0 adds the expected rate of wrong tags under the posterior (CRF.hamming_risk, token_mean) to
+            # the loss and keeps it in self.last_crf_risk; at the default 0 the step launches nothing for it.
+            risk_weight = _arg(self.args, "crf_risk_weight", 0.0)
+            if risk_weight > 0:
+                crf_risk = self.crf.hamming_risk(emissions, labels, mask=mask_u8, reduction="token_mean")
+                self.last_crf_risk = crf_risk.detach()
+                loss = loss + risk_weight * crf_risk
         elif allowed_tags is not None:
             loss = -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=_crf_reduction(self.args))
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss

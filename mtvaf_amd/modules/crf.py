@@ -2,7 +2,8 @@
 (models/bert_model.py:464 ``CRF(num_labels, batch_first=True)``, :511 ``decode``, :521
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
 mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest, and over per-position
-tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``constrained_marginals``, ``decode_constrained``).  Parameter names (``start_transitions``,
+tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``constrained_marginals``, ``decode_constrained``), and
+the gradient of posterior expectations by mtvaf_crf_risk_{fwd,bwd} (``expected_cost``, ``hamming_risk``, ``differentiable_marginals``).  Parameter names (``start_transitions``,
 ``end_transitions``, ``transitions``) and the uniform(-0.1, 0.1) initialisation follow pytorch-crf.
 """
 from __future__ import annotations
@@ -396,6 +397,89 @@ class CRF(nn.Module):
         hip.crf_lattice_viterbi(em, allowed, mask, self.start_transitions.data, self.end_transitions.data,
                                 self.transitions.data, tags, lens, score)
         return (tags, lens, score) if return_score else (tags, lens)
+
+    # ---- expected cost under the posterior (csrc/crf_risk.hip) ----
+    @staticmethod
+    def reduce_risk(risk, denominator, reduction: str):
+        """``risk`` [B] under the reductions of ``forward``: 'none' [B], 'sum', 'mean' (over sentences), 'token_mean' (sum /
+        ``denominator``, the number of columns that count)."""
+        if reduction == "none":
+            return risk
+        if reduction == "sum":
+            return risk.sum()
+        if reduction == "mean":
+            return risk.mean()
+        if reduction == "token_mean":
+            return risk.sum() / denominator
+        raise ValueError(f"invalid reduction: {reduction}")
+
+    @staticmethod
+    def hamming_cost(tags, num_tags: int, mask, keep=None):
+        """The cost of ``hamming_risk``, batch-first: -> (cost float32 [B,S,C], kept bool [B,S]).  ``kept`` = the unmasked columns
+        that ``keep`` (bool [B,S], None: all) does not drop; ``cost[b,t,c] = 1`` for ``c != tags[b,t]`` at kept columns, 0 at
+        the gold tag and at every other column.  Torch ops on the tensors' device, no sync; tags outside 0..C-1 (padding
+        labels) are clamped, which only matters at columns that do not count."""
+        kept = mask != 0
+        if keep is not None:
+            if tuple(keep.shape) != tuple(mask.shape):
+                raise ValueError(f"CRF.hamming_risk: keep {tuple(keep.shape)} does not fit mask {tuple(mask.shape)}")
+            kept = kept & (keep != 0)
+        cost = kept[..., None].to(torch.float32).repeat(1, 1, num_tags)
+        cost.scatter_(2, tags.long().clamp(0, num_tags - 1)[..., None], 0.0)
+        return cost, kept
+
+    def _risk(self, em, cost, mask, who):
+        hip.crf_risk_check(em, cost, mask, who)
+        return engine.CRFRiskFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions, cost.float(),
+                                            mask)
+
+    def expected_cost(self, emissions, cost, mask: Optional[torch.Tensor] = None, reduction: str = "none"):
+        """The expected value of a column-additive cost under the posterior: ``R[b] = E_{y ~ p(.|x_b)} sum_t cost[b,t,y_t] = sum_t
+        sum_c m_t(c) cost[b,t,c]`` over the unmasked columns (mtvaf_crf_risk_{fwd,bwd}), differentiable in the emissions, the
+        chain parameters and -- where it requires grad -- ``cost``.  Minimum-risk training, cost-sensitive variants (per-tag
+        error weights), distillation terms linear in the marginals.
+
+        ``cost`` is a floating-point tensor of the emissions' shape and follows ``batch_first`` like them; ``mask`` is a prefix
+        mask, and cost at masked columns is never read.  A constant added to ``cost[b,t,:]`` moves ``R[b]`` by it and changes
+        no gradient.  Reductions as ``forward``: 'none' [B], 'sum', 'mean' (over sentences), 'token_mean' (sum / mask.sum())."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        if not isinstance(cost, torch.Tensor) or not cost.dtype.is_floating_point:
+            raise ValueError(f"CRF.expected_cost: cost must be a floating-point tensor, got "
+                             f"{getattr(cost, 'dtype', type(cost).__name__)}")
+        if tuple(cost.shape) != tuple(emissions.shape):
+            raise ValueError(f"CRF.expected_cost: cost {tuple(cost.shape)} does not fit emissions {tuple(emissions.shape)}")
+        em, _, mask = self._prep(emissions, None, mask)
+        if not self.batch_first:
+            cost = cost.transpose(0, 1)
+        risk = self._risk(em, cost, mask, "CRF.expected_cost")
+        return self.reduce_risk(risk, mask.to(risk.dtype).sum(), reduction)
+
+    def hamming_risk(self, emissions, tags, mask: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                     reduction: str = "token_mean"):
+        """The expected number of wrong tags under the posterior, ``sum_t (1 - m_t(tags_t))`` over the columns that count
+        ('none' [B], 'sum', 'mean' over sentences), or with 'token_mean' their expected rate: the sum divided by the number
+        of columns that count.  ``keep`` bool [B,S] (``batch_first``) or [S,B] drops columns from the count, e.g. those of
+        structural labels; a column counts if it is unmasked and kept.  Where no column counts the risk is exactly 0 and so is the
+        rate (the denominator is clamped to 1).  The cost is built on the device (``hamming_cost``)."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        em, tags, mask = self._prep(emissions, tags, mask)
+        if keep is not None and not self.batch_first:
+            keep = keep.transpose(0, 1)
+        cost, kept = self.hamming_cost(tags, self.num_tags, mask, keep)
+        risk = self._risk(em, cost, mask, "CRF.hamming_risk")
+        return self.reduce_risk(risk, kept.to(risk.dtype).sum().clamp(min=1.0), reduction)
+
+    def differentiable_marginals(self, emissions, mask: Optional[torch.Tensor] = None):
+        """The values of ``marginals`` -- [B,S,C] (``batch_first``) or [S,B,C], exact zeros at masked steps -- WITH a gradient to
+        the emissions and the chain parameters (`engine.CRFMarginalsFunction`: the backward is the risk gradient with the
+        incoming cotangent as cost).  For distillation from a teacher's marginals or consistency between two passes.
+        ``mask`` is a prefix mask, C at most 64 and S at most 512 as for ``expected_cost``."""
+        em, _, mask = self._prep(emissions, None, mask)
+        hip.crf_risk_check(em, None, mask, "CRF.differentiable_marginals")
+        marg = engine.CRFMarginalsFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions, mask)
+        return marg if self.batch_first else marg.transpose(0, 1)
 
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
