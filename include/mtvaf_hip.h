@@ -334,6 +334,32 @@ int mtvaf_crf_risk_bwd(const float* grad, const float* emissions, const float* c
                        float* dtrans, int accumulate, int B, int S, int C, void* workspace, size_t workspace_bytes,
                        mtvaf_stream_t stream);
 
+/* expected PATH cost with a term on every edge, and its gradients (csrc/crf_path.hip) -- crf_risk with one more term per
+ * previous tag; with it the sequence entropy, the KL divergence between two chains and the edge marginals.
+ * cost fp32 [B,S,C] or NULL, ecost fp32 [C,C] or NULL (NULL reads as zeros):
+ *   W(y) = sum_{t < len_b} cost[b,t,y_t] + sum_{1 <= t < len_b} ecost[y_{t-1},y_t],   risk[b] = E_{y ~ p(.|x_b)} W(y).
+ * Limits and error behaviour are those of mtvaf_crf_risk_*: 1 <= C <= 64, 1 <= S <= 512 (anything else: MTVAF_ERR_SHAPE before
+ * any launch, and the workspace query returns 0; a workspace below the query: MTVAF_ERR_WORKSPACE); a prefix mask with
+ * mask[:,0] == 1; emissions and cost at or beyond len_b are never read (they may hold NaN).
+ *   path_fwd  risk [B]; logz [B] may be NULL; one launch.  Leaves in the workspace what path_bwd reads.
+ *   path_bwd  the gradients of sum_b grad[b] risk[b] + gz[b] logZ[b] (gz [B] or NULL = zeros), with cost and ecost those of
+ *             the forward call: demissions = grad dR/dem + gz m_t(c); dcost (or NULL) = grad m_t(c); decost [C,C] (or NULL) =
+ *             sum_b grad[b] sum_t xi_t(i,j); dstart / dend / dtrans the cost covariances on the end-point and edge marginals
+ *             under grad plus those marginals themselves under gz; the parameter gradients and decost are reduced over
+ *             sentences in a fixed order, overwritten or accumulated.  Two launches.
+ * The recursions are centred as crf_risk's.  Exact zeros, all written as +0.0: masked columns of demissions and dcost; a
+ * sentence with grad[b] == 0 and gz[b] == 0; every cost-covariance gradient (and risk) when cost and ecost are both zero or
+ * NULL.  Both costs NULL with gz = w gives w times the gradient of logZ.  Results are bit-reproducible.  No host sync, no
+ * allocation, no atomics; safe under single-stream capture. */
+size_t mtvaf_crf_path_workspace_bytes(int B, int S, int C);
+int mtvaf_crf_path_fwd(const float* emissions, const float* cost, const float* ecost, const uint8_t* mask, const float* start,
+                       const float* end, const float* trans, float* risk, float* logz, int B, int S, int C, void* workspace,
+                       size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_crf_path_bwd(const float* grad, const float* gz, const float* emissions, const float* cost, const float* ecost,
+                       const uint8_t* mask, const float* start, const float* end, const float* trans, float* demissions,
+                       float* dcost, float* decost, float* dstart, float* dend, float* dtrans, int accumulate, int B, int S,
+                       int C, void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+
 /* ---- visual prompt generator + VAO loss ----------------------------------------------------------------------
  * replaces TVNetSAModel2.get_visual_prompt's split-mean / gates / gated sums / cat / reshape
  * (bert_model.py:544-545, 566-585) and the KLDiv(batchmean) ANP loss (:549-563).

@@ -1336,6 +1336,121 @@ class CRFMarginalsFunction(torch.autograd.Function):
         return dem, ds, de, dt, None
 
 
+def _score_as_cost(em, start, end, mask_u8):
+    """The node part of a chain's own score as a path cost [B,S,C]: the emissions plus ``start`` at column 0 plus ``end`` at
+    the last live column (the edge part is ``trans``).  Torch ops on the device, no sync; masked columns are never read."""
+    cost = em.clone()
+    cost[:, 0] += start
+    last = torch.cumprod(mask_u8.long(), dim=1).sum(1).clamp(min=1) - 1
+    cost[torch.arange(em.shape[0], device=em.device), last] += end
+    return cost, last
+
+
+class CRFPathFunction(torch.autograd.Function):
+    """risk [B] = E_{y ~ p(.|emissions_b)} [sum_t cost[b,t,y_t] + sum_{t>=1} edge_cost[y_{t-1},y_t]] (mtvaf_crf_path_fwd); either
+    cost may be None (zeros).  The backward is one mtvaf_crf_path_bwd call on the [B] upstream gradient: gradients to the
+    emissions and the chain parameters, and to ``cost`` (node marginals) / ``edge_cost`` (edge marginals summed over columns
+    and sentences), each times the upstream gradient, only where they require one."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, cost, ecost, mask_u8):
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        cst = None if cost is None else cost.contiguous()
+        ec = None if ecost is None else ecost.contiguous()
+        ws, wsb = hip.crf_path_workspace(B, S, C, em.device)
+        risk = _empty(B, like=em)
+        hip.crf_path_fwd(em, cst, ec, mask_u8, start, end, trans, risk, None, ws, wsb)
+        ctx.stash = (em, start, end, trans, cst, ec, mask_u8, ws, wsb)
+        return risk
+
+    @staticmethod
+    def backward(ctx, gout):
+        em, start, end, trans, cst, ec, mask_u8, ws, wsb = ctx.stash
+        g = gout.contiguous().float()
+        dem = torch.empty_like(em)
+        dcost = torch.empty_like(em) if cst is not None and ctx.needs_input_grad[4] else None
+        decost = torch.empty_like(trans) if ec is not None and ctx.needs_input_grad[5] else None
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(trans)
+        hip.crf_path_bwd(g, None, em, cst, ec, mask_u8, start, end, trans, dem, dcost, decost, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, dcost, decost, None
+
+
+class CRFEntropyFunction(torch.autograd.Function):
+    """H [B] = -sum_y p(y) log p(y) = logZ - E_p[score], the expected path cost of the chain's own score (node cost: emissions
+    plus start / end at the two ends; edge cost: the transitions) taken from logZ: one mtvaf_crf_path_fwd.  The score depends
+    on the parameters, and its direct gradient E_p[d score] is the marginals, which cancel logZ's: what remains is
+    dH = -Cov_p(f, score), one mtvaf_crf_path_bwd with the upstream gradient negated and no dcost / decost."""
+
+    @staticmethod
+    def forward(ctx, emissions, start, end, trans, mask_u8):
+        B, S, C = emissions.shape
+        em = emissions.contiguous()
+        cost, _ = _score_as_cost(em, start, end, mask_u8)
+        ws, wsb = hip.crf_path_workspace(B, S, C, em.device)
+        risk, logz = _empty(B, like=em), _empty(B, like=em)
+        tr = trans.contiguous()
+        hip.crf_path_fwd(em, cost, tr, mask_u8, start, end, tr, risk, logz, ws, wsb)
+        ctx.stash = (em, start, end, tr, cost, mask_u8, ws, wsb)
+        return logz - risk
+
+    @staticmethod
+    def backward(ctx, gout):
+        em, start, end, tr, cost, mask_u8, ws, wsb = ctx.stash
+        g = -gout.contiguous().float()
+        dem = torch.empty_like(em)
+        ds, de, dt = torch.empty_like(start), torch.empty_like(end), torch.empty_like(tr)
+        hip.crf_path_bwd(g, None, em, cost, tr, mask_u8, start, end, tr, dem, None, None, ds, de, dt, False, ws, wsb)
+        return dem, ds, de, dt, None
+
+
+class CRFKLFunction(torch.autograd.Function):
+    """KL(p || q) [B] over whole tag sequences between two chains on the same mask: E_p[score_p - score_q] - logZ_p + logZ_q.
+    Forward: mtvaf_crf_path_fwd on p with the score difference as cost (node: emissions, start, end; edge: transitions), and on
+    q without costs for logZ_q.  Backward: to p's side the cost covariance alone (the +m_p of the cost's own dependence on p
+    and the -m_p of logZ_p cancel analytically and are never formed); to q's side -(node and edge marginals of p), which are
+    dcost / decost of p's backward, plus those of q from one mtvaf_crf_path_bwd on q with both costs absent and gz = the
+    upstream gradient.  A side that needs no gradient costs no call of its own (q's needs p's marginals, hence p's call)."""
+
+    @staticmethod
+    def forward(ctx, em_p, start_p, end_p, trans_p, em_q, start_q, end_q, trans_q, mask_u8):
+        B, S, C = em_p.shape
+        ep, eq = em_p.contiguous(), em_q.contiguous()
+        cost, last = _score_as_cost(ep - eq, start_p - start_q, end_p - end_q, mask_u8)
+        ecost = (trans_p - trans_q).contiguous()
+        ws_p, wsb = hip.crf_path_workspace(B, S, C, ep.device)
+        ws_q, _ = hip.crf_path_workspace(B, S, C, ep.device)
+        risk, logz_p, logz_q, zero = (_empty(B, like=ep) for _ in range(4))
+        hip.crf_path_fwd(ep, cost, ecost, mask_u8, start_p, end_p, trans_p, risk, logz_p, ws_p, wsb)
+        hip.crf_path_fwd(eq, None, None, mask_u8, start_q, end_q, trans_q, zero, logz_q, ws_q, wsb)
+        if not any(ctx.needs_input_grad[4:8]):
+            ws_q = None  # (a detached q has no backward call: its workspace is not held through the graph's lifetime)
+        ctx.stash = (ep, start_p, end_p, trans_p, eq, start_q, end_q, trans_q, cost, ecost, last, mask_u8, ws_p, ws_q, wsb)
+        return (risk - logz_p) + logz_q
+
+    @staticmethod
+    def backward(ctx, gout):
+        ep, start_p, end_p, trans_p, eq, start_q, end_q, trans_q, cost, ecost, last, mask_u8, ws_p, ws_q, wsb = ctx.stash
+        need_p, need_q = any(ctx.needs_input_grad[0:4]), any(ctx.needs_input_grad[4:8])
+        if not (need_p or need_q):
+            return (None,) * 9
+        g = gout.contiguous().float()
+        dem = torch.empty_like(ep)
+        ds, de, dt = torch.empty_like(start_p), torch.empty_like(end_p), torch.empty_like(trans_p)
+        mp = torch.empty_like(ep) if need_q else None      # g times the node marginals of p
+        xp = torch.empty_like(trans_p) if need_q else None  # sum_b g[b] times the summed edge marginals of p
+        hip.crf_path_bwd(g, None, ep, cost, ecost, mask_u8, start_p, end_p, trans_p, dem, mp, xp, ds, de, dt, False, ws_p, wsb)
+        grads_p = (dem, ds, de, dt) if need_p else (None,) * 4
+        if not need_q:
+            return grads_p + (None,) * 5
+        dem_q = torch.empty_like(eq)
+        ds_q, de_q, dt_q = torch.empty_like(start_q), torch.empty_like(end_q), torch.empty_like(trans_q)
+        hip.crf_path_bwd(torch.zeros_like(g), g, eq, None, None, mask_u8, start_q, end_q, trans_q, dem_q, None, None, ds_q, de_q,
+                         dt_q, False, ws_q, wsb)
+        rows = torch.arange(ep.shape[0], device=ep.device)
+        return grads_p + (dem_q - mp, ds_q - mp[:, 0].sum(0), de_q - mp[rows, last].sum(0), dt_q - xp, None)
+
+
 # -------------------------------------------------------------------------------------------------
 class PromptFunction(torch.autograd.Function):
     """enc [NI,B,L,4W] + packed projector weights -> pkv [NL,2,B,(NI*L)*(W/2)].

@@ -126,6 +126,9 @@ _SIGS = {
     "mtvaf_crf_risk_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_risk_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_risk_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
+    "mtvaf_crf_path_workspace_bytes": (SZ, [I, I, I]),
+    "mtvaf_crf_path_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_path_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
     "mtvaf_mask_mul": (c_int, [P, P, P, P, I, I, I, P]),
     "mtvaf_gemm_bf16x": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P]),
     "mtvaf_gemm_bf16x_ktiles": (c_int, [I, I, P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, P, I, P, SZ, I, I, I, P, P, P]),
@@ -1083,6 +1086,51 @@ def crf_risk_bwd(grad, em, cost, mask_u8, start, end, trans, dem, dcost, dstart,
     _ck(lib().mtvaf_crf_risk_bwd(_p(grad), _p(em), _p(cost), _p(mask_u8), _p(start), _p(end), _p(trans), _p(dem), _p(dcost),
                                  _p(dstart), _p(dend), _p(dtrans), int(accumulate), B, S, C, _p(ws), wsb, _st()),
         "mtvaf_crf_risk_bwd")
+
+
+# ---- expected path cost with edge terms (csrc/crf_path.hip) ---------------------------------------------------------
+def crf_path_check(em, cost=None, ecost=None, mask_u8=None, who="crf_path"):
+    """`crf_risk_check` plus the edge cost: None or a floating-point [C,C] tensor on the emissions' device."""
+    if ecost is not None and em.dim() == 3:
+        C = em.shape[2]
+        if not isinstance(ecost, torch.Tensor) or not ecost.dtype.is_floating_point:
+            raise ValueError(f"{who}: edge_cost must be a floating-point tensor, got "
+                             f"{getattr(ecost, 'dtype', type(ecost).__name__)}")
+        if tuple(ecost.shape) != (C, C):
+            raise ValueError(f"{who}: edge_cost {tuple(ecost.shape)} does not fit [{C}, {C}]")
+        if ecost.device != em.device:
+            raise ValueError(f"{who}: edge_cost on {ecost.device}, emissions on {em.device}")
+    return crf_risk_check(em, cost, mask_u8, who)
+
+
+def crf_path_workspace(B, S, C, device):
+    n = lib().mtvaf_crf_path_workspace_bytes(B, S, C)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def crf_path_fwd(em, cost, ecost, mask_u8, start, end, trans, risk, logz, ws, wsb):
+    """risk [B] = the expected path cost (cost [B,S,C] / ecost [C,C] or None = zeros); logz [B] or None; the workspace keeps
+    what crf_path_bwd reads."""
+    B, S, C = crf_path_check(em, cost, ecost, mask_u8, "crf_path_fwd")
+    _f32(em, cost, ecost, start, end, trans, risk, logz)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and risk.numel() == B
+    _ck(lib().mtvaf_crf_path_fwd(_p(em), _p(cost), _p(ecost), _p(mask_u8), _p(start), _p(end), _p(trans), _p(risk), _p(logz),
+                                 B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_path_fwd")
+
+
+def crf_path_bwd(grad, gz, em, cost, ecost, mask_u8, start, end, trans, dem, dcost, decost, dstart, dend, dtrans, accumulate,
+                 ws, wsb):
+    """grad [B] / gz [B] or None: the upstream gradients of every sentence's risk and logZ; dcost [B,S,C] / decost [C,C] or
+    None.  cost and ecost are those of the crf_path_fwd call that filled the workspace."""
+    B, S, C = crf_path_check(em, cost, ecost, mask_u8, "crf_path_bwd")
+    _f32(grad, gz, em, cost, ecost, start, end, trans, dem, dcost, decost, dstart, dend, dtrans)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous() and grad.numel() == B
+    assert gz is None or gz.numel() == B
+    assert tuple(dem.shape) == (B, S, C) and (dcost is None or tuple(dcost.shape) == (B, S, C))
+    assert decost is None or tuple(decost.shape) == (C, C)
+    _ck(lib().mtvaf_crf_path_bwd(_p(grad), _p(gz), _p(em), _p(cost), _p(ecost), _p(mask_u8), _p(start), _p(end), _p(trans),
+                                 _p(dem), _p(dcost), _p(decost), _p(dstart), _p(dend), _p(dtrans), int(accumulate), B, S, C,
+                                 _p(ws), wsb, _st()), "mtvaf_crf_path_bwd")
 
 
 CRF_CHUNKS_MAX_W = 16

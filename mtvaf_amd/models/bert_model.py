@@ -185,6 +185,7 @@ class TVNetSAModel2(nn.Module):
         self.last_prefix_mass = None  # [L,B,NH,S] after a forward with args.output_prefix_mass
         self.last_tag_marginals = None  # [B,S,num_labels] after a forward with args.output_tag_marginals
         self.last_crf_risk = None  # detached device scalar after a forward with labels and args.crf_risk_weight > 0
+        self.last_crf_entropy = None  # detached device scalar after a forward with a loss and args.crf_entropy_weight != 0
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -277,6 +278,7 @@ class TVNetSAModel2(nn.Module):
             if _arg(self.args, "output_tag_marginals") else None
         loss = None
         self.last_crf_risk = None
+        self.last_crf_entropy = None
         if labels is not None:
             reduction = _crf_reduction(self.args)
             if reduction == "mean":
@@ -298,6 +300,14 @@ class TVNetSAModel2(nn.Module):
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
             if torch.is_tensor(extra) or extra != 0:
                 loss = loss + extra
+        # args.crf_entropy_weight != 0 adds weight * the posterior's sequence entropy per unmasked column (CRF.entropy, token_mean)
+        # wherever a loss is formed -- positive minimises entropy, negative is a confidence penalty -- and keeps it in
+        # self.last_crf_entropy; at the default 0 the step launches nothing for it.
+        entropy_weight = _arg(self.args, "crf_entropy_weight", 0.0)
+        if loss is not None and entropy_weight != 0:
+            crf_entropy = self.crf.entropy(emissions, mask=mask_u8, reduction="token_mean")
+            self.last_crf_entropy = crf_entropy.detach()
+            loss = loss + entropy_weight * crf_entropy
         if decoded is not None:
             # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
             # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)

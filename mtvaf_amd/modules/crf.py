@@ -3,7 +3,8 @@
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
 mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest, and over per-position
 tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``constrained_marginals``, ``decode_constrained``), and
-the gradient of posterior expectations by mtvaf_crf_risk_{fwd,bwd} (``expected_cost``, ``hamming_risk``, ``differentiable_marginals``).  Parameter names (``start_transitions``,
+the gradient of posterior expectations by mtvaf_crf_risk_{fwd,bwd} (``expected_cost``, ``hamming_risk``, ``differentiable_marginals``)
+and, with edge costs, mtvaf_crf_path_{fwd,bwd} (``expected_path_cost``, ``entropy``, ``kl_divergence``).  Parameter names (``start_transitions``,
 ``end_transitions``, ``transitions``) and the uniform(-0.1, 0.1) initialisation follow pytorch-crf.
 """
 from __future__ import annotations
@@ -480,6 +481,72 @@ class CRF(nn.Module):
         hip.crf_risk_check(em, None, mask, "CRF.differentiable_marginals")
         marg = engine.CRFMarginalsFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions, mask)
         return marg if self.batch_first else marg.transpose(0, 1)
+
+    # ---- path costs with edge terms: expected cost, entropy, KL (csrc/crf_path.hip) ----
+    def expected_path_cost(self, emissions, cost=None, edge_cost=None, mask: Optional[torch.Tensor] = None,
+                           reduction: str = "none"):
+        """The expected value under the posterior of a path cost with a term on every edge: ``R[b] = E_{y ~ p(.|x_b)} [sum_t
+        cost[b,t,y_t] + sum_{t>=1} edge_cost[y_{t-1},y_t]]`` over the unmasked columns (mtvaf_crf_path_{fwd,bwd}),
+        differentiable in the emissions, the chain parameters and whichever cost requires grad (their gradients are the node
+        marginals and the edge marginals summed over columns).  Transition-sensitive risk: penalise ``O -> I-x`` or boundary
+        errors.  ``cost`` (emissions' shape, follows ``batch_first``) and ``edge_cost`` [C,C] (row = previous tag) may each be
+        None; ``mask`` is a prefix mask.  Reductions as ``forward``.  ``expected_cost`` stays on its own kernels."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        who = "CRF.expected_path_cost"
+        if cost is not None:
+            if not isinstance(cost, torch.Tensor) or not cost.dtype.is_floating_point:
+                raise ValueError(f"{who}: cost must be a floating-point tensor, got {getattr(cost, 'dtype', type(cost).__name__)}")
+            if tuple(cost.shape) != tuple(emissions.shape):
+                raise ValueError(f"{who}: cost {tuple(cost.shape)} does not fit emissions {tuple(emissions.shape)}")
+        em, _, mask = self._prep(emissions, None, mask)
+        if cost is not None and not self.batch_first:
+            cost = cost.transpose(0, 1)
+        hip.crf_path_check(em, cost, edge_cost, mask, who)
+        risk = engine.CRFPathFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions,
+                                            None if cost is None else cost.float(),
+                                            None if edge_cost is None else edge_cost.float(), mask)
+        return self.reduce_risk(risk, mask.to(risk.dtype).sum(), reduction)
+
+    def entropy(self, emissions, mask: Optional[torch.Tensor] = None, reduction: str = "none"):
+        """The entropy of the posterior over whole tag sequences, ``H[b] = -sum_y p(y|x_b) log p(y|x_b) = logZ - E_p[score]``, in
+        nats, with a gradient to the emissions and the chain parameters (`engine.CRFEntropyFunction`: one forward and one
+        backward kernel call).  The sequence-level uncertainty beside ``decode_nbest``'s ``p(best path)``; as a loss term,
+        entropy minimisation (or, negated, a confidence penalty).  ``0 <= H <= len * log(num_tags)``.  ``mask`` is a prefix
+        mask.  Reductions as ``forward``; 'token_mean' divides by the unmasked columns."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        em, _, mask = self._prep(emissions, None, mask)
+        hip.crf_path_check(em, None, None, mask, "CRF.entropy")
+        h = engine.CRFEntropyFunction.apply(em, self.start_transitions, self.end_transitions, self.transitions, mask)
+        return self.reduce_risk(h, mask.to(h.dtype).sum(), reduction)
+
+    def kl_divergence(self, emissions_p, emissions_q, mask: Optional[torch.Tensor] = None, other: Optional["CRF"] = None,
+                      reduction: str = "none"):
+        """``KL(p || q)[b]`` over whole tag sequences, ``p`` this chain on ``emissions_p`` and ``q`` the chain ``other`` (None:
+        this one) on ``emissions_q``, same mask: ``E_p[score_p - score_q] - logZ_p + logZ_q`` (`engine.CRFKLFunction`).
+        Gradients flow to both sides -- detach a side (emissions, and for a teacher ``other``'s parameters) and it costs no
+        backward call; with shared parameters both contributions accumulate into them.  Distillation from a teacher CRF with
+        its own transitions; consistency between two passes.  ``mask`` is a prefix mask.  Reductions as ``forward``."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        q = self if other is None else other
+        if q.num_tags != self.num_tags:
+            raise ValueError(f"CRF.kl_divergence: other has {q.num_tags} tags, this chain {self.num_tags}")
+        if q.transitions.device != self.transitions.device:
+            raise ValueError(f"CRF.kl_divergence: other's parameters on {q.transitions.device}, this chain's on "
+                             f"{self.transitions.device}")
+        if emissions_q.device != emissions_p.device:
+            raise ValueError(f"CRF.kl_divergence: emissions_q on {emissions_q.device}, emissions_p on {emissions_p.device}")
+        if tuple(emissions_p.shape) != tuple(emissions_q.shape):
+            raise ValueError(f"CRF.kl_divergence: emissions_q {tuple(emissions_q.shape)} does not fit emissions_p "
+                             f"{tuple(emissions_p.shape)}")
+        ep, _, mask = self._prep(emissions_p, None, mask)
+        eq = emissions_q.float() if self.batch_first else emissions_q.transpose(0, 1).float()
+        hip.crf_path_check(ep, eq, None, mask, "CRF.kl_divergence")
+        kl = engine.CRFKLFunction.apply(ep, self.start_transitions, self.end_transitions, self.transitions, eq,
+                                        q.start_transitions, q.end_transitions, q.transitions, mask)
+        return self.reduce_risk(kl, mask.to(kl.dtype).sum(), reduction)
 
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
