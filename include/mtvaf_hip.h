@@ -216,7 +216,9 @@ int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgam
 size_t mtvaf_colsum_workspace_bytes(int rows, int cols);
 int mtvaf_colsum(const float* x, int rows, int cols, int ld, float* out, int accumulate, void* workspace,
                  size_t workspace_bytes, mtvaf_stream_t stream);
-int mtvaf_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed, uint64_t offset,
+/* p_drop is a double: kept elements are scaled by float(1 / (1 - p)) as torch scales them (in fp32 from a float p that is
+ * 9.999998, not 10, at p = 0.9). */
+int mtvaf_dropout(const float* x, float* y, long n, double p_drop, uint64_t seed, uint64_t offset,
                   mtvaf_stream_t stream);
 
 /* ---- linear-chain CRF head --------------------------------------------------------------------------------

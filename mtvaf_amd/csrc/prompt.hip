@@ -181,19 +181,21 @@ __global__ __launch_bounds__(256) void kl_logsoftmax_kernel(const float* __restr
   for (int i = threadIdx.x; i < N; i += 256) { s += __expf(z[i] - m); ts += t[i]; }
   s = block_reduce(s, false);
   ts = block_reduce(ts, false);
-  const float lz = m + __logf(s);
+  // log p_k = (z_k - m) - log(s): the shift is taken off BEFORE the small term (m + log(s) rounds to an ulp of m, which is
+  // 1e-3 for logits with a common offset of 1e4)
+  const float ls = __logf(s);
   if (row_loss) {
     float l = 0.f;
     for (int i = threadIdx.x; i < N; i += 256) {
       const float tv = t[i];
-      if (tv > 0.f) l += tv * (__logf(tv) - (z[i] - lz));
+      if (tv > 0.f) l += tv * (__logf(tv) - ((z[i] - m) - ls));
     }
     l = block_reduce(l, false);
     if (threadIdx.x == 0) row_loss[r] = l;
   }
   if (dlogits) {
     const float g = (gout ? *gout : 1.f) * gscale / B;
-    for (int i = threadIdx.x; i < N; i += 256) dlogits[(long)r * N + i] = g * (__expf(z[i] - lz) * ts - t[i]);
+    for (int i = threadIdx.x; i < N; i += 256) dlogits[(long)r * N + i] = g * (__expf((z[i] - m) - ls) * ts - t[i]);
   }
 }
 

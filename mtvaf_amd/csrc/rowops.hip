@@ -656,10 +656,10 @@ __global__ void pos_reduce_kernel(const float* __restrict__ dz, float* __restric
   }
 }
 
-__global__ void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n4, float p_drop,
+// scale = float(1 / (1 - p)) from the host's double p, as torch scales: 1.f / (1.f - p) in fp32 is 9.999998 at p = 0.9
+__global__ void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n4, float p_drop, float scale,
                                uint64_t seed, uint64_t offset, const uint64_t* __restrict__ epoch) {
   offset = epoch_offset(offset, epoch);
-  const float scale = 1.f / (1.f - p_drop);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
     const uint32_t k = dropout_keep4(seed, offset, (uint64_t)i, p_drop);
@@ -691,7 +691,8 @@ __global__ void roberta_pos_kernel(const int64_t* __restrict__ ids, int32_t* __r
 // zero fill as a KERNEL (not hipMemsetAsync): a captured 94-MB memset node replayed wrongly on ROCm 7.2 (every fourth
 // column of the word-table gradient kept stale data under HIP graph replay), a kernel node replays exactly
 __global__ __launch_bounds__(256) void zero_f32_kernel(float* __restrict__ p, long n) {
-  const long n4 = n >> 2;
+  // vector body when the base is 16-byte aligned (a view into packed storage may not be), scalar otherwise and for the tail
+  const long n4 = ((uintptr_t)p & 15) == 0 ? (n >> 2) : 0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
     reinterpret_cast<f32x4*>(p)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = 0.f;
@@ -1192,9 +1193,9 @@ int mtvaf_colsum(const float* x, int rows, int cols, int ld, float* out, int acc
 }
 
 // y = dropout(x) (n % 4 == 0); the same call with the same (seed, offset) on a gradient is the backward.
-int mtvaf_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st) {
+int mtvaf_dropout(const float* x, float* y, long n, double p_drop, uint64_t seed, uint64_t offset, hipStream_t st) {
   if (n <= 0 || n % 4) return MTVAF_ERR_SHAPE;
-  if (p_drop <= 0.f) {
+  if (p_drop <= 0.0) {
     if (x != y) {
       hipError_t e = hipMemcpyAsync(y, x, n * sizeof(float), hipMemcpyDeviceToDevice, st);
       if (e != hipSuccess) return (int)e;
@@ -1203,7 +1204,8 @@ int mtvaf_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed,
   }
   const long n4 = n / 4;
   const int blocks = (int)std::min<long>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(dropout_kernel, dim3(blocks), dim3(256), 0, st, x, y, n4, p_drop, seed, offset, rng_epoch_ptr());
+  hipLaunchKernelGGL(dropout_kernel, dim3(blocks), dim3(256), 0, st, x, y, n4, (float)p_drop, (float)(1.0 / (1.0 - p_drop)), seed, offset,
+                     rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

@@ -82,7 +82,7 @@ _SIGS = {
     "mtvaf_dropout_res_ln_bwd_finish": (c_int, [P, I, I, P, P, P, I, P]),
     "mtvaf_colsum_workspace_bytes": (SZ, [I, I]),
     "mtvaf_colsum": (c_int, [P, I, I, I, P, I, P, SZ, P]),
-    "mtvaf_dropout": (c_int, [P, P, L, F, U64, U64, P]),
+    "mtvaf_dropout": (c_int, [P, P, L, c_double, U64, U64, P]),
     "mtvaf_crf_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_nll_fwd": (c_int, [P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_nll_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
