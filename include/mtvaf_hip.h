@@ -836,6 +836,38 @@ int mtvaf_adamw_multi(int count, float* const* p, const float* const* g, float* 
                       const long* n, float lr, double beta1, double beta2, float eps, float weight_decay, float bc1,
                       float bc2_sqrt, float grad_scale, mtvaf_stream_t stream);
 
+/* ---- gradient clipping by global L2 norm, norm reporting and a non-finite skip, all on the device (new functionality: the
+ * reference trainer does not clip, modules/train.py:620-625).  No host synchronisation, no atomics, no pass that rescales gradients.
+ * mtvaf_grad_sqnorm_multi: sum of squares of `count` fp32 tensors (host arrays of device pointers and lengths, any count; pointers
+ * 4-byte aligned).  Every tensor is cut into chunks of 65536 elements -- independent of the device and of the grid -- and one block
+ * per chunk writes one double to its own slot of `partials`, tensor after tensor; squares and sums are double from the first
+ * operation (a gradient of 1e20 gives a finite norm, and the result does not depend on the length of a run).
+ * mtvaf_grad_sqnorm_workspace_bytes: the bytes of `partials` for these lengths (8 per chunk; 0 for a bad argument); fewer in the
+ * call: MTVAF_ERR_WORKSPACE.
+ * mtvaf_grad_clip_finalize (one block) adds `count` partials in index order and writes clip_state[4] (16-byte aligned):
+ *   [0] norm = fp32(sqrt(sum))   [1] coef = min(1, max_norm / (norm + 1e-6)), torch's clip_grad_norm_ rule; 1 for max_norm <= 0
+ *   [2] finite = 1.f / 0.f       [3] 0
+ * A norm that is not finite in fp32, with skip_nonfinite != 0: coef = 0, finite = 0 and *skipped (int32, may be NULL) += 1.  With
+ * skip_nonfinite == 0, finite stays 1 and the norm reaches coef as in torch (inf -> 0, NaN -> NaN).  Same inputs, same bits.
+ * mtvaf_adamw_dev / _planes_dev / _multi_dev: the entry points above with the gradient scaled by grad_scale * clip_state[1]; with
+ * clip_state[2] == 0 they write nothing (p, m, v, the bf16 shadow and the plane images keep their bits).  With coef == 1 they
+ * equal their counterparts bit for bit. */
+size_t mtvaf_grad_sqnorm_workspace_bytes(int count, const long* n);
+int mtvaf_grad_sqnorm_multi(int count, const float* const* g, const long* n, void* partials, size_t partials_bytes,
+                            mtvaf_stream_t stream);
+int mtvaf_grad_clip_finalize(const void* partials, long count, float max_norm, int skip_nonfinite, float* clip_state,
+                             int* skipped, mtvaf_stream_t stream);
+int mtvaf_adamw_dev(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                    float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
+                    const float* clip_state, mtvaf_stream_t stream);
+int mtvaf_adamw_planes_dev(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                           float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                           const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks,
+                           const float* clip_state, mtvaf_stream_t stream);
+int mtvaf_adamw_multi_dev(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                          const long* n, float lr, double beta1, double beta2, float eps, float weight_decay, float bc1,
+                          float bc2_sqrt, float grad_scale, const float* clip_state, mtvaf_stream_t stream);
+
 /* ---- bf16 gradient wire format of the data-parallel exchange (mtvaf_amd/parallel.py; new functionality, the
  * reference never synchronises gradients: MTVAF_training.py:305-309).  pack: dst[i] = bf16(src[i]), zero padding up to
  * npad (npad % 8 == 0); reduce: out[c] = bf16(scale * sum_r recv[r*chunk + c]) with fp32 accumulation in rank order;

@@ -9,6 +9,11 @@
 //     p  -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   7 fp32 streams per parameter (read p, g, m, v; write p, m, v) = 28 B; an optional bf16 copy of the new
 //   parameter (the GEMM operand shadow of the bf16 compute mode) adds 2 B.
+//
+//   The *_dev forms read a device clip state {norm, coef, finite, -} (written by mtvaf_grad_clip_finalize, csrc/gradnorm.hip):
+//   the gradient is scaled by grad_scale * coef, and with finite == 0 the kernel returns before its first load -- p, m, v,
+//   the bf16 shadow and the plane images keep their bits.  Same bodies as the host-scalar forms (a template flag), so with
+//   coef == 1 the results are the same bits.
 #include "common.h"
 #include "planes.h"
 
@@ -69,8 +74,23 @@ __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* _
   }
 }
 
+// DEV: the clip state decides (block-uniform, two scalar loads) whether this launch writes at all and what the gradient is scaled by
+template <bool DEV>
+__device__ __forceinline__ bool clip_apply(AdamHyper& h, const float* __restrict__ clip) {
+  if constexpr (DEV) {
+    if (clip[2] == 0.f) return false;
+    h.grad_scale *= clip[1];
+  }
+  return true;
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, __bf16* ph, long n,
                                                     AdamHyper h) {
+  adamw_span(p, g, m, v, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
+}
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* p, const float* g, float* m, float* v, __bf16* ph, long n,
+                                                        AdamHyper h, const float* clip) {
+  if (!clip_apply<true>(h, clip)) return;
   adamw_span(p, g, m, v, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
 }
 
@@ -83,8 +103,8 @@ struct AdamSegs {
   unsigned char* img[4];
   int n;
 };
-__global__ __launch_bounds__(256) void adamw_planes_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg) {
+__device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg) {
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     f32x4 P = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
@@ -110,6 +130,16 @@ __global__ __launch_bounds__(256) void adamw_planes_kernel(float* __restrict__ p
     }
   }
 }
+__global__ __launch_bounds__(256) void adamw_planes_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg) {
+  adamw_planes_body(p, g, m, v, n4, h, sg);
+}
+__global__ __launch_bounds__(256) void adamw_planes_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg,
+                                                               const float* __restrict__ clip) {
+  if (!clip_apply<true>(h, clip)) return;
+  adamw_planes_body(p, g, m, v, n4, h, sg);
+}
 
 // several tensors of one parameter group in one launch: blockIdx.x -> (tensor, block within tensor) through a prefix table
 constexpr int ADAM_MAXT = 48;
@@ -123,12 +153,17 @@ struct AdamMulti {
   int count;
 };
 
-__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamMulti t, AdamHyper h) {
+__device__ __forceinline__ void adamw_multi_body(const AdamMulti& t, const AdamHyper& h) {
   int k = 0;
   const int b = blockIdx.x;
   while (k + 1 < t.count && b >= t.blk0[k + 1]) ++k;
   const int nb = t.blk0[k + 1] - t.blk0[k];
   adamw_span(t.p[k], t.g[k], t.m[k], t.v[k], nullptr, t.n[k], (long)(b - t.blk0[k]) * 256 + threadIdx.x, (long)nb * 256, h);
+}
+__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamMulti t, AdamHyper h) { adamw_multi_body(t, h); }
+__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(AdamMulti t, AdamHyper h, const float* clip) {
+  if (!clip_apply<true>(h, clip)) return;
+  adamw_multi_body(t, h);
 }
 
 // ---- bf16 gradient wire format ------------------------------------------------------------------------------
@@ -191,38 +226,28 @@ static inline int stream_grid(long work_items) {
   return (int)(b < 1 ? 1 : (b > 256 * 8 ? 256 * 8 : b));  // up to 8 blocks per CU: enough loads in flight for HBM
 }
 
-}  // namespace mtvaf
-
-using namespace mtvaf;
-
-extern "C" {
-
-// One flat tensor (an encoder layer's parameter buffer).  bias corrections are passed in: bc1 = 1 - beta1^t,
-// bc2_sqrt = sqrt(1 - beta2^t).  p_bf16 (optional) receives the updated parameter rounded to bf16.
-// max_blocks > 0 caps the grid: a BACKGROUND update.  At full width (2048 blocks) the update streams at the HBM rate
-// (6.3 TB/s) and starves the operand fetches of the MFMA-bound products it runs beside for its 32 us; 128 blocks trickle
-// at ~1 TB/s under them instead (measured per step, same box: fp32 bs 32 18.95 -> 18.70 ms, bf16 bs 64 11.78 -> 11.56;
-// 64 blocks and fewer take longer than the layer's backward pass they hide behind and lose).  0: full width.
-int mtvaf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
-                float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
-                hipStream_t stream) {
+// The launches behind the entry points: clip == nullptr is the host-scalar form, anything else the *_dev form of the same body.
+static int adamw_launch(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                        float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
+                        const float* clip, hipStream_t stream) {
   if (!p || !g || !m || !v || n <= 0) return MTVAF_ERR_ARG;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) return MTVAF_ERR_ALIGN;
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   int grid = stream_grid((n + 3) / 4);
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v,
-                     static_cast<__bf16*>(p_bf16), n, h);
+  if (clip)
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, static_cast<__bf16*>(p_bf16), n, h, clip);
+  else
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v,
+                       static_cast<__bf16*>(p_bf16), n, h);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 
-// mtvaf_adamw over a flat buffer (n % 4 == 0, 16-byte aligned) that also rewrites the plane images of nseg <= 4 row-major fp32
-// matrices inside it: matrix s starts at element seg_begin[s] (% 4 == 0) of the buffer, is [seg_rows[s]][seg_cols[s]] (cols % 32 == 0)
-// and has its tile-blocked image (6 bytes per element) at seg_img[s].  Same update as mtvaf_adamw, bit for bit.
-int mtvaf_adamw_planes(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
-                       float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
-                       const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, hipStream_t stream) {
+static int adamw_planes_launch(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                               float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                               const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, const float* clip,
+                               hipStream_t stream) {
   if (!p || !g || !m || !v || n <= 0 || nseg < 0 || nseg > 4 || (nseg && (!seg_begin || !seg_rows || !seg_cols || !seg_img))) return MTVAF_ERR_ARG;
   if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15)) return MTVAF_ERR_ALIGN;
   AdamSegs sg = {};
@@ -239,15 +264,17 @@ int mtvaf_adamw_planes(float* p, const float* g, float* m, float* v, long n, flo
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   int grid = stream_grid(n / 4);
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
-  hipLaunchKernelGGL(adamw_planes_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n / 4, h, sg);
+  if (clip)
+    hipLaunchKernelGGL(adamw_planes_dev_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n / 4, h, sg, clip);
+  else
+    hipLaunchKernelGGL(adamw_planes_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n / 4, h, sg);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 
-// `count` tensors sharing one set of hyper-parameters (a torch parameter group); host arrays of device pointers.
-int mtvaf_adamw_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
-                      float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
-                      float grad_scale, hipStream_t stream) {
+static int adamw_multi_launch(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                              float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                              float grad_scale, const float* clip, hipStream_t stream) {
   if (count < 0 || (count && (!p || !g || !m || !v || !n))) return MTVAF_ERR_ARG;
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   for (int base = 0; base < count; base += ADAM_MAXT) {
@@ -264,10 +291,76 @@ int mtvaf_adamw_multi(int count, float* const* p, const float* const* g, float* 
       blocks += (int)(b > 1024 ? 1024 : b);
     }
     t.blk0[t.count] = blocks;
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, t, h);
+    if (clip)
+      hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3(blocks), dim3(256), 0, stream, t, h, clip);
+    else
+      hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, t, h);
     MTVAF_LAUNCH_CHECK();
   }
   return MTVAF_OK;
+}
+
+}  // namespace mtvaf
+
+using namespace mtvaf;
+
+extern "C" {
+
+// One flat tensor (an encoder layer's parameter buffer).  bias corrections are passed in: bc1 = 1 - beta1^t,
+// bc2_sqrt = sqrt(1 - beta2^t).  p_bf16 (optional) receives the updated parameter rounded to bf16.
+// max_blocks > 0 caps the grid: a BACKGROUND update.  At full width (2048 blocks) the update streams at the HBM rate
+// (6.3 TB/s) and starves the operand fetches of the MFMA-bound products it runs beside for its 32 us; 128 blocks trickle
+// at ~1 TB/s under them instead (measured per step, same box: fp32 bs 32 18.95 -> 18.70 ms, bf16 bs 64 11.78 -> 11.56;
+// 64 blocks and fewer take longer than the layer's backward pass they hide behind and lose).  0: full width.
+int mtvaf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
+                hipStream_t stream) {
+  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, nullptr, stream);
+}
+
+// mtvaf_adamw with the gradient scaled by grad_scale * clip_state[1] on the device; clip_state[2] == 0: nothing is written.
+int mtvaf_adamw_dev(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                    float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
+                    const float* clip_state, hipStream_t stream) {
+  if (!clip_state) return MTVAF_ERR_ARG;
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, clip_state, stream);
+}
+
+// mtvaf_adamw over a flat buffer (n % 4 == 0, 16-byte aligned) that also rewrites the plane images of nseg <= 4 row-major fp32
+// matrices inside it: matrix s starts at element seg_begin[s] (% 4 == 0) of the buffer, is [seg_rows[s]][seg_cols[s]] (cols % 32 == 0)
+// and has its tile-blocked image (6 bytes per element) at seg_img[s].  Same update as mtvaf_adamw, bit for bit.
+int mtvaf_adamw_planes(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                       float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                       const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, hipStream_t stream) {
+  return adamw_planes_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nseg, seg_begin, seg_rows,
+                             seg_cols, seg_img, max_blocks, nullptr, stream);
+}
+
+// mtvaf_adamw_planes under a device clip state: with clip_state[2] == 0 the plane images keep their bits too.
+int mtvaf_adamw_planes_dev(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                           float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                           const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, const float* clip_state,
+                           hipStream_t stream) {
+  if (!clip_state) return MTVAF_ERR_ARG;
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  return adamw_planes_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nseg, seg_begin, seg_rows,
+                             seg_cols, seg_img, max_blocks, clip_state, stream);
+}
+
+// `count` tensors sharing one set of hyper-parameters (a torch parameter group); host arrays of device pointers.
+int mtvaf_adamw_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                      float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                      float grad_scale, hipStream_t stream) {
+  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nullptr, stream);
+}
+
+int mtvaf_adamw_multi_dev(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                          float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                          float grad_scale, const float* clip_state, hipStream_t stream) {
+  if (!clip_state) return MTVAF_ERR_ARG;
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, clip_state, stream);
 }
 
 int mtvaf_grad_pack_bf16(const float* src, void* dst, long n, long npad, hipStream_t stream) {

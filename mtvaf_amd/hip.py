@@ -148,6 +148,12 @@ _SIGS = {
     "mtvaf_adamw": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, P, I, P]),
     "mtvaf_adamw_planes": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P]),
     "mtvaf_adamw_multi": (c_int, [I, P, P, P, P, P, F, c_double, c_double, F, F, F, F, F, P]),
+    "mtvaf_grad_sqnorm_workspace_bytes": (SZ, [I, P]),
+    "mtvaf_grad_sqnorm_multi": (c_int, [I, P, P, P, SZ, P]),
+    "mtvaf_grad_clip_finalize": (c_int, [P, L, F, I, P, P, P]),
+    "mtvaf_adamw_dev": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, P, I, P, P]),
+    "mtvaf_adamw_planes_dev": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P, P]),
+    "mtvaf_adamw_multi_dev": (c_int, [I, P, P, P, P, P, F, c_double, c_double, F, F, F, F, F, P, P]),
     "mtvaf_grad_pack_bf16": (c_int, [P, P, L, L, P]),
     "mtvaf_grad_reduce_bf16": (c_int, [P, P, I, L, F, P]),
     "mtvaf_grad_unpack_bf16": (c_int, [P, P, L, P]),
@@ -1353,39 +1359,92 @@ def colsum_small(part, out, accumulate=False):
     return out
 
 
-# ---- optimizer / gradient wire format (csrc/optim.hip) ------------------------------------------------------------
-def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, grad_scale=1.0, max_blocks=0):
+# ---- optimizer / gradient wire format (csrc/optim.hip, csrc/gradnorm.hip) -------------------------------------------
+def _clip_ptr(clip):
+    """Device clip state of grad_clip_finalize for the *_dev update kernels: 4 floats {norm, coef, finite, 0}."""
+    assert clip.is_cuda and clip.dtype == torch.float32 and clip.numel() >= 4 and clip.is_contiguous(), (clip.device, clip.dtype, clip.shape)
+    return clip.data_ptr()
+
+
+def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, grad_scale=1.0, max_blocks=0, clip=None):
     """adamw over a flat buffer that also rewrites the plane images of the matrices inside it: segs = [(begin element, rows, cols,
-    image uint8 tensor), ...] (at most four)."""
+    image uint8 tensor), ...] (at most four).  clip: see adamw."""
     _f32(p, g, m, v)
     n = len(segs)
     bc1 = 1.0 - beta1 ** step
     bc2_sqrt = (1.0 - beta2 ** step) ** 0.5
-    _ck(lib().mtvaf_adamw_planes(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                 float(bc1), float(bc2_sqrt), float(grad_scale), n, (ctypes.c_long * n)(*[s[0] for s in segs]),
-                                 (ctypes.c_int * n)(*[s[1] for s in segs]), (ctypes.c_int * n)(*[s[2] for s in segs]),
-                                 (ctypes.c_void_p * n)(*[_p(s[3]) for s in segs]), int(max_blocks), _st()), "mtvaf_adamw_planes")
+    args = (_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+            float(bc1), float(bc2_sqrt), float(grad_scale), n, (ctypes.c_long * n)(*[s[0] for s in segs]),
+            (ctypes.c_int * n)(*[s[1] for s in segs]), (ctypes.c_int * n)(*[s[2] for s in segs]),
+            (ctypes.c_void_p * n)(*[_p(s[3]) for s in segs]), int(max_blocks))
+    if clip is None:
+        _ck(lib().mtvaf_adamw_planes(*args, _st()), "mtvaf_adamw_planes")
+    else:
+        _ck(lib().mtvaf_adamw_planes_dev(*args, _clip_ptr(clip), _st()), "mtvaf_adamw_planes_dev")
 
 
-def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, p_bf16=None, max_blocks=0):
+def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None):
     """In-place AdamW update of one flat fp32 tensor (torch.optim.AdamW semantics); `step` is the 1-based step count;
-    max_blocks > 0: a background update on that many blocks (runs under MFMA-bound kernels without starving them)."""
+    max_blocks > 0: a background update on that many blocks (runs under MFMA-bound kernels without starving them).
+    clip: the device state written by grad_clip_finalize -- the gradient is scaled by grad_scale * coef on the device, and a
+    state whose `finite` is 0 makes the launch write nothing."""
     n = p.numel()
     bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    _ck(lib().mtvaf_adamw(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
-                          _p(p_bf16), int(max_blocks), _st()), "mtvaf_adamw")
+    if clip is None:
+        _ck(lib().mtvaf_adamw(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
+                              _p(p_bf16), int(max_blocks), _st()), "mtvaf_adamw")
+    else:
+        _ck(lib().mtvaf_adamw_dev(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
+                                  _p(p_bf16), int(max_blocks), _clip_ptr(clip), _st()), "mtvaf_adamw_dev")
 
 
-def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
-    """One launch per 48 tensors of a parameter group sharing hyper-parameters and step count."""
+def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None):
+    """One launch per 48 tensors of a parameter group sharing hyper-parameters and step count.  clip: see adamw."""
     k = len(ps)
     if k == 0:
         return
     arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
     ns = (ctypes.c_long * k)(*[t.numel() for t in ps])
     bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    _ck(lib().mtvaf_adamw_multi(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
-                                bc2 ** 0.5, grad_scale, _st()), "mtvaf_adamw_multi")
+    if clip is None:
+        _ck(lib().mtvaf_adamw_multi(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
+                                    bc2 ** 0.5, grad_scale, _st()), "mtvaf_adamw_multi")
+    else:
+        _ck(lib().mtvaf_adamw_multi_dev(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
+                                        bc2 ** 0.5, grad_scale, _clip_ptr(clip), _st()), "mtvaf_adamw_multi_dev")
+
+
+def grad_sqnorm_slots(gs) -> int:
+    """Number of partial sums (doubles) grad_sqnorm writes for these tensors: one per chunk of 65536 elements."""
+    k = len(gs)
+    return int(lib().mtvaf_grad_sqnorm_workspace_bytes(k, (ctypes.c_long * k)(*[t.numel() for t in gs]))) // 8
+
+
+def grad_sqnorm(gs, partials=None):
+    """Sums of squares of the fp32 tensors gs (contiguous; 4-byte aligned views are fine), in double, one per chunk of 65536
+    elements, tensor after tensor -> the float64 tensor of partial sums (`partials`, or a new one of grad_sqnorm_slots(gs))."""
+    k = len(gs)
+    for t in gs:
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() > 0, (t.device, t.dtype, t.shape)
+    ns = (ctypes.c_long * k)(*[t.numel() for t in gs])
+    slots = int(lib().mtvaf_grad_sqnorm_workspace_bytes(k, ns)) // 8
+    if partials is None:
+        partials = torch.empty(slots, dtype=torch.float64, device=gs[0].device if k else "cuda")
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+    _ck(lib().mtvaf_grad_sqnorm_multi(k, (ctypes.c_void_p * k)(*[t.data_ptr() for t in gs]), ns, _p(partials),
+                                      partials.numel() * 8, _st()), "mtvaf_grad_sqnorm_multi")
+    return partials[:slots]
+
+
+def grad_clip_finalize(partials, max_norm, state, skipped=None, skip_nonfinite=True):
+    """state (4 floats on the device) <- {norm, coef, finite, 0} from the partial sums of grad_sqnorm, added in index order:
+    coef = min(1, max_norm / (norm + 1e-6)), or 1 for max_norm <= 0; a non-finite norm under skip_nonfinite gives coef = 0,
+    finite = 0 and adds 1 to `skipped` (device int32)."""
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+    assert skipped is None or (skipped.is_cuda and skipped.dtype == torch.int32)
+    _ck(lib().mtvaf_grad_clip_finalize(_p(partials), partials.numel(), float(max_norm), int(bool(skip_nonfinite)), _clip_ptr(state),
+                                       _p(skipped), _st()), "mtvaf_grad_clip_finalize")
+    return state
 
 
 def grad_pack_bf16(src, dst, n, npad):

@@ -40,13 +40,40 @@ class AdamW(torch.optim.Optimizer):
     ``overlap=False`` for it (``build_optimizer`` does).  ``step()`` then only updates what is left (embeddings, heads,
     prompt generator) and layers that could not take the fast path.
 
+    ``max_grad_norm > 0``: gradients are clipped by their global L2 norm (``torch.nn.utils.clip_grad_norm_``'s rule) INSIDE the
+    update kernels: ``step()`` launches one multi-tensor sum of squares (double) over every gradient it is about to apply and a
+    one-block finalize that leaves ``{norm, coefficient, finite}`` on the device, then every update through the ``*_dev`` entry
+    points, which scale the gradient by that coefficient -- no host synchronisation, no pass that rewrites the gradients
+    (``.grad`` keeps its unclipped values).  ``track_grad_norm=True`` alone reports the norm without clipping.  Either switch
+    makes ``last_grad_norm`` (0-dim device tensor, the pre-clip norm) and ``skipped_steps`` (device int32) live; with
+    ``skip_nonfinite`` (default) a step whose norm is inf / NaN writes NOTHING -- parameters, moments, bf16 shadows and plane
+    images keep their bits -- and is counted in ``skipped_steps``.  The host cannot know that without a sync, so the step
+    counters still advance: after a skipped step the bias correction is one step ahead.
+    ``skip_nonfinite=False`` keeps torch's behaviour (the NaN coefficient reaches the parameters).  With both switches off
+    ``step()`` issues exactly the launches it always did, and ``skip_nonfinite`` has nothing to act on.  A global norm is not
+    known while layers are still being updated inside backward: together with ``overlap=True`` either switch raises.
+
     Checkpoints: ``state_dict()`` / ``load_state_dict()`` are torch.optim's; the flat per-layer moment buffers are
     rebuilt from the loaded per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step`` entries on the first update."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None):
+                 model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None, max_grad_norm: float = 0.0,
+                 track_grad_norm: bool = False, skip_nonfinite: bool = True):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
+        max_grad_norm = float(max_grad_norm or 0.0)
+        if max_grad_norm != max_grad_norm or max_grad_norm < 0.0:
+            raise ValueError("max_grad_norm must be >= 0 (0: no clipping)")
+        if overlap and (max_grad_norm > 0.0 or track_grad_norm):
+            raise ValueError("mtvaf_amd.optim.AdamW: max_grad_norm / track_grad_norm need overlap=False -- the global gradient norm "
+                             "is not known while layers are still being updated from inside the backward pass")
+        self.max_grad_norm = max_grad_norm
+        self.track_grad_norm = bool(track_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_state = None     # device {norm, coef, finite, 0}: written by the finalize kernel, read by the *_dev updates
+        self._clip_partials = None  # device doubles, one per 65536-element chunk of the gradients
+        self.last_grad_norm = None  # 0-dim view of _clip_state[0]: the pre-clip global norm of the last step()
+        self.skipped_steps = None   # device int32: steps whose norm was not finite (skip_nonfinite)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.overlap = overlap
         self._encoder = None
@@ -150,7 +177,7 @@ class AdamW(torch.optim.Optimizer):
     BACKGROUND_BLOCKS_SHORT = 256
     BACKGROUND_SHORT_ROWS = 4096
 
-    def _update_layer_flat(self, li: int, group: dict, store, background: bool = False, rows: int = 0):
+    def _update_layer_flat(self, li: int, group: dict, store, background: bool = False, rows: int = 0, clip=None):
         st = self._layer_state(li, store)
         st["step"] += 1
         st["step_t"].fill_(st["step"])  # the 16 per-parameter state entries share this 0-dim tensor
@@ -161,12 +188,13 @@ class AdamW(torch.optim.Optimizer):
         if segs is not None and store.flat.numel() % 4 == 0:
             # fp32 mode, pre-split operands: the weights' plane images are rewritten by the update kernel itself
             hip.adamw_planes(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                             st["step"], segs, max_blocks=self.BACKGROUND_BLOCKS_PLANES if background else 0)
+                             st["step"], segs, max_blocks=self.BACKGROUND_BLOCKS_PLANES if background else 0, clip=clip)
             engine.planes_written(store.weights)
             return
         hip.adamw(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
                   st["step"], p_bf16=shadow,
-                  max_blocks=(self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0)
+                  max_blocks=(self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0,
+                  clip=clip)
         if shadow is not None:
             engine.shadow_written(store.weights)
         engine.planes_rewrite(store.weights)  # (images exist but the fused form does not apply: rebuilt behind the update)
@@ -188,13 +216,33 @@ class AdamW(torch.optim.Optimizer):
         self._early.add(li)
 
     # -- the step ------------------------------------------------------------------------------------------------
+    def _clip_launch(self, grads):
+        """Norm + finalize over the gradients this step applies, on the stream of the updates that follow; -> the device state."""
+        dev = grads[0].device
+        if self._clip_state is None or self._clip_state.device != dev:
+            self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.last_grad_norm = self._clip_state[0]
+            self.skipped_steps = torch.zeros((), dtype=torch.int32, device=dev)
+            self._clip_partials = None
+        slots = hip.grad_sqnorm_slots(grads)
+        if self._clip_partials is None or self._clip_partials.numel() < slots or self._clip_partials.device != dev:
+            self._clip_partials = torch.empty(slots, dtype=torch.float64, device=dev)
+        part = hip.grad_sqnorm(grads, self._clip_partials)
+        hip.grad_clip_finalize(part, self.max_grad_norm, self._clip_state, self.skipped_steps, self.skip_nonfinite)
+        return self._clip_state
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clipping = self.max_grad_norm > 0.0 or self.track_grad_norm
+        if clipping and hip.STREAM_OVERRIDE is not None:
+            raise RuntimeError("mtvaf_amd.optim.AdamW: step() with max_grad_norm / track_grad_norm was called from inside a backward "
+                               "hook -- the gradient norm would be taken before the pass has produced every gradient")
         done = set()
+        layer_jobs = []  # (layer index, group, store): one launch each
         enc = self._encoder
         if enc is not None and enc._stores is not None:
             if len(self._layer_group) != len(enc.layer):
@@ -210,13 +258,13 @@ class AdamW(torch.optim.Optimizer):
                 lo = store.grad.data_ptr()
                 if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
                        for i, p in enumerate(ps)):
-                    self._update_layer_flat(li, group, store)
+                    layer_jobs.append((li, group, store))
                     done.update(id(p) for p in ps)
         self._early = set()
         touched = set()  # layers updated tensor by tensor this step: ONE step counter per layer, shared with the flat path
         flat_state = self.__dict__.get("_flat_state", {})
+        group_jobs = []  # (group, step number, [(p, g, exp_avg, exp_avg_sq), ...]): one launch per 48 tensors each
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             buckets: Dict[int, list] = {}
             for p in group["params"]:
                 if p.grad is None or id(p) in done:
@@ -241,9 +289,20 @@ class AdamW(torch.optim.Optimizer):
                 if not p.is_contiguous():
                     raise RuntimeError("non-contiguous parameter")
                 buckets.setdefault(step_no, []).append((p, g, stt["exp_avg"], stt["exp_avg_sq"]))
-            for step_no, items in buckets.items():
-                hip.adamw_multi([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
-                                float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step_no)
+            group_jobs.extend((group, step_no, items) for step_no, items in buckets.items())
+        clip = None
+        if clipping:
+            # every gradient about to be applied, each once: a layer's flat gradient buffer stands for its 16 views.  The launches
+            # go to the stream of the updates below, behind the producers of every gradient
+            grads = [store.grad for _, _, store in layer_jobs] + [i[1] for _, _, items in group_jobs for i in items]
+            if grads:
+                clip = self._clip_launch(grads)
+        for li, group, store in layer_jobs:
+            self._update_layer_flat(li, group, store, clip=clip)
+        for group, step_no, items in group_jobs:
+            b1, b2 = group["betas"]
+            hip.adamw_multi([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
+                            float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step_no, clip=clip)
         for li in touched:
             fst = flat_state[("layer", li)]
             fst["step"] += 1
@@ -285,13 +344,20 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
             if "image_model" in n:
                 p.requires_grad = False
     on_gpu = any(p.is_cuda for g in groups for p in g["params"])
+    max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)  # 0: unchanged, the reference does not clip (train.py:620-625)
+    track_grad_norm = bool(getattr(args, "track_grad_norm", False))
     if on_gpu:
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
         accum = int(getattr(args, "gradient_accumulation_steps", 1) or 1)
-        overlap = bool(getattr(args, "overlap_optimizer", True)) and accum == 1
-        opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None))
+        # a global gradient norm exists only once the whole backward pass has ended: clipping / tracking steps after it
+        overlap = bool(getattr(args, "overlap_optimizer", True)) and accum == 1 and not (max_grad_norm > 0.0 or track_grad_norm)
+        opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
+                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm)
     else:
+        if max_grad_norm > 0.0:
+            raise ValueError("build_optimizer: max_grad_norm is implemented by the gfx950 AdamW kernels; the CPU fallback "
+                             "(torch.optim.AdamW) would ignore it -- clip with torch.nn.utils.clip_grad_norm_ there")
         opt = torch.optim.AdamW(groups, lr=args.lr)
     sched = linear_schedule_with_warmup(opt, getattr(args, "warmup_ratio", 0.01) * train_num_steps, train_num_steps)
     return opt, sched
