@@ -273,6 +273,29 @@ int mtvaf_crf_nbest(const float* emissions, const uint8_t* mask, const float* st
                     int K, int32_t* tags_out, float* scores_out, float* logprob_out, int32_t* n_paths_out, int B, int S,
                     int C, void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
 
+/* Posterior sampling (csrc/crf_sample.hip): K tag sequences of every sentence drawn from p(y | x) by forward-filter
+ * backward-sample, 1 <= K <= 64, 1 <= C <= 64, 1 <= S <= 512 (anything else: MTVAF_ERR_SHAPE before any launch, and the
+ * workspace query returns 0; a workspace below the query: MTVAF_ERR_WORKSPACE).  mask is a prefix mask with mask[:,0] == 1, as
+ * for mtvaf_crf_nbest.  The forward recursion is mtvaf_crf_marginals' first launch; its alphas are read from the workspace.
+ * Sample k of sentence b, columns t = len_b - 1 .. 0:  x_i = log alpha_t[i] + (t == len_b - 1 ? end[i] : trans[i][y_{t+1}]),
+ * w_i = exp(x_i - max_i x_i), F_j = sum_{i <= j} w_i in ascending tag order in fp32; y_t = the smallest j with
+ * F_j > u * F_{C-1}; if rounding leaves none, the highest j with w_j > 0.
+ *   uniforms     [B,K,S] fp32 in [0,1): u of (b, k, t) is read here; NULL: Philox4x32-10 with counter (lo32(idx), hi32(idx),
+ *                lo32(offset), hi32(offset)), idx = (b * 64 + k) * 128 + (t >> 2), key (lo32(seed), hi32(seed)), word t & 3,
+ *                u = (word >> 8) * 2^-24; offset takes the dropout epoch (mtvaf_rng_set_epoch_ptr) like a dropout site
+ *   tags_out     int32 [B,K,S]: sample k in columns < len_b, -1 behind it
+ *   scores_out   [B,K] unnormalised path scores (the terms of mtvaf_crf_nbest's scores_out)
+ *   logprob_out  [B,K] = score - logZ_b, or NULL
+ *   uniforms_out [B,K,S] the uniform used at every column < len_b, 0 behind it, or NULL
+ * Every element of every non-NULL output is written.  workspace bytes: round256(4 B) logZ + mtvaf_crf_workspace_bytes(B, S, C).
+ * No host sync, no allocation; safe under stream capture (the forward's LDS opt-in for C <= 16 and S above about 470: as
+ * mtvaf_crf_marginals). */
+size_t mtvaf_crf_sample_workspace_bytes(int B, int S, int C, int K);
+int mtvaf_crf_sample(const float* emissions, const uint8_t* mask, const float* start, const float* end, const float* trans,
+                     int K, const float* uniforms, uint64_t seed, uint64_t offset, int32_t* tags_out, float* scores_out,
+                     float* logprob_out, float* uniforms_out, int B, int S, int C, void* workspace, size_t workspace_bytes,
+                     mtvaf_stream_t stream);
+
 /* per-token tag constraints (csrc/crf_lattice.hip): likelihood, posteriors and decoding over the paths a per-position tag
  * set allows.  allowed int64 [B,S], read as an unsigned word: bit j set = tag j may be taken at that column.  The effective
  * set is A[b,t] = allowed[b,t] & (2^C - 1), and the full set where that is empty (0 = no constraint, bits >= C ignored), so
@@ -466,6 +489,14 @@ int mtvaf_span_propose(const float* logits, int ld, const int* word_index, const
 int mtvaf_entity_counts(const int* pred, int ldp, const int64_t* gold, const uint8_t* mask, const uint8_t* start_tab,
                         const uint8_t* end_tab, const int* type_of, const uint8_t* gold_skip, int B, int S, int C,
                         int n_types, int64_t* counts, mtvaf_stream_t stream);
+
+/* The same chunking per row: rows_out int32 [R,3] = (predicted, gold, correct) chunks of row r summed over the types; every
+ * element is written and nothing is added anywhere.  pred [R,ldp] int32; row r is scored against gold / mask row r / group
+ * (gold and mask [R/group,S]), so hypotheses [B,K,S] go in as R = B K, group = K.  Kept columns, tables, gold_skip and shape
+ * rules as mtvaf_entity_counts, plus group >= 1 and R % group == 0 (else MTVAF_ERR_SHAPE before any launch). */
+int mtvaf_entity_counts_rows(const int* pred, int ldp, int group, const int64_t* gold, const uint8_t* mask,
+                             const uint8_t* start_tab, const uint8_t* end_tab, const int* type_of, const uint8_t* gold_skip,
+                             int R, int S, int C, int n_types, int32_t* rows_out, mtvaf_stream_t stream);
 
 /* Aspect-level score of the span model's predictions, the counting of modules/eval_metrics.py::eval_absa (:80-124) without
  * the per-sentence host copies of modules/train.py:200-209: common / retrieved / relevant per polarity class, ADDED into a

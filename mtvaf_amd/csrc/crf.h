@@ -14,4 +14,9 @@ namespace mtvaf {
 int crf_logz(const float* em, const uint8_t* mask, const float* start, const float* end, const float* trans, float* logz,
              int B, int S, int C, void* workspace, hipStream_t st);
 
+// Where crf_logz (and every other forward launch on `workspace`) leaves the alphas: row t of sentence b starts at
+// result + ((size_t)b * S + t) * *ld and holds C floats, alpha_t[.] divided by a positive constant of that row (the scaled
+// linear domain of both paths); rows of masked columns repeat the last unmasked one.
+const float* crf_alpha(const void* workspace, int B, int S, int C, int* ld);
+
 }  // namespace mtvaf

@@ -903,6 +903,16 @@ int mtvaf::crf_logz(const float* em, const uint8_t* mask, const float* start, co
   return MTVAF_OK;
 }
 
+const float* mtvaf::crf_alpha(const void* workspace, int B, int S, int C, int* ld) {
+  if (C > CMAX) {
+    const CrfWideWs w = crf_wide_ws(const_cast<void*>(workspace), B, S, C);
+    *ld = (int)((w.sp - w.alpha) / ((size_t)B * S));  // alpha [B,S,CT] is followed by sp
+    return w.alpha;
+  }
+  *ld = CMAX;
+  return crf16_ws(const_cast<void*>(workspace), B, S).alpha;
+}
+
 extern "C" {
 
 // C <= 16: Crf16Ws.  16 < C <= 64 (S <= 512): the wide path's layout (crf_wide.h).  0 for a shape neither path takes.

@@ -115,6 +115,9 @@ _SIGS = {
     "mtvaf_span_counts": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
     "mtvaf_crf_nbest_workspace_bytes": (SZ, [I, I, I, I]),
     "mtvaf_crf_nbest": (c_int, [P, P, P, P, P, I, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_crf_sample_workspace_bytes": (SZ, [I, I, I, I]),
+    "mtvaf_crf_sample": (c_int, [P, P, P, P, P, I, P, U64, U64, P, P, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_entity_counts_rows": (c_int, [P, I, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "mtvaf_crf_chunk_posteriors_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_chunk_posteriors": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, P, P, I, I, I, P, SZ, P]),
@@ -847,6 +850,38 @@ def entity_counts(pred, gold, mask_u8, start_tab, end_tab, type_of, gold_skip, n
     return counts
 
 
+def entity_counts_rows(pred, gold, mask_u8, start_tab, end_tab, type_of, gold_skip, n_types, group=1, out=None):
+    """Per-row entity counts (csrc/entity.hip), one launch and no host sync: pred [R,>=S] int32, row r scored against gold /
+    mask_u8 row r // group (gold [R/group,S] int64, mask_u8 [R/group,S] uint8); tables as `entity_counts`.
+    -> rows int32 [R,3] = (predicted, gold, correct) chunks of each row summed over the types; ``out``: overwritten."""
+    C = gold_skip.numel()
+    if gold.dim() != 2 or pred.dim() != 2:
+        raise ValueError(f"entity_counts_rows: pred {tuple(pred.shape)}, gold {tuple(gold.shape)}: expected [R, >=S] and [R/group, S]")
+    G, S = gold.shape
+    R, group = pred.shape[0], int(group)
+    if not 1 <= S <= ENTITY_MAX_S:
+        raise ValueError(f"entity_counts_rows: S={S} outside 1..{ENTITY_MAX_S}")
+    if not 1 <= C <= ENTITY_MAX_C:
+        raise ValueError(f"entity_counts_rows: C={C} outside 1..{ENTITY_MAX_C}")
+    if group < 1 or R < 1 or R % group != 0 or R // group != G:
+        raise ValueError(f"entity_counts_rows: {R} rows in groups of {group} do not fit {G} gold rows")
+    if pred.shape[1] < S or tuple(mask_u8.shape) != (G, S):
+        raise ValueError(f"entity_counts_rows: pred {tuple(pred.shape)} / mask {tuple(mask_u8.shape)} do not fit gold [{G}, {S}]")
+    if (start_tab.numel(), end_tab.numel(), type_of.numel()) != ((C + 1) ** 2, (C + 1) ** 2, C + 1) or not 1 <= n_types <= C + 1:
+        raise ValueError("entity_counts_rows: tables do not fit C and n_types")
+    ldp = pred.stride(0)
+    assert pred.dtype == torch.int32 and pred.stride(1) == 1 and ldp >= S, (pred.dtype, pred.stride())
+    assert gold.dtype == torch.int64 and gold.is_contiguous() and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert start_tab.dtype == end_tab.dtype == gold_skip.dtype == torch.uint8 and type_of.dtype == torch.int32
+    assert all(t.is_contiguous() for t in (start_tab, end_tab, type_of, gold_skip))
+    if out is None:
+        out = torch.empty((R, 3), dtype=torch.int32, device=pred.device)
+    assert tuple(out.shape) == (R, 3) and out.dtype == torch.int32 and out.is_contiguous()
+    _ck(lib().mtvaf_entity_counts_rows(_p(pred), ldp, group, _p(gold), _p(mask_u8), _p(start_tab), _p(end_tab), _p(type_of),
+                                       _p(gold_skip), R, S, C, int(n_types), _p(out), _st()), "mtvaf_entity_counts_rows")
+    return out
+
+
 SPAN_COUNTS_MAX_S, SPAN_COUNTS_MAX_N, SPAN_COUNTS_MAX_G, SPAN_COUNTS_MIN_K, SPAN_COUNTS_MAX_K = 512, 32, 32, 2, 8
 
 
@@ -976,6 +1011,53 @@ def crf_nbest(em, mask_u8, start, end, trans, nbest, return_logprob=True, out=No
     _ck(lib().mtvaf_crf_nbest(_p(em), _p(mask_u8), _p(start), _p(end), _p(trans), K, _p(tags), _p(scores), _p(logprob),
                               _p(n_paths), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_nbest")
     return tags, scores, logprob, n_paths
+
+
+CRF_SAMPLE_MAX_K = 64
+
+
+def crf_sample(em, mask_u8, start, end, trans, n_samples, uniforms=None, seed=0, offset=0, return_logprob=True,
+               return_uniforms=False, out=None):
+    """``n_samples`` tag sequences of every sentence drawn from the posterior (csrc/crf_sample.hip); no host sync.  em [B,S,C]
+    fp32, mask_u8 [B,S] uint8 (a prefix mask with mask[:,0] == 1), start / end [C], trans [C,C] fp32.  ``uniforms`` [B,K,S] fp32
+    in [0,1): the uniform of every draw; None: Philox keyed by (seed, offset).
+    -> tags [B,K,S] int32 (-1 behind the sentence), scores [B,K] fp32 (unnormalised), logprob [B,K] fp32 = score - logZ (None
+    without ``return_logprob``), uniforms_out [B,K,S] fp32 (the uniforms used, 0 behind the sentence; None without
+    ``return_uniforms``).  ``out``: that quadruple, to be overwritten."""
+    if em.dim() != 3:
+        raise ValueError(f"crf_sample: emissions {tuple(em.shape)}: expected [B, S, C]")
+    B, S, C = em.shape
+    K = int(n_samples)
+    if not 1 <= K <= CRF_SAMPLE_MAX_K:
+        raise ValueError(f"crf_sample: n_samples={K} outside 1..{CRF_SAMPLE_MAX_K}")
+    if not 1 <= S <= ENTITY_MAX_S:
+        raise ValueError(f"crf_sample: S={S} outside 1..{ENTITY_MAX_S}")
+    if not 1 <= C <= ENTITY_MAX_C:
+        raise ValueError(f"crf_sample: C={C} outside 1..{ENTITY_MAX_C}")
+    if B < 1 or tuple(mask_u8.shape) != (B, S):
+        raise ValueError(f"crf_sample: mask {tuple(mask_u8.shape)} does not fit emissions [{B}, {S}, {C}]")
+    if (start.numel(), end.numel(), trans.numel()) != (C, C, C * C):
+        raise ValueError("crf_sample: CRF parameters do not fit C")
+    if uniforms is not None and tuple(uniforms.shape) != (B, K, S):
+        raise ValueError(f"crf_sample: uniforms {tuple(uniforms.shape)}: expected [{B}, {K}, {S}]")
+    _f32(em, start, end, trans, uniforms)
+    assert mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    if out is None:
+        out = (torch.empty((B, K, S), dtype=torch.int32, device=em.device),
+               torch.empty((B, K), dtype=torch.float32, device=em.device),
+               torch.empty((B, K), dtype=torch.float32, device=em.device) if return_logprob else None,
+               torch.empty((B, K, S), dtype=torch.float32, device=em.device) if return_uniforms else None)
+    tags, scores, logprob, uout = out
+    assert tuple(tags.shape) == (B, K, S) and tuple(scores.shape) == (B, K)
+    assert tags.dtype == torch.int32 and tags.is_contiguous()
+    _f32(scores, logprob, uout)
+    assert logprob is None or tuple(logprob.shape) == (B, K)
+    assert uout is None or tuple(uout.shape) == (B, K, S)
+    wsb = lib().mtvaf_crf_sample_workspace_bytes(B, S, C, K)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=em.device)
+    _ck(lib().mtvaf_crf_sample(_p(em), _p(mask_u8), _p(start), _p(end), _p(trans), K, _p(uniforms), int(seed), int(offset),
+                               _p(tags), _p(scores), _p(logprob), _p(uout), B, S, C, _p(ws), wsb, _st()), "mtvaf_crf_sample")
+    return tags, scores, logprob, uout
 
 
 # ---- per-token tag constraints (csrc/crf_lattice.hip) -------------------------------------------------------------

@@ -139,7 +139,36 @@ def entity_device_tables(tables: dict, device) -> dict:
         return tables
     out = {k: torch.from_numpy(np.ascontiguousarray(tables[k])).reshape(-1).to(device) for k in ("start", "end", "type_of")}
     out.update(n_types=len(tables["types"]), types=list(tables["types"]), names=list(tables["names"]), C=tables["C"])
+    if "gold_skip" in tables:  # what the counting kernels read besides (`sentence_f1_cost`)
+        out["gold_skip"] = torch.from_numpy(np.ascontiguousarray(tables["gold_skip"])).reshape(-1).to(device)
     return out
+
+
+def sentence_f1_cost(hyp_tags: torch.Tensor, gold: torch.Tensor, mask: torch.Tensor, tables: dict, return_counts: bool = False):
+    """The entity-level cost of every hypothesis against its sentence's labels, on the device with no host sync (one
+    `mtvaf_entity_counts_rows` launch): ``cost[b,k] = 1 - F1 = 1 - 2 c / (p + g)`` with p / g / c the predicted / gold / correct
+    chunks of hypothesis k under `EntityScorer`'s counting rule, and 0 where ``p + g == 0`` (nothing to find, nothing found).
+
+    ``hyp_tags`` int [B,K,S] (``CRF.sample`` / ``CRF.decode_nbest`` tags, -1 behind the sentence), ``gold`` [B,S] labels,
+    ``mask`` [B,S]; ``tables``: the dict of `entity_tables` or of `entity_device_tables` (which carries ``gold_skip``), the way
+    `EntityScorer` / `TVNetSAModel2._entity_tables` build them.  -> cost float32 [B,K]; with ``return_counts`` also the counts
+    int32 [B,K,3].  The cost of MRT (`CRF.minimum_risk`); it carries no gradient."""
+    from . import hip
+    if hyp_tags.dim() != 3 or gold.dim() != 2 or hyp_tags.shape[0] != gold.shape[0] or hyp_tags.shape[2] != gold.shape[1]:
+        raise ValueError(f"sentence_f1_cost: hypotheses {tuple(hyp_tags.shape)} do not fit gold {tuple(gold.shape)}: expected "
+                         "[B, K, S] and [B, S]")
+    B, K, S = hyp_tags.shape
+    t = entity_device_tables(tables, hyp_tags.device)
+    if "gold_skip" not in t:
+        raise ValueError("sentence_f1_cost: the tables carry no gold_skip (build them with entity_tables / entity_device_tables)")
+    hyp = hyp_tags if hyp_tags.dtype == torch.int32 else hyp_tags.to(torch.int32)
+    mask_u8 = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
+    gold = gold if gold.dtype == torch.int64 else gold.to(torch.int64)
+    rows = hip.entity_counts_rows(hyp.contiguous().view(B * K, S), gold.contiguous(), mask_u8.contiguous(), t["start"], t["end"],
+                                  t["type_of"], t["gold_skip"], t["n_types"], group=K).view(B, K, 3)
+    p, g, c = (rows[..., i].to(torch.float32) for i in range(3))
+    cost = torch.where(p + g > 0, 1.0 - 2.0 * c / (p + g).clamp(min=1.0), torch.zeros_like(p))
+    return (cost, rows) if return_counts else cost
 
 
 def entities_to_lists(result: dict, types: Sequence[str]) -> List[List[dict]]:

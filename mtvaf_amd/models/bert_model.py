@@ -186,6 +186,7 @@ class TVNetSAModel2(nn.Module):
         self.last_tag_marginals = None  # [B,S,num_labels] after a forward with args.output_tag_marginals
         self.last_crf_risk = None  # detached device scalar after a forward with labels and args.crf_risk_weight > 0
         self.last_crf_entropy = None  # detached device scalar after a forward with a loss and args.crf_entropy_weight != 0
+        self.last_crf_mrt = None  # detached device scalar after a forward with labels and args.crf_mrt_weight > 0
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -279,6 +280,7 @@ class TVNetSAModel2(nn.Module):
         loss = None
         self.last_crf_risk = None
         self.last_crf_entropy = None
+        self.last_crf_mrt = None
         if labels is not None:
             reduction = _crf_reduction(self.args)
             if reduction == "mean":
@@ -295,6 +297,26 @@ class TVNetSAModel2(nn.Module):
                 crf_risk = self.crf.hamming_risk(emissions, labels, mask=mask_u8, reduction="token_mean")
                 self.last_crf_risk = crf_risk.detach()
                 loss = loss + risk_weight * crf_risk
+            # args.crf_mrt_weight > 0 adds minimum-risk training on the sentence-level entity F1 (CRF.minimum_risk, mean over
+            # sentences): the hypothesis set is the decoded path above plus args.crf_mrt_samples (8) posterior samples
+            # (CRF.sample: one dropout offset), the cost is 1 - F1 against the labels under args.entity_scheme
+            # (metrics.sentence_f1_cost), the set's weights are softmax(args.crf_mrt_alpha * llh).  The mean risk stays in
+            # self.last_crf_mrt; at the default 0 the step launches nothing for it and takes no offset.
+            mrt_weight = _arg(self.args, "crf_mrt_weight", 0.0)
+            if mrt_weight > 0:
+                from ..metrics import sentence_f1_cost
+                best = logits.device_tags
+                if decoded is not None:  # the Viterbi tags come from the second stream
+                    torch.cuda.current_stream().wait_event(decoded)
+                    best.record_stream(torch.cuda.current_stream())
+                drawn = self.crf.sample(emissions.detach(), mask_u8, n_samples=int(_arg(self.args, "crf_mrt_samples", 8)),
+                                        return_logprob=False)
+                hyp = torch.cat([best[:, None, :], drawn["tags"]], dim=1)
+                cost = sentence_f1_cost(hyp, labels, mask_u8, self._entity_tables(emissions.device))
+                crf_mrt = self.crf.minimum_risk(emissions, hyp, cost, mask=mask_u8, alpha=float(_arg(self.args, "crf_mrt_alpha", 1.0)),
+                                                reduction="mean")
+                self.last_crf_mrt = crf_mrt.detach()
+                loss = loss + mrt_weight * crf_mrt
         elif allowed_tags is not None:
             loss = -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=_crf_reduction(self.args))
             extra = _arg(self.args, "alpha", 0.0) * img_tag_loss

@@ -1,7 +1,8 @@
 """Linear-chain CRF module with the public surface of ``torchcrf.CRF`` as the reference uses it
 (models/bert_model.py:464 ``CRF(num_labels, batch_first=True)``, :511 ``decode``, :521
 ``crf(emissions, labels, mask=..., reduction='mean')``), computed by the gfx950 kernels
-mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest, and over per-position
+mtvaf_crf_nll_{fwd,bwd} / mtvaf_crf_llh_{fwd,bwd} / mtvaf_crf_marginals / mtvaf_crf_viterbi / mtvaf_crf_nbest / mtvaf_crf_sample
+(``sample``, and ``minimum_risk`` over a sampled hypothesis set), and over per-position
 tag sets by mtvaf_crf_lattice_{fwd,bwd,marginals,viterbi} (``partial_llh``, ``constrained_marginals``, ``decode_constrained``), and
 the gradient of posterior expectations by mtvaf_crf_risk_{fwd,bwd} (``expected_cost``, ``hamming_risk``, ``differentiable_marginals``)
 and, with edge costs, mtvaf_crf_path_{fwd,bwd} (``expected_path_cost``, ``entropy``, ``kl_divergence``).  Parameter names (``start_transitions``,
@@ -203,6 +204,69 @@ class CRF(nn.Module):
         tags, scores, logprob, n_paths = hip.crf_nbest(emissions.contiguous(), mask, self.start_transitions.data,
                                                        self.end_transitions.data, self.transitions.data, nbest, return_logprob)
         return {"tags": tags, "scores": scores, "logprob": logprob, "n_paths": n_paths}
+
+    @torch.no_grad()
+    def sample(self, emissions, mask: Optional[torch.Tensor] = None, n_samples: int = 8, uniforms: Optional[torch.Tensor] = None,
+               return_logprob: bool = True, return_uniforms: bool = False) -> dict:
+        """``n_samples`` (1..64) tag sequences of every sentence drawn from the posterior ``p(y | emissions)`` on the device
+        (mtvaf_crf_sample: forward-filter backward-sample); no host sync.
+
+        ``mask`` is a prefix mask; emissions and mask follow ``batch_first``, every result is batch-first.  Without ``uniforms``
+        the draws come from the dropout generator: seed ``engine.RNG.seed()`` and ONE offset ``engine.RNG.next(1)`` per call, as a
+        dropout site takes.  ``uniforms`` float32 [B,K,S] in [0,1) (batch-first) supplies the uniform of every draw instead and
+        leaves ``engine.RNG`` alone: the call is then a pure function of its arguments.
+        -> dict: tags [B,K,S] int32 (-1 behind the sentence), scores [B,K] (unnormalised path scores), logprob [B,K] = score -
+        logZ (None without ``return_logprob``) and, with ``return_uniforms``, uniforms [B,K,S] (those used; 0 behind the
+        sentence).  Nothing here carries a gradient: a differentiable log-probability of a sample is
+        ``self(emissions, tags, mask, reduction="none")`` on its tags, and ``minimum_risk`` builds a loss on a sampled set."""
+        emissions, _, mask = self._prep(emissions, None, mask)
+        if uniforms is None:
+            seed, offset = engine.RNG.seed(), engine.RNG.next(1)
+        else:
+            seed, offset, uniforms = 0, 0, uniforms.float().contiguous()
+        tags, scores, logprob, uout = hip.crf_sample(emissions.contiguous(), mask, self.start_transitions.data,
+                                                     self.end_transitions.data, self.transitions.data, n_samples, uniforms, seed,
+                                                     offset, return_logprob, return_uniforms)
+        out = {"tags": tags, "scores": scores, "logprob": logprob}
+        if return_uniforms:
+            out["uniforms"] = uout
+        return out
+
+    def minimum_risk(self, emissions, hypotheses, cost, mask: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                     reduction: str = "none"):
+        """Minimum-risk training over a hypothesis set: ``risk[b] = sum_k q_k cost[b,k]`` with ``q = softmax_k(alpha * llh_k)``, the
+        posterior renormalised over the set, for a cost of whole tag sequences that need not decompose (sentence F1:
+        `mtvaf_amd.metrics.sentence_f1_cost`).
+
+        ``hypotheses`` int [B,K,S] batch-first (``sample``'s / ``decode_nbest``'s tags, rows may be concatenated); a row is valid
+        iff its first column is >= 0, and a row identical to an earlier valid row of the same sentence (over the unmasked columns)
+        is dropped.  ``cost`` [B,K] carries no gradient.  ``llh_k`` comes from mtvaf_crf_llh_{fwd,bwd} at B * K rows, so the
+        gradient flows to the emissions and to the chain parameters.  A sentence without a valid row has risk 0 and no gradient.
+        Reductions as ``forward``: 'none' [B], 'sum', 'mean' (over sentences), 'token_mean' (sum / mask.sum())."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        em, _, mask = self._prep(emissions, None, mask)
+        B, S, C = em.shape
+        if hypotheses.dim() != 3 or hypotheses.shape[0] != B or hypotheses.shape[2] != S or hypotheses.dtype.is_floating_point:
+            raise ValueError(f"CRF.minimum_risk: hypotheses {tuple(hypotheses.shape)} {hypotheses.dtype}: expected int [{B}, K, {S}]")
+        K = hypotheses.shape[1]
+        if tuple(cost.shape) != (B, K):
+            raise ValueError(f"CRF.minimum_risk: cost {tuple(cost.shape)} does not fit hypotheses [{B}, {K}, {S}]")
+        on = (mask != 0)[:, None, :]
+        hyp = torch.where(on, hypotheses.long(), torch.full((), -1, dtype=torch.long, device=em.device))
+        valid = hypotheses[:, :, 0] >= 0
+        same = (hyp[:, :, None, :] == hyp[:, None, :, :]).all(-1) & valid[:, None, :]      # [b,k,k']: k' valid and equal to k
+        valid = valid & ~torch.tril(same, diagonal=-1).any(-1)                              # no earlier valid twin
+        llh = engine.CRFLLHFunction.apply(em[:, None].expand(B, K, S, C).reshape(B * K, S, C), self.start_transitions,
+                                          self.end_transitions, self.transitions, hyp.clamp(0, C - 1).reshape(B * K, S),
+                                          mask[:, None].expand(B, K, S).reshape(B * K, S).contiguous()).view(B, K)
+        z = torch.where(valid, alpha * llh, torch.full((), float("-inf"), device=em.device))
+        top = z.detach().max(dim=1, keepdim=True).values
+        e = torch.exp(z - torch.where(torch.isfinite(top), top, torch.zeros_like(top)))    # 0 at dropped rows
+        den = e.sum(dim=1, keepdim=True)                                                    # >= 1 with a valid row, else 0
+        q = e / torch.where(den > 0, den, torch.ones_like(den))
+        risk = (q * cost.detach().to(q.dtype)).sum(dim=1)
+        return self.reduce_risk(risk, mask.to(risk.dtype).sum(), reduction)
 
     @torch.no_grad()
     def entities(self, emissions, mask, tables, tags=None, keep=None, max_entities: int = 32) -> dict:
