@@ -23,43 +23,39 @@
 // every gap) and the forward sweep (alpha; g0 of every kept column; logZ_A); g0 and eta go to a caller-provided global workspace,
 // [B][S][64] floats each.  Then the four waves share the start columns: the running g row stays in one register per lane.  No
 // atomics, no host read-back, every output element written.
-#include "common.h"
+#include "crf_chain.h"
 #include "entity_bits.h"
 
 namespace mtvaf {
 namespace chk {
 
-constexpr int MAX_S = 512;
-constexpr int MAX_C = 64;
+constexpr int MAX_S = CRF_CHAIN_SMAX;
+constexpr int MAX_C = CRF_CHAIN_CMAX;
 constexpr int MAX_W = 16;
 constexpr int WORDS = MAX_S / 64;
 constexpr int WAVES = 4;
-constexpr int LD = MAX_C + 1;  // row stride of trans in the LDS: rows and columns both spread over the banks
-constexpr int WS_LD = 64;      // floats per column in the workspace
-constexpr int ADJ = 255;       // gap record of a kept column that follows the previous one directly
-
-__device__ __forceinline__ float lane_of(float x, int i) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i));
-}
+constexpr int LD = CRF_CHAIN_LD;  // row stride of trans in the LDS: rows and columns both spread over the banks
+constexpr int WS_LD = 64;         // floats per column in the workspace
+constexpr int ADJ = 255;          // gap record of a kept column that follows the previous one directly
 
 // log sum over i < C with bit i of m set of exp(x_i + row[i * stride]), x_i = lane i of x; -inf without a finite term
 __device__ __forceinline__ float masked_lse(float x, const float* row, int stride, uint64_t m, int C) {
   const float NINF = -__builtin_inff();
   float mx = NINF;
-  for (int i = 0; i < C; ++i) mx = fmaxf(mx, (m >> i) & 1 ? lane_of(x, i) + row[i * stride] : NINF);
+  for (int i = 0; i < C; ++i) mx = fmaxf(mx, (m >> i) & 1 ? lane_val(x, i) + row[i * stride] : NINF);
   const float sh = mx == NINF ? 0.f : mx;
   float s = 0.f;
-  for (int i = 0; i < C; ++i) s += (m >> i) & 1 ? __expf(lane_of(x, i) + row[i * stride] - sh) : 0.f;
+  for (int i = 0; i < C; ++i) s += (m >> i) & 1 ? __expf(lane_val(x, i) + row[i * stride] - sh) : 0.f;
   return mx == NINF ? NINF : sh + __logf(s);
 }
 // the same over x alone
 __device__ __forceinline__ float masked_lse(float x, uint64_t m, int C) {
   const float NINF = -__builtin_inff();
   float mx = NINF;
-  for (int i = 0; i < C; ++i) mx = fmaxf(mx, (m >> i) & 1 ? lane_of(x, i) : NINF);
+  for (int i = 0; i < C; ++i) mx = fmaxf(mx, (m >> i) & 1 ? lane_val(x, i) : NINF);
   const float sh = mx == NINF ? 0.f : mx;
   float s = 0.f;
-  for (int i = 0; i < C; ++i) s += (m >> i) & 1 ? __expf(lane_of(x, i) - sh) : 0.f;
+  for (int i = 0; i < C; ++i) s += (m >> i) & 1 ? __expf(lane_val(x, i) - sh) : 0.f;
   return mx == NINF ? NINF : sh + __logf(s);
 }
 
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(64 * WAVES) void crf_chunk_kernel(
   const float NINF = -__builtin_inff();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
   const int C1 = C + 1, nW = (S + 63) >> 6;
-  for (int i = tid; i < C * C; i += 64 * WAVES) s_trans[(i / C) * LD + i % C] = trans[i];
+  stage_trans(s_trans, trans, C, tid, 64 * WAVES);
   const bool tag_lane = lane < C;
   const int jj = tag_lane ? lane : C - 1;  // lanes >= C compute on a valid address and are set to -inf afterwards
   const float start_l = start[jj], end_l = end[jj];
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(64 * WAVES) void crf_chunk_kernel(
         xk = x;
       } else if (nk >= 0 && t > k_first) {  // a column of the gap in front of nk: its only tag
         const int xt = __ffsll((long long)A) - 1;
-        gs += lane_of(et, xt);
+        gs += lane_val(et, xt);
         if (gxg < 0)
           gxg = xt;
         else
@@ -251,8 +247,6 @@ __global__ __launch_bounds__(64 * WAVES) void crf_chunk_kernel(
   }
 }
 
-inline bool bad_shape(int B, int S, int C) { return B <= 0 || S < 1 || S > MAX_S || C < 1 || C > MAX_C; }
-
 }  // namespace chk
 }  // namespace mtvaf
 
@@ -261,14 +255,14 @@ using namespace mtvaf;
 extern "C" {
 
 size_t mtvaf_crf_chunk_posteriors_workspace_bytes(int B, int S, int C) {
-  return chk::bad_shape(B, S, C) ? 0 : (size_t)2 * B * S * chk::WS_LD * sizeof(float);
+  return bad_shape(B, S, C) ? 0 : (size_t)2 * B * S * chk::WS_LD * sizeof(float);
 }
 
 int mtvaf_crf_chunk_posteriors(const float* emissions, const int64_t* allowed, const uint8_t* mask, const uint8_t* keep,
                                const float* start, const float* end, const float* trans, const uint8_t* start_tab,
                                const uint8_t* end_tab, const int* type_of, int n_types, int max_width, float* log_post,
                                float* logz_a, int B, int S, int C, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (chk::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (n_types < 1 || n_types > 64 || max_width < 1 || max_width > chk::MAX_W) return MTVAF_ERR_ARG;
   if (!workspace || workspace_bytes < mtvaf_crf_chunk_posteriors_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   float* g0 = (float*)workspace;

@@ -14,31 +14,26 @@
 // register per lane and is read across lanes with v_readlane; lanes >= C carry -inf and are never read.  The sweeps leave two numbers
 // per column in the LDS, alpha_t(tag_t) and beta_t(tag_t); emissions pass through a 16-column LDS window filled by coalesced loads.
 // No workspace, no atomics, every output element written: slot numbers are prefix counts of the end ballots.
-#include "common.h"
+#include "crf_chain.h"
 #include "entity_bits.h"
 
 namespace mtvaf {
 
-constexpr int CE_MAX_S = 512;
-constexpr int CE_MAX_C = 64;
+constexpr int CE_MAX_S = CRF_CHAIN_SMAX;
+constexpr int CE_MAX_C = CRF_CHAIN_CMAX;
 constexpr int CE_MAX_E = 64;                  // slots per sentence: one per lane when the unused ones are filled
 constexpr int CE_WORDS = CE_MAX_S / 64;
 constexpr int CE_WAVES = 4;                   // sentences in flight per block
-constexpr int CE_LD = CE_MAX_C + 1;           // row stride of trans in the LDS: rows (backward) and columns (forward) both hit 32 banks
+constexpr int CE_LD = CRF_CHAIN_LD;           // row stride of trans in the LDS: rows (backward) and columns (forward) both hit 32 banks
 constexpr int CE_WIN = 16;                    // columns of emissions per LDS window
 enum { CE_KEEP = 0, CE_START = 1, CE_SETS = 2 };
-
-// lane i of x for the whole wave (i wave-uniform)
-__device__ __forceinline__ float ce_lane(float x, int i) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i));
-}
 
 // log sum_i exp(x_i + row[i * stride]) over i < C, x_i = lane i of x; every term finite
 __device__ __forceinline__ float ce_lse(float x, const float* row, int stride, int C) {
   float m = -INFINITY;
-  for (int i = 0; i < C; ++i) m = fmaxf(m, ce_lane(x, i) + row[i * stride]);
+  for (int i = 0; i < C; ++i) m = fmaxf(m, lane_val(x, i) + row[i * stride]);
   float s = 0.f;
-  for (int i = 0; i < C; ++i) s += __expf(ce_lane(x, i) + row[i * stride] - m);
+  for (int i = 0; i < C; ++i) s += __expf(lane_val(x, i) + row[i * stride] - m);
   return m + __logf(s);
 }
 
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(64 * CE_WAVES) void crf_entities_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int C1 = C + 1, W = (S + 63) >> 6, n_win = (S + CE_WIN - 1) / CE_WIN;
-  for (int i = tid; i < C * C; i += 64 * CE_WAVES) s_trans[(i / C) * CE_LD + i % C] = trans[i];
+  stage_trans(s_trans, trans, C, tid, 64 * CE_WAVES);
   for (int i = tid; i < C1 * C1; i += 64 * CE_WAVES) {
     s_start[i] = start_tab[i];
     s_end[i] = end_tab[i];
@@ -204,7 +199,7 @@ int mtvaf_crf_entities(const float* emissions, const uint8_t* mask, const int32_
                        const float* start, const float* end, const float* trans, const uint8_t* start_tab,
                        const uint8_t* end_tab, const int* type_of, int n_types, int32_t* ents, float* log_conf,
                        int32_t* count, int B, int S, int C, int max_entities, hipStream_t st) {
-  if (B <= 0 || S < 1 || S > CE_MAX_S || C < 1 || C > CE_MAX_C || ldt < S) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C) || ldt < S) return MTVAF_ERR_SHAPE;
   if (n_types < 1 || n_types > C + 1 || max_entities < 1 || max_entities > CE_MAX_E) return MTVAF_ERR_ARG;
   const int blocks = min((B + CE_WAVES - 1) / CE_WAVES, 1024);
   hipLaunchKernelGGL(crf_entities_kernel, dim3(blocks), dim3(64 * CE_WAVES), 0, st, emissions, mask, tags, ldt, keep, start, end,

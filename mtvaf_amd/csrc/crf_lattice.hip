@@ -27,82 +27,18 @@
 
 #pragma clang fp contract(off)
 
+#include "crf_chain.h"  // (behind the pragma: lds_fence, prefix_len, trans_max, dot_sum, dot_dot, param_reduce, the dispatch)
+
 namespace mtvaf {
 namespace lat {
 
-constexpr int CMAX = 64;
-constexpr int SMAX = 512;
-constexpr float NEG = -1.0e30f;
-typedef float f4 __attribute__((ext_vector_type(4)));
+constexpr int CMAX = CRF_CHAIN_CMAX;
+constexpr int SMAX = CRF_CHAIN_SMAX;
 
-// one wave: LDS operations execute in program order, the fences keep the compiler from moving them across
-__device__ __forceinline__ void lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// len_b: the leading ones of the mask row (at least 1: mask[:,0] == 1 is the caller's contract)
-__device__ __forceinline__ int prefix_len(const uint8_t* __restrict__ mrow, int S, int lane) {
-  int len = S;
-  for (int t = lane; t < S; t += 64)
-    if (!mrow[t]) len = min(len, t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len = min(len, __shfl_xor(len, o, 64));
-  return max(len, 1);
-}
 __device__ __forceinline__ uint64_t full_set(int C) { return C >= 64 ? ~0ull : (1ull << C) - 1ull; }
 __device__ __forceinline__ uint64_t tag_set(const int64_t* __restrict__ arow, int t, uint64_t full) {
   const uint64_t a = (uint64_t)arow[t] & full;
   return a ? a : full;
-}
-__device__ __forceinline__ float trans_max(const float* __restrict__ trans, int C, int lane) {
-  float tm = NEG;
-  if (lane < C)
-    for (int i = 0; i < C; ++i) tm = fmaxf(tm, trans[i * C + lane]);
-  return wave_max(tm);
-}
-
-// sum_i v[i] w[i] and sum_i v[i] over the CT values of a broadcast row; the same additions in every lane
-template <int CT>
-__device__ __forceinline__ void dot_sum(const float* row, const float (&w)[CT], float& dot, float& sum) {
-  const f4* r4 = reinterpret_cast<const f4*>(row);
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int q = 0; q < CT / 4; ++q) {
-    const f4 x = r4[q];
-    d0 = __builtin_fmaf(x.x, w[4 * q], d0);
-    d1 = __builtin_fmaf(x.y, w[4 * q + 1], d1);
-    d2 = __builtin_fmaf(x.z, w[4 * q + 2], d2);
-    d3 = __builtin_fmaf(x.w, w[4 * q + 3], d3);
-    s0 += x.x;
-    s1 += x.y;
-    s2 += x.z;
-    s3 += x.w;
-  }
-  dot = (d0 + d1) + (d2 + d3);
-  sum = (s0 + s1) + (s2 + s3);
-}
-// sum_i v[i] w[i] and sum_i v[i] p[i] over two broadcast rows
-template <int CT>
-__device__ __forceinline__ void dot_dot(const float* vrow, const float* prow, const float (&w)[CT], float& dw, float& dp) {
-  const f4* v4 = reinterpret_cast<const f4*>(vrow);
-  const f4* p4 = reinterpret_cast<const f4*>(prow);
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int q = 0; q < CT / 4; ++q) {
-    const f4 x = v4[q], p = p4[q];
-    d0 = __builtin_fmaf(x.x, w[4 * q], d0);
-    d1 = __builtin_fmaf(x.y, w[4 * q + 1], d1);
-    d2 = __builtin_fmaf(x.z, w[4 * q + 2], d2);
-    d3 = __builtin_fmaf(x.w, w[4 * q + 3], d3);
-    s0 = __builtin_fmaf(x.x, p.x, s0);
-    s1 = __builtin_fmaf(x.y, p.y, s1);
-    s2 = __builtin_fmaf(x.z, p.z, s2);
-    s3 = __builtin_fmaf(x.w, p.w, s3);
-  }
-  dw = (d0 + d1) + (d2 + d3);
-  dp = (s0 + s1) + (s2 + s3);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -361,18 +297,11 @@ __global__ __launch_bounds__(64) void lat_bwd_kernel(const float* __restrict__ g
   }
 }
 
-// d[i] = sum_b grad[b] partial[b][i], overwritten or accumulated
+// d[i] = sum_b grad[b] partial[b][i], overwritten or accumulated (crf_chain.h; compiled here with contraction off)
 __global__ void lat_param_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ grad, int B, int C,
                                         float* __restrict__ dstart, float* __restrict__ dend, float* __restrict__ dtrans,
                                         int accumulate) {
-  const int n = 2 * C + C * C;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += grad[b] * partial[(long)b * n + i];
-  float* d = i < C ? dstart + i : (i < 2 * C ? dend + (i - C) : dtrans + (i - 2 * C));
-  if (accumulate) s += *d;
-  *d = s;
+  param_reduce(partial, grad, B, C, dstart, dend, dtrans, accumulate);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -461,8 +390,6 @@ __global__ __launch_bounds__(64) void lat_viterbi_kernel(const float* __restrict
 struct Ws {
   float *alpha, *sp, *mx, *partial;
 };
-inline int width(int C) { return C <= 16 ? 16 : (C <= 32 ? 32 : 64); }
-inline bool bad_shape(int B, int S, int C) { return B <= 0 || S < 1 || S > SMAX || C < 1 || C > CMAX; }
 inline size_t ws_floats(int B, int S, int C) {
   const size_t n = (size_t)B * S;
   return 4 * n * width(C) + 2 * n + (size_t)B * (2 * C + C * C);
@@ -483,11 +410,7 @@ int launch_fwd(const float* em, const int64_t* allowed, const uint8_t* mask, con
 #define LAT_FWD(CT)                                                                                                    \
   hipLaunchKernelGGL((lat_fwd_kernel<CT, NCH>), dim3(B), dim3(64), 0, st, em, allowed, mask, start, end, trans, w.alpha, \
                      w.sp, w.mx, pllh, logz_a, logz, B, S, C)
-  switch (width(C)) {
-    case 16: LAT_FWD(16); break;
-    case 32: LAT_FWD(32); break;
-    default: LAT_FWD(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, LAT_FWD)
 #undef LAT_FWD
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -499,11 +422,7 @@ int launch_bwd(const float* grad, const float* em, const int64_t* allowed, const
 #define LAT_BWD(CT)                                                                                                    \
   hipLaunchKernelGGL((lat_bwd_kernel<CT, NCH, MARG>), dim3(B), dim3(64), 0, st, grad, em, allowed, mask, end, trans,    \
                      w.alpha, w.sp, w.mx, out, w.partial, B, S, C)
-  switch (width(C)) {
-    case 16: LAT_BWD(16); break;
-    case 32: LAT_BWD(32); break;
-    default: LAT_BWD(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, LAT_BWD)
 #undef LAT_BWD
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -517,14 +436,14 @@ using namespace mtvaf;
 extern "C" {
 
 size_t mtvaf_crf_lattice_workspace_bytes(int B, int S, int C) {
-  return lat::bad_shape(B, S, C) ? 0 : lat::ws_floats(B, S, C) * sizeof(float);
+  return bad_shape(B, S, C) ? 0 : lat::ws_floats(B, S, C) * sizeof(float);
 }
 
 // pllh [B] = logZ_A - logZ; logz_a [B], logz [B] nullable.  One launch; the workspace keeps what lattice_bwd reads.
 int mtvaf_crf_lattice_fwd(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
                           const float* end, const float* trans, float* pllh, float* logz_a, float* logz, int B, int S,
                           int C, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (lat::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_lattice_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   return lat::launch_fwd<2>(emissions, allowed, mask, start, end, trans, lat::ws_of(workspace, B, S, C), pllh, logz_a, logz,
                             B, S, C, st);
@@ -537,7 +456,7 @@ int mtvaf_crf_lattice_bwd(const float* grad, const float* emissions, const int64
                           float* dend, float* dtrans, int accumulate, int B, int S, int C, void* workspace,
                           size_t workspace_bytes, hipStream_t st) {
   (void)start;  // (enters through the workspace's alphas)
-  if (lat::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_lattice_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const lat::Ws w = lat::ws_of(workspace, B, S, C);
   if (int rc = lat::launch_bwd<2, false>(grad, emissions, allowed, mask, end, trans, w, demissions, B, S, C, st)) return rc;
@@ -553,7 +472,7 @@ int mtvaf_crf_lattice_bwd(const float* grad, const float* emissions, const int64
 int mtvaf_crf_lattice_marginals(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
                                 const float* end, const float* trans, float* marg, float* logz_a, int B, int S, int C,
                                 void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (lat::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_lattice_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const lat::Ws w = lat::ws_of(workspace, B, S, C);
   if (int rc = lat::launch_fwd<1>(emissions, allowed, mask, start, end, trans, w, nullptr, logz_a, nullptr, B, S, C, st))
@@ -566,15 +485,11 @@ int mtvaf_crf_lattice_marginals(const float* emissions, const int64_t* allowed, 
 int mtvaf_crf_lattice_viterbi(const float* emissions, const int64_t* allowed, const uint8_t* mask, const float* start,
                               const float* end, const float* trans, int32_t* tags_out, int32_t* lens_out, float* score_out,
                               int B, int S, int C, hipStream_t st) {
-  if (lat::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
 #define LAT_VIT(CT)                                                                                                    \
   hipLaunchKernelGGL(lat::lat_viterbi_kernel<CT>, dim3(B), dim3(64), (size_t)S * CT, st, emissions, allowed, mask, start, \
                      end, trans, tags_out, lens_out, score_out, S, C)
-  switch (lat::width(C)) {
-    case 16: LAT_VIT(16); break;
-    case 32: LAT_VIT(32); break;
-    default: LAT_VIT(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, LAT_VIT)
 #undef LAT_VIT
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;

@@ -18,20 +18,15 @@
 // The n-best kernel sets no function attribute (33 KB of static LDS).  With logprob_out the call also runs crf_logz (crf.h), which
 // for C <= 16 and S above about 470 opts into more than 64 KB of LDS at the call: stream capture of that shape is as safe as
 // capture of mtvaf_crf_marginals, and a first call outside the capture settles it.
-#include "common.h"
 #include "crf.h"
+#include "crf_chain.h"
 
 namespace mtvaf {
 
 constexpr int NB_MAX_K = 8;
-constexpr int NB_MAX_C = 64;
-constexpr int NB_MAX_S = 512;
-constexpr int NB_LD = NB_MAX_C + 1;   // row stride of trans in the LDS
+constexpr int NB_MAX_C = CRF_CHAIN_CMAX;
+constexpr int NB_LD = CRF_CHAIN_LD;   // row stride of trans in the LDS
 constexpr int NB_STAGE = 8192;        // back-pointers per LDS stage: at least 16 steps at K = 8, C = 64
-
-__device__ __forceinline__ float nb_lane(float x, int i) {  // lane i of x for the whole wave (i wave-uniform)
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), i));
-}
 
 // v enters the sorted list at the bottom and rises past strictly smaller entries (v > top[K-1] is the caller's test)
 template <int K>
@@ -55,7 +50,7 @@ template <int K>
 __device__ __forceinline__ void nb_offer(float (&top)[K], int (&id)[K], const float (&sc)[K], int i, float w) {
 #pragma unroll
   for (int r = 0; r < K; ++r) {
-    const float v = nb_lane(sc[r], i) + w;
+    const float v = lane_val(sc[r], i) + w;
     if (!(v > top[K - 1])) break;
     nb_insert<K>(top, id, v, i * NB_MAX_K + r);
   }
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(64) void crf_nbest_kernel(const float* __restrict__
   __shared__ float s_trans[NB_MAX_C * NB_LD];
   __shared__ uint16_t s_bp[NB_STAGE];
   const int b = blockIdx.x, lane = threadIdx.x;
-  for (int i = lane; i < C * C; i += 64) s_trans[(i / C) * NB_LD + i % C] = trans[i];
+  stage_trans(s_trans, trans, C, lane, 64);
   int len = S;  // leading ones of the mask
   for (int w = 0; w < S; w += 64) {
     const int c = w + lane;
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(64) void crf_nbest_kernel(const float* __restrict__
   __syncthreads();
 
   const bool act = lane < C;
-  const int j = act ? lane : C - 1;  // lanes >= C shadow the last tag: never read by nb_lane, nothing stored
+  const int j = act ? lane : C - 1;  // lanes >= C shadow the last tag: never read by lane_val, nothing stored
   const float* e = em + (long)b * S * C + j;
   float sc[K];
   sc[0] = act ? start[j] + e[0] : -INFINITY;
@@ -174,7 +169,7 @@ using namespace mtvaf;
 
 namespace {
 bool nb_bad_shape(int B, int S, int C, int K) {
-  return B <= 0 || S < 1 || S > NB_MAX_S || C < 1 || C > NB_MAX_C || K < 1 || K > NB_MAX_K;
+  return bad_shape(B, S, C) || K < 1 || K > NB_MAX_K;
 }
 // workspace: back-pointers u16 [B,S,K,C] (rounded up to 256 bytes) | logZ f32 [B] (rounded up to 256 bytes) | the forward
 // recursion's own workspace (mtvaf_crf_workspace_bytes)

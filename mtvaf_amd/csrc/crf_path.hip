@@ -12,7 +12,7 @@
 //   mask is a prefix mask; len_b = its leading ones; cost and emissions at or beyond len_b are never read.
 // One wavefront per sentence, tag j on lane j, 1 <= C <= 64, 1 <= S <= 512; CT = 16, 32 or 64 is the unrolled width; EC says
 // whether ecost is given.  The scaled linear domain, the LDS lane broadcast, the two interleaved chains and the CENTRING are
-// those of crf_risk.hip (its header has the derivation; that file is untouched and the helpers are restated here).  With
+// those of crf_risk.hip (its header has the derivation; the helpers both files use are in crf_chain.h).  With
 // E = exp(trans - tmax) and F = E o ecost the edge term enters in four places:
 //   forward    at_t(j) = cost_t(j) + ((abar_{t-1} o ac_{t-1}) E + abar_{t-1} F)(j) / sp_t(j):  one more FMA per previous tag;
 //   backward   eq = E q + F u  (one more FMA per next tag),  dq = sum_j (sp_t(j) q(j) + spf_t(j) u(j))  with spf_t = abar_{t-1} F
@@ -31,57 +31,13 @@
 //     are zeros whose sums with +0.0 are +0.0: R == +0.0 and every cost-covariance gradient is +0.0 whatever the sign of grad;
 //   * grad[b] == 0 and gz[b] == 0: that sentence's dem, dcost and shares of the parameter gradients are zeros (x + 0.0);
 //   * masked columns of dem and dcost are written as +0.0.
-#include "common.h"
+#include "crf_chain.h"
 
 namespace mtvaf {
 namespace path {
 
-constexpr int CMAX = 64;
-constexpr int SMAX = 512;
-constexpr float NEG = -1.0e30f;
-typedef float f4 __attribute__((ext_vector_type(4)));
+constexpr int SMAX = CRF_CHAIN_SMAX;
 
-// (crf_risk.hip) one wave: LDS operations execute in program order, the fences keep the compiler from moving them across
-__device__ __forceinline__ void lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// (crf_risk.hip) len_b: the leading ones of the mask row (at least 1: mask[:,0] == 1 is the caller's contract)
-__device__ __forceinline__ int prefix_len(const uint8_t* __restrict__ mrow, int S, int lane) {
-  int len = S;
-  for (int t = lane; t < S; t += 64)
-    if (!mrow[t]) len = min(len, t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len = min(len, __shfl_xor(len, o, 64));
-  return max(len, 1);
-}
-__device__ __forceinline__ float trans_max(const float* __restrict__ trans, int C, int lane) {
-  float tm = NEG;
-  if (lane < C)
-    for (int i = 0; i < C; ++i) tm = fmaxf(tm, trans[i * C + lane]);
-  return wave_max(tm);
-}
-// (crf_risk.hip) sum_i v[i] w[i] and sum_i v[i] over the CT values of a broadcast row; the same additions in every lane
-template <int CT>
-__device__ __forceinline__ void dot_sum(const float* row, const float (&w)[CT], float& dot, float& sum) {
-  const f4* r4 = reinterpret_cast<const f4*>(row);
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int q = 0; q < CT / 4; ++q) {
-    const f4 x = r4[q];
-    d0 = __builtin_fmaf(x.x, w[4 * q], d0);
-    d1 = __builtin_fmaf(x.y, w[4 * q + 1], d1);
-    d2 = __builtin_fmaf(x.z, w[4 * q + 2], d2);
-    d3 = __builtin_fmaf(x.w, w[4 * q + 3], d3);
-    s0 += x.x;
-    s1 += x.y;
-    s2 += x.z;
-    s3 += x.w;
-  }
-  dot = (d0 + d1) + (d2 + d3);
-  sum = (s0 + s1) + (s2 + s3);
-}
 // sum_i v[i] f[i * stride] over a broadcast row and this lane's own strided LDS values.  A real loop over 16 tags at a time
 // (nothing here indexes a register array): unrolled in full, the compiler issues every load first and spills around them.
 template <int CT>
@@ -466,8 +422,6 @@ __global__ void path_param_reduce_kernel(const float* __restrict__ partial, cons
 struct Ws {
   float *alpha, *sp, *ac, *spf, *mx, *mean, *partial;
 };
-inline int width(int C) { return C <= 16 ? 16 : (C <= 32 ? 32 : 64); }
-inline bool bad_shape(int B, int S, int C) { return B <= 0 || S < 1 || S > SMAX || C < 1 || C > CMAX; }
 inline size_t ws_floats(int B, int S, int C) {
   const size_t n = (size_t)B * S;
   return 4 * n * width(C) + 2 * n + (size_t)B * (4 * C + 2 * C * C);
@@ -493,14 +447,14 @@ using namespace mtvaf;
 extern "C" {
 
 size_t mtvaf_crf_path_workspace_bytes(int B, int S, int C) {
-  return path::bad_shape(B, S, C) ? 0 : path::ws_floats(B, S, C) * sizeof(float);
+  return bad_shape(B, S, C) ? 0 : path::ws_floats(B, S, C) * sizeof(float);
 }
 
 // risk [B] = the expected path cost; logz [B] nullable.  One launch; the workspace keeps what path_bwd reads.
 int mtvaf_crf_path_fwd(const float* emissions, const float* cost, const float* ecost, const uint8_t* mask, const float* start,
                        const float* end, const float* trans, float* risk_out, float* logz, int B, int S, int C,
                        void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (path::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_path_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const path::Ws w = path::ws_of(workspace, B, S, C);
 #define PATH_FWD(CT, EC)                                                                                                 \
@@ -511,11 +465,7 @@ int mtvaf_crf_path_fwd(const float* emissions, const float* cost, const float* e
     PATH_FWD(CT, true);  \
   else                   \
     PATH_FWD(CT, false)
-  switch (path::width(C)) {
-    case 16: PATH_FWD_W(16); break;
-    case 32: PATH_FWD_W(32); break;
-    default: PATH_FWD_W(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, PATH_FWD_W)
 #undef PATH_FWD_W
 #undef PATH_FWD
   MTVAF_LAUNCH_CHECK();
@@ -530,7 +480,7 @@ int mtvaf_crf_path_bwd(const float* grad, const float* gz, const float* emission
                        float* dcost, float* decost, float* dstart, float* dend, float* dtrans, int accumulate, int B, int S,
                        int C, void* workspace, size_t workspace_bytes, hipStream_t st) {
   (void)start;  // (enters through the workspace's alphas)
-  if (path::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_path_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const path::Ws w = path::ws_of(workspace, B, S, C);
 #define PATH_BWD(CT, EC)                                                                                                  \
@@ -541,11 +491,7 @@ int mtvaf_crf_path_bwd(const float* grad, const float* gz, const float* emission
     PATH_BWD(CT, true);  \
   else                   \
     PATH_BWD(CT, false)
-  switch (path::width(C)) {
-    case 16: PATH_BWD_W(16); break;
-    case 32: PATH_BWD_W(32); break;
-    default: PATH_BWD_W(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, PATH_BWD_W)
 #undef PATH_BWD_W
 #undef PATH_BWD
   MTVAF_LAUNCH_CHECK();

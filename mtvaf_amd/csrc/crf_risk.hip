@@ -8,8 +8,8 @@
 //     dR/dstart = dR/dem[0], dR/dend = dR/dem[len-1], dR/dcost[t,c] = m_t(c).
 //   mask is a prefix mask; len_b = its leading ones; cost and emissions at or beyond len_b are never read.
 // One wavefront per sentence, tag j on lane j, 1 <= C <= 64, 1 <= S <= 512; CT = 16, 32 or 64 is the unrolled width.  The
-// scaled linear domain and the LDS lane broadcast are those of crf_wide.hip / crf_lattice.hip (the helpers are restated here,
-// those files are untouched), and as in crf_lattice.hip two chains run interleaved in one wave through the same statements
+// scaled linear domain and the LDS lane broadcast are those of crf_wide.hip / crf_lattice.hip (the helpers are shared:
+// crf_chain.h), and as in crf_lattice.hip two chains run interleaved in one wave through the same statements
 // with the transition factors shared in registers: chain 0 is the scaled alpha (beta), chain 1 the cost-weighted one.
 //
 // CENTRING is part of the contract.  As written above a, b and R grow like len |cost| while every gradient is a difference
@@ -32,78 +32,12 @@
 //   * g[b] == 0: that sentence's dem, dcost and its share of dstart / dend / dtrans are g times a finite number, i.e. zeros,
 //     written as +0.0 in the same way;
 //   * masked columns of dem, dcost and marg are written as +0.0.
-#include "common.h"
+#include "crf_chain.h"
 
 namespace mtvaf {
 namespace risk {
 
-constexpr int CMAX = 64;
-constexpr int SMAX = 512;
-constexpr float NEG = -1.0e30f;
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// (crf_lattice.hip) one wave: LDS operations execute in program order, the fences keep the compiler from moving them across
-__device__ __forceinline__ void lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// (crf_lattice.hip) len_b: the leading ones of the mask row (at least 1: mask[:,0] == 1 is the caller's contract)
-__device__ __forceinline__ int prefix_len(const uint8_t* __restrict__ mrow, int S, int lane) {
-  int len = S;
-  for (int t = lane; t < S; t += 64)
-    if (!mrow[t]) len = min(len, t);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len = min(len, __shfl_xor(len, o, 64));
-  return max(len, 1);
-}
-__device__ __forceinline__ float trans_max(const float* __restrict__ trans, int C, int lane) {
-  float tm = NEG;
-  if (lane < C)
-    for (int i = 0; i < C; ++i) tm = fmaxf(tm, trans[i * C + lane]);
-  return wave_max(tm);
-}
-// (crf_lattice.hip) sum_i v[i] w[i] and sum_i v[i] over the CT values of a broadcast row; the same additions in every lane
-template <int CT>
-__device__ __forceinline__ void dot_sum(const float* row, const float (&w)[CT], float& dot, float& sum) {
-  const f4* r4 = reinterpret_cast<const f4*>(row);
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int q = 0; q < CT / 4; ++q) {
-    const f4 x = r4[q];
-    d0 = __builtin_fmaf(x.x, w[4 * q], d0);
-    d1 = __builtin_fmaf(x.y, w[4 * q + 1], d1);
-    d2 = __builtin_fmaf(x.z, w[4 * q + 2], d2);
-    d3 = __builtin_fmaf(x.w, w[4 * q + 3], d3);
-    s0 += x.x;
-    s1 += x.y;
-    s2 += x.z;
-    s3 += x.w;
-  }
-  dot = (d0 + d1) + (d2 + d3);
-  sum = (s0 + s1) + (s2 + s3);
-}
-// (crf_lattice.hip) sum_i v[i] w[i] and sum_i v[i] p[i] over two broadcast rows
-template <int CT>
-__device__ __forceinline__ void dot_dot(const float* vrow, const float* prow, const float (&w)[CT], float& dw, float& dp) {
-  const f4* v4 = reinterpret_cast<const f4*>(vrow);
-  const f4* p4 = reinterpret_cast<const f4*>(prow);
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-  for (int q = 0; q < CT / 4; ++q) {
-    const f4 x = v4[q], p = p4[q];
-    d0 = __builtin_fmaf(x.x, w[4 * q], d0);
-    d1 = __builtin_fmaf(x.y, w[4 * q + 1], d1);
-    d2 = __builtin_fmaf(x.z, w[4 * q + 2], d2);
-    d3 = __builtin_fmaf(x.w, w[4 * q + 3], d3);
-    s0 = __builtin_fmaf(x.x, p.x, s0);
-    s1 = __builtin_fmaf(x.y, p.y, s1);
-    s2 = __builtin_fmaf(x.z, p.z, s2);
-    s3 = __builtin_fmaf(x.w, p.w, s3);
-  }
-  dw = (d0 + d1) + (d2 + d3);
-  dp = (s0 + s1) + (s2 + s3);
-}
+constexpr int SMAX = CRF_CHAIN_SMAX;
 
 // ---------------------------------------------------------------------------------------------
 // forward.  s is the scaled alpha, u = s at the (signed) cost-weighted chain; both go through one broadcast, from which every
@@ -367,18 +301,12 @@ __global__ __launch_bounds__(64) void risk_bwd_kernel(const float* __restrict__ 
   }
 }
 
-// d[i] = sum_b grad[b] partial[b][i] in the order of b, overwritten or accumulated (as crf_lattice.hip's reduction)
+// d[i] = sum_b grad[b] partial[b][i] in the order of b, overwritten or accumulated (crf_chain.h; compiled here with the
+// library's contraction mode, so not the same instructions as crf_lattice.hip's reduction)
 __global__ void risk_param_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ grad, int B, int C,
                                          float* __restrict__ dstart, float* __restrict__ dend, float* __restrict__ dtrans,
                                          int accumulate) {
-  const int n = 2 * C + C * C;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += grad[b] * partial[(long)b * n + i];
-  float* d = i < C ? dstart + i : (i < 2 * C ? dend + (i - C) : dtrans + (i - 2 * C));
-  if (accumulate) s += *d;
-  *d = s;
+  param_reduce(partial, grad, B, C, dstart, dend, dtrans, accumulate);
 }
 
 // workspace, in floats, CT = 16, 32 or 64:  alpha [B,S,CT] | sp [B,S,CT] | ac [B,S,CT] | mx [B,S] | mean [B,S] |
@@ -386,8 +314,6 @@ __global__ void risk_param_reduce_kernel(const float* __restrict__ partial, cons
 struct Ws {
   float *alpha, *sp, *ac, *mx, *mean, *partial;
 };
-inline int width(int C) { return C <= 16 ? 16 : (C <= 32 ? 32 : 64); }
-inline bool bad_shape(int B, int S, int C) { return B <= 0 || S < 1 || S > SMAX || C < 1 || C > CMAX; }
 inline size_t ws_floats(int B, int S, int C) {
   const size_t n = (size_t)B * S;
   return 3 * n * width(C) + 2 * n + (size_t)B * (2 * C + C * C);
@@ -410,11 +336,7 @@ int launch_bwd(const float* grad, const float* em, const float* cost, const uint
 #define RISK_BWD(CT)                                                                                                  \
   hipLaunchKernelGGL((risk_bwd_kernel<CT, MARG>), dim3(B), dim3(64), 0, st, grad, em, cost, mask, end, trans, w.alpha, \
                      w.sp, w.ac, w.mx, w.mean, dem, dcost, w.partial, S, C)
-  switch (width(C)) {
-    case 16: RISK_BWD(16); break;
-    case 32: RISK_BWD(32); break;
-    default: RISK_BWD(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, RISK_BWD)
 #undef RISK_BWD
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -428,7 +350,7 @@ using namespace mtvaf;
 extern "C" {
 
 size_t mtvaf_crf_risk_workspace_bytes(int B, int S, int C) {
-  return risk::bad_shape(B, S, C) ? 0 : risk::ws_floats(B, S, C) * sizeof(float);
+  return bad_shape(B, S, C) ? 0 : risk::ws_floats(B, S, C) * sizeof(float);
 }
 
 // risk [B] = the expected cost; logz [B] and marg [B,S,C] nullable.  One launch (two with marg: the beta chain alone); the
@@ -436,17 +358,13 @@ size_t mtvaf_crf_risk_workspace_bytes(int B, int S, int C) {
 int mtvaf_crf_risk_fwd(const float* emissions, const float* cost, const uint8_t* mask, const float* start, const float* end,
                        const float* trans, float* risk_out, float* logz, float* marg, int B, int S, int C, void* workspace,
                        size_t workspace_bytes, hipStream_t st) {
-  if (risk::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_risk_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const risk::Ws w = risk::ws_of(workspace, B, S, C);
 #define RISK_FWD(CT)                                                                                                   \
   hipLaunchKernelGGL(risk::risk_fwd_kernel<CT>, dim3(B), dim3(64), 0, st, emissions, cost, mask, start, end, trans, w.alpha, \
                      w.sp, w.ac, w.mx, w.mean, risk_out, logz, S, C)
-  switch (risk::width(C)) {
-    case 16: RISK_FWD(16); break;
-    case 32: RISK_FWD(32); break;
-    default: RISK_FWD(64); break;
-  }
+  CRF_CHAIN_DISPATCH(C, RISK_FWD)
 #undef RISK_FWD
   MTVAF_LAUNCH_CHECK();
   if (!marg) return MTVAF_OK;
@@ -460,7 +378,7 @@ int mtvaf_crf_risk_bwd(const float* grad, const float* emissions, const float* c
                        float* dtrans, int accumulate, int B, int S, int C, void* workspace, size_t workspace_bytes,
                        hipStream_t st) {
   (void)start;  // (enters through the workspace's alphas)
-  if (risk::bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
+  if (bad_shape(B, S, C)) return MTVAF_ERR_SHAPE;
   if (workspace_bytes < mtvaf_crf_risk_workspace_bytes(B, S, C)) return MTVAF_ERR_WORKSPACE;
   const risk::Ws w = risk::ws_of(workspace, B, S, C);
   if (int rc = risk::launch_bwd<false>(grad, emissions, cost, mask, end, trans, w, demissions, dcost, B, S, C, st)) return rc;

@@ -22,15 +22,14 @@
 //     counter = (lo32(idx), hi32(idx), lo32(offset), hi32(offset)),  idx = (b * 64 + k) * 128 + (t >> 2),  key = (lo32(seed), hi32(seed)),
 // word t & 3 of the four results, u = (word >> 8) * 2^-24 in [0, 1).  offset passes through epoch_offset (common.h) like a dropout
 // site's, so a captured launch draws fresh samples on every replay once the epoch word is advanced.
-#include "common.h"
 #include "crf.h"
+#include "crf_chain.h"
 
 namespace mtvaf {
 
 constexpr int SM_MAX_K = 64;
-constexpr int SM_MAX_C = 64;
-constexpr int SM_MAX_S = 512;
-constexpr int SM_LD = SM_MAX_C + 1;  // row stride of trans in the LDS
+constexpr int SM_MAX_C = CRF_CHAIN_CMAX;
+constexpr int SM_LD = CRF_CHAIN_LD;  // row stride of trans in the LDS
 constexpr int SM_T = 32;             // columns per LDS stage
 constexpr int SM_ULD = SM_T + 1;     // row stride of the staged uniforms
 
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(64) void crf_sample_kernel(const float* __restrict_
   __shared__ float s_u[SM_MAX_K * SM_ULD];    // their uniforms, [k][column]
   __shared__ float s_w[SM_MAX_C * 64];        // [i][lane]: the weights of the column a lane is drawing
   const int b = blockIdx.x, lane = threadIdx.x;
-  for (int i = lane; i < C * C; i += 64) s_trans[(i / C) * SM_LD + i % C] = trans[i];
+  stage_trans(s_trans, trans, C, lane, 64);
   if (lane < C) {
     s_start[lane] = start[lane];
     s_end[lane] = end[lane];
@@ -142,7 +141,7 @@ using namespace mtvaf;
 
 namespace {
 bool sm_bad_shape(int B, int S, int C, int K) {
-  return B <= 0 || S < 1 || S > SM_MAX_S || C < 1 || C > SM_MAX_C || K < 1 || K > SM_MAX_K;
+  return bad_shape(B, S, C) || K < 1 || K > SM_MAX_K;
 }
 // workspace: logZ f32 [B] (rounded up to 256 bytes) | the forward recursion's own workspace (mtvaf_crf_workspace_bytes), whose
 // alpha rows the kernel reads

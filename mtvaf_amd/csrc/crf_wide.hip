@@ -10,23 +10,18 @@
 // Per-step operands (emission rows, predicted alphas) are fetched CHUNK steps ahead into registers; nothing is held
 // per time step in LDS except mask, tags, maxima and the Viterbi back-pointers (one byte per step and tag), so no
 // kernel needs more than the default 64 KiB and nothing is set on a function at launch.
+#include "crf_chain.h"
 #include "crf_wide.h"
 
 namespace mtvaf {
 namespace crfw {
 
-constexpr float NEG = -1.0e30f;
 constexpr int CHUNK = 16;  // steps whose per-step operands are loaded together, one chunk ahead of use
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 template <int K>
 __device__ __forceinline__ float ror16(float v) {  // DPP row_ror:K
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + K, 0xf, 0xf, true));
 }
-__device__ __forceinline__ float lane_val(float v, int i) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
-}
-__device__ __forceinline__ int lane_val(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
 
 // sum over the first CT lanes, wave-uniform and bit-identical everywhere: row sums by DPP rotation, then the row
 // results added in a fixed order
@@ -42,15 +37,12 @@ __device__ __forceinline__ float sum_u(float v) {
   return s;
 }
 
-// this lane's value to LDS, then sum_i bc[i] * w[i] over the CT broadcast values.  One wave: LDS operations execute in
-// program order, the fences only keep the compiler from moving the reads above the write.
+// this lane's value to LDS, then sum_i bc[i] * w[i] over the CT broadcast values (lds_fence: the reads stay behind the write).
 // The products are v_pk_fma_f32 on register pairs as the broadcast reads deliver them (w holds pairs (i, i+1)).
 template <int CT>
 __device__ __forceinline__ float bcast_dot(float* bc, int lane, float v, const f32x2 (&w)[CT / 2]) {
   bc[lane] = v;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  lds_fence();
   const f4* b4 = reinterpret_cast<const f4*>(bc);
   f32x2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
 #pragma unroll
@@ -77,13 +69,6 @@ __device__ __forceinline__ void stage(const float* __restrict__ em, const int64_
       if (mx_out) mx_out[b * S + t] = m;
     }
   }
-}
-
-__device__ __forceinline__ float trans_max(const float* __restrict__ trans, int C, int lane) {
-  float tm = NEG;
-  if (lane < C)
-    for (int i = 0; i < C; ++i) tm = fmaxf(tm, trans[i * C + lane]);
-  return wave_max(tm);
 }
 
 __device__ __forceinline__ int mask_count(const uint8_t* mk, int S, int lane) {
@@ -373,9 +358,7 @@ __global__ __launch_bounds__(64) void crf_wide_bwd_kernel(const float* __restric
 template <int CT>
 __device__ __forceinline__ void vit_best(float* bc, int lane, float score, const float (&tc)[CT], float& best, int& bi) {
   bc[lane] = score;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  lds_fence();
   const f4* b4 = reinterpret_cast<const f4*>(bc);
   float bv[4] = {NEG, NEG, NEG, NEG};
   int bx[4] = {0, 1, 2, 3};

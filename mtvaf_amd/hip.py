@@ -1065,9 +1065,8 @@ CRF_LATTICE_MAX_S = 512
 CRF_LATTICE_MAX_C = 64
 
 
-def crf_lattice_check(em, allowed, mask_u8=None, who="crf_lattice"):
-    """Argument checks shared by the lattice entry points (host-side: shapes and dtypes only, nothing is read).  em [B,S,C]
-    fp32, allowed [B,S] int64 (bit j of a word = tag j allowed; 0 = no constraint), mask_u8 [B,S] uint8."""
+def _crf_chain_shape(em, who):
+    """The [B,S,C] / C / S / B checks every chain entry point starts with (csrc/crf_chain.h: bad_shape)."""
     if em.dim() != 3:
         raise ValueError(f"{who}: emissions {tuple(em.shape)}: expected [B, S, C]")
     B, S, C = em.shape
@@ -1077,6 +1076,19 @@ def crf_lattice_check(em, allowed, mask_u8=None, who="crf_lattice"):
         raise ValueError(f"{who}: S={S} outside 1..{CRF_LATTICE_MAX_S}")
     if B < 1:
         raise ValueError(f"{who}: empty batch")
+    return B, S, C
+
+
+def _crf_workspace(bytes_fn, B, S, C, device):
+    """(uint8 workspace on ``device``, its size in bytes) for a ``mtvaf_crf_*_workspace_bytes(B, S, C)``."""
+    n = bytes_fn(B, S, C)
+    return torch.empty(n, dtype=torch.uint8, device=device), n
+
+
+def crf_lattice_check(em, allowed, mask_u8=None, who="crf_lattice"):
+    """Argument checks shared by the lattice entry points (host-side: shapes and dtypes only, nothing is read).  em [B,S,C]
+    fp32, allowed [B,S] int64 (bit j of a word = tag j allowed; 0 = no constraint), mask_u8 [B,S] uint8."""
+    B, S, C = _crf_chain_shape(em, who)
     if not isinstance(allowed, torch.Tensor) or allowed.dtype != torch.int64:
         raise ValueError(f"{who}: allowed must be an int64 tensor of tag-set words, got "
                          f"{getattr(allowed, 'dtype', type(allowed).__name__)}")
@@ -1088,8 +1100,7 @@ def crf_lattice_check(em, allowed, mask_u8=None, who="crf_lattice"):
 
 
 def crf_lattice_workspace(B, S, C, device):
-    n = lib().mtvaf_crf_lattice_workspace_bytes(B, S, C)
-    return torch.empty(n, dtype=torch.uint8, device=device), n
+    return _crf_workspace(lib().mtvaf_crf_lattice_workspace_bytes, B, S, C, device)
 
 
 def crf_lattice_fwd(em, allowed, mask_u8, start, end, trans, pllh, logz_a, logz, ws, wsb):
@@ -1125,15 +1136,7 @@ def crf_lattice_viterbi(em, allowed, mask_u8, start, end, trans, tags_out, lens_
 def crf_risk_check(em, cost=None, mask_u8=None, who="crf_risk"):
     """Argument checks shared by the risk entry points (host-side: shapes, dtypes and devices only, nothing is read).  em
     [B,S,C] fp32 on the GPU, cost (None: a call without one) floating-point [B,S,C] on the same device, mask_u8 [B,S] uint8."""
-    if em.dim() != 3:
-        raise ValueError(f"{who}: emissions {tuple(em.shape)}: expected [B, S, C]")
-    B, S, C = em.shape
-    if not 1 <= C <= CRF_LATTICE_MAX_C:
-        raise ValueError(f"{who}: C={C} outside 1..{CRF_LATTICE_MAX_C}")
-    if not 1 <= S <= CRF_LATTICE_MAX_S:
-        raise ValueError(f"{who}: S={S} outside 1..{CRF_LATTICE_MAX_S}")
-    if B < 1:
-        raise ValueError(f"{who}: empty batch")
+    B, S, C = _crf_chain_shape(em, who)
     if cost is not None:
         if not isinstance(cost, torch.Tensor) or not cost.dtype.is_floating_point:
             raise ValueError(f"{who}: cost must be a floating-point tensor, got {getattr(cost, 'dtype', type(cost).__name__)}")
@@ -1150,8 +1153,7 @@ def crf_risk_check(em, cost=None, mask_u8=None, who="crf_risk"):
 
 
 def crf_risk_workspace(B, S, C, device):
-    n = lib().mtvaf_crf_risk_workspace_bytes(B, S, C)
-    return torch.empty(n, dtype=torch.uint8, device=device), n
+    return _crf_workspace(lib().mtvaf_crf_risk_workspace_bytes, B, S, C, device)
 
 
 def crf_risk_fwd(em, cost, mask_u8, start, end, trans, risk, logz, marg, ws, wsb):
@@ -1192,8 +1194,7 @@ def crf_path_check(em, cost=None, ecost=None, mask_u8=None, who="crf_path"):
 
 
 def crf_path_workspace(B, S, C, device):
-    n = lib().mtvaf_crf_path_workspace_bytes(B, S, C)
-    return torch.empty(n, dtype=torch.uint8, device=device), n
+    return _crf_workspace(lib().mtvaf_crf_path_workspace_bytes, B, S, C, device)
 
 
 def crf_path_fwd(em, cost, ecost, mask_u8, start, end, trans, risk, logz, ws, wsb):
