@@ -172,7 +172,7 @@ int mtvaf_zero_f32(float* p, long n, mtvaf_stream_t stream);
 int mtvaf_roberta_position_ids(const int64_t* ids, int32_t* pos_ids, int B, int S, int pad_idx, mtvaf_stream_t stream);
 int mtvaf_embed_ln_fwd(const int64_t* ids, const int64_t* type_ids, const int32_t* pos_ids, const float* word,
                        const float* pos, const float* type, const float* gamma, const float* beta, float* out,
-                       float* mean, float* rstd, int B, int S, int H, float eps, float p_drop, uint64_t seed,
+                       float* mean, float* rstd, int B, int S, int H, float eps, double p_drop, uint64_t seed,
                        uint64_t offset, void* out_bf16 /* nullable: bf16 copy of out (mixed-precision GEMM operand) */,
                        mtvaf_stream_t stream);
 size_t mtvaf_embed_ln_bwd_workspace_bytes(int M, int H, int vocab, int max_pos);
@@ -180,7 +180,7 @@ int mtvaf_embed_ln_bwd(const float* dout, const int64_t* ids, const int64_t* typ
                        const float* word, const float* pos, const float* type, const float* gamma, const float* mean,
                        const float* rstd, float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta,
                        int accumulate, int B, int S, int H, int vocab, int max_pos, int type_vocab, int word_pad,
-                       int pos_pad, float p_drop, uint64_t seed, uint64_t offset, float* dz_ws, void* workspace,
+                       int pos_pad, double p_drop, uint64_t seed, uint64_t offset, float* dz_ws, void* workspace,
                        size_t workspace_bytes, mtvaf_stream_t stream);
 /* How mtvaf_embed_ln_bwd adds token-row gradients into the word (and RoBERTa position) table: 0 (default) one owner wave per
  * table row sums its tokens in row order -- bit-reproducible; 1 float atomics (MTVAF_EMBED_ATOMIC=1).  mode 0 / 1 sets, any
@@ -193,11 +193,11 @@ int mtvaf_embed_scatter_mode(int mode);
  * (dbias_x, nullable) = the gradient of that dense bias, saving a separate reduction pass. */
 size_t mtvaf_ln_bwd_workspace_bytes(int M, int H);
 int mtvaf_dropout_res_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* out,
-                             float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
+                             float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                              uint64_t offset, void* out_bf16 /* nullable */, mtvaf_stream_t stream);
 int mtvaf_dropout_res_ln_bwd(const float* dout, const float* x, const float* res, const float* gamma,
                              const float* mean, const float* rstd, float* dx, float* dres, int dres_accumulate,
-                             float* dgamma, float* dbeta, float* dbias_x, int accumulate, int M, int H, float p_drop,
+                             float* dgamma, float* dbeta, float* dbias_x, int accumulate, int M, int H, double p_drop,
                              uint64_t seed, uint64_t offset, void* workspace, size_t workspace_bytes,
                              void* dx_bf16 /* nullable: dx rounded to bf16; dx may then be NULL */, mtvaf_stream_t stream);
 /* The two halves of mtvaf_dropout_res_ln_bwd as separate calls: _rows writes dx / dres and per-block partial sums into `part`
@@ -205,7 +205,7 @@ int mtvaf_dropout_res_ln_bwd(const float* dout, const float* x, const float* res
  * dgamma / dbeta / dbias_x.  The layer executor runs _finish on its weight-gradient stream: the sums feed parameter
  * gradients only (autograd backward of modeling_bert.py:354-355, 434-435). */
 int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
-                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, float p_drop,
+                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, double p_drop,
                                   uint64_t seed, uint64_t offset, float* part, void* dx_bf16 /* nullable */,
                                   mtvaf_stream_t stream);
 int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgamma, float* dbeta, float* dbias_x /* nullable */,
@@ -624,11 +624,11 @@ int mtvaf_gemm_f32_slabs(int layout_a, int layout_b, const float* A, int lda, co
                          int K, const float* bias, int accumulate, void* workspace, size_t workspace_bytes, int* splits_out,
                          mtvaf_stream_t stream);
 int mtvaf_dropout_res_ln_fwd_slabs(const float* slabs, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                    uint64_t seed, uint64_t offset, void* out_bf16, mtvaf_stream_t st);
 int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                         const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                        int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                        int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                         void* dx_bf16, mtvaf_stream_t st);
 /* Round 5, pre-split operands: the two LayerNorm kernels that ALSO write the tile-blocked plane image [H / 32][3][M][32] of their
  * output (H % 32 == 0), bit for bit what mtvaf_f32_split_planes would write behind them.  _fwd_planes: nslab == 0 -> x is the dense
@@ -636,11 +636,11 @@ int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* sla
  * _bwd_rows_planes: nslab == 0 -> dout = dout_base (as mtvaf_dropout_res_ln_bwd_rows), nslab >= 1 -> dout = slabs + dout_base; dx may
  * be NULL (a gradient only GEMMs read). */
 int mtvaf_dropout_res_ln_fwd_planes(const float* x, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                     uint64_t seed, uint64_t offset, void* out_planes, mtvaf_stream_t st);
 int mtvaf_dropout_res_ln_bwd_rows_planes(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                          const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                         int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                         int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                          void* dx_planes, mtvaf_stream_t st);
 int mtvaf_f32x3_trace(void* buf);
 
@@ -780,7 +780,9 @@ int mtvaf_cast_bf16(const float* x, int ldx, void* out, int ldo, void* outT, int
 typedef struct {
   int B, S, P, NH, H, I;
   int bf16;
-  float eps, p_hidden, p_attn;
+  float eps;
+  double p_hidden; /* a double: the LayerNorm sites scale kept elements by float(1 / (1 - p)), as torch does */
+  float p_attn;
   uint64_t seed, offset;
   const float *wqkv, *wo, *w1, *w2;
   const void *wqkv_h, *wo_h, *w1_h, *w2_h;

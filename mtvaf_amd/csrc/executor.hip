@@ -102,10 +102,10 @@ int mtvaf_prefix_attn_bf16_varlen_bwd(const void* dctx16, const void* qkv16, con
                                       float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
                                       uint64_t offset, hipStream_t st);
 int mtvaf_dropout_res_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* out,
-                             float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
+                             float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                              uint64_t offset, void* out_bf16, hipStream_t st);
 int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
-                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, float p_drop,
+                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, double p_drop,
                                   uint64_t seed, uint64_t offset, float* part, void* dx_bf16, hipStream_t st);
 int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgamma, float* dbeta, float* dbias_x, int accumulate,
                                     hipStream_t st);
@@ -113,22 +113,22 @@ int mtvaf_gemm_f32_slabs(int layout_a, int layout_b, const float* A, int lda, co
                          int K, const float* bias, int accumulate, void* workspace, size_t workspace_bytes, int* splits_out,
                          hipStream_t stream);
 int mtvaf_dropout_res_ln_fwd_slabs(const float* slabs, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                    uint64_t seed, uint64_t offset, void* out_bf16, hipStream_t st);
 int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                         const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                        int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                        int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                         void* dx_bf16, hipStream_t st);
 int mtvaf_dropout_res_ln_fwd_planes(const float* x, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                     uint64_t seed, uint64_t offset, void* out_planes, hipStream_t st);
 int mtvaf_dropout_res_ln_bwd_rows_planes(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                          const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                         int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                         int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                          void* dx_planes, hipStream_t st);
 int mtvaf_dropout_res_ln_bwd(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
                              const float* rstd, float* dx, float* dres, int dres_accumulate, float* dgamma, float* dbeta,
-                             float* dbias_x, int accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset,
+                             float* dbias_x, int accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset,
                              void* workspace, size_t workspace_bytes, void* dx_bf16, hipStream_t st);
 }
 
@@ -164,7 +164,7 @@ using namespace mtvaf;
 
 // dense product (+ bias) -> dropout + residual + LayerNorm, with the split-K slabs of the product handed to the LayerNorm
 static int dense_ln_fwd(const float* A, int K, const float* W, const float* bias, float* x_out, const float* res, const float* gamma,
-                        const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
+                        const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                         uint64_t offset, void* ws, size_t ws_bytes, hipStream_t st) {
   if (ws) {
     int ns = 1;
@@ -214,7 +214,9 @@ extern "C" {
 struct mtvaf_layer_t {
   int B, S, P, NH, H, I;
   int bf16;
-  float eps, p_hidden, p_attn;
+  float eps;
+  double p_hidden;                             // (a double: the LayerNorm sites scale kept elements by float(1 / (1 - p)), as torch)
+  float p_attn;
   uint64_t seed, offset;
   const float *wqkv, *wo, *w1, *w2;            // fp32 masters [3H,H] [H,H] [I,H] [H,I] (fp32 mode)
   const void *wqkv_h, *wo_h, *w1_h, *w2_h;     // bf16 images (bf16 mode)
@@ -275,7 +277,7 @@ static bool planes_mode(const mtvaf_layer_t* L) {
 
 // dense product on the pre-split kernel (+ bias) -> dropout + residual + LayerNorm, the product's split-K slabs handed to the LayerNorm
 static int dense_ln_fwd_p(const void* Ap, int K, const void* Wp, const float* bias, float* x_out, const float* res, const float* gamma,
-                          const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
+                          const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                           uint64_t offset, void* ws, size_t ws_bytes, void* out_planes, hipStream_t st) {
   int ns = 1;
   const int rc = p16(0, Ap, Wp, x_out, H, M, H, K, bias, X_EPI_NONE, nullptr, 0, 0, ws, ws_bytes, &ns, st);
@@ -388,7 +390,7 @@ int mtvaf_dw_group_wanted(int rows, int H, int I) {
 // partial buffers (g->lnpart*) and a second stream, the column sums (dgamma, dbeta, the dense bias gradient: parameter
 // gradients only) run THERE: 24 launches of ~12 us leave the main chain of a step.
 static int ln_bwd_forked(const float* dout, const float* x, const float* res, const float* gamma, const float* mean, const float* rstd,
-                         float* dx, float* dres, float* dgamma, float* dbeta, float* dbias, int M, int H, float p_drop, uint64_t seed,
+                         float* dx, float* dres, float* dgamma, float* dbeta, float* dbias, int M, int H, double p_drop, uint64_t seed,
                          uint64_t offset, float* part, void* ws, size_t ws_bytes, void* dx16, hipStream_t mainS, hipStream_t side) {
   if (part && side != mainS) {
     MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows(dout, x, res, gamma, mean, rstd, dx, dres, 0, M, H, p_drop, seed, offset, part, dx16, mainS));

@@ -36,13 +36,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float* __restrict__ out, float* __restrict__ mean_o,
                                                     float* __restrict__ rstd_o, int M, int S, int H, float eps,
-                                                    float p_drop, uint64_t seed, uint64_t offset,
+                                                    float p_drop, float scale, uint64_t seed, uint64_t offset,
                                                     __bf16* __restrict__ out16, const uint64_t* __restrict__ epoch) {
   offset = epoch_offset(offset, epoch);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int nch = H >> 2;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
     f32x4 z[MAXC];
     float s = 0.f;
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
                                                     const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
                                                     float* __restrict__ dx, float* __restrict__ dres, int dres_acc,
                                                     float* __restrict__ partials, int M, int S, int H, float p_drop,
-                                                    uint64_t seed, uint64_t offset, __bf16* __restrict__ dx16,
+                                                    float scale, uint64_t seed, uint64_t offset, __bf16* __restrict__ dx16,
                                                     const uint64_t* __restrict__ epoch) {
   offset = epoch_offset(offset, epoch);
   constexpr int NP = MODE == 1 ? 4 : 3;
@@ -136,7 +135,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int nch = H >> 2;
-  const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   f32x4 ag[MAXC], ab[MAXC], at0[MAXC], at1[MAXC];
 #pragma unroll
   for (int i = 0; i < MAXC; ++i) ag[i] = ab[i] = at0[i] = at1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -279,14 +277,14 @@ __global__ __launch_bounds__(256) void ln_bwd_lean_kernel(const float* __restric
                                                          const float* __restrict__ gamma, const float* __restrict__ mean_i,
                                                          const float* __restrict__ rstd_i, float* __restrict__ dx,
                                                          float* __restrict__ dres, int dres_acc, float* __restrict__ partials, int M,
-                                                         int H, float p_drop, uint64_t seed, uint64_t offset,
+                                                         int H, float p_drop, float scale_, uint64_t seed, uint64_t offset,
                                                          __bf16* __restrict__ dx16, const uint64_t* __restrict__ epoch) {
   offset = epoch_offset(offset, epoch);
   __shared__ float red[2][4][2];
   const int c = threadIdx.x;  // this lane's float4 column chunk; blockDim.x == H / 4
   const int lane = c & 63, wave = c >> 6;
   const int nch = H >> 2;
-  const float scale = uni(p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f);
+  const float scale = uni(scale_);
   const float invH = uni(1.f / H);
   const uint32_t thr = __builtin_amdgcn_readfirstlane((uint32_t)fminf(p_drop * 4294967296.0f, 4294967040.0f));
   const unsigned rowb = (unsigned)H * 4u;        // bytes of a row
@@ -715,14 +713,18 @@ static inline bool ln_lean(int M, int H, int nslab) {
   return on && H % 256 == 0 && H <= 1024 && (size_t)std::max(nslab, 2) * M * H * 4 < ((size_t)1 << 31);
 }
 
+// what the kept elements of a dropout site are multiplied by: float(1 / (1 - p)) from the caller's double p, as mtvaf_dropout and
+// torch scale (1.f / (1.f - p) in fp32 is 9.999998 at p = 0.9).  The keep threshold stays a function of float(p): same masks.
+static inline float drop_scale(double p_drop) { return p_drop > 0.0 ? (float)(1.0 / (1.0 - p_drop)) : 1.f; }
+
 template <bool PL>
 static void ln_bwd_lean(int g, hipStream_t st, const float* dout, const float* slabs, int nslab, const float* x, const float* res,
                         const float* gamma, const float* mean, const float* rstd, float* dx, float* dres, int dres_acc, float* part, int M,
-                        int H, float p_drop, uint64_t seed, uint64_t offset, __bf16* dx16) {
+                        int H, double p_drop, uint64_t seed, uint64_t offset, __bf16* dx16) {
   if (!slabs) nslab = 0;
 #define MTVAF_LEAN(NS_)                                                                                                             \
   hipLaunchKernelGGL((ln_bwd_lean_kernel<PL, NS_>), dim3(g), dim3(H / 4), 0, st, dout, slabs, nslab, x, res, gamma, mean, rstd, dx, \
-                     dres, dres_acc, part, M, H, p_drop, seed, offset, dx16, rng_epoch_ptr())
+                     dres, dres_acc, part, M, H, (float)p_drop, drop_scale(p_drop), seed, offset, dx16, rng_epoch_ptr())
   if (nslab == 0) MTVAF_LEAN(0);
   else if (nslab == 1) MTVAF_LEAN(1);
   else if (nslab == 2) MTVAF_LEAN(2);
@@ -752,35 +754,35 @@ int mtvaf_roberta_position_ids(const int64_t* ids, int32_t* pos_ids, int B, int 
 
 int mtvaf_embed_ln_fwd(const int64_t* ids, const int64_t* type_ids, const int32_t* pos_ids, const float* word,
                        const float* pos, const float* type, const float* gamma, const float* beta, float* out,
-                       float* mean, float* rstd, int B, int S, int H, float eps, float p_drop, uint64_t seed,
+                       float* mean, float* rstd, int B, int S, int H, float eps, double p_drop, uint64_t seed,
                        uint64_t offset, void* out_bf16, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || B <= 0 || S <= 0) return MTVAF_ERR_SHAPE;
   const int M = B * S;
   hipLaunchKernelGGL((ln_fwd_kernel<1>), dim3(row_grid(M)), dim3(256), 0, st, nullptr, nullptr, ids, type_ids, pos_ids,
-                     word, pos, type, gamma, beta, out, mean, rstd, M, S, H, eps, p_drop, seed, offset,
+                     word, pos, type, gamma, beta, out, mean, rstd, M, S, H, eps, (float)p_drop, drop_scale(p_drop), seed, offset,
                      static_cast<__bf16*>(out_bf16), rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 
 int mtvaf_dropout_res_ln_fwd_slabs(const float* slabs, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                    uint64_t seed, uint64_t offset, void* out_bf16, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || M <= 0 || nslab < 1) return MTVAF_ERR_SHAPE;
   if (!slabs || !x_out) return MTVAF_ERR_ARG;
   hipLaunchKernelGGL((ln_fwd_kernel<2>), dim3(row_grid(M)), dim3(256), 0, st, slabs, res, nullptr, nullptr, nullptr, bias, x_out,
-                     nullptr, gamma, beta, out, mean, rstd, M, nslab, H, eps, p_drop, seed, offset, static_cast<__bf16*>(out_bf16),
+                     nullptr, gamma, beta, out, mean, rstd, M, nslab, H, eps, (float)p_drop, drop_scale(p_drop), seed, offset, static_cast<__bf16*>(out_bf16),
                      rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 
 int mtvaf_dropout_res_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* out,
-                             float* mean, float* rstd, int M, int H, float eps, float p_drop, uint64_t seed,
+                             float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                              uint64_t offset, void* out_bf16, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || M <= 0) return MTVAF_ERR_SHAPE;
   hipLaunchKernelGGL((ln_fwd_kernel<0>), dim3(row_grid(M)), dim3(256), 0, st, x, res, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, gamma, beta, out, mean, rstd, M, 1, H, eps, p_drop, seed, offset,
+                     nullptr, nullptr, nullptr, gamma, beta, out, mean, rstd, M, 1, H, eps, (float)p_drop, drop_scale(p_drop), seed, offset,
                      static_cast<__bf16*>(out_bf16), rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -794,7 +796,7 @@ int mtvaf_dropout_res_ln_fwd(const float* x, const float* res, const float* gamm
 // per-block partial sums into `part` (mtvaf_ln_bwd_workspace_bytes(M, H) bytes, owned by the caller until _finish has run);
 // _finish reduces them into dgamma / dbeta / dbias_x in fixed order.
 int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
-                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, float p_drop,
+                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, double p_drop,
                                   uint64_t seed, uint64_t offset, float* part, void* dx_bf16, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || M <= 0) return MTVAF_ERR_SHAPE;
   if ((!dx && !dx_bf16) || !part) return MTVAF_ERR_ARG;
@@ -804,7 +806,7 @@ int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float
                        static_cast<__bf16*>(dx_bf16));
   else
     hipLaunchKernelGGL((ln_bwd_kernel<0>), dim3(g), dim3(256), 0, st, dout, x, res, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, gamma, mean, rstd, dx, dres, dres_accumulate, part, M, 1, H, p_drop, seed,
+                       nullptr, nullptr, gamma, mean, rstd, dx, dres, dres_accumulate, part, M, 1, H, (float)p_drop, drop_scale(p_drop), seed,
                        offset, static_cast<__bf16*>(dx_bf16), rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -813,7 +815,7 @@ int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float
 // LayerNorm (mtvaf_gemm_f32_slabs), added in the order of the reduction launch it replaces.
 int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                         const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                        int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                        int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                         void* dx_bf16, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || M <= 0 || nslab < 1) return MTVAF_ERR_SHAPE;
   if ((!dx && !dx_bf16) || !part || !slabs || !dout_base) return MTVAF_ERR_ARG;
@@ -823,7 +825,7 @@ int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* sla
                        static_cast<__bf16*>(dx_bf16));
   else
     hipLaunchKernelGGL((ln_bwd_kernel<0>), dim3(g), dim3(256), 0, st, dout_base, x, res, nullptr, nullptr, nullptr, slabs, nullptr,
-                       nullptr, gamma, mean, rstd, dx, dres, dres_accumulate, part, M, nslab, H, p_drop, seed, offset,
+                       nullptr, gamma, mean, rstd, dx, dres, dres_accumulate, part, M, nslab, H, (float)p_drop, drop_scale(p_drop), seed, offset,
                        static_cast<__bf16*>(dx_bf16), rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
@@ -834,24 +836,24 @@ int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* sla
 // (as mtvaf_dropout_res_ln_fwd_slabs: bias added, the sum stored to x_out).  _bwd_rows_planes: nslab == 0 -> dout = dout_base (as
 // mtvaf_dropout_res_ln_bwd_rows), nslab >= 1 -> dout = slabs + dout_base; dx may be NULL (a gradient only GEMMs read).
 int mtvaf_dropout_res_ln_fwd_planes(const float* x, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, float p_drop,
+                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
                                     uint64_t seed, uint64_t offset, void* out_planes, hipStream_t st) {
   if (H % 32 || H > MAXC * 256 || M <= 0 || nslab < 0) return MTVAF_ERR_SHAPE;
   if (!x || !out_planes || (nslab >= 1 && !x_out) || (((uintptr_t)out_planes) & 15)) return MTVAF_ERR_ARG;
   if (nslab >= 1)
     hipLaunchKernelGGL((ln_fwd_kernel<2, true>), dim3(row_grid(M)), dim3(256), 0, st, x, res, nullptr, nullptr, nullptr, bias, x_out,
-                       nullptr, gamma, beta, out, mean, rstd, M, nslab, H, eps, p_drop, seed, offset, static_cast<__bf16*>(out_planes),
+                       nullptr, gamma, beta, out, mean, rstd, M, nslab, H, eps, (float)p_drop, drop_scale(p_drop), seed, offset, static_cast<__bf16*>(out_planes),
                        rng_epoch_ptr());
   else
     hipLaunchKernelGGL((ln_fwd_kernel<0, true>), dim3(row_grid(M)), dim3(256), 0, st, x, res, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, gamma, beta, out, mean, rstd, M, 1, H, eps, p_drop, seed, offset, static_cast<__bf16*>(out_planes),
+                       nullptr, gamma, beta, out, mean, rstd, M, 1, H, eps, (float)p_drop, drop_scale(p_drop), seed, offset, static_cast<__bf16*>(out_planes),
                        rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
 int mtvaf_dropout_res_ln_bwd_rows_planes(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
                                          const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                         int dres_accumulate, int M, int H, float p_drop, uint64_t seed, uint64_t offset, float* part,
+                                         int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
                                          void* dx_planes, hipStream_t st) {
   if (H % 32 || H > MAXC * 256 || M <= 0 || nslab < 0) return MTVAF_ERR_SHAPE;
   if (!dx_planes || !part || !dout_base || (nslab >= 1 && !slabs) || (((uintptr_t)dx_planes) & 15)) return MTVAF_ERR_ARG;
@@ -862,7 +864,7 @@ int mtvaf_dropout_res_ln_bwd_rows_planes(const float* dout_base, const float* sl
   else
     hipLaunchKernelGGL((ln_bwd_kernel<0, true>), dim3(g), dim3(256), 0, st, dout_base, x, res, nullptr, nullptr, nullptr,
                        nslab >= 1 ? slabs : nullptr, nullptr, nullptr, gamma, mean, rstd, dx, dres, dres_accumulate, part, M,
-                       nslab >= 1 ? nslab : 1, H, p_drop, seed, offset, static_cast<__bf16*>(dx_planes), rng_epoch_ptr());
+                       nslab >= 1 ? nslab : 1, H, (float)p_drop, drop_scale(p_drop), seed, offset, static_cast<__bf16*>(dx_planes), rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -883,7 +885,7 @@ int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgam
 
 int mtvaf_dropout_res_ln_bwd(const float* dout, const float* x, const float* res, const float* gamma,
                              const float* mean, const float* rstd, float* dx, float* dres, int dres_accumulate,
-                             float* dgamma, float* dbeta, float* dbias_x, int accumulate, int M, int H, float p_drop,
+                             float* dgamma, float* dbeta, float* dbias_x, int accumulate, int M, int H, double p_drop,
                              uint64_t seed, uint64_t offset, void* workspace, size_t workspace_bytes, void* dx_bf16,
                              hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || M <= 0) return MTVAF_ERR_SHAPE;
@@ -917,7 +919,7 @@ int mtvaf_embed_ln_bwd(const float* dout, const int64_t* ids, const int64_t* typ
                        const float* word, const float* pos, const float* type, const float* gamma, const float* mean,
                        const float* rstd, float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta,
                        int accumulate, int B, int S, int H, int vocab, int max_pos, int type_vocab, int word_pad,
-                       int pos_pad, float p_drop, uint64_t seed, uint64_t offset, float* dz_ws, void* workspace,
+                       int pos_pad, double p_drop, uint64_t seed, uint64_t offset, float* dz_ws, void* workspace,
                        size_t workspace_bytes, hipStream_t st) {
   if (H % 4 || H > MAXC * 256 || B <= 0 || S <= 0 || type_vocab > 2) return MTVAF_ERR_SHAPE;
   const int M = B * S;
@@ -925,7 +927,7 @@ int mtvaf_embed_ln_bwd(const float* dout, const int64_t* ids, const int64_t* typ
   if (workspace_bytes < mtvaf_embed_ln_bwd_workspace_bytes(M, H, vocab, max_pos)) return MTVAF_ERR_WORKSPACE;
   float* part = (float*)workspace;
   hipLaunchKernelGGL((ln_bwd_kernel<1>), dim3(g), dim3(256), 0, st, dout, nullptr, nullptr, ids, type_ids, pos_ids,
-                     word, pos, type, gamma, mean, rstd, dz_ws, nullptr, 0, part, M, S, H, p_drop, seed, offset,
+                     word, pos, type, gamma, mean, rstd, dz_ws, nullptr, 0, part, M, S, H, (float)p_drop, drop_scale(p_drop), seed, offset,
                      (__bf16*)nullptr, rng_epoch_ptr());
   MTVAF_LAUNCH_CHECK();
   OutPtrs outs{{dgamma, dbeta, dtype, type_vocab > 1 ? dtype + H : nullptr}};

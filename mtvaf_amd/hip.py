@@ -38,10 +38,10 @@ _SIGS = {
     "mtvaf_f32_split": (c_int, [I]),
     "mtvaf_f32x3_trace": (c_int, [P]),
     "mtvaf_gemm_f32_slabs": (c_int, [I, I, P, I, P, I, P, I, I, I, I, P, I, P, SZ, P, P]),
-    "mtvaf_dropout_res_ln_fwd_slabs": (c_int, [P, I, P, P, P, P, P, P, P, P, I, I, F, F, U64, U64, P, P]),
-    "mtvaf_dropout_res_ln_bwd_rows_slabs": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, F, U64, U64, P, P, P]),
-    "mtvaf_dropout_res_ln_fwd_planes": (c_int, [P, I, P, P, P, P, P, P, P, P, I, I, F, F, U64, U64, P, P]),
-    "mtvaf_dropout_res_ln_bwd_rows_planes": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, F, U64, U64, P, P, P]),
+    "mtvaf_dropout_res_ln_fwd_slabs": (c_int, [P, I, P, P, P, P, P, P, P, P, I, I, F, c_double, U64, U64, P, P]),
+    "mtvaf_dropout_res_ln_bwd_rows_slabs": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, c_double, U64, U64, P, P, P]),
+    "mtvaf_dropout_res_ln_fwd_planes": (c_int, [P, I, P, P, P, P, P, P, P, P, I, I, F, c_double, U64, U64, P, P]),
+    "mtvaf_dropout_res_ln_bwd_rows_planes": (c_int, [P, P, I, P, P, P, P, P, P, P, I, I, I, c_double, U64, U64, P, P, P]),
     "mtvaf_f32_split_planes": (c_int, [P, P, I, I, I, L, L, L, P]),
     "mtvaf_gemm_f32p": (c_int, [I, P, L, L, L, L, I, P, L, L, L, L, P, I, I, I, I, P, I, P, I, I, I, P, SZ, I, P]),
     "mtvaf_f32p_trace": (c_int, [P]),
@@ -73,12 +73,12 @@ _SIGS = {
     "mtvaf_prefix_attn_bf16_bwd_tail": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, I, P]),
     "mtvaf_ln_bwd_workspace_bytes": (SZ, [I, I]),
     "mtvaf_roberta_position_ids": (c_int, [P, P, I, I, I, P]),
-    "mtvaf_embed_ln_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, F, F, U64, U64, P, P]),
-    "mtvaf_embed_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, U64,
+    "mtvaf_embed_ln_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, F, c_double, U64, U64, P, P]),
+    "mtvaf_embed_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, c_double, U64,
                                    U64, P, P, SZ, P]),
-    "mtvaf_dropout_res_ln_fwd": (c_int, [P, P, P, P, P, P, P, I, I, F, F, U64, U64, P, P]),
-    "mtvaf_dropout_res_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, I, P, P, P, I, I, I, F, U64, U64, P, SZ, P, P]),
-    "mtvaf_dropout_res_ln_bwd_rows": (c_int, [P, P, P, P, P, P, P, P, I, I, I, F, U64, U64, P, P, P]),
+    "mtvaf_dropout_res_ln_fwd": (c_int, [P, P, P, P, P, P, P, I, I, F, c_double, U64, U64, P, P]),
+    "mtvaf_dropout_res_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, I, P, P, P, I, I, I, c_double, U64, U64, P, SZ, P, P]),
+    "mtvaf_dropout_res_ln_bwd_rows": (c_int, [P, P, P, P, P, P, P, P, I, I, I, c_double, U64, U64, P, P, P]),
     "mtvaf_dropout_res_ln_bwd_finish": (c_int, [P, I, I, P, P, P, I, P]),
     "mtvaf_colsum_workspace_bytes": (SZ, [I, I]),
     "mtvaf_colsum": (c_int, [P, I, I, I, P, I, P, SZ, P]),
@@ -165,7 +165,7 @@ _SIGS = {
 class LayerStruct(ctypes.Structure):
     """mtvaf_layer_t (include/mtvaf_hip.h): one encoder layer's shapes, parameters, input and activation buffers."""
     _fields_ = ([(n, c_int) for n in ("B", "S", "P", "NH", "H", "I", "bf16")] +
-                [(n, c_float) for n in ("eps", "p_hidden", "p_attn")] + [("seed", c_uint64), ("offset", c_uint64)] +
+                [("eps", c_float), ("p_hidden", c_double), ("p_attn", c_float)] + [("seed", c_uint64), ("offset", c_uint64)] +
                 [(n, c_void_p) for n in ("wqkv", "wo", "w1", "w2", "wqkv_h", "wo_h", "w1_h", "w2_h", "bqkv", "bo", "g1", "b1",
                                          "bi1", "bi2", "g2", "b2", "x", "x_h", "pk", "pv", "addmask", "qkv", "cx", "lse", "a",
                                          "h1", "h1_h", "mean1", "rstd1", "pre", "act", "f", "h2", "h2_h", "mean2", "rstd2",
