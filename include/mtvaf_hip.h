@@ -28,7 +28,10 @@
 extern "C" {
 #endif
 
-typedef void* mtvaf_stream_t; /* hipStream_t */
+/* hipStream_t, spelled as hip_runtime_api.h spells it: the struct stays incomplete, so this header needs no HIP header and is
+ * valid C99, and the library's own sources -- every one includes this header -- define the entry points with hipStream_t
+ * against these very prototypes.  A plain pointer in the ABI (ctypes: c_void_p). */
+typedef struct ihipStream_t* mtvaf_stream_t;
 
 #define MTVAF_OK 0
 #define MTVAF_ERR_SHAPE (-1)
@@ -784,22 +787,22 @@ typedef struct {
   double p_hidden; /* a double: the LayerNorm sites scale kept elements by float(1 / (1 - p)), as torch does */
   float p_attn;
   uint64_t seed, offset;
-  const float *wqkv, *wo, *w1, *w2;
-  const void *wqkv_h, *wo_h, *w1_h, *w2_h;
+  const float *wqkv, *wo, *w1, *w2;        /* fp32 masters [3H,H] [H,H] [I,H] [H,I] (fp32 mode) */
+  const void *wqkv_h, *wo_h, *w1_h, *w2_h; /* bf16 images (bf16 mode) */
   const float *bqkv, *bo, *g1, *b1, *bi1, *bi2, *g2, *b2;
-  const float* x;
-  const void* x_h;
-  const void *pk, *pv;
-  const float* addmask;
-  void *qkv, *cx;
-  float *lse, *a, *h1;
+  const float* x;                          /* [M,H] layer input */
+  const void* x_h;                         /* bf16 copy (bf16 mode) */
+  const void *pk, *pv;                     /* prefix slabs [B, P*H] or NULL */
+  const float* addmask;                    /* [B, P+S] */
+  void *qkv, *cx;                          /* [M,3H], [M,H] */
+  float *lse, *a, *h1;                     /* [B,NH,S], [M,H], [M,H] */
   void* h1_h;
   float *mean1, *rstd1;
-  void *pre, *act;
-  float *f, *h2;
+  void *pre, *act;                         /* [M,I] */
+  float *f, *h2;                           /* [M,H] */
   void* h2_h;
   float *mean2, *rstd2;
-  void* ws; size_t ws_bytes;
+  void* ws; size_t ws_bytes;               /* main-stream scratch of the forward pass (split-K slabs of small-M products) */
   /* padding-free execution: cu != NULL -> the token tensors (x, qkv ... h2, and the gradient buffers) hold Mp
    * PACKED rows -- the Mv unmasked tokens sentence by sentence (cu [B+1] int32 row offsets), then Mp - Mv zero rows that
    * pad the image to whole 128-row tiles; lse / delta keep [B,NH,S].  cu == NULL: the padded [B*S] layout. */
@@ -816,14 +819,15 @@ typedef struct {
 
 typedef struct {
   float* dh;                              /* in: d loss / d h2 [M,H]; out: d loss / d x */
-  float* dh1;
-  void *df, *dpre, *da, *dctx, *dqkv;
-  float *part, *partq, *partkv;           /* bf16 mode: epilogue / attention column-sum partials */
+  float* dh1;                             /* [M,H] scratch */
+  void *df, *dpre, *da, *dctx, *dqkv;     /* [M,H] [M,I] [M,H] [M,H] [M,3H]  (bf16 in bf16 mode) */
+  float *part, *partq, *partkv;           /* bf16 mode: epilogue / attention column-sum partials
+                                           * [M/128, I], [B*ceil(S/64), H], [B*ceil((P+S)/64), 2H] */
   float* delta;                           /* fp32 mode: [B,NH,S] */
   float *dwqkv, *dbqkv, *dwo, *dbo, *dg1, *db1, *dw1, *dbi1, *dw2, *dbi2, *dg2, *db2;
-  float *dpk, *dpv;
-  void* ws_main; size_t ws_main_bytes;
-  void* ws_side; size_t ws_side_bytes;
+  float *dpk, *dpv;                       /* [B, P*H] or NULL */
+  void* ws_main; size_t ws_main_bytes;    /* scratch of the main stream (LayerNorm partials, split-K slabs) */
+  void* ws_side; size_t ws_side_bytes;    /* scratch of the second stream (split-K slabs, column-sum partials) */
   /* optional: k-tile list of the token axis for the weight-gradient products (mtvaf_build_ktiles; 32-row tiles in fp32
    * mode, 64-row tiles in bf16 mode) */
   const int* klist;
@@ -831,11 +835,12 @@ typedef struct {
   /* the caller's word: token rows behind a sentence's last unmasked position carry exactly-zero gradients (what a k-tile list
    * implies as well): the attention backward stops its query loops there (mtvaf_prefix_attn_bwd_tail) */
   int zero_tail;
-  /* optional (both or neither): the layer's own LayerNorm-backward partials of the FFN / attention block,
-   * mtvaf_ln_bwd_workspace_bytes(M, H) each -- their column sums then run on `side` instead of the main chain */
+  /* optional (both or neither; required with plane images): the layer's own LayerNorm-backward partials of the FFN / attention
+   * block, mtvaf_ln_bwd_workspace_bytes(M, H) each -- their column sums then run on `side` instead of the main chain */
   float *lnpart2, *lnpart1;
   /* fp32 mode with pre-split operands (see mtvaf_layer_t::x_p): scratch plane images of the four upstream gradients that are GEMM
-   * operands -- [Mp, H], [Mp, I], [Mp, H], [Mp, 3H] -- alive until the second stream has finished the layer's weight gradients */
+   * operands -- [Mp, H], [Mp, I], [Mp, H], [Mp, 3H] -- alive until the second stream has finished the layer's weight gradients;
+   * with `part`, both lnpart and ws_main they are required when the layer struct has plane images, NULL otherwise */
   void *df_p, *dpre_p, *da_p, *dqkv_p;
 } mtvaf_layer_grads_t;
 

@@ -15,6 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+PUBLIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "mtvaf_hip.h")
 # MTVAF_LIBDIR: build into another directory (A/B variants with MTVAF_EXTRA_FLAGS; load them with MTVAF_LIB=<dir>/libmtvaf_hip.so).
 # The flags are part of every object's stamp, so a variant can never be mistaken for the product build.
 LIBDIR = os.environ.get("MTVAF_LIBDIR") or os.path.join(HERE, "lib")
@@ -35,11 +36,13 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 
 
 def _headers_digest() -> bytes:
+    """csrc/*.h and the public header, which csrc/common.h includes: an edit to any of them rebuilds every object."""
     h = hashlib.sha256()
     for f in sorted(os.listdir(CSRC)):
         if f.endswith(".h"):
             h.update(f.encode())
             h.update(open(os.path.join(CSRC, f), "rb").read())
+    h.update(open(PUBLIC_HEADER, "rb").read())
     return h.digest()
 
 

@@ -228,8 +228,6 @@ using namespace mtvaf;
 
 extern "C" {
 
-int mtvaf_f32_split(int on);  // (gemm.hip)
-
 // Round 6: under the split arithmetic (the library default: mtvaf_f32_split) the attention products are split bf16 products too
 // (csrc/attention_f32s.hip: same interface, geometry and outputs); the fp32 MFMA pipe keeps the kernels of this file.
 static bool attn_split_on() { return mtvaf_f32_split(-1) != 0; }

@@ -3,11 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MTVAF_OK 0
-#define MTVAF_ERR_SHAPE (-1)
-#define MTVAF_ERR_ALIGN (-2)
-#define MTVAF_ERR_ARG (-3)
-#define MTVAF_ERR_WORKSPACE (-4)
+// The C ABI (status codes, structs, every entry point): each definition in csrc/ is compiled against its public prototype.
+#include "../../include/mtvaf_hip.h"
 
 #define MTVAF_LAUNCH_CHECK()                      \
   do {                                            \

@@ -2,9 +2,6 @@
 #pragma once
 #include "common.h"
 
-// (include/mtvaf_hip.h: bytes of the workspace of the forward / backward recursions, 0 for a shape neither path takes)
-extern "C" size_t mtvaf_crf_workspace_bytes(int B, int S, int C);
-
 namespace mtvaf {
 
 // Both paths (C <= 16 and the wide one): logz[b] = log-partition of sentence b by the forward recursion without the gold path -- the

@@ -14,128 +14,7 @@
 
 #include <cstddef>
 
-extern "C" {
-// (the library's own C ABI; declared here instead of including the public header, which is C99 with void* streams)
-int mtvaf_gemm_f32(int layout_a, int layout_b, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M,
-                   int N, int K, const float* bias, int epi, float* aux, int ldaux, int accumulate, int allow_split,
-                   void* workspace, size_t workspace_bytes, int cfg, int splits, hipStream_t stream);
-int mtvaf_gemm_bf16x(int layout_a, int layout_b, const void* A, int lda, const void* B, int ldb, float* C32, int ldc32,
-                     void* C16, int ldc16, int M, int N, int K, const float* bias, int epi, void* aux16, int ldaux,
-                     int accumulate, float* colpart, int allow_split, void* workspace, size_t workspace_bytes, int tile,
-                     int splits, int stages, hipStream_t stream);
-int mtvaf_gemm_f32_dw_group(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
-                            const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt,
-                            void* workspace, size_t workspace_bytes, int splits, hipStream_t stream);
-int mtvaf_gemm_f32_dw_group_bias(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
-                                 const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt,
-                                 float* const* dbias, void* workspace, size_t workspace_bytes, int splits, hipStream_t stream);
-int mtvaf_streamk_attached(hipStream_t stream);
-int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
-                              const int* ldc32, const int* M, const int* N, int K, hipStream_t stream);
-int mtvaf_gemm_bf16x_ktiles(int layout_a, int layout_b, const void* A, int lda, const void* B, int ldb, float* C32, int ldc32,
-                            void* C16, int ldc16, int M, int N, int K, const float* bias, int epi, void* aux16, int ldaux,
-                            int accumulate, float* colpart, int allow_split, void* workspace, size_t workspace_bytes, int tile,
-                            int splits, int stages, const int* klist, const int* kcnt, hipStream_t stream);
-int mtvaf_colsum_small(const float* part, int rows, int cols, float* out, int accumulate, hipStream_t stream);
-int mtvaf_colsum(const float* x, int rows, int cols, int ld, float* out, int accumulate, void* workspace,
-                 size_t workspace_bytes, hipStream_t st);
-int mtvaf_prefix_attn_fwd(const float* qkv, const float* pk, const float* pv, const float* addmask, float* ctx, float* lse,
-                          int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
-                          hipStream_t st);
-int mtvaf_prefix_attn_bwd_tail(const float* dctx, const float* qkv, const float* pk, const float* pv, const float* addmask,
-                               const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv, int B, int S,
-                               int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset, int zero_tail,
-                               hipStream_t st);
-int mtvaf_prefix_attn_bwd(const float* dctx, const float* qkv, const float* pk, const float* pv, const float* addmask,
-                          const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv, int B,
-                          int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st);
-int mtvaf_prefix_attn_bf16_fwd(const void* qkv16, const void* pk16, const void* pv16, const float* addmask, void* ctx16,
-                               float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                               uint64_t offset, hipStream_t st);
-int mtvaf_prefix_attn_bf16_bwd_tail(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16, const float* addmask,
-                                    const void* ctx16, const float* lse, void* dqkv16, float* dpk, float* dpv, float* partq,
-                                    float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                                    uint64_t offset, int zero_tail, hipStream_t st);
-int mtvaf_prefix_attn_bf16_bwd(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16,
-                               const float* addmask, const void* ctx16, const float* lse, void* dqkv16, float* dpk,
-                               float* dpv, float* partq, float* partkv, int B, int S, int P, int NH, int head_dim,
-                               float p_drop, uint64_t seed, uint64_t offset, hipStream_t st);
-int mtvaf_prefix_attn_varlen_fwd(const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows, float* ctx,
-                                 float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
-                                 hipStream_t st);
-int mtvaf_prefix_attn_varlen_bwd(const float* dctx, const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
-                                 const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv, int B, int S,
-                                 int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st);
-int mtvaf_prefix_attn_varlen_fwd_planes(const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows, float* ctx,
-                                        float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                                        uint64_t offset, void* ctx_planes, int rows, hipStream_t st);
-int mtvaf_prefix_attn_varlen_bwd_planes(const float* dctx, const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
-                                        const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv, int B,
-                                        int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
-                                        void* dqkv_planes, int rows, hipStream_t st);
-int mtvaf_zero_f32(float* p, long n, hipStream_t st);
-int mtvaf_gemm_f32p(int layout_a, const void* Aplanes, long a_plane, long a_row, long a_kt, long a_col, int layout_b, const void* Bplanes,
-                    long b_plane, long b_row, long b_kt, long b_col, float* C, int ldc, int M, int N, int K, const float* bias, int epi,
-                    float* aux, int ldaux, int accumulate, int splits, void* workspace, size_t workspace_bytes, int ablate,
-                    hipStream_t stream);
-int mtvaf_gemm_f32p_slabs(int layout_a, const void* Aplanes, long a_plane, long a_row, long a_kt, long a_col, int layout_b, const void* Bplanes,
-                          long b_plane, long b_row, long b_kt, long b_col, float* C, int ldc, int M, int N, int K, const float* bias,
-                          int accumulate, int splits, void* workspace, size_t workspace_bytes, int* splits_out, hipStream_t stream);
-int mtvaf_gemm_f32p_ep(int layout_a, const void* Aplanes, long a_plane, long a_row, long a_kt, long a_col, int layout_b, const void* Bplanes,
-                       long b_plane, long b_row, long b_kt, long b_col, float* C, int ldc, void* c_planes, float* colpart, int M, int N, int K,
-                       const float* bias, int epi, float* aux, int ldaux, int accumulate, hipStream_t stream);
-int mtvaf_gemm_f32p_dw_group(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C, const int* ldc,
-                             const int* M, const int* N, int K, hipStream_t stream);
-int mtvaf_gemm_f32p_dw_group_colsum(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C,
-                                    const int* ldc, const int* M, const int* N, int K, int njobs, const float* const* cs_src,
-                                    const int* cs_rows, const int* cs_cols, const int* cs_ld, float* const* cs_dst, hipStream_t stream);
-size_t mtvaf_ln_bwd_workspace_bytes(int M, int H);
-int mtvaf_gemm_f32_ktiles(int layout_a, int layout_b, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                          int M, int N, int K, const float* bias, int epi, float* aux, int ldaux, int accumulate,
-                          int allow_split, void* workspace, size_t workspace_bytes, int cfg, int splits, const int* klist,
-                          const int* kcnt, hipStream_t stream);
-int mtvaf_prefix_attn_bf16_varlen_fwd(const void* qkv16, const void* pk16, const void* pv16, const int* cu, int pad_rows, void* ctx16,
-                                      float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                                      uint64_t offset, hipStream_t st);
-int mtvaf_prefix_attn_bf16_varlen_bwd(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16, const int* cu,
-                                      int pad_rows, const void* ctx16, const float* lse, void* dqkv16, float* dpk, float* dpv, float* partq,
-                                      float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                                      uint64_t offset, hipStream_t st);
-int mtvaf_dropout_res_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* out,
-                             float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
-                             uint64_t offset, void* out_bf16, hipStream_t st);
-int mtvaf_dropout_res_ln_bwd_rows(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
-                                  const float* rstd, float* dx, float* dres, int dres_accumulate, int M, int H, double p_drop,
-                                  uint64_t seed, uint64_t offset, float* part, void* dx_bf16, hipStream_t st);
-int mtvaf_dropout_res_ln_bwd_finish(const float* part, int M, int H, float* dgamma, float* dbeta, float* dbias_x, int accumulate,
-                                    hipStream_t st);
-int mtvaf_gemm_f32_slabs(int layout_a, int layout_b, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N,
-                         int K, const float* bias, int accumulate, void* workspace, size_t workspace_bytes, int* splits_out,
-                         hipStream_t stream);
-int mtvaf_dropout_res_ln_fwd_slabs(const float* slabs, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                   const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
-                                   uint64_t seed, uint64_t offset, void* out_bf16, hipStream_t st);
-int mtvaf_dropout_res_ln_bwd_rows_slabs(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
-                                        const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                        int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
-                                        void* dx_bf16, hipStream_t st);
-int mtvaf_dropout_res_ln_fwd_planes(const float* x, int nslab, const float* bias, float* x_out, const float* res, const float* gamma,
-                                    const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop,
-                                    uint64_t seed, uint64_t offset, void* out_planes, hipStream_t st);
-int mtvaf_dropout_res_ln_bwd_rows_planes(const float* dout_base, const float* slabs, int nslab, const float* x, const float* res,
-                                         const float* gamma, const float* mean, const float* rstd, float* dx, float* dres,
-                                         int dres_accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset, float* part,
-                                         void* dx_planes, hipStream_t st);
-int mtvaf_dropout_res_ln_bwd(const float* dout, const float* x, const float* res, const float* gamma, const float* mean,
-                             const float* rstd, float* dx, float* dres, int dres_accumulate, float* dgamma, float* dbeta,
-                             float* dbias_x, int accumulate, int M, int H, double p_drop, uint64_t seed, uint64_t offset,
-                             void* workspace, size_t workspace_bytes, void* dx_bf16, hipStream_t st);
-}
-
 namespace mtvaf {
-enum { X_KC = 0, X_KM = 1 };
-enum { X_EPI_NONE = 0, X_EPI_GELU = 1, X_EPI_DGELU = 3 };
-
 // events that order the second stream behind the main one: recycled ring (a wait captures the record that precedes it)
 static hipEvent_t g_ev[64];
 static int g_ev_n = 0, g_ev_i = 0;
@@ -208,59 +87,6 @@ static int p16(int lb, const void* Ap, const void* Wp, float* C, int ldc, int M,
 
 extern "C" {
 
-// One encoder layer.  `bf16` selects the kernel family: 0 = fp32 (qkv / cx / pre / act are float*, weights w*, prefix pk /
-// pv float*), 1 = mixed precision (those four are bf16, weights w*_h bf16 images, x_h / h1_h / h2_h bf16 copies, prefix
-// bf16).  Dropout sites of the layer: attention `offset`, attention-output `offset + 1`, FFN-output `offset + 2`.
-struct mtvaf_layer_t {
-  int B, S, P, NH, H, I;
-  int bf16;
-  float eps;
-  double p_hidden;                             // (a double: the LayerNorm sites scale kept elements by float(1 / (1 - p)), as torch)
-  float p_attn;
-  uint64_t seed, offset;
-  const float *wqkv, *wo, *w1, *w2;            // fp32 masters [3H,H] [H,H] [I,H] [H,I] (fp32 mode)
-  const void *wqkv_h, *wo_h, *w1_h, *w2_h;     // bf16 images (bf16 mode)
-  const float *bqkv, *bo, *g1, *b1, *bi1, *bi2, *g2, *b2;
-  const float* x;                              // [M,H] layer input
-  const void* x_h;                             // bf16 copy (bf16 mode)
-  const void *pk, *pv;                         // prefix slabs [B, P*H] or NULL
-  const float* addmask;                        // [B, P+S]
-  void *qkv, *cx;                              // [M,3H], [M,H]
-  float *lse, *a, *h1;                         // [B,NH,S], [M,H], [M,H]
-  void* h1_h;
-  float *mean1, *rstd1;
-  void *pre, *act;                             // [M,I]
-  float *f, *h2;                               // [M,H]
-  void* h2_h;
-  float *mean2, *rstd2;
-  void* ws; size_t ws_bytes;                   // main-stream scratch of the forward pass (split-K slabs of small-M products)
-  const int* cu;                               // padding-free execution: [B+1] row offsets of the PACKED token tensors, or NULL
-  int Mv, Mp;                                  // valid rows, rows of the packed image (Mv rounded up to whole 128-row tiles)
-  const void* x_p;                             // fp32 mode, pre-split operands (round 5): tile-blocked plane image of x, or NULL
-  void *cx_p, *h1_p, *act_p, *h2_p;            // ... and of cx / h1 / act / h2 (written by the forward; h2_p may be NULL)
-};
-
-struct mtvaf_layer_grads_t {
-  float* dh;                                   // in: d/d h2, out: d/d x  [M,H]
-  float* dh1;                                  // [M,H] scratch
-  void *df, *dpre, *da, *dctx, *dqkv;          // [M,H] [M,I] [M,H] [M,H] [M,3H]  (bf16 in bf16 mode)
-  float *part, *partq, *partkv;                // bf16 mode: [M/128, I], [B*ceil(S/64), H], [B*ceil((P+S)/64), 2H]
-  float* delta;                                // fp32 mode: [B,NH,S]
-  float *dwqkv, *dbqkv, *dwo, *dbo, *dg1, *db1, *dw1, *dbi1, *dw2, *dbi2, *dg2, *db2;
-  float *dpk, *dpv;                            // [B, P*H] or NULL
-  void* ws_main; size_t ws_main_bytes;         // scratch of the main stream (LayerNorm partials, split-K slabs)
-  void* ws_side; size_t ws_side_bytes;         // scratch of the second stream (split-K slabs, column-sum partials)
-  const int* klist;                            // optional: k-tile list of the token axis for the dW products (32-row tiles in fp32 mode, 64 in bf16)
-  const int* kcnt;
-  int zero_tail;                               // the caller's word: token rows behind a sentence's last unmasked position carry exactly-zero
-                                               // gradients (what a k-tile list implies): attention backward stops its query loops there
-  float *lnpart2, *lnpart1;                    // optional (both or neither; required with plane images): per-layer LayerNorm-backward
-                                               // partials of the FFN / attention block (mtvaf_ln_bwd_workspace_bytes each) -- their column
-                                               // sums then run on `side`
-  void *df_p, *dpre_p, *da_p, *dqkv_p;         // pre-split operands: scratch plane images of df / dpre / da / dqkv (with `part`, both
-                                               // lnpart and ws_main: required when the layer struct has plane images), or NULL
-};
-
 // fp32 mode with pre-split operands: every plane image present, packed rows (whole 128-row tiles), whole 128-column tiles
 // p16 whose result leaves as a plane image (and per-tile column sums), no fp32 copy (mtvaf_gemm_f32p_ep)
 static int p16_ep(int lb, const void* Ap, const void* Wp, void* Cp, float* colpart, int M, int N, int K, const float* bias, int epi, float* aux,
@@ -280,7 +106,7 @@ static int dense_ln_fwd_p(const void* Ap, int K, const void* Wp, const float* bi
                           const float* beta, float* out, float* mean, float* rstd, int M, int H, float eps, double p_drop, uint64_t seed,
                           uint64_t offset, void* ws, size_t ws_bytes, void* out_planes, hipStream_t st) {
   int ns = 1;
-  const int rc = p16(0, Ap, Wp, x_out, H, M, H, K, bias, X_EPI_NONE, nullptr, 0, 0, ws, ws_bytes, &ns, st);
+  const int rc = p16(0, Ap, Wp, x_out, H, M, H, K, bias, MTVAF_EPI_NONE, nullptr, 0, 0, ws, ws_bytes, &ns, st);
   if (rc != MTVAF_OK) return rc;
   if (out_planes)  // (the LayerNorm writes the plane image of its output itself)
     return mtvaf_dropout_res_ln_fwd_planes(ns > 1 ? static_cast<const float*>(ws) : x_out, ns > 1 ? ns : 0, bias, x_out, res, gamma, beta, out,
@@ -297,7 +123,7 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
   if (L->cu && (L->Mp <= 0 || L->Mp % 128 || L->Mv <= 0 || L->Mv > L->Mp)) return MTVAF_ERR_ARG;
   const int M = L->cu ? L->Mp : L->B * L->S, H = L->H, I = L->I;
   if (L->bf16) {
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KC, L->x_h, H, L->wqkv_h, H, nullptr, 0, L->qkv, 3 * H, M, 3 * H, H, L->bqkv, X_EPI_NONE,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KC, L->x_h, H, L->wqkv_h, H, nullptr, 0, L->qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE,
                                nullptr, 0, 0, nullptr, 0, nullptr, 0, 0, -1, 0, st));
     if (L->cu) {
       // (the rows that pad the packed image belong to no sentence: an extra slice of the launch zero-fills them)
@@ -307,13 +133,13 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
       MTVAF_TRY(mtvaf_prefix_attn_bf16_fwd(L->qkv, L->pk, L->pv, L->addmask, L->cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn,
                                            L->seed, L->offset, st));
     }
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KC, L->cx, H, L->wo_h, H, L->a, H, nullptr, 0, M, H, H, L->bo, X_EPI_NONE, nullptr, 0, 0,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KC, L->cx, H, L->wo_h, H, L->a, H, nullptr, 0, M, H, H, L->bo, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, st));
     MTVAF_TRY(mtvaf_dropout_res_ln_fwd(L->a, L->x, L->g1, L->b1, L->h1, L->mean1, L->rstd1, M, H, L->eps, L->p_hidden, L->seed,
                                        L->offset + 1, L->h1_h, st));
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KC, L->h1_h, H, L->w1_h, H, nullptr, 0, L->act, I, M, I, H, L->bi1, X_EPI_GELU, L->pre, I, 0,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KC, L->h1_h, H, L->w1_h, H, nullptr, 0, L->act, I, M, I, H, L->bi1, MTVAF_EPI_GELU, L->pre, I, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, st));
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KC, L->act, I, L->w2_h, I, L->f, H, nullptr, 0, M, H, I, L->bi2, X_EPI_NONE, nullptr, 0, 0,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KC, L->act, I, L->w2_h, I, L->f, H, nullptr, 0, M, H, I, L->bi2, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, st));
     MTVAF_TRY(mtvaf_dropout_res_ln_fwd(L->f, L->h1, L->g2, L->b2, L->h2, L->mean2, L->rstd2, M, H, L->eps, L->p_hidden, L->seed,
                                        L->offset + 2, L->h2_h, st));
@@ -327,20 +153,20 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
     // pre-split operands (round 5): the same layer on the kernels of csrc/gemm_f32p.hip; every GEMM operand is read as a plane
     // image -- weights written once per optimizer step, activations by the kernel that produces them (the attention forward, the
     // LayerNorms and the FFN-1 epilogue write plane images themselves)
-    MTVAF_TRY(p16(0, L->x_p, L->wqkv_h, qkv, 3 * H, M, 3 * H, H, L->bqkv, X_EPI_NONE, nullptr, 0, 0, L->ws, L->ws_bytes, nullptr, st));
+    MTVAF_TRY(p16(0, L->x_p, L->wqkv_h, qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE, nullptr, 0, 0, L->ws, L->ws_bytes, nullptr, st));
     MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_planes(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
                                                   L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset,
                                                   L->cx_p, M, st));
     MTVAF_TRY(dense_ln_fwd_p(L->cx_p, H, L->wo_h, L->bo, L->a, L->x, L->g1, L->b1, L->h1, L->mean1, L->rstd1, M, H, L->eps, L->p_hidden,
                              L->seed, L->offset + 1, L->ws, L->ws_bytes, L->h1_p, st));
     // (the GELU output is read by GEMMs only: it leaves the FFN-1 epilogue as a plane image, no fp32 copy -- L->act is not read)
-    MTVAF_TRY(p16_ep(0, L->h1_p, L->w1_h, L->act_p, nullptr, M, I, H, L->bi1, X_EPI_GELU, pre, I, st));
+    MTVAF_TRY(p16_ep(0, L->h1_p, L->w1_h, L->act_p, nullptr, M, I, H, L->bi1, MTVAF_EPI_GELU, pre, I, st));
     MTVAF_TRY(dense_ln_fwd_p(L->act_p, I, L->w2_h, L->bi2, L->f, L->h1, L->g2, L->b2, L->h2, L->mean2, L->rstd2, M, H, L->eps, L->p_hidden,
                              L->seed, L->offset + 2, L->ws, L->ws_bytes, L->h2_p, st));
     return MTVAF_OK;
   }
   // (plain-bias products may use the deterministic split-K: the planner only splits when the tile grid underfills the chip)
-  MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KC, L->x, H, L->wqkv, H, qkv, 3 * H, M, 3 * H, H, L->bqkv, X_EPI_NONE, nullptr, 0, 0, 1, L->ws,
+  MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KC, L->x, H, L->wqkv, H, qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE, nullptr, 0, 0, 1, L->ws,
                            L->ws_bytes, -1, -1, st));
   if (L->cu) {
     // the rows that pad the packed image belong to no sentence: an extra slice of the launch zero-fills them (0 x NaN of an
@@ -353,7 +179,7 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
   }
   MTVAF_TRY(dense_ln_fwd(cx, H, L->wo, L->bo, L->a, L->x, L->g1, L->b1, L->h1, L->mean1, L->rstd1, M, H, L->eps, L->p_hidden, L->seed,
                          L->offset + 1, L->ws, L->ws_bytes, st));
-  MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KC, L->h1, H, L->w1, H, act, I, M, I, H, L->bi1, X_EPI_GELU, pre, I, 0, 1, L->ws, L->ws_bytes, -1, -1, st));
+  MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KC, L->h1, H, L->w1, H, act, I, M, I, H, L->bi1, MTVAF_EPI_GELU, pre, I, 0, 1, L->ws, L->ws_bytes, -1, -1, st));
   MTVAF_TRY(dense_ln_fwd(act, I, L->w2, L->bi2, L->f, L->h1, L->g2, L->b2, L->h2, L->mean2, L->rstd2, M, H, L->eps, L->p_hidden, L->seed,
                          L->offset + 2, L->ws, L->ws_bytes, st));
   return MTVAF_OK;
@@ -378,7 +204,6 @@ int mtvaf_dw_group_rows(int rows) {
 // UNSPLIT launch of the wave-specialised split kernel's GROUP form when every product is whole 128 x 128 tiles (432 tiles at
 // BERT-base: 1.7 rounds of the CUs; MTVAF_X3_DW_GROUP=0 keeps one launch + one slab reduction per product).  The Python
 // orchestration asks the same function.
-int mtvaf_f32_split(int on);
 int mtvaf_dw_group_wanted(int rows, int H, int I) {
   static const int x3_group = [] { const char* e = getenv("MTVAF_X3_DW_GROUP"); return e ? atoi(e) : 1; }();
   if (rows <= 0 || rows % 32 || H % 128 || I % 128) return 0;
@@ -416,21 +241,21 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     const bool grp = mtvaf_streamk_attached(side) > 0 && !g->klist && M % 256 == 0 && H % 256 == 0 && I % 256 == 0;
     MTVAF_TRY(ln_bwd_forked(g->dh, L->f, L->h1, L->g2, L->mean2, L->rstd2, nullptr, g->dh1, g->dg2, g->db2, g->dbi2, M, H, L->p_hidden,
                             L->seed, L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, g->df, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(X_KM, X_KM, g->df, H, L->act, I, g->dw2, I, nullptr, 0, H, I, M, nullptr, X_EPI_NONE, nullptr, 0, 0,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->df, H, L->act, I, g->dw2, I, nullptr, 0, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KM, g->df, H, L->w2_h, I, nullptr, 0, g->dpre, I, M, I, H, nullptr, X_EPI_DGELU, L->pre, I, 0,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->df, H, L->w2_h, I, nullptr, 0, g->dpre, I, M, I, H, nullptr, MTVAF_EPI_DGELU, L->pre, I, 0,
                                g->part, 0, nullptr, 0, 0, -1, 0, mainS));
     MTVAF_TRY(fork_to(mainS, side));
     MTVAF_TRY(mtvaf_colsum_small(g->part, M / 128, I, g->dbi1, 0, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(X_KM, X_KM, g->dpre, I, L->h1_h, H, g->dw1, H, nullptr, 0, I, H, M, nullptr, X_EPI_NONE, nullptr, 0, 0,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->dpre, I, L->h1_h, H, g->dw1, H, nullptr, 0, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KM, g->dpre, I, L->w1_h, H, g->dh1, H, nullptr, 0, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->dpre, I, L->w1_h, H, g->dh1, H, nullptr, 0, M, H, I, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1,
                                nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
     MTVAF_TRY(ln_bwd_forked(g->dh1, L->a, L->x, L->g1, L->mean1, L->rstd1, nullptr, g->dh, g->dg1, g->db1, g->dbo, M, H, L->p_hidden,
                             L->seed, L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, g->da, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(X_KM, X_KM, g->da, H, L->cx, H, g->dwo, H, nullptr, 0, H, H, M, nullptr, X_EPI_NONE, nullptr, 0, 0,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->da, H, L->cx, H, g->dwo, H, nullptr, 0, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KM, g->da, H, L->wo_h, H, nullptr, 0, g->dctx, H, M, H, H, nullptr, X_EPI_NONE, nullptr, 0, 0,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->da, H, L->wo_h, H, nullptr, 0, g->dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
     if (L->cu) {
       MTVAF_TRY(mtvaf_prefix_attn_bf16_varlen_bwd(g->dctx, L->qkv, L->pk, L->pv, L->cu, L->Mp - L->Mv, L->cx, L->lse, g->dqkv, g->dpk,
@@ -443,7 +268,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     MTVAF_TRY(fork_to(mainS, side));
     MTVAF_TRY(mtvaf_colsum_small(g->partq, B * ((S + 63) / 64), H, g->dbqkv, 0, side));
     MTVAF_TRY(mtvaf_colsum_small(g->partkv, B * ((P + S + 63) / 64), 2 * H, g->dbqkv + H, 0, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(X_KM, X_KM, g->dqkv, 3 * H, L->x_h, H, g->dwqkv, H, nullptr, 0, 3 * H, H, M, nullptr, X_EPI_NONE,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->dqkv, 3 * H, L->x_h, H, g->dwqkv, H, nullptr, 0, 3 * H, H, M, nullptr, MTVAF_EPI_NONE,
                                nullptr, 0, 0, nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     if (grp) {
       const void* const As[4] = {g->df, g->dpre, g->da, g->dqkv};
@@ -453,7 +278,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       const int Ms[4] = {H, I, H, 3 * H}, Ns[4] = {I, H, H, H};
       MTVAF_TRY(mtvaf_gemm_bf16x_dw_group(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, side));
     }
-    MTVAF_TRY(mtvaf_gemm_bf16x(X_KC, X_KM, g->dqkv, 3 * H, L->wqkv_h, H, g->dh, H, nullptr, 0, M, H, 3 * H, nullptr, X_EPI_NONE,
+    MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->dqkv, 3 * H, L->wqkv_h, H, g->dh, H, nullptr, 0, M, H, 3 * H, nullptr, MTVAF_EPI_NONE,
                                nullptr, 0, 1, nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
   } else {
     float* df = static_cast<float*>(g->df);
@@ -474,13 +299,13 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh, nullptr, 0, L->f, L->h1, L->g2, L->mean2, L->rstd2, nullptr, g->dh1, 0, M, H,
                                                      L->p_hidden, L->seed, L->offset + 2, g->lnpart2, g->df_p, mainS));
       // (dpre is also summed over its rows for the FFN-1 bias gradient: per-tile sums from the epilogue)
-      MTVAF_TRY(p16_ep(1, g->df_p, L->w2_h, g->dpre_p, g->part, M, I, H, nullptr, X_EPI_DGELU, pre, I, mainS));
+      MTVAF_TRY(p16_ep(1, g->df_p, L->w2_h, g->dpre_p, g->part, M, I, H, nullptr, MTVAF_EPI_DGELU, pre, I, mainS));
       int ns1 = 1;  // (the LayerNorm's partials have buffers of their own: the product's split-K slabs stay in ws_main for it)
-      MTVAF_TRY(p16(1, g->dpre_p, L->w1_h, g->dh1, H, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
+      MTVAF_TRY(p16(1, g->dpre_p, L->w1_h, g->dh1, H, M, H, I, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
       MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_planes(g->dh1, static_cast<const float*>(g->ws_main), ns1 > 1 ? ns1 : 0, L->a, L->x, L->g1,
                                                      L->mean1, L->rstd1, nullptr, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1,
                                                      g->lnpart1, g->da_p, mainS));
-      MTVAF_TRY(p16(1, g->da_p, L->wo_h, dctx, H, M, H, H, nullptr, X_EPI_NONE, nullptr, 0, 0, g->ws_main, g->ws_main_bytes, nullptr, mainS));
+      MTVAF_TRY(p16(1, g->da_p, L->wo_h, dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, g->ws_main, g->ws_main_bytes, nullptr, mainS));
       MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_planes(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
                                                     L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
                                                     L->seed, L->offset, g->dqkv_p, M, mainS));
@@ -509,7 +334,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
         if (nj > 0) MTVAF_TRY(mtvaf_gemm_f32p_dw_group_colsum(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, nj, js, jr, jc, jl, jd, side));
         else MTVAF_TRY(mtvaf_gemm_f32p_dw_group(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, side));
       }
-      MTVAF_TRY(p16(1, g->dqkv_p, L->wqkv_h, g->dh, H, M, H, 3 * H, nullptr, X_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, nullptr,
+      MTVAF_TRY(p16(1, g->dqkv_p, L->wqkv_h, g->dh, H, M, H, 3 * H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, nullptr,
                     mainS));
       if (settle) MTVAF_TRY(fork_to(mainS, side));
       return MTVAF_OK;
@@ -517,22 +342,22 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     const bool grp = mtvaf_dw_group_wanted(M, H, I) != 0;
     MTVAF_TRY(ln_bwd_forked(g->dh, L->f, L->h1, L->g2, L->mean2, L->rstd2, df, g->dh1, g->dg2, g->db2, g->dbi2, M, H, L->p_hidden, L->seed,
                             L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(X_KM, X_KM, df, H, act, I, g->dw2, I, H, I, M, nullptr, X_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, df, H, act, I, g->dw2, I, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
-    MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KM, df, H, L->w2, I, dpre, I, M, I, H, nullptr, X_EPI_DGELU, pre, I, 0, 1, g->ws_main, g->ws_main_bytes, -1, -1,
+    MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, df, H, L->w2, I, dpre, I, M, I, H, nullptr, MTVAF_EPI_DGELU, pre, I, 0, 1, g->ws_main, g->ws_main_bytes, -1, -1,
                              mainS));
     MTVAF_TRY(fork_to(mainS, side));
     // (grouped weight gradients: the bias gradients dbi1 / dbqkv come out of that launch -- column sums of the dY tiles it stages)
     if (!grp) MTVAF_TRY(mtvaf_colsum(dpre, M, I, I, g->dbi1, 0, g->ws_side, g->ws_side_bytes, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(X_KM, X_KM, dpre, I, L->h1, H, g->dw1, H, I, H, M, nullptr, X_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dpre, I, L->h1, H, g->dw1, H, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     // (the LayerNorm backward behind this accumulating product adds its split-K slabs itself when its column sums have their
     // own partial buffer -- otherwise its scratch would be the workspace that holds the slabs)
     int ns1 = 1;
     if (g->lnpart1 && side != mainS && g->ws_main) {
-      MTVAF_TRY(mtvaf_gemm_f32_slabs(X_KC, X_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
+      MTVAF_TRY(mtvaf_gemm_f32_slabs(MTVAF_KC, MTVAF_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, 1, g->ws_main, g->ws_main_bytes, &ns1, mainS));
     } else {
-      MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, X_EPI_NONE, nullptr, 0, 1, 1, g->ws_main,
+      MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, dpre, I, L->w1, H, g->dh1, H, M, H, I, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, 1, g->ws_main,
                                g->ws_main_bytes, -1, -1, mainS));
     }
     if (ns1 > 1) {
@@ -544,9 +369,9 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       MTVAF_TRY(ln_bwd_forked(g->dh1, L->a, L->x, L->g1, L->mean1, L->rstd1, da, g->dh, g->dg1, g->db1, g->dbo, M, H, L->p_hidden, L->seed,
                               L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
     }
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(X_KM, X_KM, da, H, cx, H, g->dwo, H, H, H, M, nullptr, X_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, da, H, cx, H, g->dwo, H, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
-    MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KM, da, H, L->wo, H, dctx, H, M, H, H, nullptr, X_EPI_NONE, nullptr, 0, 0, 1, g->ws_main,
+    MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, da, H, L->wo, H, dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_main,
                              g->ws_main_bytes, -1, -1, mainS));
     if (L->cu) {
       MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
@@ -561,7 +386,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     }
     MTVAF_TRY(fork_to(mainS, side));
     if (!grp) MTVAF_TRY(mtvaf_colsum(dqkv, M, 3 * H, 3 * H, g->dbqkv, 0, g->ws_side, g->ws_side_bytes, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(X_KM, X_KM, dqkv, 3 * H, L->x, H, g->dwqkv, H, 3 * H, H, M, nullptr, X_EPI_NONE, nullptr, 0, 0, 1,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dqkv, 3 * H, L->x, H, g->dwqkv, H, 3 * H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1,
                              g->ws_side, g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     if (grp) {
       const float* const As[4] = {df, dpre, da, dqkv};
@@ -573,7 +398,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       MTVAF_TRY(mtvaf_gemm_f32_dw_group_bias(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, g->klist, g->kcnt, dbs, g->ws_side, g->ws_side_bytes, -1,
                                              side));
     }
-    MTVAF_TRY(mtvaf_gemm_f32(X_KC, X_KM, dqkv, 3 * H, L->wqkv, H, g->dh, H, M, H, 3 * H, nullptr, X_EPI_NONE, nullptr, 0, 1, 1,
+    MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, dqkv, 3 * H, L->wqkv, H, g->dh, H, M, H, 3 * H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, 1,
                              g->ws_main, g->ws_main_bytes, -1, -1, mainS));
   }
   if (settle) MTVAF_TRY(fork_to(mainS, side));

@@ -1170,9 +1170,6 @@ size_t mtvaf_gemm_f32_dw_group_workspace_bytes(int n, const int* M, const int* N
   return s > 1 ? (size_t)s * outs * sizeof(float) : 0;
 }
 
-int mtvaf_colsum(const float* x, int rows, int cols, int ld, float* out, int accumulate, void* workspace, size_t workspace_bytes,
-                 hipStream_t st);  // rowops.hip
-
 // dbias (nullable; entries nullable): dbias[i][0 .. M_i) = column sums of A_i over the reduction axis -- the bias gradient of the
 // dense layer whose weight gradient product i is (A_i = its dY).  The unsplit grouped launch of the split kernel takes them
 // from the A tiles it stages anyway (no extra pass over dY, no extra launch); every other plan runs mtvaf_colsum behind the

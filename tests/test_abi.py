@@ -1,16 +1,17 @@
-"""CPU-side ABI checks: the library builds for gfx950, loads, and exports every symbol that
-include/mtvaf_hip.h declares (no compute calls: there is no GPU here)."""
+"""CPU-side ABI checks: the library builds for gfx950, loads, and exports every symbol that include/mtvaf_hip.h declares; the
+ctypes binding (mtvaf_amd/hip.py) agrees with the header in every prototype, both structs and the constants it mirrors; every
+source that defines an entry point is compiled against the header (no compute calls: there is no GPU here)."""
 import ctypes
 import os
 import re
+
+import abi_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared():
-    src = open(os.path.join(ROOT, "include", "mtvaf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mtvaf_[a-z0-9_]+)\s*\(", src)))
+    return sorted(name for _, name, _ in abi_header.prototypes())
 
 
 def test_library_builds_and_exports_header_symbols():
@@ -27,9 +28,65 @@ def test_library_builds_and_exports_header_symbols():
 
 
 def test_binding_matches_header():
+    """Every prototype of the header against hip._SIGS: the same names, and for each the result type and the whole argument
+    list (a type outside abi_header's mapping fails); none is left out."""
     from mtvaf_amd import hip
-    assert set(hip.exported_symbols()) == set(_declared())
+    protos = abi_header.prototypes()
+    names = [name for _, name, _ in protos]
+    assert len(names) == len(set(names)) == len(hip._SIGS)
+    assert set(names) == set(hip.exported_symbols())
+    for res, name, args in protos:
+        want = (abi_header.ctype(res), [abi_header.ctype(t) for t, _ in args])
+        got = hip._SIGS[name]
+        assert (got[0], list(got[1])) == want, (name, res, args)
     hip.lib()  # binds every signature; raises if a symbol is missing
+
+
+def test_struct_mirrors_match_header():
+    """LayerStruct / LayerGradsStruct against mtvaf_layer_t / mtvaf_layer_grads_t: field names, order and types."""
+    from mtvaf_amd import hip
+    structs = abi_header.structs()
+    assert set(structs) == {"mtvaf_layer_t", "mtvaf_layer_grads_t"}
+    for mirror, name in ((hip.LayerStruct, "mtvaf_layer_t"), (hip.LayerGradsStruct, "mtvaf_layer_grads_t")):
+        assert list(mirror._fields_) == [(f, abi_header.ctype(t)) for f, t in structs[name]], name
+
+
+def test_constants_match_header():
+    """What hip.py mirrors of the header's defines: the operand layouts, every epilogue and the error codes."""
+    from mtvaf_amd import hip
+    d = abi_header.defines()
+    assert d["MTVAF_OK"] == 0 and (hip.KC, hip.KM) == (d["MTVAF_KC"], d["MTVAF_KM"])
+    epi = {n[len("MTVAF_"):]: v for n, v in d.items() if n.startswith("MTVAF_EPI_")}
+    assert epi and epi == {n: getattr(hip, n) for n in dir(hip) if n.startswith("EPI_")}
+    err = {v for n, v in d.items() if n.startswith("MTVAF_ERR_")}
+    assert len(err) == 4 and err == set(hip._ERR)
+
+
+def test_every_defining_source_includes_the_header():
+    """The textual include closure (quoted includes, followed through csrc/*.h) of every .hip that defines an mtvaf_* entry
+    reaches include/mtvaf_hip.h: the compiler checks each definition against its public prototype."""
+    from mtvaf_amd.build import CSRC, SOURCES
+
+    def text(path):
+        return re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(path).read(), flags=re.S)
+
+    def closure(path, seen):
+        path = os.path.normpath(path)
+        if path in seen or not os.path.exists(path):
+            return seen
+        seen.add(path)
+        if path != abi_header.HEADER:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text(path), flags=re.M):
+                closure(os.path.join(os.path.dirname(path), inc), seen)
+        return seen
+
+    defined = set()
+    for src in SOURCES:
+        path = os.path.join(CSRC, src)
+        here = set(re.findall(r"\b(?:int|size_t)\s+(mtvaf_\w+)\s*\([^;{}]*\)\s*\{", text(path)))
+        assert not here or abi_header.HEADER in closure(path, set()), f"{src} defines {sorted(here)[:3]} without the public header"
+        defined |= here
+    assert defined == set(_declared())
 
 
 def test_header_compiles_as_c():

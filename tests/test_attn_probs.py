@@ -1,39 +1,24 @@
 """Attention probabilities on request (output_attentions), the part that needs no GPU: the C ABI of the new entry points
 and the two ``args`` switches of the drop-in models."""
 import ctypes
-import os
-import re
 import types
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P, I = ctypes.c_void_p, ctypes.c_int
-
-
-def _prototype(name):
-    src = open(os.path.join(ROOT, "include", "mtvaf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"{name} is not declared in include/mtvaf_hip.h"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
-def _ctype(decl):
-    return P if ("*" in decl or decl.startswith("mtvaf_stream_t")) else I
+import abi_header
 
 
 @pytest.mark.parametrize("name,nargs", [("mtvaf_prefix_attn_probs", 12), ("mtvaf_prefix_attn_mass", 11)])
 def test_header_declares_the_symbol_and_the_binding_matches(name, nargs):
     from mtvaf_amd import hip
-    args = _prototype(name)
-    assert len(args) == nargs, args
+    res, _, args = abi_header.prototype(name)
+    assert res == "int" and len(args) == nargs, args
     assert name in hip.exported_symbols()
     restype, argtypes = hip._SIGS[name]
     assert restype is ctypes.c_int
-    assert list(argtypes) == [_ctype(a) for a in args], (args, argtypes)
+    assert list(argtypes) == abi_header.signature(name)[1], (args, argtypes)
     # B, S, P, NH, head_dim, zero_masked_queries, stream close the list
-    assert [a.split()[-1] for a in args[-7:]] == ["B", "S", "P", "NH", "head_dim", "zero_masked_queries", "stream"]
+    assert [a for _, a in args[-7:]] == ["B", "S", "P", "NH", "head_dim", "zero_masked_queries", "stream"]
 
 
 def test_library_exports_the_symbols():
@@ -45,10 +30,11 @@ def test_library_exports_the_symbols():
 def test_argument_checks_come_before_any_launch():
     """The header's convention: a negative code for head_dim != 64, a null output, non-positive dimensions (host-side tests:
     nothing is launched, so this runs without a GPU)."""
+    from mtvaf_amd import hip
     from mtvaf_amd.build import build_library
     lib = ctypes.CDLL(build_library(verbose=False))
     fn = lib.mtvaf_prefix_attn_probs
-    fn.restype, fn.argtypes = I, [P, P, P, P, P, I, I, I, I, I, I, P]
+    fn.restype, fn.argtypes = hip._SIGS["mtvaf_prefix_attn_probs"]
     x = ctypes.c_void_p(64)  # (never dereferenced: every call below is refused)
     assert fn(x, x, x, x, None, 2, 16, 4, 2, 32, 0, None) < 0      # head_dim
     assert fn(x, x, x, None, None, 2, 16, 4, 2, 64, 0, None) < 0    # probs == NULL
@@ -59,7 +45,7 @@ def test_argument_checks_come_before_any_launch():
     assert fn(x, None, x, x, None, 2, 16, 4, 2, 64, 0, None) < 0    # P > 0 without a prefix slab
     assert fn(x, x, None, x, None, 2, 16, 4, 2, 64, 0, None) < 0    # no mask
     gn = lib.mtvaf_prefix_attn_mass
-    gn.restype, gn.argtypes = I, [P, P, P, P, I, I, I, I, I, I, P]
+    gn.restype, gn.argtypes = hip._SIGS["mtvaf_prefix_attn_mass"]
     assert gn(x, x, x, None, 2, 16, 4, 2, 64, 0, None) < 0          # prefix_mass == NULL
     assert gn(x, x, x, x, 2, 16, 4, 2, 48, 0, None) < 0
 

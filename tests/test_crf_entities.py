@@ -1,19 +1,16 @@
 """CPU side of the tagger-inference tests: the references of tests/crf_entities_cases.py against brute force, the host helpers of
 `mtvaf_amd.metrics`, and the declaration of `mtvaf_crf_entities` (header, ctypes mirror, exported symbol)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import crf_entities_cases as X
 import crf_llh_cases as K
 import crf_wide_cases as W
 import entity_cases as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("case", [(3, 4, 5, 76, (4, 2, 1)), (2, 3, 2, 79, (3, 1)), (1, 6, 3, 80, (6,))])
@@ -105,20 +102,15 @@ def test_entity_device_tables_keep_the_layout_of_entity_tables():
 def test_header_binding_and_export_agree():
     from mtvaf_amd import hip
     from mtvaf_amd.build import build_library
-    src = open(os.path.join(ROOT, "include", "mtvaf_hip.h")).read()
-    m = re.search(r"int mtvaf_crf_entities\((.*?)\);", re.sub(r"/\*.*?\*/", "", src, flags=re.S), flags=re.S)
-    assert m, "mtvaf_crf_entities is not declared in include/mtvaf_hip.h"
-    params = [p.strip() for p in m.group(1).split(",")]
-    kinds = [ctypes.c_void_p if "*" in p or "mtvaf_stream_t" in p else ctypes.c_int for p in params]
     res, args = hip._SIGS["mtvaf_crf_entities"]
-    assert res is ctypes.c_int and list(args) == kinds
-    assert [p.split()[-1].lstrip("*") for p in params] == [
+    assert (res, list(args)) == abi_header.signature("mtvaf_crf_entities") and res is ctypes.c_int
+    assert [name for _, name in abi_header.prototype("mtvaf_crf_entities")[2]] == [
         "emissions", "mask", "tags", "ldt", "keep", "start", "end", "trans", "start_tab", "end_tab", "type_of", "n_types", "ents",
         "log_conf", "count", "B", "S", "C", "max_entities", "stream"]
     assert "mtvaf_crf_entities" in hip.exported_symbols()
     assert hasattr(ctypes.CDLL(build_library(verbose=False)), "mtvaf_crf_entities")
     assert "crf_entities.hip" in __import__("mtvaf_amd.build", fromlist=["SOURCES"]).SOURCES
-    comment = src[src.rfind("/*", 0, src.find("int mtvaf_crf_entities(")):src.find("int mtvaf_crf_entities(")]
+    comment = abi_header.comment_before("mtvaf_crf_entities")
     for word in ("models/bert_model.py:511", "modules/eval_metrics.py::get_chunks", "prefix", "holes"):
         assert word in comment.replace("PREFIX", "prefix"), word
 

@@ -2,18 +2,16 @@
 oracle, the gap of every listed gapped seed, the tie order, and the shape checks of mtvaf_crf_nbest, which answer before any
 launch."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import crf_nbest_cases as N
 from mtvaf_amd.hip import crf_nbest  # (the binding this file is about: absent, nothing below has a subject)
 from oracle import mtvaf_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [c for c in N.CASES + N.GAPPED if c[0] ** c[1] <= 4096]
 
 
@@ -85,10 +83,11 @@ def test_tie_case_order():
 def test_symbols_declared_exported_and_built():
     from mtvaf_amd import hip
     from mtvaf_amd.build import SOURCES, build_library
-    src = open(os.path.join(ROOT, "include", "mtvaf_hip.h")).read()
-    m = re.search(r"int mtvaf_crf_nbest\(([^;]*)\);", src)
-    assert m and "int32_t* n_paths_out" in m.group(1) and "size_t mtvaf_crf_nbest_workspace_bytes(int B, int S, int C, int K);" in src
-    assert len(m.group(1).split(",")) == len(hip._SIGS["mtvaf_crf_nbest"][1]) == 16
+    res, _, args = abi_header.prototype("mtvaf_crf_nbest")
+    assert res == "int" and ("int32_t*", "n_paths_out") in args
+    assert abi_header.prototype("mtvaf_crf_nbest_workspace_bytes") == (
+        "size_t", "mtvaf_crf_nbest_workspace_bytes", [("int", "B"), ("int", "S"), ("int", "C"), ("int", "K")])
+    assert len(args) == len(hip._SIGS["mtvaf_crf_nbest"][1]) == 16
     assert {"mtvaf_crf_nbest", "mtvaf_crf_nbest_workspace_bytes"} <= set(hip.exported_symbols())
     assert "crf_nbest.hip" in SOURCES
     lib = ctypes.CDLL(build_library(verbose=False))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import entity_cases as E
 
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -136,7 +137,7 @@ def test_entity_counts_is_exported_and_rejects_shapes_beyond_its_limits():
     from mtvaf_amd import hip
     assert "mtvaf_entity_counts" in hip.exported_symbols()
     f = hip.lib().mtvaf_entity_counts
-    assert f.argtypes == hip._SIGS["mtvaf_entity_counts"][1]
+    assert f.argtypes == hip._SIGS["mtvaf_entity_counts"][1] == abi_header.signature("mtvaf_entity_counts")[1]
     assert f(None, 513, None, None, None, None, None, None, 2, 513, 11, 4, None, None) == -1   # S = 513
     assert f(None, 16, None, None, None, None, None, None, 2, 16, 65, 4, None, None) == -1     # C = 65
     assert f(None, 15, None, None, None, None, None, None, 2, 16, 11, 4, None, None) == -1     # tags narrower than the labels

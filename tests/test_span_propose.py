@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import span_propose_cases as C
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "span_candidates_ref.npz")
@@ -53,7 +54,7 @@ def test_symbol_exported_and_bound():
     assert "mtvaf_span_propose" in hip.exported_symbols()
     lib = ctypes.CDLL(build_library(verbose=False))
     assert hasattr(lib, "mtvaf_span_propose")
-    assert hip.lib().mtvaf_span_propose.argtypes == hip._SIGS["mtvaf_span_propose"][1]
+    assert hip.lib().mtvaf_span_propose.argtypes == hip._SIGS["mtvaf_span_propose"][1] == abi_header.signature("mtvaf_span_propose")[1]
 
 
 @pytest.mark.parametrize("S,n_best", [(0, 20), (513, 20), (16, 0), (16, 33)])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import span_score_cases as C
 from span_propose_cases import signature
 
@@ -172,7 +173,7 @@ def test_compute_equals_eval_absa_on_the_fixture_counts():
 def test_symbol_exported_and_bound():
     from mtvaf_amd import hip
     assert "mtvaf_span_counts" in hip.exported_symbols()
-    assert hip.lib().mtvaf_span_counts.argtypes == hip._SIGS["mtvaf_span_counts"][1]
+    assert hip.lib().mtvaf_span_counts.argtypes == hip._SIGS["mtvaf_span_counts"][1] == abi_header.signature("mtvaf_span_counts")[1]
     assert "span_score.hip" in __import__("mtvaf_amd.build", fromlist=["SOURCES"]).SOURCES
 
 
