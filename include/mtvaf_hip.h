@@ -906,6 +906,31 @@ int mtvaf_adamw_multi_dev(int count, float* const* p, const float* const* g, flo
                           const long* n, float lr, double beta1, double beta2, float eps, float weight_decay, float bc1,
                           float bc2_sqrt, float grad_scale, const float* clip_state, mtvaf_stream_t stream);
 
+/* ---- an exponential moving average (EMA) of the parameters, kept by the update kernels themselves (new functionality: the
+ * reference trainer keeps none).  mtvaf_adamw_ema / _planes_ema / _multi_ema are the three updates above with one more fp32 buffer
+ * per tensor, `ema` (as long as p, aligned like m and v), and ema_omd = 1 - decay in [0, 1]: after its update every element does
+ *   ema = fmaf(ema_omd, p_new - ema, ema)
+ * -- one more load and one more store (8 bytes per parameter) in the pass that already holds p_new in registers.  ema_omd == 1 makes
+ * the average the new parameter exactly (how a zero-initialised average starts).  p, m, v, the bf16 shadow and the plane images are
+ * the bits of the entry points without `ema`: the average feeds nothing.  clip_state NULL: the host-scalar form; otherwise the
+ * *_dev form, and with clip_state[2] == 0 the average keeps its bits with everything else.  A NULL `ema` or an ema_omd outside
+ * [0, 1]: MTVAF_ERR_ARG.
+ * mtvaf_swap_f32_multi exchanges a[i] and b[i] (n[i] floats each, 4-byte aligned; host arrays of device pointers, any count) bit
+ * for bit -- the parameters against their averages, and back.  A pair whose two sides overlap, a NULL pointer or n[i] <= 0:
+ * MTVAF_ERR_ARG, and nothing is written. */
+int mtvaf_adamw_ema(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                    float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks, float* ema,
+                    float ema_omd, const float* clip_state, mtvaf_stream_t stream);
+int mtvaf_adamw_planes_ema(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                           float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                           const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, float* ema,
+                           float ema_omd, const float* clip_state, mtvaf_stream_t stream);
+int mtvaf_adamw_multi_ema(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                          const long* n, float lr, double beta1, double beta2, float eps, float weight_decay, float bc1,
+                          float bc2_sqrt, float grad_scale, float* const* ema, float ema_omd, const float* clip_state,
+                          mtvaf_stream_t stream);
+int mtvaf_swap_f32_multi(int count, float* const* a, float* const* b, const long* n, mtvaf_stream_t stream);
+
 /* ---- bf16 gradient wire format of the data-parallel exchange (mtvaf_amd/parallel.py; new functionality, the
  * reference never synchronises gradients: MTVAF_training.py:305-309).  pack: dst[i] = bf16(src[i]), zero padding up to
  * npad (npad % 8 == 0); reduce: out[c] = bf16(scale * sum_r recv[r*chunk + c]) with fp32 accumulation in rank order;

@@ -14,6 +14,11 @@
 //   the gradient is scaled by grad_scale * coef, and with finite == 0 the kernel returns before its first load -- p, m, v,
 //   the bf16 shadow and the plane images keep their bits.  Same bodies as the host-scalar forms (a template flag), so with
 //   coef == 1 the results are the same bits.
+//
+//   The *_ema forms (a second template flag, EMA) also keep an exponential moving average of the parameters, on the element they
+//   have just updated:  e = fmaf(ema_omd, p_new - e, e),  ema_omd = 1 - decay  -- one more load and one more store, 8 B per
+//   parameter, instead of an averaging pass of 12 B after the step.  The average feeds nothing: the bf16 shadow and the plane
+//   images are written from p.  EMA == false is the code of the forms above.
 #include "common.h"
 #include "planes.h"
 
@@ -37,12 +42,25 @@ __device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, co
   p -= (h.lr / h.bc1) * (m / denom);
 }
 
+// the average of one element behind its update: explicitly one fma (the difference rounds once, the product and the sum once)
+// (p_new passes through an empty asm: the optimizer sees the update's arithmetic end where it ends without the average, so it
+// pairs and contracts adamw1's operations exactly as in the EMA == false instantiations -- p, m, v stay the same bits)
+__device__ __forceinline__ float ema1(float e, float p_new, float omd) {
+  asm volatile("" : "+v"(p_new));
+  return fmaf(omd, p_new - e, e);
+}
+
+template <bool EMA>
 __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, __bf16* __restrict__ ph, long n, long i0, long stride,
-                                           const AdamHyper& h) {
+                                           float* __restrict__ v, float* __restrict__ e, float ema_omd, __bf16* __restrict__ ph,
+                                           long n, long i0, long stride, const AdamHyper& h) {
   // vector body: 4 floats per lane per iteration when every base is 16-byte aligned (views into packed parameter
   // storage may not be), scalar otherwise and for the tail
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && (!ph || ((uintptr_t)ph & 7) == 0);
+  // the average has an alignment test of its own: float4 accesses only on a 16-byte base.  It does not move p, g, m, v to the scalar
+  // body -- the two bodies contract adamw1 differently in some instantiations, and an average must never change the update's bits --
+  // so an average that alone is off the boundary is read and written element by element inside the vector body
+  const bool evec = EMA && (((uintptr_t)e & 15) == 0);
   const long n4 = vec ? (n >> 2) : 0;
   for (long i = i0; i < n4; i += stride) {
     // non-temporal streams: 28 bytes per parameter pass through once per step -- keeping them out of L2 / Infinity Cache
@@ -60,6 +78,20 @@ __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* _
     reinterpret_cast<f32x4*>(p)[i] = P;  // (read again by the next forward pass)
     __builtin_nontemporal_store(M, reinterpret_cast<f32x4*>(m) + i);
     __builtin_nontemporal_store(V, reinterpret_cast<f32x4*>(v) + i);
+    if constexpr (EMA) {  // (touched once per step, like the moments)
+      if (evec) {
+        f32x4 E = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(e) + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) E[j] = ema1(E[j], P[j], ema_omd);
+        __builtin_nontemporal_store(E, reinterpret_cast<f32x4*>(e) + i);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float* ej = e + 4 * i + j;
+          __builtin_nontemporal_store(ema1(__builtin_nontemporal_load(ej), P[j], ema_omd), ej);
+        }
+      }
+    }
     if (ph) {
       typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
       bf16x4 o = {(__bf16)P.x, (__bf16)P.y, (__bf16)P.z, (__bf16)P.w};
@@ -70,6 +102,9 @@ __device__ __forceinline__ void adamw_span(float* __restrict__ p, const float* _
     float P = p[i], M = m[i], V = v[i];
     adamw1(P, g[i], M, V, h);
     p[i] = P; m[i] = M; v[i] = V;
+    // (the scalar body -- tails and unaligned views -- reads the parameter it has just stored back: with P itself as an operand
+    // the compiler pairs adamw1's scalar operations differently and p, m, v lose the bits of the EMA == false code)
+    if constexpr (EMA) e[i] = ema1(e[i], *reinterpret_cast<volatile float*>(p + i), ema_omd);
     if (ph) ph[i] = (__bf16)P;
   }
 }
@@ -86,12 +121,19 @@ __device__ __forceinline__ bool clip_apply(AdamHyper& h, const float* __restrict
 
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, __bf16* ph, long n,
                                                     AdamHyper h) {
-  adamw_span(p, g, m, v, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
+  adamw_span<false>(p, g, m, v, nullptr, 0.f, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
 }
 __global__ __launch_bounds__(256) void adamw_dev_kernel(float* p, const float* g, float* m, float* v, __bf16* ph, long n,
                                                         AdamHyper h, const float* clip) {
   if (!clip_apply<true>(h, clip)) return;
-  adamw_span(p, g, m, v, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
+  adamw_span<false>(p, g, m, v, nullptr, 0.f, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
+}
+// the update that also averages; DEV as above (clip is not read without it)
+template <bool DEV>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* p, const float* g, float* m, float* v, float* e, float ema_omd,
+                                                        __bf16* ph, long n, AdamHyper h, const float* clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  adamw_span<true>(p, g, m, v, e, ema_omd, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
 }
 
 // The update of a flat parameter buffer that ALSO rewrites the plane images (planes.h) of up to four row-major matrices inside it
@@ -103,8 +145,10 @@ struct AdamSegs {
   unsigned char* img[4];
   int n;
 };
+template <bool EMA>
 __device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg) {
+                                                  float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4, AdamHyper h,
+                                                  AdamSegs sg) {
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     f32x4 P = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
@@ -120,6 +164,12 @@ __device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const f
     reinterpret_cast<f32x4*>(p)[i] = P;
     __builtin_nontemporal_store(M, reinterpret_cast<f32x4*>(m) + i);
     __builtin_nontemporal_store(V, reinterpret_cast<f32x4*>(v) + i);
+    if constexpr (EMA) {
+      f32x4 E = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(e) + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) E[j] = ema1(E[j], P[j], ema_omd);
+      __builtin_nontemporal_store(E, reinterpret_cast<f32x4*>(e) + i);
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if (s < sg.n && i >= sg.b4[s] && i < sg.e4[s]) {
@@ -132,13 +182,20 @@ __device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const f
 }
 __global__ __launch_bounds__(256) void adamw_planes_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg) {
-  adamw_planes_body(p, g, m, v, n4, h, sg);
+  adamw_planes_body<false>(p, g, m, v, nullptr, 0.f, n4, h, sg);
 }
 __global__ __launch_bounds__(256) void adamw_planes_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                float* __restrict__ v, long n4, AdamHyper h, AdamSegs sg,
                                                                const float* __restrict__ clip) {
   if (!clip_apply<true>(h, clip)) return;
-  adamw_planes_body(p, g, m, v, n4, h, sg);
+  adamw_planes_body<false>(p, g, m, v, nullptr, 0.f, n4, h, sg);
+}
+template <bool DEV>
+__global__ __launch_bounds__(256) void adamw_planes_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4,
+                                                               AdamHyper h, AdamSegs sg, const float* __restrict__ clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  adamw_planes_body<true>(p, g, m, v, e, ema_omd, n4, h, sg);
 }
 
 // several tensors of one parameter group in one launch: blockIdx.x -> (tensor, block within tensor) through a prefix table
@@ -151,19 +208,57 @@ struct AdamMulti {
   long n[ADAM_MAXT];
   int blk0[ADAM_MAXT + 1];
   int count;
+  float* e[ADAM_MAXT];  // the averages (EMA forms only; last, so that the other columns stay where they were)
 };
 
-__device__ __forceinline__ void adamw_multi_body(const AdamMulti& t, const AdamHyper& h) {
+template <bool EMA>
+__device__ __forceinline__ void adamw_multi_body(const AdamMulti& t, const AdamHyper& h, float ema_omd) {
   int k = 0;
   const int b = blockIdx.x;
   while (k + 1 < t.count && b >= t.blk0[k + 1]) ++k;
   const int nb = t.blk0[k + 1] - t.blk0[k];
-  adamw_span(t.p[k], t.g[k], t.m[k], t.v[k], nullptr, t.n[k], (long)(b - t.blk0[k]) * 256 + threadIdx.x, (long)nb * 256, h);
+  adamw_span<EMA>(t.p[k], t.g[k], t.m[k], t.v[k], EMA ? t.e[k] : nullptr, ema_omd, nullptr, t.n[k],
+                  (long)(b - t.blk0[k]) * 256 + threadIdx.x, (long)nb * 256, h);
 }
-__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamMulti t, AdamHyper h) { adamw_multi_body(t, h); }
+__global__ __launch_bounds__(256) void adamw_multi_kernel(AdamMulti t, AdamHyper h) { adamw_multi_body<false>(t, h, 0.f); }
 __global__ __launch_bounds__(256) void adamw_multi_dev_kernel(AdamMulti t, AdamHyper h, const float* clip) {
   if (!clip_apply<true>(h, clip)) return;
-  adamw_multi_body(t, h);
+  adamw_multi_body<false>(t, h, 0.f);
+}
+template <bool DEV>
+__global__ __launch_bounds__(256) void adamw_multi_ema_kernel(AdamMulti t, AdamHyper h, float ema_omd, const float* clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  adamw_multi_body<true>(t, h, ema_omd);
+}
+
+// exchange of up to 48 pairs of fp32 buffers, bit for bit (the parameters against their averages): the prefix table of AdamMulti
+struct SwapMulti {
+  float* a[ADAM_MAXT];
+  float* b[ADAM_MAXT];
+  long n[ADAM_MAXT];
+  int blk0[ADAM_MAXT + 1];
+  int count;
+};
+__global__ __launch_bounds__(256) void swap_multi_kernel(SwapMulti t) {
+  int k = 0;
+  const int blk = blockIdx.x;
+  while (k + 1 < t.count && blk >= t.blk0[k + 1]) ++k;
+  float* __restrict__ a = t.a[k];
+  float* __restrict__ b = t.b[k];
+  const long n = t.n[k];
+  const long i0 = (long)(blk - t.blk0[k]) * 256 + threadIdx.x, stride = (long)(t.blk0[k + 1] - t.blk0[k]) * 256;
+  const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+  const long n4 = vec ? (n >> 2) : 0;
+  for (long i = i0; i < n4; i += stride) {
+    const f32x4 A = reinterpret_cast<const f32x4*>(a)[i], B = reinterpret_cast<const f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = B;
+    reinterpret_cast<f32x4*>(b)[i] = A;
+  }
+  for (long i = (n4 << 2) + i0; i < n; i += stride) {
+    const float A = a[i], B = b[i];
+    a[i] = B;
+    b[i] = A;
+  }
 }
 
 // ---- bf16 gradient wire format ------------------------------------------------------------------------------
@@ -226,16 +321,33 @@ static inline int stream_grid(long work_items) {
   return (int)(b < 1 ? 1 : (b > 256 * 8 ? 256 * 8 : b));  // up to 8 blocks per CU: enough loads in flight for HBM
 }
 
+// what the *_ema entry points add: the average(s) and 1 - decay.  on == false: the entry points without it
+struct EmaArgs {
+  bool on;
+  float* e;          // one buffer (mtvaf_adamw_ema, mtvaf_adamw_planes_ema)
+  float* const* es;  // host array of device pointers (mtvaf_adamw_multi_ema)
+  float omd;
+};
+static const EmaArgs NO_EMA = {false, nullptr, nullptr, 0.f};
+static inline bool ema_omd_ok(float omd) { return omd >= 0.f && omd <= 1.f; }  // (false for NaN)
+
 // The launches behind the entry points: clip == nullptr is the host-scalar form, anything else the *_dev form of the same body.
 static int adamw_launch(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
                         float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
-                        const float* clip, hipStream_t stream) {
+                        const float* clip, const EmaArgs& ema, hipStream_t stream) {
   if (!p || !g || !m || !v || n <= 0) return MTVAF_ERR_ARG;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) return MTVAF_ERR_ALIGN;
+  if (ema.on && (!ema.e || !ema_omd_ok(ema.omd))) return MTVAF_ERR_ARG;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema.e) & 3) return MTVAF_ERR_ALIGN;
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   int grid = stream_grid((n + 3) / 4);
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
-  if (clip)
+  if (ema.on && clip)
+    hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3(grid), dim3(256), 0, stream, p, g, m, v, ema.e, ema.omd,
+                       static_cast<__bf16*>(p_bf16), n, h, clip);
+  else if (ema.on)
+    hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, m, v, ema.e, ema.omd,
+                       static_cast<__bf16*>(p_bf16), n, h, clip);
+  else if (clip)
     hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, static_cast<__bf16*>(p_bf16), n, h, clip);
   else
     hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v,
@@ -247,9 +359,10 @@ static int adamw_launch(float* p, const float* g, float* m, float* v, long n, fl
 static int adamw_planes_launch(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
                                float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
                                const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, const float* clip,
-                               hipStream_t stream) {
+                               const EmaArgs& ema, hipStream_t stream) {
   if (!p || !g || !m || !v || n <= 0 || nseg < 0 || nseg > 4 || (nseg && (!seg_begin || !seg_rows || !seg_cols || !seg_img))) return MTVAF_ERR_ARG;
-  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15)) return MTVAF_ERR_ALIGN;
+  if (ema.on && (!ema.e || !ema_omd_ok(ema.omd))) return MTVAF_ERR_ARG;
+  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema.e) & 15)) return MTVAF_ERR_ALIGN;
   AdamSegs sg = {};
   sg.n = nseg;
   for (int s = 0; s < nseg; ++s) {
@@ -264,7 +377,11 @@ static int adamw_planes_launch(float* p, const float* g, float* m, float* v, lon
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   int grid = stream_grid(n / 4);
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
-  if (clip)
+  if (ema.on && clip)
+    hipLaunchKernelGGL(adamw_planes_ema_kernel<true>, dim3(grid), dim3(256), 0, stream, p, g, m, v, ema.e, ema.omd, n / 4, h, sg, clip);
+  else if (ema.on)
+    hipLaunchKernelGGL(adamw_planes_ema_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, m, v, ema.e, ema.omd, n / 4, h, sg, clip);
+  else if (clip)
     hipLaunchKernelGGL(adamw_planes_dev_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n / 4, h, sg, clip);
   else
     hipLaunchKernelGGL(adamw_planes_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, n / 4, h, sg);
@@ -274,8 +391,9 @@ static int adamw_planes_launch(float* p, const float* g, float* m, float* v, lon
 
 static int adamw_multi_launch(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
                               float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
-                              float grad_scale, const float* clip, hipStream_t stream) {
+                              float grad_scale, const float* clip, const EmaArgs& ema, hipStream_t stream) {
   if (count < 0 || (count && (!p || !g || !m || !v || !n))) return MTVAF_ERR_ARG;
+  if (ema.on && ((count && !ema.es) || !ema_omd_ok(ema.omd))) return MTVAF_ERR_ARG;
   const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale);
   for (int base = 0; base < count; base += ADAM_MAXT) {
     AdamMulti t;
@@ -286,15 +404,52 @@ static int adamw_multi_launch(int count, float* const* p, const float* const* g,
       if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] <= 0) return MTVAF_ERR_ARG;
       if (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3) return MTVAF_ERR_ALIGN;
       t.p[k] = p[i]; t.g[k] = g[i]; t.m[k] = m[i]; t.v[k] = v[i]; t.n[k] = n[i];
+      t.e[k] = nullptr;
+      if (ema.on) {
+        if (!ema.es[i]) return MTVAF_ERR_ARG;
+        if ((uintptr_t)ema.es[i] & 3) return MTVAF_ERR_ALIGN;
+        t.e[k] = ema.es[i];
+      }
       t.blk0[k] = blocks;
       long b = ((n[i] + 3) / 4 + 255) / 256;
       blocks += (int)(b > 1024 ? 1024 : b);
     }
     t.blk0[t.count] = blocks;
-    if (clip)
+    if (ema.on && clip)
+      hipLaunchKernelGGL(adamw_multi_ema_kernel<true>, dim3(blocks), dim3(256), 0, stream, t, h, ema.omd, clip);
+    else if (ema.on)
+      hipLaunchKernelGGL(adamw_multi_ema_kernel<false>, dim3(blocks), dim3(256), 0, stream, t, h, ema.omd, clip);
+    else if (clip)
       hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3(blocks), dim3(256), 0, stream, t, h, clip);
     else
       hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, stream, t, h);
+    MTVAF_LAUNCH_CHECK();
+  }
+  return MTVAF_OK;
+}
+
+static int swap_multi_launch(int count, float* const* a, float* const* b, const long* n, hipStream_t stream) {
+  if (count < 0 || (count && (!a || !b || !n))) return MTVAF_ERR_ARG;
+  // every pair is checked before the first launch: a refused call has written nothing
+  for (int i = 0; i < count; ++i) {
+    if (!a[i] || !b[i] || n[i] <= 0) return MTVAF_ERR_ARG;
+    if (((uintptr_t)a[i] | (uintptr_t)b[i]) & 3) return MTVAF_ERR_ALIGN;
+    const uintptr_t lo_a = (uintptr_t)a[i], lo_b = (uintptr_t)b[i], bytes = (uintptr_t)n[i] * 4;
+    if (lo_a < lo_b + bytes && lo_b < lo_a + bytes) return MTVAF_ERR_ARG;  // the two sides of a pair overlap
+  }
+  for (int base = 0; base < count; base += ADAM_MAXT) {
+    SwapMulti t;
+    t.count = count - base < ADAM_MAXT ? count - base : ADAM_MAXT;
+    int blocks = 0;
+    for (int k = 0; k < t.count; ++k) {
+      const int i = base + k;
+      t.a[k] = a[i]; t.b[k] = b[i]; t.n[k] = n[i];
+      t.blk0[k] = blocks;
+      long nb = ((n[i] + 3) / 4 + 255) / 256;
+      blocks += (int)(nb > 1024 ? 1024 : nb);
+    }
+    t.blk0[t.count] = blocks;
+    hipLaunchKernelGGL(swap_multi_kernel, dim3(blocks), dim3(256), 0, stream, t);
     MTVAF_LAUNCH_CHECK();
   }
   return MTVAF_OK;
@@ -315,7 +470,7 @@ extern "C" {
 int mtvaf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
                 float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
                 hipStream_t stream) {
-  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, nullptr, stream);
+  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, nullptr, NO_EMA, stream);
 }
 
 // mtvaf_adamw with the gradient scaled by grad_scale * clip_state[1] on the device; clip_state[2] == 0: nothing is written.
@@ -324,7 +479,7 @@ int mtvaf_adamw_dev(float* p, const float* g, float* m, float* v, long n, float 
                     const float* clip_state, hipStream_t stream) {
   if (!clip_state) return MTVAF_ERR_ARG;
   if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
-  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, clip_state, stream);
+  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, clip_state, NO_EMA, stream);
 }
 
 // mtvaf_adamw over a flat buffer (n % 4 == 0, 16-byte aligned) that also rewrites the plane images of nseg <= 4 row-major fp32
@@ -334,7 +489,7 @@ int mtvaf_adamw_planes(float* p, const float* g, float* m, float* v, long n, flo
                        float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
                        const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, hipStream_t stream) {
   return adamw_planes_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nseg, seg_begin, seg_rows,
-                             seg_cols, seg_img, max_blocks, nullptr, stream);
+                             seg_cols, seg_img, max_blocks, nullptr, NO_EMA, stream);
 }
 
 // mtvaf_adamw_planes under a device clip state: with clip_state[2] == 0 the plane images keep their bits too.
@@ -345,14 +500,14 @@ int mtvaf_adamw_planes_dev(float* p, const float* g, float* m, float* v, long n,
   if (!clip_state) return MTVAF_ERR_ARG;
   if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
   return adamw_planes_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nseg, seg_begin, seg_rows,
-                             seg_cols, seg_img, max_blocks, clip_state, stream);
+                             seg_cols, seg_img, max_blocks, clip_state, NO_EMA, stream);
 }
 
 // `count` tensors sharing one set of hyper-parameters (a torch parameter group); host arrays of device pointers.
 int mtvaf_adamw_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
                       float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
                       float grad_scale, hipStream_t stream) {
-  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nullptr, stream);
+  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nullptr, NO_EMA, stream);
 }
 
 int mtvaf_adamw_multi_dev(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
@@ -360,7 +515,42 @@ int mtvaf_adamw_multi_dev(int count, float* const* p, const float* const* g, flo
                           float grad_scale, const float* clip_state, hipStream_t stream) {
   if (!clip_state) return MTVAF_ERR_ARG;
   if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
-  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, clip_state, stream);
+  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, clip_state, NO_EMA, stream);
+}
+
+// The three updates with an exponential moving average of the parameters kept in the same pass (see the head of this file):
+// ema / ema[i] as long as p / p[i], ema_omd = 1 - decay in [0, 1] (1: the average becomes the new parameter exactly).  clip_state
+// NULL: the host-scalar form; otherwise the *_dev form -- with clip_state[2] == 0 the average keeps its bits like everything else.
+int mtvaf_adamw_ema(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                    float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks, float* ema,
+                    float ema_omd, const float* clip_state, hipStream_t stream) {
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  const EmaArgs ea = {true, ema, nullptr, ema_omd};
+  return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks, clip_state, ea, stream);
+}
+
+int mtvaf_adamw_planes_ema(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
+                           float weight_decay, float bc1, float bc2_sqrt, float grad_scale, int nseg, const long* seg_begin,
+                           const int* seg_rows, const int* seg_cols, void* const* seg_img, int max_blocks, float* ema, float ema_omd,
+                           const float* clip_state, hipStream_t stream) {
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  const EmaArgs ea = {true, ema, nullptr, ema_omd};
+  return adamw_planes_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, nseg, seg_begin, seg_rows,
+                             seg_cols, seg_img, max_blocks, clip_state, ea, stream);
+}
+
+int mtvaf_adamw_multi_ema(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                          float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                          float grad_scale, float* const* ema, float ema_omd, const float* clip_state, hipStream_t stream) {
+  if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
+  const EmaArgs ea = {true, nullptr, ema, ema_omd};
+  return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, clip_state, ea, stream);
+}
+
+// a[i] <-> b[i], n[i] floats each, bit for bit; host arrays of device pointers, any count (48 pairs per launch).  A pair whose two
+// sides overlap is refused before anything is launched.
+int mtvaf_swap_f32_multi(int count, float* const* a, float* const* b, const long* n, hipStream_t stream) {
+  return swap_multi_launch(count, a, b, n, stream);
 }
 
 int mtvaf_grad_pack_bf16(const float* src, void* dst, long n, long npad, hipStream_t stream) {

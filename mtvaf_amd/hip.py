@@ -157,6 +157,10 @@ _SIGS = {
     "mtvaf_adamw_dev": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, P, I, P, P]),
     "mtvaf_adamw_planes_dev": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P, P]),
     "mtvaf_adamw_multi_dev": (c_int, [I, P, P, P, P, P, F, c_double, c_double, F, F, F, F, F, P, P]),
+    "mtvaf_adamw_ema": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, P, I, P, F, P, P]),
+    "mtvaf_adamw_planes_ema": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P, F, P, P]),
+    "mtvaf_adamw_multi_ema": (c_int, [I, P, P, P, P, P, F, c_double, c_double, F, F, F, F, F, P, F, P, P]),
+    "mtvaf_swap_f32_multi": (c_int, [I, P, P, P, P]),
     "mtvaf_grad_pack_bf16": (c_int, [P, P, L, L, P]),
     "mtvaf_grad_reduce_bf16": (c_int, [P, P, I, L, F, P]),
     "mtvaf_grad_unpack_bf16": (c_int, [P, P, L, P]),
@@ -1449,9 +1453,17 @@ def _clip_ptr(clip):
     return clip.data_ptr()
 
 
-def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, grad_scale=1.0, max_blocks=0, clip=None):
+def _ema_arg(ema, like):
+    """Device pointer of the average an *_ema update keeps: fp32, contiguous, as long as the parameter."""
+    assert ema.is_cuda and ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == like.numel(), (ema.device, ema.dtype,
+                                                                                                                  ema.shape, like.shape)
+    return ema.data_ptr()
+
+
+def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, grad_scale=1.0, max_blocks=0, clip=None, ema=None,
+                 ema_omd=0.0):
     """adamw over a flat buffer that also rewrites the plane images of the matrices inside it: segs = [(begin element, rows, cols,
-    image uint8 tensor), ...] (at most four).  clip: see adamw."""
+    image uint8 tensor), ...] (at most four).  clip, ema, ema_omd: see adamw."""
     _f32(p, g, m, v)
     n = len(segs)
     bc1 = 1.0 - beta1 ** step
@@ -1460,20 +1472,30 @@ def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, gr
             float(bc1), float(bc2_sqrt), float(grad_scale), n, (ctypes.c_long * n)(*[s[0] for s in segs]),
             (ctypes.c_int * n)(*[s[1] for s in segs]), (ctypes.c_int * n)(*[s[2] for s in segs]),
             (ctypes.c_void_p * n)(*[_p(s[3]) for s in segs]), int(max_blocks))
-    if clip is None:
+    if ema is not None:
+        _ck(lib().mtvaf_adamw_planes_ema(*args, _ema_arg(ema, p), float(ema_omd), None if clip is None else _clip_ptr(clip), _st()),
+            "mtvaf_adamw_planes_ema")
+    elif clip is None:
         _ck(lib().mtvaf_adamw_planes(*args, _st()), "mtvaf_adamw_planes")
     else:
         _ck(lib().mtvaf_adamw_planes_dev(*args, _clip_ptr(clip), _st()), "mtvaf_adamw_planes_dev")
 
 
-def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None):
+def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None,
+          ema_omd=0.0):
     """In-place AdamW update of one flat fp32 tensor (torch.optim.AdamW semantics); `step` is the 1-based step count;
     max_blocks > 0: a background update on that many blocks (runs under MFMA-bound kernels without starving them).
     clip: the device state written by grad_clip_finalize -- the gradient is scaled by grad_scale * coef on the device, and a
-    state whose `finite` is 0 makes the launch write nothing."""
+    state whose `finite` is 0 makes the launch write nothing.
+    ema: an fp32 tensor as long as p that the same launch averages the new parameter into, ema += ema_omd * (p_new - ema) with
+    ema_omd = 1 - decay (1: ema becomes p_new exactly); None: the launch without it."""
     n = p.numel()
     bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    if clip is None:
+    if ema is not None:
+        _ck(lib().mtvaf_adamw_ema(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
+                                  _p(p_bf16), int(max_blocks), _ema_arg(ema, p), float(ema_omd),
+                                  None if clip is None else _clip_ptr(clip), _st()), "mtvaf_adamw_ema")
+    elif clip is None:
         _ck(lib().mtvaf_adamw(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
                               _p(p_bf16), int(max_blocks), _st()), "mtvaf_adamw")
     else:
@@ -1481,20 +1503,41 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0,
                                   _p(p_bf16), int(max_blocks), _clip_ptr(clip), _st()), "mtvaf_adamw_dev")
 
 
-def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None):
-    """One launch per 48 tensors of a parameter group sharing hyper-parameters and step count.  clip: see adamw."""
+def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_omd=0.0):
+    """One launch per 48 tensors of a parameter group sharing hyper-parameters and step count.  clip: see adamw; ema: a list of
+    averages parallel to ps (one ema_omd for all of them), None: without."""
     k = len(ps)
     if k == 0:
         return
     arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
     ns = (ctypes.c_long * k)(*[t.numel() for t in ps])
     bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    if clip is None:
+    if ema is not None:
+        assert len(ema) == k
+        es = (ctypes.c_void_p * k)(*[_ema_arg(e, t) for e, t in zip(ema, ps)])
+        _ck(lib().mtvaf_adamw_multi_ema(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
+                                        bc2 ** 0.5, grad_scale, es, float(ema_omd), None if clip is None else _clip_ptr(clip), _st()),
+            "mtvaf_adamw_multi_ema")
+    elif clip is None:
         _ck(lib().mtvaf_adamw_multi(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
                                     bc2 ** 0.5, grad_scale, _st()), "mtvaf_adamw_multi")
     else:
         _ck(lib().mtvaf_adamw_multi_dev(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
                                         bc2 ** 0.5, grad_scale, _clip_ptr(clip), _st()), "mtvaf_adamw_multi_dev")
+
+
+def swap_f32(a_list, b_list):
+    """a_list[i] <-> b_list[i], bit for bit, for fp32 tensors of equal length pair by pair (48 pairs per launch)."""
+    k = len(a_list)
+    assert len(b_list) == k
+    if k == 0:
+        return
+    for a, b in zip(a_list, b_list):
+        assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() \
+            and a.numel() == b.numel(), (a.device, b.device, a.dtype, b.dtype, a.shape, b.shape)
+    _ck(lib().mtvaf_swap_f32_multi(k, (ctypes.c_void_p * k)(*[t.data_ptr() for t in a_list]),
+                                   (ctypes.c_void_p * k)(*[t.data_ptr() for t in b_list]),
+                                   (ctypes.c_long * k)(*[t.numel() for t in a_list]), _st()), "mtvaf_swap_f32_multi")
 
 
 def grad_sqnorm_slots(gs) -> int:

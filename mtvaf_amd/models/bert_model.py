@@ -357,7 +357,9 @@ class TVNetSAModel2(nn.Module):
         label is structural (`mtvaf_amd.metrics.structural_labels`: PAD, X, [CLS], [SEP]), and only those of ``word_mask``
         [B,S] when it is given (e.g. first sub-tokens).  args.entity_scheme ("seqeval" | "reference"), args.max_entities (32).
         -> the dict of `CRF.entities` (tags, lengths, entities, log_confidence, confidence, count) plus ``types``, the type
-        names the entities' type indices refer to; `mtvaf_amd.metrics.entities_to_lists` turns it into Python lists."""
+        names the entities' type indices refer to; `mtvaf_amd.metrics.entities_to_lists` turns it into Python lists.
+        This and the other ``predict_*`` methods read the weights the module holds: to evaluate the averaged weights of a run with
+        ``args.ema_decay``, call them inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         # (an eval pass still reserves dropout offsets: the counter is put back, so a training run draws the same masks with or
         # without predictions in between)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
@@ -851,7 +853,9 @@ class TVNetSAModel(nn.Module):
         ``gold``: dict ``starts, ends, classes, masks`` [B,G], the feature's start_indexes, end_indexes, polarity_labels and
         label_masks.  With ``args.score_spans`` the call then adds the batch's aspect counts to ``self.span_scorer`` (one more
         launch on the same stream, on the word map the proposal read) and the dict also holds pred_class, matched_gold [B,n]
-        int32 (`SpanScorer.update`).  Without ``gold`` or without the switch nothing more is launched."""
+        int32 (`SpanScorer.update`).  Without ``gold`` or without the switch nothing more is launched.
+        The weights read are the ones the module holds: to evaluate the averaged weights of a run with ``args.ema_decay``, call
+        this inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         with torch.no_grad():
             prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, False)
             ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids)

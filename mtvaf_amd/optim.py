@@ -19,11 +19,24 @@ group (the second group looks for the long-gone ``gates``), so the reference nev
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional
 
 import torch
 
 from . import hip
+
+
+def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
+    """Decay of EMA update number ``t`` (0-based: the count of EMA updates already applied to that tensor or layer).
+
+    ``t == 0`` -> 0: on the zero-initialised average ``fmaf(1, p - 0, 0)`` is ``p`` exactly, so the average starts as the
+    parameters after their first update, written by the update kernel on the update's own stream -- no copy.  Then, with
+    ``warmup``, ``min(decay, (1 + t) / (10 + t))`` (the early average follows the weights instead of remembering the
+    initialisation for 1 / (1 - decay) steps); without, ``decay``."""
+    if t <= 0:
+        return 0.0
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
 class AdamW(torch.optim.Optimizer):
@@ -53,12 +66,24 @@ class AdamW(torch.optim.Optimizer):
     ``step()`` issues exactly the launches it always did, and ``skip_nonfinite`` has nothing to act on.  A global norm is not
     known while layers are still being updated inside backward: together with ``overlap=True`` either switch raises.
 
+    ``ema_decay > 0``: every update kernel also keeps an exponential moving average of the parameter it has just written,
+    ``ema += (1 - d) * (p_new - ema)`` with ``d = ema_decay_at(t, ema_decay, ema_warmup)`` -- on every path: the per-layer flat update
+    and its plane-image form, the tensor-by-tensor launches, with and without clipping, and ``overlap=True`` from inside backward.
+    ``state[p]["ema"]`` is the average (an encoder layer's are views of one flat buffer, like ``exp_avg``) and ``state[p]["ema_step"]``
+    the number of updates it has seen, so both travel through ``state_dict()`` / ``load_state_dict()``; a checkpoint written without
+    them starts the average at the next step.  ``ema_decay`` is a setting of the optimizer like ``max_grad_norm``, not of a
+    parameter group: it is not in ``defaults`` and a group cannot override it.  ``swap_ema()`` exchanges the parameters with their
+    averages (and back: bit for bit), ``averaged_parameters()`` does so around a block, ``ema_state_dict(model)`` is the averaged
+    model to save.  While the averages are swapped in (``ema_swapped``) ``step()`` and the backward hook raise.  On a step the
+    non-finite skip drops, the average keeps its bits but ``ema_step`` advances like the step counters (same caveat).  At
+    ``ema_decay == 0`` (default) nothing is allocated and ``step()`` issues the launches it always did.
+
     Checkpoints: ``state_dict()`` / ``load_state_dict()`` are torch.optim's; the flat per-layer moment buffers are
     rebuilt from the loaded per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step`` entries on the first update."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None, max_grad_norm: float = 0.0,
-                 track_grad_norm: bool = False, skip_nonfinite: bool = True):
+                 track_grad_norm: bool = False, skip_nonfinite: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
         max_grad_norm = float(max_grad_norm or 0.0)
@@ -67,6 +92,12 @@ class AdamW(torch.optim.Optimizer):
         if overlap and (max_grad_norm > 0.0 or track_grad_norm):
             raise ValueError("mtvaf_amd.optim.AdamW: max_grad_norm / track_grad_norm need overlap=False -- the global gradient norm "
                              "is not known while layers are still being updated from inside the backward pass")
+        ema_decay = float(ema_decay or 0.0)
+        if not (0.0 <= ema_decay < 1.0):  # (NaN fails both comparisons)
+            raise ValueError("ema_decay must be in [0, 1) (0: no averaged weights)")
+        self.ema_decay = ema_decay
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_swapped = False  # True: the parameters hold the averages, state[p]["ema"] the training weights (swap_ema)
         self.max_grad_norm = max_grad_norm
         self.track_grad_norm = bool(track_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -106,6 +137,9 @@ class AdamW(torch.optim.Optimizer):
                 sink.raw_stream_hook = True  # the update is one library launch on hip._st()
         return self
 
+    def __repr__(self):
+        return super().__repr__() + (f"\n(ema_decay: {self.ema_decay}, ema_warmup: {self.ema_warmup})" if self.ema_decay > 0.0 else "")
+
     def _sink_hook(self, li: int, flat):
         """GradSink.on_layer_done without data parallelism.  flat is None: the pass could not use the flat gradient buffers
         (some .grad pre-existed: gradient accumulation, or two encoder nodes under one backward) -- that layer is left to
@@ -137,8 +171,11 @@ class AdamW(torch.optim.Optimizer):
         if st is None or st["m"].numel() != store.flat.numel() or st["m"].device != store.flat.device:
             st = {"m": torch.zeros_like(store.flat), "v": torch.zeros_like(store.flat), "step": 0,
                   "step_t": torch.zeros((), dtype=torch.float32)}
+            ema = self.ema_decay > 0.0
+            if ema:
+                st["ema"], st["ema_step"], st["ema_step_t"] = torch.zeros_like(store.flat), 0, torch.zeros((), dtype=torch.float32)
             self._flat_state[key] = st
-            steps = set()
+            steps, ema_steps = set(), set()
             for i, p in enumerate(self._encoder.layer[li].ordered_params()):
                 off, n = store.offsets[i], p.numel()
                 ps = self.state[p]
@@ -149,12 +186,23 @@ class AdamW(torch.optim.Optimizer):
                     steps.add(int(ps.get("step", 0)))
                 ps["exp_avg"], ps["exp_avg_sq"] = m_v, v_v
                 ps["step"] = st["step_t"]  # (torch.optim keeps `step` as a tensor too)
+                if ema:
+                    e_v = st["ema"][off:off + n].view(p.shape)
+                    if "ema" in ps:
+                        e_v.copy_(ps["ema"])
+                    ema_steps.add(int(ps.get("ema_step", 0)) if "ema" in ps else 0)  # (a checkpoint without averages: they start now)
+                    ps["ema"], ps["ema_step"] = e_v, st["ema_step_t"]
                 self._param_layer[id(p)] = li
             if len(steps) > 1:
                 raise RuntimeError(f"AdamW: the parameters of encoder layer {li} carry different step counts {sorted(steps)}")
+            if len(ema_steps) > 1:
+                raise RuntimeError(f"AdamW: the parameters of encoder layer {li} carry different EMA update counts {sorted(ema_steps)}")
             if steps:
                 st["step"] = steps.pop()
                 st["step_t"].fill_(st["step"])
+            if ema_steps:
+                st["ema_step"] = ema_steps.pop()
+                st["ema_step_t"].fill_(st["ema_step"])
         return st
 
     def load_state_dict(self, state_dict):
@@ -163,6 +211,82 @@ class AdamW(torch.optim.Optimizer):
         self.__dict__["_flat_state"] = {}
         self._param_layer = {}
         self._early = set()
+
+    # -- averaged weights --------------------------------------------------------------------------------------------
+    def _ema_omd(self, t: int) -> float:
+        """1 - decay of EMA update t, in double: the C ABI rounds it to float once."""
+        return float(1.0 - ema_decay_at(t, self.ema_decay, self.ema_warmup))
+
+    def _ema_pairs(self):
+        """-> (parameter side, average side): one pair per encoder layer whose flat buffers hold both, one per remaining tensor."""
+        a, b, seen = [], [], set()
+        flat_state = self.__dict__.get("_flat_state", {})
+        enc = self._encoder
+        if enc is not None and enc._stores is not None:
+            for li, layer in enumerate(enc.layer):
+                st, store = flat_state.get(("layer", li)), enc._stores[li]
+                if st is None or "ema" not in st or not store.valid(layer) or st["ema"].numel() != store.flat.numel():
+                    continue
+                ps = layer.ordered_params()
+                if all(self.state[p].get("ema") is not None and self.state[p]["ema"].data_ptr() == st["ema"].data_ptr() + 4 * store.offsets[i]
+                       for i, p in enumerate(ps)):
+                    a.append(store.flat)
+                    b.append(st["ema"])
+                    seen.update(id(p) for p in ps)
+        for group in self.param_groups:
+            for p in group["params"]:
+                e = self.state[p].get("ema") if p in self.state else None
+                if e is None or id(p) in seen:
+                    continue
+                if not p.is_contiguous() or not e.is_contiguous():
+                    raise RuntimeError("non-contiguous parameter")
+                seen.add(id(p))
+                a.append(p.data)
+                b.append(e)
+        return a, b
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every parameter the optimizer holds an average for with that average, bit for bit (one pair per encoder
+        layer, the rest 48 pairs per launch), and declare the encoder's cached weight images stale.  A second call restores
+        the training weights.  Until then ``ema_swapped`` is True and ``step()`` / the backward hook raise."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("mtvaf_amd.optim.AdamW.swap_ema: the optimizer keeps no averaged weights (ema_decay == 0)")
+        if self._early:
+            raise RuntimeError("mtvaf_amd.optim.AdamW.swap_ema: a backward pass has updated layers and optimizer.step() has not run yet")
+        a, b = self._ema_pairs()
+        hip.swap_f32(a, b)
+        self.ema_swapped = not self.ema_swapped
+        from . import engine
+        engine.invalidate_weight_images()
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """``with optimizer.averaged_parameters(): evaluate(model)`` -- the averages swapped in for the block, the training
+        weights back afterwards, also when the block raises."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self, model: torch.nn.Module) -> Dict[str, torch.Tensor]:
+        """``model.state_dict()`` with every parameter the optimizer averages replaced by (a copy of) its average: the model to
+        ship.  Parameters without an average (frozen ones, the ResNet, anything no step has reached yet) and buffers keep their
+        own values.  While the averages are swapped in the parameters ARE the averages, and that is what is returned."""
+        out = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        if self.ema_swapped:
+            return out
+        for name, p in model.named_parameters():
+            e = self.state[p].get("ema") if p in self.state else None
+            if e is not None and name in out and int(self.state[p].get("ema_step", 0)) > 0:
+                out[name] = e.detach().clone().view(p.shape)
+        return out
+
+    def _refuse_swapped(self, what: str):
+        if self.ema_swapped:
+            raise RuntimeError(f"mtvaf_amd.optim.AdamW: {what} while the averaged weights are swapped in (swap_ema / "
+                               "averaged_parameters): swap the training weights back first")
 
     # an update enqueued from inside the backward pass runs beside MFMA-bound products: on 128 blocks it trickles under
     # them (csrc/optim.hip); below this many token rows a layer's backward is shorter than such an update and it would
@@ -181,6 +305,11 @@ class AdamW(torch.optim.Optimizer):
         st = self._layer_state(li, store)
         st["step"] += 1
         st["step_t"].fill_(st["step"])  # the 16 per-parameter state entries share this 0-dim tensor
+        ema, omd = None, 0.0
+        if "ema" in st:
+            ema, omd = st["ema"], self._ema_omd(st["ema_step"])
+            st["ema_step"] += 1
+            st["ema_step_t"].fill_(st["ema_step"])
         b1, b2 = group["betas"]
         from . import engine
         shadow = engine.shadow_for_update(store.weights)  # bf16 compute mode: the GEMM operand image, written in the same pass
@@ -188,13 +317,14 @@ class AdamW(torch.optim.Optimizer):
         if segs is not None and store.flat.numel() % 4 == 0:
             # fp32 mode, pre-split operands: the weights' plane images are rewritten by the update kernel itself
             hip.adamw_planes(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                             st["step"], segs, max_blocks=self.BACKGROUND_BLOCKS_PLANES if background else 0, clip=clip)
+                             st["step"], segs, max_blocks=self.BACKGROUND_BLOCKS_PLANES if background else 0, clip=clip,
+                             **({} if ema is None else dict(ema=ema, ema_omd=omd)))
             engine.planes_written(store.weights)
             return
         hip.adamw(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
                   st["step"], p_bf16=shadow,
                   max_blocks=(self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0,
-                  clip=clip)
+                  clip=clip, **({} if ema is None else dict(ema=ema, ema_omd=omd)))
         if shadow is not None:
             engine.shadow_written(store.weights)
         engine.planes_rewrite(store.weights)  # (images exist but the fused form does not apply: rebuilt behind the update)
@@ -205,6 +335,7 @@ class AdamW(torch.optim.Optimizer):
         stores = self._encoder._stores
         if self.suspended or group is None or stores is None or stores[li].grad is None:
             return
+        self._refuse_swapped("a backward pass that updates the encoder layers (overlap=True) ran")
         if li in self._early:
             raise RuntimeError("mtvaf_amd.optim.AdamW(overlap=True): a second backward pass ran before optimizer.step()")
         # (the sink that is calling us: `encoder.grad_sink` would re-validate all twelve layer stores on each of the twelve calls --
@@ -237,7 +368,9 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._refuse_swapped("step() was called")
         clipping = self.max_grad_norm > 0.0 or self.track_grad_norm
+        ema_on = self.ema_decay > 0.0
         if clipping and hip.STREAM_OVERRIDE is not None:
             raise RuntimeError("mtvaf_amd.optim.AdamW: step() with max_grad_norm / track_grad_norm was called from inside a backward "
                                "hook -- the gradient norm would be taken before the pass has produced every gradient")
@@ -263,7 +396,7 @@ class AdamW(torch.optim.Optimizer):
         self._early = set()
         touched = set()  # layers updated tensor by tensor this step: ONE step counter per layer, shared with the flat path
         flat_state = self.__dict__.get("_flat_state", {})
-        group_jobs = []  # (group, step number, [(p, g, exp_avg, exp_avg_sq), ...]): one launch per 48 tensors each
+        group_jobs = []  # (group, (step number, EMA update number), [(p, g, exp_avg, exp_avg_sq, ema), ...]): one launch per 48 tensors each
         for group in self.param_groups:
             buckets: Dict[int, list] = {}
             for p in group["params"]:
@@ -274,22 +407,30 @@ class AdamW(torch.optim.Optimizer):
                 stt = self.state[p]
                 if "exp_avg" not in stt:
                     stt["exp_avg"], stt["exp_avg_sq"], stt["step"] = torch.zeros_like(p), torch.zeros_like(p), 0
+                if ema_on and "ema" not in stt:  # (with exp_avg, or behind a checkpoint written without averages: they start now)
+                    stt["ema"], stt["ema_step"] = torch.zeros_like(p), 0
                 li = self._param_layer.get(id(p))
                 fst = flat_state.get(("layer", li)) if li is not None else None
+                ema_no = -1
                 if fst is not None and stt["step"] is fst["step_t"]:
                     # moments live in the layer's flat buffers (views): this tensor-by-tensor update advances the layer's counter
                     step_no = fst["step"] + 1
+                    if ema_on:
+                        ema_no = fst["ema_step"]
                     touched.add(li)
                 else:
                     if torch.is_tensor(stt["step"]):
                         stt["step"] = int(stt["step"])
                     stt["step"] += 1
                     step_no = stt["step"]
+                    if ema_on:
+                        ema_no = stt["ema_step"] = int(stt["ema_step"])
+                        stt["ema_step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 if not p.is_contiguous():
                     raise RuntimeError("non-contiguous parameter")
-                buckets.setdefault(step_no, []).append((p, g, stt["exp_avg"], stt["exp_avg_sq"]))
-            group_jobs.extend((group, step_no, items) for step_no, items in buckets.items())
+                buckets.setdefault((step_no, ema_no), []).append((p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
+            group_jobs.extend((group, nos, items) for nos, items in buckets.items())
         clip = None
         if clipping:
             # every gradient about to be applied, each once: a layer's flat gradient buffer stands for its 16 views.  The launches
@@ -299,14 +440,18 @@ class AdamW(torch.optim.Optimizer):
                 clip = self._clip_launch(grads)
         for li, group, store in layer_jobs:
             self._update_layer_flat(li, group, store, clip=clip)
-        for group, step_no, items in group_jobs:
+        for group, (step_no, ema_no), items in group_jobs:
             b1, b2 = group["betas"]
             hip.adamw_multi([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
-                            float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step_no, clip=clip)
+                            float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step_no, clip=clip,
+                            **(dict(ema=[i[4] for i in items], ema_omd=self._ema_omd(ema_no)) if ema_on else {}))
         for li in touched:
             fst = flat_state[("layer", li)]
             fst["step"] += 1
             fst["step_t"].fill_(fst["step"])
+            if ema_on:
+                fst["ema_step"] += 1
+                fst["ema_step_t"].fill_(fst["ema_step"])
         return loss
 
 
@@ -346,6 +491,8 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
     on_gpu = any(p.is_cuda for g in groups for p in g["params"])
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)  # 0: unchanged, the reference does not clip (train.py:620-625)
     track_grad_norm = bool(getattr(args, "track_grad_norm", False))
+    ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)  # 0: unchanged, the reference keeps no averaged weights
+    ema_warmup = bool(getattr(args, "ema_warmup", True))
     if on_gpu:
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
@@ -353,11 +500,14 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         # a global gradient norm exists only once the whole backward pass has ended: clipping / tracking steps after it
         overlap = bool(getattr(args, "overlap_optimizer", True)) and accum == 1 and not (max_grad_norm > 0.0 or track_grad_norm)
         opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
-                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm)
+                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
     else:
         if max_grad_norm > 0.0:
             raise ValueError("build_optimizer: max_grad_norm is implemented by the gfx950 AdamW kernels; the CPU fallback "
                              "(torch.optim.AdamW) would ignore it -- clip with torch.nn.utils.clip_grad_norm_ there")
+        if ema_decay > 0.0:
+            raise ValueError("build_optimizer: ema_decay is implemented by the gfx950 AdamW kernels; the CPU fallback "
+                             "(torch.optim.AdamW) would ignore it")
         opt = torch.optim.AdamW(groups, lr=args.lr)
     sched = linear_schedule_with_warmup(opt, getattr(args, "warmup_ratio", 0.01) * train_num_steps, train_num_steps)
     return opt, sched
