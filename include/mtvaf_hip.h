@@ -931,6 +931,32 @@ int mtvaf_adamw_multi_ema(int count, float* const* p, const float* const* g, flo
                           mtvaf_stream_t stream);
 int mtvaf_swap_f32_multi(int count, float* const* a, float* const* b, const long* n, mtvaf_stream_t stream);
 
+/* ---- lr and weight decay that differ INSIDE one flat buffer (new functionality: the reference trains every parameter of the
+ * encoder with one weight decay, modules/train.py:894-916; the usual BERT fine-tuning recipe exempts biases and LayerNorm weights).
+ * mtvaf_adamw_seg / mtvaf_adamw_planes_seg are mtvaf_adamw / mtvaf_adamw_planes (same update, torch.optim.AdamW's, same reference
+ * lines; bc1, bc2_sqrt, grad_scale, max_blocks as there) over a buffer cut into nseg consecutive segments: segment k is the elements
+ * [seg_end[k-1], seg_end[k]) (from 0 for k == 0) and is updated with seg_lr[k] and seg_wd[k]; beta1, beta2, eps, the bias corrections
+ * and grad_scale belong to the launch.  The three host arrays are read during the call (the table travels in the kernel arguments).
+ * An element gets the bits mtvaf_adamw gives it when run on its segment alone with that segment's lr and weight decay.
+ *   1 <= nseg <= 16; seg_end strictly increasing, seg_end[nseg - 1] == n, every other end a multiple of 4; otherwise MTVAF_ERR_ARG.
+ *   n > 2^33 - 8: MTVAF_ERR_SHAPE.  p, g, m, v (and ema) 16-byte aligned, p_bf16 8-byte; n % 4 may be anything for mtvaf_adamw_seg.
+ * The options of the unsegmented entry points are nullable arguments here, there is no _dev / _ema family:
+ *   clip_state  NULL: host scalars only.  Otherwise the state of mtvaf_grad_clip_finalize: the gradient is scaled by grad_scale *
+ *               clip_state[1], and with clip_state[2] == 0 the launch writes nothing.
+ *   ema         NULL: no average (ema_omd is not read).  Otherwise ema = fmaf(ema_omd, p_new - ema, ema) as in mtvaf_adamw_ema;
+ *               ema_omd outside [0, 1]: MTVAF_ERR_ARG.
+ *   p_bf16      (mtvaf_adamw_seg) NULL or the bf16 shadow of the whole buffer.
+ * mtvaf_adamw_planes_seg also rewrites the plane images of nmat <= 4 matrices inside the buffer, under the conditions of
+ * mtvaf_adamw_planes (n % 4 == 0; mat_begin % 4 == 0, cols % 32 == 0, images 16-byte aligned: MTVAF_ERR_ALIGN / MTVAF_ERR_SHAPE as
+ * there).  A matrix may lie across segment ends.  A refused call launches nothing. */
+int mtvaf_adamw_seg(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const float* seg_lr,
+                    const float* seg_wd, double beta1, double beta2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                    void* p_bf16, int max_blocks, float* ema, float ema_omd, const float* clip_state, mtvaf_stream_t stream);
+int mtvaf_adamw_planes_seg(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const float* seg_lr,
+                           const float* seg_wd, double beta1, double beta2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                           int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols, void* const* mat_img,
+                           int max_blocks, float* ema, float ema_omd, const float* clip_state, mtvaf_stream_t stream);
+
 /* ---- bf16 gradient wire format of the data-parallel exchange (mtvaf_amd/parallel.py; new functionality, the
  * reference never synchronises gradients: MTVAF_training.py:305-309).  pack: dst[i] = bf16(src[i]), zero padding up to
  * npad (npad % 8 == 0); reduce: out[c] = bf16(scale * sum_r recv[r*chunk + c]) with fp32 accumulation in rank order;

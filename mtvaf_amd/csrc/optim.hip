@@ -19,6 +19,12 @@
 //   have just updated:  e = fmaf(ema_omd, p_new - e, e),  ema_omd = 1 - decay  -- one more load and one more store, 8 B per
 //   parameter, instead of an averaging pass of 12 B after the step.  The average feeds nothing: the bf16 shadow and the plane
 //   images are written from p.  EMA == false is the code of the forms above.
+//
+//   The *_seg forms (mtvaf_adamw_seg, mtvaf_adamw_planes_seg) take lr and weight decay per segment of the flat buffer from a table
+//   passed by value -- parameter groups that differ inside an encoder layer, still one launch.  Same adamw1 / ema1; their options
+//   (clip state, average, bf16 shadow) are nullable arguments of one entry point each.
+#include <climits>
+
 #include "common.h"
 #include "planes.h"
 
@@ -196,6 +202,106 @@ __global__ __launch_bounds__(256) void adamw_planes_ema_kernel(float* __restrict
                                                                AdamHyper h, AdamSegs sg, const float* __restrict__ clip) {
   if (!clip_apply<DEV>(h, clip)) return;
   adamw_planes_body<true>(p, g, m, v, e, ema_omd, n4, h, sg);
+}
+
+// ---- segmented forms: lr and weight decay per stretch of the flat buffer (mtvaf_adamw_seg, mtvaf_adamw_planes_seg) -------------
+// A fine-tuning recipe that exempts biases and LayerNorm weights from weight decay puts two parameter groups inside every encoder
+// layer; the layer's flat buffer is then up to 16 consecutive segments with an lr and a weight decay each.  The table travels by
+// value in the kernel arguments (33 dwords: it sits in SGPRs), and every lane picks the segment of the float4 it is about to update
+// with a branch-free scan -- 15 compares and 30 selects per 16 elements of a stream that moves 112 bytes for them.  Everything
+// else of AdamHyper belongs to the launch.  The arithmetic is adamw1 / ema1 above; only where h.lr and h.wd come from differs.
+constexpr int ADAM_MAXSEG = 16;
+struct AdamSegTable {
+  int end4[ADAM_MAXSEG];  // end of segment k in float4 units for k < n - 1; INT_MAX from the last segment on (it ends with the buffer)
+  float lr[ADAM_MAXSEG], wd[ADAM_MAXSEG];
+  int n;
+};
+__device__ __forceinline__ void seg_hyper(const AdamSegTable& t, int i4, AdamHyper& h) {
+  float lr = t.lr[0], wd = t.wd[0];
+#pragma unroll
+  for (int k = 0; k + 1 < ADAM_MAXSEG; ++k) {
+    const bool past = i4 >= t.end4[k];
+    lr = past ? t.lr[k + 1] : lr;
+    wd = past ? t.wd[k + 1] : wd;
+  }
+  h.lr = lr;
+  h.wd = wd;
+}
+
+// one float4 of the update (and of the average), every base on a 16-byte boundary: the vector body of adamw_span; -> the new parameters
+template <bool EMA>
+__device__ __forceinline__ f32x4 adamw_vec4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, float* __restrict__ e, float ema_omd, long i, const AdamHyper& h) {
+  f32x4 P = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
+  const f32x4 G = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+  f32x4 M = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
+  f32x4 V = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float pj = P[j], mj = M[j], vj = V[j];
+    adamw1(pj, G[j], mj, vj, h);
+    P[j] = pj; M[j] = mj; V[j] = vj;
+  }
+  reinterpret_cast<f32x4*>(p)[i] = P;
+  __builtin_nontemporal_store(M, reinterpret_cast<f32x4*>(m) + i);
+  __builtin_nontemporal_store(V, reinterpret_cast<f32x4*>(v) + i);
+  if constexpr (EMA) {
+    f32x4 E = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(e) + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) E[j] = ema1(E[j], P[j], ema_omd);
+    __builtin_nontemporal_store(E, reinterpret_cast<f32x4*>(e) + i);
+  }
+  return P;
+}
+
+// the flat form: n % 4 elements of a scalar tail, which lie in the last segment (every other end is a multiple of 4)
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ e, float ema_omd,
+                                                        __bf16* __restrict__ ph, long n, AdamHyper h, AdamSegTable t,
+                                                        const float* __restrict__ clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  const long n4 = n >> 2;
+  for (long i = i0; i < n4; i += stride) {
+    seg_hyper(t, (int)i, h);
+    const f32x4 P = adamw_vec4<EMA>(p, g, m, v, e, ema_omd, i, h);
+    if (ph) {
+      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+      bf16x4 o = {(__bf16)P.x, (__bf16)P.y, (__bf16)P.z, (__bf16)P.w};
+      reinterpret_cast<bf16x4*>(ph)[i] = o;
+    }
+  }
+  seg_hyper(t, (int)n4, h);
+  for (long i = (n4 << 2) + i0; i < n; i += stride) {
+    float P = p[i], M = m[i], V = v[i];
+    adamw1(P, g[i], M, V, h);
+    p[i] = P; m[i] = M; v[i] = V;
+    if constexpr (EMA) e[i] = ema1(e[i], *reinterpret_cast<volatile float*>(p + i), ema_omd);  // (as in adamw_span's scalar body)
+    if (ph) ph[i] = (__bf16)P;
+  }
+}
+
+// the plane-image form (n % 4 == 0): the matrices of AdamSegs are independent of the segments, a matrix may lie across their ends
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_planes_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4,
+                                                               AdamHyper h, AdamSegTable t, AdamSegs sg,
+                                                               const float* __restrict__ clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    seg_hyper(t, (int)i, h);
+    const f32x4 P = adamw_vec4<EMA>(p, g, m, v, e, ema_omd, i, h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (s < sg.n && i >= sg.b4[s] && i < sg.e4[s]) {
+        const long el = (i - sg.b4[s]) * 4;
+        const long row = el / sg.cols[s];
+        planes_store4(sg.img[s], sg.rows[s], row, (int)(el - row * sg.cols[s]), P);
+      }
+    }
+  }
 }
 
 // several tensors of one parameter group in one launch: blockIdx.x -> (tensor, block within tensor) through a prefix table
@@ -389,6 +495,80 @@ static int adamw_planes_launch(float* p, const float* g, float* m, float* v, lon
   return MTVAF_OK;
 }
 
+// The segmented forms: what both check before anything is launched, and the table they pass by value.
+static int seg_table(AdamSegTable& t, long n, int nseg, const long* seg_end, const float* seg_lr, const float* seg_wd) {
+  if (n <= 0 || nseg < 1 || nseg > ADAM_MAXSEG || !seg_end || !seg_lr || !seg_wd) return MTVAF_ERR_ARG;
+  long prev = 0;
+  for (int k = 0; k < nseg; ++k) {
+    if (seg_end[k] <= prev || (k + 1 < nseg && (seg_end[k] & 3))) return MTVAF_ERR_ARG;
+    prev = seg_end[k];
+  }
+  if (prev != n) return MTVAF_ERR_ARG;
+  if ((n + 3) / 4 >= (long)INT_MAX) return MTVAF_ERR_SHAPE;  // (the scan compares float4 indices as int)
+  t.n = nseg;
+  for (int k = 0; k < ADAM_MAXSEG; ++k) {
+    t.end4[k] = k + 1 < nseg ? (int)(seg_end[k] / 4) : INT_MAX;
+    t.lr[k] = k < nseg ? seg_lr[k] : 0.f;
+    t.wd[k] = k < nseg ? seg_wd[k] : 0.f;
+  }
+  return MTVAF_OK;
+}
+
+template <typename K, typename... A>
+static inline void seg_launch(K k_ema_dev, K k_ema, K k_dev, K k_plain, bool ema, bool dev, int grid, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(ema ? (dev ? k_ema_dev : k_ema) : (dev ? k_dev : k_plain), dim3(grid), dim3(256), 0, stream, args...);
+}
+
+static int adamw_seg_launch(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const float* seg_lr,
+                            const float* seg_wd, double beta1, double beta2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                            void* p_bf16, int max_blocks, float* ema, float ema_omd, const float* clip, hipStream_t stream) {
+  if (!p || !g || !m || !v) return MTVAF_ERR_ARG;
+  if (ema && !ema_omd_ok(ema_omd)) return MTVAF_ERR_ARG;
+  AdamSegTable t;
+  if (const int rc = seg_table(t, n, nseg, seg_end, seg_lr, seg_wd)) return rc;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || ((uintptr_t)p_bf16 & 7) || ((uintptr_t)clip & 3))
+    return MTVAF_ERR_ALIGN;
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, 0.f, bc1, bc2_sqrt, grad_scale);  // (lr, wd: per segment, from the table)
+  int grid = stream_grid((n + 3) / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_seg_kernel<true, true>, adamw_seg_kernel<true, false>, adamw_seg_kernel<false, true>, adamw_seg_kernel<false, false>,
+             ema != nullptr, clip != nullptr, grid, stream, p, g, m, v, ema, ema_omd, static_cast<__bf16*>(p_bf16), n, h, t, clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int adamw_planes_seg_launch(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end,
+                                   const float* seg_lr, const float* seg_wd, double beta1, double beta2, float eps, float bc1,
+                                   float bc2_sqrt, float grad_scale, int nmat, const long* mat_begin, const int* mat_rows,
+                                   const int* mat_cols, void* const* mat_img, int max_blocks, float* ema, float ema_omd,
+                                   const float* clip, hipStream_t stream) {
+  if (!p || !g || !m || !v || nmat < 0 || nmat > 4 || (nmat && (!mat_begin || !mat_rows || !mat_cols || !mat_img))) return MTVAF_ERR_ARG;
+  if (ema && !ema_omd_ok(ema_omd)) return MTVAF_ERR_ARG;
+  AdamSegTable t;
+  if (const int rc = seg_table(t, n, nseg, seg_end, seg_lr, seg_wd)) return rc;
+  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || ((uintptr_t)clip & 3))
+    return MTVAF_ERR_ALIGN;
+  AdamSegs sg = {};  // (the conditions of adamw_planes_launch)
+  sg.n = nmat;
+  for (int s = 0; s < nmat; ++s) {
+    const long cnt = (long)mat_rows[s] * mat_cols[s];
+    if (mat_rows[s] <= 0 || mat_cols[s] <= 0 || mat_cols[s] % 32 || mat_begin[s] < 0 || (mat_begin[s] & 3) || mat_begin[s] + cnt > n ||
+        !mat_img[s] || (((uintptr_t)mat_img[s]) & 15))
+      return MTVAF_ERR_SHAPE;
+    sg.b4[s] = mat_begin[s] / 4; sg.e4[s] = (mat_begin[s] + cnt) / 4;
+    sg.rows[s] = mat_rows[s]; sg.cols[s] = mat_cols[s];
+    sg.img[s] = static_cast<unsigned char*>(mat_img[s]);
+  }
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, 0.f, bc1, bc2_sqrt, grad_scale);
+  int grid = stream_grid(n / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_planes_seg_kernel<true, true>, adamw_planes_seg_kernel<true, false>, adamw_planes_seg_kernel<false, true>,
+             adamw_planes_seg_kernel<false, false>, ema != nullptr, clip != nullptr, grid, stream, p, g, m, v, ema, ema_omd, n / 4, h, t,
+             sg, clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
 static int adamw_multi_launch(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
                               float lr, double beta1, double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
                               float grad_scale, const float* clip, const EmaArgs& ema, hipStream_t stream) {
@@ -545,6 +725,23 @@ int mtvaf_adamw_multi_ema(int count, float* const* p, const float* const* g, flo
   if ((uintptr_t)clip_state & 3) return MTVAF_ERR_ALIGN;
   const EmaArgs ea = {true, nullptr, ema, ema_omd};
   return adamw_multi_launch(count, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, clip_state, ea, stream);
+}
+
+// mtvaf_adamw / mtvaf_adamw_planes with lr and weight decay per segment of the buffer (the head of the segmented kernels above);
+// clip_state, ema and p_bf16 are nullable arguments: one entry point each instead of a _dev / _ema family.
+int mtvaf_adamw_seg(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const float* seg_lr,
+                    const float* seg_wd, double beta1, double beta2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                    void* p_bf16, int max_blocks, float* ema, float ema_omd, const float* clip_state, hipStream_t stream) {
+  return adamw_seg_launch(p, g, m, v, n, nseg, seg_end, seg_lr, seg_wd, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, p_bf16, max_blocks,
+                          ema, ema_omd, clip_state, stream);
+}
+
+int mtvaf_adamw_planes_seg(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const float* seg_lr,
+                           const float* seg_wd, double beta1, double beta2, float eps, float bc1, float bc2_sqrt, float grad_scale,
+                           int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols, void* const* mat_img,
+                           int max_blocks, float* ema, float ema_omd, const float* clip_state, hipStream_t stream) {
+  return adamw_planes_seg_launch(p, g, m, v, n, nseg, seg_end, seg_lr, seg_wd, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, nmat,
+                                 mat_begin, mat_rows, mat_cols, mat_img, max_blocks, ema, ema_omd, clip_state, stream);
 }
 
 // a[i] <-> b[i], n[i] floats each, bit for bit; host arrays of device pointers, any count (48 pairs per launch).  A pair whose two

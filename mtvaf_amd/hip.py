@@ -161,6 +161,8 @@ _SIGS = {
     "mtvaf_adamw_planes_ema": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P, F, P, P]),
     "mtvaf_adamw_multi_ema": (c_int, [I, P, P, P, P, P, F, c_double, c_double, F, F, F, F, F, P, F, P, P]),
     "mtvaf_swap_f32_multi": (c_int, [I, P, P, P, P]),
+    "mtvaf_adamw_seg": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, F, F, P, I, P, F, P, P]),
+    "mtvaf_adamw_planes_seg": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, F, F, I, P, P, P, P, I, P, F, P, P]),
     "mtvaf_grad_pack_bf16": (c_int, [P, P, L, L, P]),
     "mtvaf_grad_reduce_bf16": (c_int, [P, P, I, L, F, P]),
     "mtvaf_grad_unpack_bf16": (c_int, [P, P, L, P]),
@@ -1524,6 +1526,36 @@ def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_
     else:
         _ck(lib().mtvaf_adamw_multi_dev(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
                                         bc2 ** 0.5, grad_scale, _clip_ptr(clip), _st()), "mtvaf_adamw_multi_dev")
+
+
+def _seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale):
+    """The leading arguments of the two segmented updates: segments = [(end element, lr, weight_decay), ...] in buffer order."""
+    _f32(p, g, m, v)
+    k = len(segments)
+    return (_p(p), _p(g), _p(m), _p(v), p.numel(), k, (ctypes.c_long * k)(*[int(s[0]) for s in segments]),
+            (ctypes.c_float * k)(*[float(s[1]) for s in segments]), (ctypes.c_float * k)(*[float(s[2]) for s in segments]),
+            float(beta1), float(beta2), float(eps), float(1.0 - beta1 ** step), float((1.0 - beta2 ** step) ** 0.5), float(grad_scale))
+
+
+def adamw_seg(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None, ema_omd=0.0):
+    """adamw with lr and weight decay per segment of the flat buffer: segments = [(end element, lr, weight_decay), ...], at most 16,
+    ends strictly increasing, the last one p.numel(), every other one a multiple of 4.  One launch; each element gets the bits
+    adamw gives it on its segment alone.  p_bf16, max_blocks, clip, ema, ema_omd: see adamw (all optional, one entry point)."""
+    _ck(lib().mtvaf_adamw_seg(*_seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale), _p(p_bf16), int(max_blocks),
+                              None if ema is None else _ema_arg(ema, p), float(ema_omd), None if clip is None else _clip_ptr(clip),
+                              _st()), "mtvaf_adamw_seg")
+
+
+def adamw_planes_seg(p, g, m, v, segments, beta1, beta2, eps, step, mats, grad_scale=1.0, max_blocks=0, clip=None, ema=None,
+                     ema_omd=0.0):
+    """adamw_seg that also rewrites the plane images of the matrices inside the buffer: mats = [(begin element, rows, cols, image
+    uint8 tensor), ...] (at most four, as adamw_planes' segs; a matrix may lie across segment ends)."""
+    n = len(mats)
+    _ck(lib().mtvaf_adamw_planes_seg(*_seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale), n,
+                                     (ctypes.c_long * n)(*[s[0] for s in mats]), (ctypes.c_int * n)(*[s[1] for s in mats]),
+                                     (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]),
+                                     int(max_blocks), None if ema is None else _ema_arg(ema, p), float(ema_omd),
+                                     None if clip is None else _clip_ptr(clip), _st()), "mtvaf_adamw_planes_seg")
 
 
 def swap_f32(a_list, b_list):

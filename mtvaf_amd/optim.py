@@ -14,6 +14,11 @@ schedule; ``bert_before_train`` (:887-892) is the text-only variant (one group, 
 grouping is reproduced here (``reference_param_groups`` / ``build_optimizer``) on top of ``AdamW`` below, so a step of
 the reference trainer costs what ``bench.py`` measures.
 
+``finetune_param_groups`` is the usual BERT fine-tuning recipe on the same partition (no weight decay on biases and LayerNorm
+weights, lr decaying with depth; ``args.no_decay`` / ``args.layer_lr_decay``): an encoder layer then holds two parameter groups
+and is still ONE launch -- the segmented kernels of ``csrc/optim.hip`` take lr and weight decay per stretch of the layer's buffer
+(``layer_segments``).
+
 Reference quirk kept on purpose: ``projectors.*``, ``img_classifier.*`` and ``aux_img_classifier.*`` match no
 group (the second group looks for the long-gone ``gates``), so the reference never updates them.
 """
@@ -39,11 +44,52 @@ def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
+MAX_SEGMENTS = 16  # of one segmented launch (csrc/optim.hip, ADAM_MAXSEG): an encoder layer has 16 parameters
+
+
+def _same_lr_wd(a, b) -> bool:
+    return a is b or (a["lr"], a["weight_decay"]) == (b["lr"], b["weight_decay"])
+
+
+def layer_segments(offsets, numels, hypers, same=_same_lr_wd):
+    """The plan of ONE launch over a flat buffer whose tensors do not share their hyper-parameters (``hip.adamw_seg``).
+
+    Tensor i lies at elements ``[offsets[i], offsets[i] + numels[i])`` and is trained with the mapping ``hypers[i]`` (keys ``lr``,
+    ``weight_decay``, ``betas``, ``eps``: a parameter group, or a plain dict).  -> ``[(end element, hypers of the segment), ...]`` in
+    buffer order, adjacent tensors merged where ``same(a, b)`` (default: equal ``(lr, weight_decay)``); or None where one launch
+    cannot do it: the tensors do not tile the buffer from 0 without gaps, ``betas`` or ``eps`` differ (they belong to the launch), an
+    end other than the last is not a multiple of 4 elements (the kernel works in float4s), or more than 16 segments remain.
+    Pure host logic.  The optimizer passes ``same = identity of the group``: two groups whose lr are equal today need not stay so
+    under a scheduler, and ``group["lr"]`` is read at every update."""
+    order = sorted(range(len(offsets)), key=lambda i: offsets[i])
+    if not order:
+        return None
+    h0 = hypers[order[0]]
+    segs, end = [], 0
+    for i in order:
+        h = hypers[i]
+        if offsets[i] != end or numels[i] <= 0 or tuple(h["betas"]) != tuple(h0["betas"]) or h["eps"] != h0["eps"]:
+            return None
+        end += numels[i]
+        if segs and same(segs[-1][1], h):
+            segs[-1] = (end, segs[-1][1])
+        else:
+            segs.append((end, h))
+    if len(segs) > MAX_SEGMENTS or any(e % 4 for e, _ in segs[:-1]):
+        return None
+    return segs
+
+
 class AdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (decoupled weight decay, bias correction, no amsgrad) on the gfx950 kernels.
 
     ``attach(model)`` (or ``model=`` at construction) lets the optimizer see the encoder's per-layer flat buffers
-    (``BertEncoder._stores``): a layer whose 16 parameters sit in one parameter group is updated by ONE launch.
+    (``BertEncoder._stores``): a layer whose 16 parameters sit in one parameter group is updated by ONE launch -- and so is a layer
+    whose parameters sit in several groups that differ in ``lr`` and ``weight_decay`` only (biases and LayerNorm weights without
+    weight decay, ``finetune_param_groups``): the layer's buffer is then updated as up to 16 segments (``layer_segments``,
+    ``hip.adamw_seg`` / ``hip.adamw_planes_seg``) on every path the single-group launch takes -- ``step()``, ``overlap=True``, under
+    ``GradSync``, with clipping, the averaged weights, the bf16 shadow and the plane images.  Groups of one layer that differ in
+    ``betas`` or ``eps`` leave that layer to the tensor-by-tensor launches.
 
     ``overlap=True``: layers are updated from inside ``loss.backward()`` as soon as their gradients are final (after
     the all-reduce under data parallelism).  Contract: every backward pass is followed by exactly one ``step()`` before
@@ -156,13 +202,34 @@ class AdamW(torch.optim.Optimizer):
             raise RuntimeError("mtvaf_amd.optim.AdamW(overlap=True): a second backward pass ran before optimizer.step() "
                                "(gradient accumulation needs overlap=False)")
 
+    SEGMENT_PLANS = True  # (tests switch it off on an instance: layers with several groups then go tensor by tensor, as they used to)
+
     def _map_layers(self):
+        """Every layer's plan: its parameter group (all 16 parameters in one: ``hip.adamw`` / ``hip.adamw_planes``), a list
+        ``[(end element, group), ...]`` (several groups that one segmented launch can serve, ``layer_segments``), or None (tensor by
+        tensor).  Groups are kept, not their values: ``group["lr"]`` is read at every update."""
         group_of = {id(p): g for g in self.param_groups for p in g["params"]}
         self._layer_group = {}
+        stores = None
         for li, layer in enumerate(self._encoder.layer):
-            gs = {id(group_of.get(id(p))) for p in layer.ordered_params()}
-            g0 = group_of.get(id(layer.ordered_params()[0]))
-            self._layer_group[li] = g0 if (len(gs) == 1 and g0 is not None) else None
+            ps = layer.ordered_params()
+            groups = [group_of.get(id(p)) for p in ps]
+            plan = None
+            if all(g is groups[0] for g in groups):
+                plan = groups[0]
+            elif self.SEGMENT_PLANS and all(g is not None for g in groups):
+                if stores is None:
+                    stores = self._encoder._prepare()[0]
+                plan = layer_segments([stores[li].offsets[i] for i in range(len(ps))], [p.numel() for p in ps], groups,
+                                      same=lambda a, b: a is b)
+            self._layer_group[li] = plan
+
+    def _plan(self, li: int, store):
+        """The layer's plan (_map_layers); a segmented one only while it still describes the store's buffer."""
+        plan = self._layer_group.get(li)
+        if isinstance(plan, list) and plan[-1][0] != store.flat.numel():
+            return None
+        return plan
 
     def _layer_state(self, li: int, store):
         """Flat moment buffers of layer li; the per-parameter state entries are views of them."""
@@ -310,30 +377,42 @@ class AdamW(torch.optim.Optimizer):
             ema, omd = st["ema"], self._ema_omd(st["ema_step"])
             st["ema_step"] += 1
             st["ema_step_t"].fill_(st["ema_step"])
+        # a segmented plan ([(end element, group), ...]): lr and weight decay per segment, read now; betas and eps are the launch's
+        table = [(end, float(g["lr"]), g["weight_decay"]) for end, g in group] if isinstance(group, list) else None
+        if table is not None:
+            group = group[0][1]
         b1, b2 = group["betas"]
         from . import engine
         shadow = engine.shadow_for_update(store.weights)  # bf16 compute mode: the GEMM operand image, written in the same pass
         segs = engine.planes_for_update(store.weights) if shadow is None else None
+        ema_kw = {} if ema is None else dict(ema=ema, ema_omd=omd)
         if segs is not None and store.flat.numel() % 4 == 0:
             # fp32 mode, pre-split operands: the weights' plane images are rewritten by the update kernel itself
-            hip.adamw_planes(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                             st["step"], segs, max_blocks=self.BACKGROUND_BLOCKS_PLANES if background else 0, clip=clip,
-                             **({} if ema is None else dict(ema=ema, ema_omd=omd)))
+            blocks = self.BACKGROUND_BLOCKS_PLANES if background else 0
+            if table is not None:
+                hip.adamw_planes_seg(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], st["step"], segs,
+                                     max_blocks=blocks, clip=clip, **ema_kw)
+            else:
+                hip.adamw_planes(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                                 st["step"], segs, max_blocks=blocks, clip=clip, **ema_kw)
             engine.planes_written(store.weights)
             return
-        hip.adamw(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                  st["step"], p_bf16=shadow,
-                  max_blocks=(self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0,
-                  clip=clip, **({} if ema is None else dict(ema=ema, ema_omd=omd)))
+        blocks = ((self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0)
+        if table is not None:
+            hip.adamw_seg(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], st["step"], p_bf16=shadow,
+                          max_blocks=blocks, clip=clip, **ema_kw)
+        else:
+            hip.adamw(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                      st["step"], p_bf16=shadow, max_blocks=blocks, clip=clip, **ema_kw)
         if shadow is not None:
             engine.shadow_written(store.weights)
         engine.planes_rewrite(store.weights)  # (images exist but the fused form does not apply: rebuilt behind the update)
 
     def _early_layer_update(self, li: int):
         """Called from inside the backward pass (current stream: the one the layer's gradients are final on)."""
-        group = self._layer_group.get(li)
         stores = self._encoder._stores
-        if self.suspended or group is None or stores is None or stores[li].grad is None:
+        group = self._plan(li, stores[li]) if stores is not None else None
+        if self.suspended or group is None or stores[li].grad is None:
             return
         self._refuse_swapped("a backward pass that updates the encoder layers (overlap=True) ran")
         if li in self._early:
@@ -385,7 +464,8 @@ class AdamW(torch.optim.Optimizer):
                 if li in self._early:
                     done.update(id(p) for p in ps)
                     continue
-                group, store = self._layer_group.get(li), enc._stores[li]
+                store = enc._stores[li]
+                group = self._plan(li, store)
                 if group is None or store.grad is None or not store.valid(layer):
                     continue
                 lo = store.grad.data_ptr()
@@ -468,6 +548,49 @@ def reference_param_groups(model: torch.nn.Module, lr: float, use_prefix: bool =
     return groups
 
 
+DEFAULT_NO_DECAY = ("bias", "LayerNorm.weight")
+
+
+def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float = 1e-2, no_decay=DEFAULT_NO_DECAY,
+                          layer_lr_decay: float = 1.0, head_lr: float = 5e-2, use_prefix: bool = True) -> List[Dict]:
+    """The usual BERT fine-tuning recipe on the reference's name partition (new functionality: the reference trains with one weight
+    decay everywhere and one lr per group, modules/train.py:894-916).
+
+    The partition by name is ``reference_param_groups``'s -- ``bert*``; ``encoder_conv*`` / ``gates*``; ``crf*`` / ``fc*`` at
+    ``head_lr``; with the quirk that ``projectors.*`` / ``*img_classifier.*`` match no group; ``use_prefix=False``: every parameter,
+    one partition.  Then
+      * every partition is split by the ``no_decay`` name test (a parameter whose name contains one of the strings gets weight
+        decay 0, the others ``weight_decay``), and
+      * the encoder is split by depth: layer ``l`` of ``L`` (``encoder.layer.<l>.``) trains at ``lr * layer_lr_decay ** (L - 1 - l)``,
+        the embeddings at ``lr * layer_lr_decay ** L``, whatever sits above the last layer (the pooler) at ``lr``.
+    Groups come in the order their first parameter has in ``named_parameters()``.  With ``no_decay=()`` and ``layer_lr_decay=1`` these
+    are the reference groups.  An encoder layer then holds two groups; ``AdamW`` still updates it with one launch (``layer_segments``)."""
+    import re
+    named = list(model.named_parameters())
+    no_decay = tuple(no_decay or ())
+    if use_prefix:
+        parts = [(lr, [(n, p) for n, p in named if "bert" in n], True),
+                 (lr, [(n, p) for n, p in named if "encoder_conv" in n or "gates" in n], False),
+                 (head_lr, [(n, p) for n, p in named if "crf" in n or n.startswith("fc")], False)]
+    else:
+        parts = [(lr, named, True)]
+    layer_of = lambda n: re.search(r"encoder\.layer\.(\d+)\.", n)
+    L = 1 + max((int(layer_of(n).group(1)) for n, _ in named if layer_of(n)), default=-1)
+    groups = []
+    for base_lr, items, by_depth in parts:
+        split: Dict[tuple, list] = {}
+        for n, p in items:
+            power = 0
+            if by_depth and layer_lr_decay != 1.0:
+                power = L - 1 - int(layer_of(n).group(1)) if layer_of(n) else (L if "embeddings." in n else 0)
+            split.setdefault((power, any(s in n for s in no_decay)), []).append(p)
+        if not split:  # (the reference keeps its empty second group too)
+            split[(0, False)] = []
+        groups.extend({"lr": base_lr * layer_lr_decay ** power, "weight_decay": 0.0 if exempt else weight_decay, "params": ps}
+                      for (power, exempt), ps in split.items())
+    return groups
+
+
 def linear_schedule_with_warmup(optimizer, num_warmup_steps: float, num_training_steps: int):
     """transformers.get_linear_schedule_with_warmup restated (the reference passes a float warm-up count,
     train.py:922-924): lr factor = step / warmup while warming up, then linear decay to 0."""
@@ -483,7 +606,15 @@ def linear_schedule_with_warmup(optimizer, num_warmup_steps: float, num_training
 def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
     """-> (optimizer, scheduler) as SATrainer2.train() sets them up (train.py:574-578, 887-926)."""
     use_prefix = bool(getattr(args, "use_prefix", False))
-    groups = reference_param_groups(model, args.lr, use_prefix)
+    # the fine-tuning recipe (not the reference's): args.no_decay -- False (default), True (DEFAULT_NO_DECAY) or a tuple of name
+    # fragments whose parameters get weight decay 0 -- and args.layer_lr_decay (1.0: one lr for the whole encoder)
+    no_decay = getattr(args, "no_decay", False)
+    no_decay = DEFAULT_NO_DECAY if no_decay is True else tuple(no_decay or ())
+    layer_lr_decay = float(getattr(args, "layer_lr_decay", 1.0) or 1.0)
+    if no_decay or layer_lr_decay != 1.0:
+        groups = finetune_param_groups(model, args.lr, no_decay=no_decay, layer_lr_decay=layer_lr_decay, use_prefix=use_prefix)
+    else:
+        groups = reference_param_groups(model, args.lr, use_prefix)
     if use_prefix:
         for n, p in model.named_parameters():  # freeze resnet (:920-921)
             if "image_model" in n:
