@@ -686,6 +686,13 @@ int mtvaf_gemm_f32p_dw_group(int n, const void* const* Aplanes, const void* cons
 int mtvaf_gemm_f32p_dw_group_colsum(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C,
                                     const int* ldc, const int* M, const int* N, int K, int njobs, const float* const* cs_src,
                                     const int* cs_rows, const int* cs_cols, const int* cs_ld, float* const* cs_dst, mtvaf_stream_t stream);
+/* The two entries above with an `accumulate` flag (njobs 0 .. 8): != 0 -> every tile stores old + product and every column-sum job
+ * old + sum.  Product and sum are formed exactly as by the overwriting form and the destination's old value is added once, last, so
+ * the result is one IEEE add away from it (gradient accumulation over micro-batches).  0: those entries, bit for bit. */
+int mtvaf_gemm_f32p_dw_group_acc(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C,
+                                 const int* ldc, const int* M, const int* N, int K, int njobs, const float* const* cs_src,
+                                 const int* cs_rows, const int* cs_cols, const int* cs_ld, float* const* cs_dst, int accumulate,
+                                 mtvaf_stream_t stream);
 /* mtvaf_gemm_f32p with a plain epilogue that leaves a split-K plan's slabs unreduced (as mtvaf_gemm_f32_slabs: *splits_out = 1 -> C
  * holds the result; s > 1 -> `workspace` holds s slabs [M][N], bias / accumulate not applied): the LayerNorm kernels behind the Wo /
  * FFN-2 / FFN-1 dX products add them (modeling_bert.py:353-355, 433-435 and their backward). */
@@ -723,6 +730,13 @@ int mtvaf_gemm_f32_dw_group_bias(int n, const float* const* A, const int* lda, c
                                  float* const* C, const int* ldc, const int* M, const int* N, int K, const int* klist,
                                  const int* kcnt, float* const* dbias, void* workspace, size_t workspace_bytes, int splits,
                                  mtvaf_stream_t stream);
+/* mtvaf_gemm_f32_dw_group_bias (dbias nullable) with an `accumulate` flag: != 0 -> dW_i += the product, dbias_i += the column sums,
+ * each one add behind the value the overwriting form stores (the same plan on the same kernels: the old value enters in the
+ * epilogue of an unsplit launch, in the ordered slab reduction of a split one).  0: that entry, bit for bit. */
+int mtvaf_gemm_f32_dw_group_acc(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb,
+                                float* const* C, const int* ldc, const int* M, const int* N, int K, const int* klist,
+                                const int* kcnt, float* const* dbias, void* workspace, size_t workspace_bytes, int splits,
+                                int accumulate, mtvaf_stream_t stream);
 int mtvaf_dw_group_rows(int rows);
 int mtvaf_dw_group_wanted(int rows, int H, int I);
 
@@ -742,6 +756,14 @@ int mtvaf_streamk_attached(mtvaf_stream_t stream); /* -> blocks the attached scr
  * Needs an attached scratch (MTVAF_ERR_WORKSPACE otherwise); M_i % 256 == 0, N_i % 256 == 0, K % 64 == 0. */
 int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
                               const int* ldc32, const int* M, const int* N, int K, mtvaf_stream_t stream);
+/* ... with an `accumulate` flag: != 0 -> C32_i += the product: the block that finishes a tile adds the old value behind the
+ * contributions it has combined in k order; a block that only contributes never reads the destination.  0: the entry above. */
+int mtvaf_gemm_bf16x_dw_group_acc(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
+                                  const int* ldc32, const int* M, const int* N, int K, int accumulate, mtvaf_stream_t stream);
+/* The cut mtvaf_gemm_bf16x_dw_group[_acc] takes for these products on `stream`: the pieces S every tile's reduction is divided into (1: whole tiles, no
+ * block contributes to another's tile; S > 1: S - 1 contributing blocks and one finishing block per tile).  0: the call would be
+ * refused (shapes, or no scratch attached to the stream).  The launch's own planner call. */
+int mtvaf_gemm_bf16x_dw_group_pieces(int n, const int* M, const int* N, int K, mtvaf_stream_t stream);
 
 /* Prefix attention of the mixed-precision mode: the algorithm of mtvaf_prefix_attn_fwd / _bwd (same key order, mask,
  * dropout hash) on bf16 operands with fp32 softmax statistics and accumulation.  qkv16 [B*S,3H], pk16 / pv16 [B,P*H],
@@ -842,6 +864,10 @@ typedef struct {
    * operands -- [Mp, H], [Mp, I], [Mp, H], [Mp, 3H] -- alive until the second stream has finished the layer's weight gradients;
    * with `part`, both lnpart and ws_main they are required when the layer struct has plane images, NULL otherwise */
   void *df_p, *dpre_p, *da_p, *dqkv_p;
+  /* != 0: the sixteen parameter gradients (dwqkv .. db2) are ADDED to: every launch that writes one takes its accumulating form
+   * (value formed as at 0, the old value added once, last).  dh, dpk and dpv are activations' gradients and are always overwritten.
+   * 0: every launch is what it was before this field existed. */
+  int accumulate;
 } mtvaf_layer_grads_t;
 
 int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* layer, mtvaf_stream_t stream);

@@ -213,16 +213,16 @@ int mtvaf_dw_group_wanted(int rows, int H, int I) {
 
 // LayerNorm backward of one block of the layer, then the fork the weight gradients behind it need anyway.  With per-layer
 // partial buffers (g->lnpart*) and a second stream, the column sums (dgamma, dbeta, the dense bias gradient: parameter
-// gradients only) run THERE: 24 launches of ~12 us leave the main chain of a step.
+// gradients only) run THERE: 24 launches of ~12 us leave the main chain of a step.  acc: they are added to (mtvaf_layer_grads_t::accumulate).
 static int ln_bwd_forked(const float* dout, const float* x, const float* res, const float* gamma, const float* mean, const float* rstd,
                          float* dx, float* dres, float* dgamma, float* dbeta, float* dbias, int M, int H, double p_drop, uint64_t seed,
-                         uint64_t offset, float* part, void* ws, size_t ws_bytes, void* dx16, hipStream_t mainS, hipStream_t side) {
+                         uint64_t offset, float* part, void* ws, size_t ws_bytes, void* dx16, int acc, hipStream_t mainS, hipStream_t side) {
   if (part && side != mainS) {
     MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows(dout, x, res, gamma, mean, rstd, dx, dres, 0, M, H, p_drop, seed, offset, part, dx16, mainS));
     MTVAF_TRY(fork_to(mainS, side));
-    return mtvaf_dropout_res_ln_bwd_finish(part, M, H, dgamma, dbeta, dbias, 0, side);
+    return mtvaf_dropout_res_ln_bwd_finish(part, M, H, dgamma, dbeta, dbias, acc, side);
   }
-  MTVAF_TRY(mtvaf_dropout_res_ln_bwd(dout, x, res, gamma, mean, rstd, dx, dres, 0, dgamma, dbeta, dbias, 0, M, H, p_drop, seed, offset, ws,
+  MTVAF_TRY(mtvaf_dropout_res_ln_bwd(dout, x, res, gamma, mean, rstd, dx, dres, 0, dgamma, dbeta, dbias, acc, M, H, p_drop, seed, offset, ws,
                                      ws_bytes, dx16, mainS));
   return fork_to(mainS, side);
 }
@@ -234,26 +234,29 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
   if (!L || !g) return MTVAF_ERR_ARG;
   if (L->cu && (L->Mp <= 0 || L->Mp % 128 || L->Mv <= 0 || L->Mv > L->Mp)) return MTVAF_ERR_ARG;
   const int M = L->cu ? L->Mp : L->B * L->S, H = L->H, I = L->I, B = L->B, S = L->S, P = L->P, NH = L->NH;
+  // gradient accumulation: every launch that writes one of the sixteen PARAMETER gradients takes its accumulating form (dst = old +
+  // the value it stores at 0); dh / dh1 / dpk / dpv and the GEMM-operand gradients are activations' and are overwritten as ever
+  const int acc = g->accumulate ? 1 : 0;
   if (L->bf16) {
     // the four weight-gradient products of the layer as ONE launch (mtvaf_gemm_bf16x_dw_group: every tile's reduction over the
     // tokens cut in two, combined inside the launch) when a stream-K scratch is attached to the second stream: 36 + 36 + 27 + 9
     // output tiles fill 256 CUs together, not one product at a time.  Enqueued behind the last of their operands (dqkv).
     const bool grp = mtvaf_streamk_attached(side) > 0 && !g->klist && M % 256 == 0 && H % 256 == 0 && I % 256 == 0;
     MTVAF_TRY(ln_bwd_forked(g->dh, L->f, L->h1, L->g2, L->mean2, L->rstd2, nullptr, g->dh1, g->dg2, g->db2, g->dbi2, M, H, L->p_hidden,
-                            L->seed, L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, g->df, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->df, H, L->act, I, g->dw2, I, nullptr, 0, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
+                            L->seed, L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, g->df, acc, mainS, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->df, H, L->act, I, g->dw2, I, nullptr, 0, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->df, H, L->w2_h, I, nullptr, 0, g->dpre, I, M, I, H, nullptr, MTVAF_EPI_DGELU, L->pre, I, 0,
                                g->part, 0, nullptr, 0, 0, -1, 0, mainS));
     MTVAF_TRY(fork_to(mainS, side));
-    MTVAF_TRY(mtvaf_colsum_small(g->part, M / 128, I, g->dbi1, 0, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->dpre, I, L->h1_h, H, g->dw1, H, nullptr, 0, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
+    MTVAF_TRY(mtvaf_colsum_small(g->part, M / 128, I, g->dbi1, acc, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->dpre, I, L->h1_h, H, g->dw1, H, nullptr, 0, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->dpre, I, L->w1_h, H, g->dh1, H, nullptr, 0, M, H, I, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1,
                                nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
     MTVAF_TRY(ln_bwd_forked(g->dh1, L->a, L->x, L->g1, L->mean1, L->rstd1, nullptr, g->dh, g->dg1, g->db1, g->dbo, M, H, L->p_hidden,
-                            L->seed, L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, g->da, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->da, H, L->cx, H, g->dwo, H, nullptr, 0, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
+                            L->seed, L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, g->da, acc, mainS, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->da, H, L->cx, H, g->dwo, H, nullptr, 0, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc,
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->da, H, L->wo_h, H, nullptr, 0, g->dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
@@ -266,17 +269,17 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
                                                 (g->klist != nullptr || g->zero_tail) ? 1 : 0, mainS));
     }
     MTVAF_TRY(fork_to(mainS, side));
-    MTVAF_TRY(mtvaf_colsum_small(g->partq, B * ((S + 63) / 64), H, g->dbqkv, 0, side));
-    MTVAF_TRY(mtvaf_colsum_small(g->partkv, B * ((P + S + 63) / 64), 2 * H, g->dbqkv + H, 0, side));
+    MTVAF_TRY(mtvaf_colsum_small(g->partq, B * ((S + 63) / 64), H, g->dbqkv, acc, side));
+    MTVAF_TRY(mtvaf_colsum_small(g->partkv, B * ((P + S + 63) / 64), 2 * H, g->dbqkv + H, acc, side));
     if (!grp) MTVAF_TRY(mtvaf_gemm_bf16x_ktiles(MTVAF_KM, MTVAF_KM, g->dqkv, 3 * H, L->x_h, H, g->dwqkv, H, nullptr, 0, 3 * H, H, M, nullptr, MTVAF_EPI_NONE,
-                               nullptr, 0, 0, nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
+                               nullptr, 0, acc, nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     if (grp) {
       const void* const As[4] = {g->df, g->dpre, g->da, g->dqkv};
       const void* const Bs[4] = {L->act, L->h1_h, L->cx, L->x_h};
       float* const Cs[4] = {static_cast<float*>(g->dw2), static_cast<float*>(g->dw1), static_cast<float*>(g->dwo), static_cast<float*>(g->dwqkv)};
       const int lda[4] = {H, I, H, 3 * H}, ldb[4] = {I, H, H, H}, ldc[4] = {I, H, H, H};
       const int Ms[4] = {H, I, H, 3 * H}, Ns[4] = {I, H, H, H};
-      MTVAF_TRY(mtvaf_gemm_bf16x_dw_group(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, side));
+      MTVAF_TRY(mtvaf_gemm_bf16x_dw_group_acc(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, acc, side));
     }
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->dqkv, 3 * H, L->wqkv_h, H, g->dh, H, nullptr, 0, M, H, 3 * H, nullptr, MTVAF_EPI_NONE,
                                nullptr, 0, 1, nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
@@ -331,8 +334,7 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
         const int G = (int)(mtvaf_ln_bwd_workspace_bytes(M, H) / ((size_t)16 * H));  // partial rows [G][3][H] of each LayerNorm backward
         job(g->lnpart2, G, H, 3 * H, g->dg2); job(g->lnpart2 + H, G, H, 3 * H, g->db2); job(g->lnpart2 + 2 * H, G, H, 3 * H, g->dbi2);
         job(g->lnpart1, G, H, 3 * H, g->dg1); job(g->lnpart1 + H, G, H, 3 * H, g->db1); job(g->lnpart1 + 2 * H, G, H, 3 * H, g->dbo);
-        if (nj > 0) MTVAF_TRY(mtvaf_gemm_f32p_dw_group_colsum(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, nj, js, jr, jc, jl, jd, side));
-        else MTVAF_TRY(mtvaf_gemm_f32p_dw_group(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, side));
+        MTVAF_TRY(mtvaf_gemm_f32p_dw_group_acc(4, As, Bs, strides, Cs, ldc, Ms, Ns, M, nj, js, jr, jc, jl, jd, acc, side));
       }
       MTVAF_TRY(p16(1, g->dqkv_p, L->wqkv_h, g->dh, H, M, H, 3 * H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, g->ws_main, g->ws_main_bytes, nullptr,
                     mainS));
@@ -341,15 +343,15 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
     }
     const bool grp = mtvaf_dw_group_wanted(M, H, I) != 0;
     MTVAF_TRY(ln_bwd_forked(g->dh, L->f, L->h1, L->g2, L->mean2, L->rstd2, df, g->dh1, g->dg2, g->db2, g->dbi2, M, H, L->p_hidden, L->seed,
-                            L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, df, H, act, I, g->dw2, I, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+                            L->offset + 2, g->lnpart2, g->ws_main, g->ws_main_bytes, nullptr, acc, mainS, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, df, H, act, I, g->dw2, I, H, I, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, df, H, L->w2, I, dpre, I, M, I, H, nullptr, MTVAF_EPI_DGELU, pre, I, 0, 1, g->ws_main, g->ws_main_bytes, -1, -1,
                              mainS));
     MTVAF_TRY(fork_to(mainS, side));
     // (grouped weight gradients: the bias gradients dbi1 / dbqkv come out of that launch -- column sums of the dY tiles it stages)
-    if (!grp) MTVAF_TRY(mtvaf_colsum(dpre, M, I, I, g->dbi1, 0, g->ws_side, g->ws_side_bytes, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dpre, I, L->h1, H, g->dw1, H, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+    if (!grp) MTVAF_TRY(mtvaf_colsum(dpre, M, I, I, g->dbi1, acc, g->ws_side, g->ws_side_bytes, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dpre, I, L->h1, H, g->dw1, H, I, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     // (the LayerNorm backward behind this accumulating product adds its split-K slabs itself when its column sums have their
     // own partial buffer -- otherwise its scratch would be the workspace that holds the slabs)
@@ -364,12 +366,12 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       MTVAF_TRY(mtvaf_dropout_res_ln_bwd_rows_slabs(g->dh1, static_cast<const float*>(g->ws_main), ns1, L->a, L->x, L->g1, L->mean1, L->rstd1,
                                                     da, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1, g->lnpart1, nullptr, mainS));
       MTVAF_TRY(fork_to(mainS, side));
-      MTVAF_TRY(mtvaf_dropout_res_ln_bwd_finish(g->lnpart1, M, H, g->dg1, g->db1, g->dbo, 0, side));
+      MTVAF_TRY(mtvaf_dropout_res_ln_bwd_finish(g->lnpart1, M, H, g->dg1, g->db1, g->dbo, acc, side));
     } else {
       MTVAF_TRY(ln_bwd_forked(g->dh1, L->a, L->x, L->g1, L->mean1, L->rstd1, da, g->dh, g->dg1, g->db1, g->dbo, M, H, L->p_hidden, L->seed,
-                              L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, nullptr, mainS, side));
+                              L->offset + 1, g->lnpart1, g->ws_main, g->ws_main_bytes, nullptr, acc, mainS, side));
     }
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, da, H, cx, H, g->dwo, H, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_side,
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, da, H, cx, H, g->dwo, H, H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc, 1, g->ws_side,
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, da, H, L->wo, H, dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_main,
                              g->ws_main_bytes, -1, -1, mainS));
@@ -385,8 +387,8 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
                                            (g->klist != nullptr || g->zero_tail) ? 1 : 0, mainS));
     }
     MTVAF_TRY(fork_to(mainS, side));
-    if (!grp) MTVAF_TRY(mtvaf_colsum(dqkv, M, 3 * H, 3 * H, g->dbqkv, 0, g->ws_side, g->ws_side_bytes, side));
-    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dqkv, 3 * H, L->x, H, g->dwqkv, H, 3 * H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1,
+    if (!grp) MTVAF_TRY(mtvaf_colsum(dqkv, M, 3 * H, 3 * H, g->dbqkv, acc, g->ws_side, g->ws_side_bytes, side));
+    if (!grp) MTVAF_TRY(mtvaf_gemm_f32_ktiles(MTVAF_KM, MTVAF_KM, dqkv, 3 * H, L->x, H, g->dwqkv, H, 3 * H, H, M, nullptr, MTVAF_EPI_NONE, nullptr, 0, acc, 1,
                              g->ws_side, g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     if (grp) {
       const float* const As[4] = {df, dpre, da, dqkv};
@@ -395,8 +397,8 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
       const int lda[4] = {H, I, H, 3 * H}, ldb[4] = {I, H, H, H}, ldc[4] = {I, H, H, H};
       const int Ms[4] = {H, I, H, 3 * H}, Ns[4] = {I, H, H, H};
       float* const dbs[4] = {nullptr, g->dbi1, nullptr, g->dbqkv};
-      MTVAF_TRY(mtvaf_gemm_f32_dw_group_bias(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, g->klist, g->kcnt, dbs, g->ws_side, g->ws_side_bytes, -1,
-                                             side));
+      MTVAF_TRY(mtvaf_gemm_f32_dw_group_acc(4, As, lda, Bs, ldb, Cs, ldc, Ms, Ns, M, g->klist, g->kcnt, dbs, g->ws_side, g->ws_side_bytes, -1, acc,
+                                            side));
     }
     MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, dqkv, 3 * H, L->wqkv, H, g->dh, H, M, H, 3 * H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 1, 1,
                              g->ws_main, g->ws_main_bytes, -1, -1, mainS));

@@ -1176,9 +1176,13 @@ size_t mtvaf_gemm_f32_dw_group_workspace_bytes(int n, const int* M, const int* N
 // products (`workspace` is theirs again by then, in stream order).
 static int dw_group_impl(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
                          const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt, float* const* dbias,
-                         void* workspace, size_t workspace_bytes, int splits, hipStream_t stream) {
+                         void* workspace, size_t workspace_bytes, int splits, int accumulate, hipStream_t stream) {
   if (n < 1 || n > 4 || K <= 0 || K % 32) return MTVAF_ERR_SHAPE;
   GemmArgs a = {};
+  // accumulate: an unsplit launch adds the old value in its epilogue, a split plan in its ordered slab reduction, the bias sums in
+  // their own epilogue / reduction: always one add behind the value the overwriting form stores
+  accumulate = accumulate ? 1 : 0;
+  a.accumulate = accumulate;
   long tiles = 0, outs = 0;
   for (int i = 0; i < n; ++i)
     if (M[i] <= 0 || N[i] <= 0) return MTVAF_ERR_SHAPE;
@@ -1221,12 +1225,12 @@ static int dw_group_impl(int n, const float* const* A, const int* lda, const flo
     if (rc != MTVAF_OK) return rc;
     if (splits > 1)
       for (int i = 0; i < n; ++i) {
-        const int r2 = launch_splitk_reduce(a.grp[i].C, splits, C[i], M[i], N[i], ldc[i], nullptr, 0, EPI_NONE, nullptr, 0, stream);
+        const int r2 = launch_splitk_reduce(a.grp[i].C, splits, C[i], M[i], N[i], ldc[i], nullptr, accumulate, EPI_NONE, nullptr, 0, stream);
         if (r2 != MTVAF_OK) return r2;
       }
     for (int i = 0; dbias && i < n; ++i)  // (the sums the launch did not take itself)
       if (dbias[i] && !a.grp[i].colsum) {
-        const int r3 = mtvaf_colsum(A[i], K, M[i], lda[i], dbias[i], 0, workspace, workspace_bytes, stream);
+        const int r3 = mtvaf_colsum(A[i], K, M[i], lda[i], dbias[i], accumulate, workspace, workspace_bytes, stream);
         if (r3 != MTVAF_OK) return r3;
       }
     return MTVAF_OK;
@@ -1291,13 +1295,13 @@ static int dw_group_impl(int n, const float* const* A, const int* lda, const flo
   MTVAF_LAUNCH_CHECK();
   if (splits > 1) {
     for (int i = 0; i < n; ++i) {
-      const int rc = launch_splitk_reduce(a.grp[i].C, splits, C[i], M[i], N[i], ldc[i], nullptr, 0, EPI_NONE, nullptr, 0, stream);
+      const int rc = launch_splitk_reduce(a.grp[i].C, splits, C[i], M[i], N[i], ldc[i], nullptr, accumulate, EPI_NONE, nullptr, 0, stream);
       if (rc != MTVAF_OK) return rc;
     }
   }
   for (int i = 0; dbias && i < n; ++i)
     if (dbias[i]) {
-      const int rc = mtvaf_colsum(A[i], K, M[i], lda[i], dbias[i], 0, workspace, workspace_bytes, stream);
+      const int rc = mtvaf_colsum(A[i], K, M[i], lda[i], dbias[i], accumulate, workspace, workspace_bytes, stream);
       if (rc != MTVAF_OK) return rc;
     }
   return MTVAF_OK;
@@ -1306,7 +1310,7 @@ static int dw_group_impl(int n, const float* const* A, const int* lda, const flo
 int mtvaf_gemm_f32_dw_group(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
                             const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt,
                             void* workspace, size_t workspace_bytes, int splits, hipStream_t stream) {
-  return dw_group_impl(n, A, lda, B, ldb, C, ldc, M, N, K, klist, kcnt, nullptr, workspace, workspace_bytes, splits, stream);
+  return dw_group_impl(n, A, lda, B, ldb, C, ldc, M, N, K, klist, kcnt, nullptr, workspace, workspace_bytes, splits, 0, stream);
 }
 
 // mtvaf_gemm_f32_dw_group + the bias gradients that go with the weight gradients: dbias[i] (nullable) <- column sums of A_i
@@ -1314,7 +1318,15 @@ int mtvaf_gemm_f32_dw_group(int n, const float* const* A, const int* lda, const 
 int mtvaf_gemm_f32_dw_group_bias(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
                                  const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt,
                                  float* const* dbias, void* workspace, size_t workspace_bytes, int splits, hipStream_t stream) {
-  return dw_group_impl(n, A, lda, B, ldb, C, ldc, M, N, K, klist, kcnt, dbias, workspace, workspace_bytes, splits, stream);
+  return dw_group_impl(n, A, lda, B, ldb, C, ldc, M, N, K, klist, kcnt, dbias, workspace, workspace_bytes, splits, 0, stream);
+}
+// mtvaf_gemm_f32_dw_group[_bias] (dbias nullable) with an `accumulate` flag: != 0 -> dW_i += the product, dbias_i += the column sums,
+// each one add behind the value the overwriting form stores (same plan, same kernels); 0: the entries above, bit for bit.
+int mtvaf_gemm_f32_dw_group_acc(int n, const float* const* A, const int* lda, const float* const* B, const int* ldb, float* const* C,
+                                const int* ldc, const int* M, const int* N, int K, const int* klist, const int* kcnt,
+                                float* const* dbias, void* workspace, size_t workspace_bytes, int splits, int accumulate,
+                                hipStream_t stream) {
+  return dw_group_impl(n, A, lda, B, ldb, C, ldc, M, N, K, klist, kcnt, dbias, workspace, workspace_bytes, splits, accumulate, stream);
 }
 
 // Same contract as mtvaf_gemm_f32 (fp32 operands and results in memory), but the products run on the bf16

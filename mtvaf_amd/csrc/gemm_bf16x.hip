@@ -769,8 +769,8 @@ size_t mtvaf_streamk_scratch_bytes(int blocks) { return SK_HEADER + (size_t)std:
 // fp32 results) that share the reduction length K -- the four products of one encoder layer -- in ONE stream-K launch of the
 // 256x256 kernel: 36 + 36 + 27 + 9 output tiles cannot fill 256 CUs one product at a time.  Requires a scratch attached to
 // `stream` (MTVAF_ERR_WORKSPACE otherwise), M_i % 256 == 0, N_i % 256 == 0, K % 64 == 0, leading dimensions % 8 == 0.
-int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
-                              const int* ldc32, const int* M, const int* N, int K, hipStream_t stream) {
+static int bf16x_dw_group_run(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
+                              const int* ldc32, const int* M, const int* N, int K, int accumulate, hipStream_t stream) {
   if (n < 1 || n > 4 || K <= 0 || K % 64) return MTVAF_ERR_SHAPE;
   P256SK sk = {};
   int blocks = 0;
@@ -789,6 +789,8 @@ int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const
   a.A = sk.pr[0].A; a.B = sk.pr[0].B; a.C32 = sk.pr[0].C32;
   a.M = M[0]; a.N = N[0]; a.K = K; a.lda = lda[0]; a.ldb = ldb[0]; a.ldc32 = ldc32[0]; a.k_chunk = K; a.tiles_n = N[0] / 256;
   a.epi = EPI_NONE;
+  // (the block that FINISHES a tile adds the destination's old value behind the combined contributions; a contributing block never reads it)
+  a.accumulate = accumulate ? 1 : 0;
   long flop_m = 0;
   for (int i = 0; i < n; ++i) flop_m += (long)M[i] * N[i];
   const int key[8] = {300 + 1 + 4 + 8 + 16 + 64 + 128 + 256, 1, 1, 2, (int)(flop_m / 768), 768, K, n};  // (M x 768 x K: the group's flops)
@@ -798,6 +800,35 @@ int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const
   const int rc = launch_p256_streamk(a, sk, 1, 1, blocks, sk.KT / S, stream);
   prof_end(rec, stream);
   return rc;
+}
+
+// The cut mtvaf_gemm_bf16x_dw_group[_acc] takes for these products on `stream`: the pieces S every tile's reduction is divided into
+// (1: whole tiles, no contribution and no finisher; S > 1: S - 1 contributing blocks and one finishing block per tile).  0: the call
+// would be refused (shapes, or no scratch attached to the stream).  The same planner call as the launch's.
+int mtvaf_gemm_bf16x_dw_group_pieces(int n, const int* M, const int* N, int K, hipStream_t stream) {
+  if (n < 1 || n > 4 || !M || !N || K <= 0 || K % 64) return 0;
+  P256SK sk = {};
+  int blocks = 0;
+  if (!streamk_lookup(stream, &sk, &blocks)) return 0;
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    if (M[i] <= 0 || N[i] <= 0 || M[i] % 256 || N[i] % 256) return 0;
+    tiles += (long)(M[i] / 256) * (N[i] / 256);
+  }
+  int S = 1;
+  p256_plan(tiles, K / 64, blocks, &S);
+  return S;
+}
+
+int mtvaf_gemm_bf16x_dw_group(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
+                              const int* ldc32, const int* M, const int* N, int K, hipStream_t stream) {
+  return bf16x_dw_group_run(n, A, lda, B, ldb, C32, ldc32, M, N, K, 0, stream);
+}
+// ... with an `accumulate` flag: != 0 -> C32_i += the product (the tile's value, combined in k order as always, then one add of the
+// old value); 0: the entry above, bit for bit.
+int mtvaf_gemm_bf16x_dw_group_acc(int n, const void* const* A, const int* lda, const void* const* B, const int* ldb, float* const* C32,
+                                  const int* ldc32, const int* M, const int* N, int K, int accumulate, hipStream_t stream) {
+  return bf16x_dw_group_run(n, A, lda, B, ldb, C32, ldc32, M, N, K, accumulate, stream);
 }
 
 // out[c] (+)= sum over rows of part[rows][cols] (fixed order): finishes the epilogue column sums of mtvaf_gemm_bf16x

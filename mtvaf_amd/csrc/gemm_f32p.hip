@@ -109,7 +109,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f32p16_kernel(GemmArgsP p) {
         float t = red[tid & 63];
 #pragma unroll
         for (int i = 1; i < 8; ++i) t += red[i * 64 + (tid & 63)];
-        jb.dst[c] = t;
+        jb.dst[c] = p.accumulate ? jb.dst[c] + t : t;  // (accumulating form: the old value is added last)
       }
       return;
     }
@@ -656,10 +656,11 @@ int mtvaf_gemm_f32p_slabs(int layout_a, const void* Aplanes, long a_plane, long 
 // b_kt, b_col (see mtvaf_gemm_f32p; tile-blocked images: row 64, k-tile 2048, col 12 x K x 64).  M_i, N_i % 128 == 0, K % 32 == 0.
 static int f32p_dw_group_run(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C, const int* ldc,
                              const int* M, const int* N, int K, int njobs, const float* const* cs_src, const int* cs_rows, const int* cs_cols,
-                             const int* cs_ld, float* const* cs_dst, hipStream_t stream) {
+                             const int* cs_ld, float* const* cs_dst, int accumulate, hipStream_t stream) {
   if (n < 1 || n > 4 || !Aplanes || !Bplanes || !strides || !C || !ldc || !M || !N || K <= 0 || K % 32) return MTVAF_ERR_ARG;
   GemmArgsP a = {};
   a.K = K; a.k_chunk = K; a.slab_stride = 0; a.epi = EPI_NONE; a.ngrp = n;
+  a.accumulate = accumulate ? 1 : 0;  // (tiles and column-sum jobs alike: dst = old + result, one add behind the finished value)
   long tiles = 0;
   bool wide = (g_p16_wide & 4) != 0;
   for (int i = 0; i < n && wide; ++i) wide = N[i] > 0 && N[i] % 256 == 0;
@@ -701,7 +702,7 @@ static int f32p_dw_group_run(int n, const void* const* Aplanes, const void* cons
 
 int mtvaf_gemm_f32p_dw_group(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C, const int* ldc,
                              const int* M, const int* N, int K, hipStream_t stream) {
-  return f32p_dw_group_run(n, Aplanes, Bplanes, strides, C, ldc, M, N, K, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  return f32p_dw_group_run(n, Aplanes, Bplanes, strides, C, ldc, M, N, K, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
 // ... with up to eight COLUMN-SUM jobs as extra blocks of the same launch: job j sums the fp32 matrix cs_src[j] [cs_rows[j]][cs_cols[j]]
 // (leading dimension cs_ld[j]) over its rows into cs_dst[j] [cs_cols[j]], fixed summation order.  The small reductions of a layer's
@@ -712,7 +713,17 @@ int mtvaf_gemm_f32p_dw_group_colsum(int n, const void* const* Aplanes, const voi
                                     const int* ldc, const int* M, const int* N, int K, int njobs, const float* const* cs_src,
                                     const int* cs_rows, const int* cs_cols, const int* cs_ld, float* const* cs_dst, hipStream_t stream) {
   if (njobs < 1) return MTVAF_ERR_ARG;
-  return f32p_dw_group_run(n, Aplanes, Bplanes, strides, C, ldc, M, N, K, njobs, cs_src, cs_rows, cs_cols, cs_ld, cs_dst, stream);
+  return f32p_dw_group_run(n, Aplanes, Bplanes, strides, C, ldc, M, N, K, njobs, cs_src, cs_rows, cs_cols, cs_ld, cs_dst, 0, stream);
+}
+// The two entries above with an `accumulate` flag (njobs may be 0): != 0 -> every weight-gradient tile stores old + product and every
+// column-sum job old + sum -- the product and the sum are formed exactly as by the overwriting form (same MFMA order, same summation
+// order) and the destination's old value is added once, last: gradient accumulation over micro-batches on the launch that carries the
+// step.  accumulate == 0: the entries above, bit for bit.
+int mtvaf_gemm_f32p_dw_group_acc(int n, const void* const* Aplanes, const void* const* Bplanes, const long* strides, float* const* C,
+                                 const int* ldc, const int* M, const int* N, int K, int njobs, const float* const* cs_src,
+                                 const int* cs_rows, const int* cs_cols, const int* cs_ld, float* const* cs_dst, int accumulate,
+                                 hipStream_t stream) {
+  return f32p_dw_group_run(n, Aplanes, Bplanes, strides, C, ldc, M, N, K, njobs, cs_src, cs_rows, cs_cols, cs_ld, cs_dst, accumulate, stream);
 }
 
 }  // extern "C"

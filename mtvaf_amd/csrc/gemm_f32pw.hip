@@ -74,7 +74,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f32p16w_kernel(GemmArgsP p) {
         float t = red[tid & 63];
 #pragma unroll
         for (int i = 1; i < 8; ++i) t += red[i * 64 + (tid & 63)];
-        jb.dst[c] = t;
+        jb.dst[c] = p.accumulate ? jb.dst[c] + t : t;  // (accumulating form: the old value is added last)
       }
       return;
     }

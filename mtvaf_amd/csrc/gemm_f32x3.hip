@@ -589,7 +589,10 @@ __global__ __launch_bounds__(512, 1) void gemm_f32x3_ws_kernel(GemmArgs p) {
           csum.z += __shfl_xor(csum.z, d, 64);
           csum.w += __shfl_xor(csum.w, d, 64);
         }
-        if (kq_ == 0) *reinterpret_cast<f32x4*>(colsum + m0 + c4_) = csum;
+        if (kq_ == 0) {
+          f32x4* const d = reinterpret_cast<f32x4*>(colsum + m0 + c4_);
+          *d = p.accumulate ? *d + csum : csum;  // (accumulating form: the old value is added last)
+        }
       }
     }
   }

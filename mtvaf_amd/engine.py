@@ -690,7 +690,12 @@ def _native_backward(ctx, douts):
     dev = x0.device
     dpkv = torch.empty_like(pkv) if Pn else None
     need_param_grads = any(p.requires_grad for p in params)
-    gviews = grad_sink.acquire(params) if grad_sink is not None else None
+    # fused accumulation (GradSink.accumulate_passes, opt-in): a node may ADD into the flat buffers only where this function would
+    # also install them as .grad itself -- the conditions of `direct` below
+    can_acc = bool(grad_sink is not None and grad_sink.accumulate_passes and DIRECT_GRADS and not _has_grad_hooks(params)
+                   and not _ddp_without_gradsync(grad_sink))
+    gviews = (grad_sink.acquire(params, can_accumulate=True) if can_acc else grad_sink.acquire(params)) if grad_sink is not None else None
+    acc = bool(can_acc and gviews is not None and grad_sink.accumulate)  # every .grad IS its flat view already: the executor adds
     if grad_sink is not None:
         grad_sink.token_rows = M
     # zero-copy gradients bypass AccumulateGrad: only when nobody listens there (tensor hooks, post-accumulate hooks).  NOT
@@ -809,6 +814,7 @@ def _native_backward(ctx, douts):
         # (the caller vouches that masked token rows carry exactly-zero gradients -- cfg[5], BertModel.allow_unpad: the contract of
         # the k-tile lists, which the bf16 kernels do not take by default)
         gs.zero_tail = int(zero_tail)
+        gs.accumulate = int(acc)
         hip._ck(fn(ctypes.byref(st), ctypes.byref(gs), main_h, side_h, settle), "mtvaf_encoder_layer_bwd")
         if gviews is None:
             G[0], G[2], G[4] = dwqkv[:H], dwqkv[H:2 * H], dwqkv[2 * H:]
@@ -817,8 +823,9 @@ def _native_backward(ctx, douts):
         if direct:
             # zero-copy fast path: the flat-buffer views become .grad directly (what AccumulateGrad would do with a
             # stolen gradient), and autograd is handed None for these 16 inputs -- 192 accumulation nodes less per step
-            for p, gt in zip(params[base_i:base_i + N_LAYER_PARAMS], G):
-                p.grad = gt
+            if not acc:  # (an accumulating node found them installed)
+                for p, gt in zip(params[base_i:base_i + N_LAYER_PARAMS], G):
+                    p.grad = gt
         else:
             pgrads[base_i:base_i + N_LAYER_PARAMS] = G
         if grad_sink is not None:

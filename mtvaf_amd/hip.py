@@ -48,6 +48,7 @@ _SIGS = {
     "mtvaf_f32p_wide": (c_int, [I]),
     "mtvaf_gemm_f32p_dw_group": (c_int, [I, P, P, P, P, P, P, P, I, P]),
     "mtvaf_gemm_f32p_dw_group_colsum": (c_int, [I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P]),
+    "mtvaf_gemm_f32p_dw_group_acc": (c_int, [I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, I, P]),
     "mtvaf_gemm_f32p_slabs": (c_int, [I, P, L, L, L, L, I, P, L, L, L, L, P, I, I, I, I, P, I, I, P, SZ, P, P]),
     "mtvaf_gemm_f32p_ep": (c_int, [I, P, L, L, L, L, I, P, L, L, L, L, P, I, P, P, I, I, I, P, I, P, I, I, P]),
     "mtvaf_gemm_bf16": (c_int, [I, I, P, I, P, I, P, I, I, I, I, P, I, P, I, I, I, P, SZ, I, I, P]),
@@ -140,6 +141,7 @@ _SIGS = {
     "mtvaf_embed_ln_bwd_workspace_bytes": (SZ, [I, I, I, I]),
     "mtvaf_gemm_f32_dw_group": (c_int, [I, P, P, P, P, P, P, P, P, I, P, P, P, SZ, I, P]),
     "mtvaf_gemm_f32_dw_group_bias": (c_int, [I, P, P, P, P, P, P, P, P, I, P, P, P, P, SZ, I, P]),
+    "mtvaf_gemm_f32_dw_group_acc": (c_int, [I, P, P, P, P, P, P, P, P, I, P, P, P, P, SZ, I, I, P]),
     "mtvaf_gemm_f32_dw_group_workspace_bytes": (SZ, [I, P, P, I, I]),
     "mtvaf_dw_group_rows": (c_int, [I]),
     "mtvaf_dw_group_wanted": (c_int, [I, I, I]),
@@ -147,6 +149,8 @@ _SIGS = {
     "mtvaf_streamk_scratch_bytes": (SZ, [I]),
     "mtvaf_streamk_attached": (c_int, [P]),
     "mtvaf_gemm_bf16x_dw_group": (c_int, [I, P, P, P, P, P, P, P, P, I, P]),
+    "mtvaf_gemm_bf16x_dw_group_acc": (c_int, [I, P, P, P, P, P, P, P, P, I, I, P]),
+    "mtvaf_gemm_bf16x_dw_group_pieces": (c_int, [I, P, P, I, P]),
     "mtvaf_cast_bf16": (c_int, [P, I, P, I, P, I, I, I, P]),
     "mtvaf_adamw": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, P, I, P]),
     "mtvaf_adamw_planes": (c_int, [P, P, P, P, L, F, c_double, c_double, F, F, F, F, F, I, P, P, P, P, I, P]),
@@ -187,7 +191,7 @@ class LayerGradsStruct(ctypes.Structure):
                                                                             ("ws_side_bytes", c_size_t), ("klist", c_void_p),
                                                                             ("kcnt", c_void_p), ("zero_tail", c_int),
                                                                             ("lnpart2", c_void_p), ("lnpart1", c_void_p)] +
-                [(n, c_void_p) for n in ("df_p", "dpre_p", "da_p", "dqkv_p")])
+                [(n, c_void_p) for n in ("df_p", "dpre_p", "da_p", "dqkv_p")] + [("accumulate", c_int)])
 
 
 _lib = None
@@ -447,10 +451,11 @@ def _km_strides(pl: "Planes"):
     return (pl.s_plane, 64, 32 * 64, 4 * pl.s_kt)  # tile-blocked [cols / 32][3][rows][32]: a 32-column block is pl.s_kt apart
 
 
-def gemm_planes_dw_group(items, colsum=None):
+def gemm_planes_dw_group(items, colsum=None, accumulate=False):
     """items: up to four (a: Planes of dY [K, M], b: Planes of X [K, N], out [M, N] fp32): out = dY^T . X for each, one unsplit launch
     (mtvaf_gemm_f32p_dw_group; natural or tile-blocked images).  colsum = (src fp32 [K, C], dst [C]): dst = column sums of src, as
-    extra blocks of the same launch; or a list of up to eight such pairs."""
+    extra blocks of the same launch; or a list of up to eight such pairs.  accumulate: every out and every dst is ADDED to (the value the
+    overwriting form stores, then one add of the old value: mtvaf_gemm_f32p_dw_group_acc)."""
     n = len(items)
     K = items[0][0].rows
     assert all(a.rows == K and b.rows == K for a, b, _ in items)
@@ -459,6 +464,19 @@ def gemm_planes_dw_group(items, colsum=None):
     st = []
     for a, b, _ in items:
         st += list(_km_strides(a)) + list(_km_strides(b))
+    if accumulate:
+        jobs = [] if colsum is None else ([colsum] if isinstance(colsum, tuple) else list(colsum))
+        nj = len(jobs)
+        pj = lambda ts: (ctypes.c_void_p * max(nj, 1))(*[_p(t) for t in ts])
+        ij = lambda xs: (ctypes.c_int * max(nj, 1))(*xs)
+        _ck(lib().mtvaf_gemm_f32p_dw_group_acc(n, vp([a.img for a, _, _ in items]), vp([b.img for _, b, _ in items]),
+                                               (ctypes.c_long * (8 * n))(*st), vp([o for _, _, o in items]),
+                                               ia([o.stride(0) for _, _, o in items]), ia([a.cols for a, _, _ in items]),
+                                               ia([b.cols for _, b, _ in items]), K, nj, pj([s_ for s_, _ in jobs]),
+                                               ij([s_.shape[0] for s_, _ in jobs]), ij([s_.shape[1] for s_, _ in jobs]),
+                                               ij([s_.stride(0) for s_, _ in jobs]), pj([d for _, d in jobs]), 1, _st()),
+            "mtvaf_gemm_f32p_dw_group_acc")
+        return
     if colsum is not None:
         jobs = [colsum] if isinstance(colsum, tuple) else list(colsum)
         nj = len(jobs)
@@ -1403,11 +1421,12 @@ def dw_group_wanted(rows: int, H: int, I: int) -> bool:
     return bool(lib().mtvaf_dw_group_wanted(rows, H, I))
 
 
-def gemm_f32_dw_group(items, K, ktiles=None, splits=-1, dbias=None):
+def gemm_f32_dw_group(items, K, ktiles=None, splits=-1, dbias=None, accumulate=False):
     """items: up to four (a [K,M] fp32, b [K,N] fp32, out [M,N] fp32): out = a^T . b for each, ONE launch (the 128x96 LDS-DMA
     kernel, or -- split arithmetic, K > 1024, whole 128x128 tiles -- the GROUP form of the wave-specialised split kernel) + one
     ordered slab reduction per product when the reduction is split.  dbias: list of len(items) tensors / None -- dbias[i] [M]
-    <- column sums of a over its K rows (the bias gradient that goes with the weight gradient)."""
+    <- column sums of a over its K rows (the bias gradient that goes with the weight gradient).  accumulate: out and dbias are ADDED to
+    (mtvaf_gemm_f32_dw_group_acc: the same plan, the old value added last)."""
     n = len(items)
     vp = lambda ts: (ctypes.c_void_p * n)(*[_p(t) for t in ts])
     ia = lambda xs: (ctypes.c_int * n)(*xs)
@@ -1418,7 +1437,14 @@ def gemm_f32_dw_group(items, K, ktiles=None, splits=-1, dbias=None):
         wsb = max(wsb, max(int(lib().mtvaf_colsum_workspace_bytes(K, t.shape[1])) for t in As))
     ws = workspace(max(wsb, 16), As[0].device)
     kl, kc = (ktiles if ktiles is not None else (None, None))
-    if dbias is None:
+    if accumulate:
+        if dbias is not None:
+            assert len(dbias) == n
+            _f32(*[t for t in dbias if t is not None])
+        _ck(lib().mtvaf_gemm_f32_dw_group_acc(n, vp(As), ia([t.stride(0) for t in As]), vp(Bs), ia([t.stride(0) for t in Bs]), vp(Cs),
+                                              ia([t.stride(0) for t in Cs]), Ms, Ns, K, _p(kl), _p(kc), vp(dbias) if dbias is not None else None,
+                                              _p(ws), ws.numel(), splits, 1, _st()), "mtvaf_gemm_f32_dw_group_acc")
+    elif dbias is None:
         _ck(lib().mtvaf_gemm_f32_dw_group(n, vp(As), ia([t.stride(0) for t in As]), vp(Bs), ia([t.stride(0) for t in Bs]), vp(Cs),
                                           ia([t.stride(0) for t in Cs]), Ms, Ns,
                                           K, _p(kl), _p(kc), _p(ws), ws.numel(), splits, _st()), "mtvaf_gemm_f32_dw_group")
@@ -1430,16 +1456,31 @@ def gemm_f32_dw_group(items, K, ktiles=None, splits=-1, dbias=None):
                                                splits, _st()), "mtvaf_gemm_f32_dw_group_bias")
 
 
-def gemm_bf16x_dw_group(items, K):
+def gemm_bf16x_dw_group(items, K, accumulate=False):
     """items: up to four (a [K,M] bf16, b [K,N] bf16, out [M,N] fp32): out = a^T . b for each, ONE stream-K launch."""
     n = len(items)
     vp = lambda ts: (ctypes.c_void_p * n)(*[_p(t) for t in ts])
     ia = lambda xs: (ctypes.c_int * n)(*xs)
     As, Bs, Cs = [i[0] for i in items], [i[1] for i in items], [i[2] for i in items]
     streamk_ensure(As[0].device)
+    if accumulate:  # (out += a^T . b: the block that finishes a tile adds the old value last)
+        _ck(lib().mtvaf_gemm_bf16x_dw_group_acc(n, vp(As), ia([t.stride(0) for t in As]), vp(Bs), ia([t.stride(0) for t in Bs]), vp(Cs),
+                                                ia([t.stride(0) for t in Cs]), ia([t.shape[1] for t in As]), ia([t.shape[1] for t in Bs]),
+                                                K, 1, _st()), "mtvaf_gemm_bf16x_dw_group_acc")
+        return
     _ck(lib().mtvaf_gemm_bf16x_dw_group(n, vp(As), ia([t.stride(0) for t in As]), vp(Bs), ia([t.stride(0) for t in Bs]), vp(Cs),
                                         ia([t.stride(0) for t in Cs]), ia([t.shape[1] for t in As]), ia([t.shape[1] for t in Bs]),
                                         K, _st()), "mtvaf_gemm_bf16x_dw_group")
+
+
+def gemm_bf16x_dw_group_pieces(shapes, K, device=None) -> int:
+    """shapes: the (M, N) of up to four products over K token rows -> the pieces every tile's reduction is cut into by
+    gemm_bf16x_dw_group on the current stream (1: whole tiles; > 1: tiles are shared between blocks; 0: the launch would be refused)."""
+    n = len(shapes)
+    ia = lambda xs: (ctypes.c_int * n)(*xs)
+    if device is not None:
+        streamk_ensure(device)
+    return int(lib().mtvaf_gemm_bf16x_dw_group_pieces(n, ia([m for m, _ in shapes]), ia([c for _, c in shapes]), K, _st()))
 
 
 def colsum_small(part, out, accumulate=False):

@@ -727,6 +727,24 @@ class TVNetSAModel(nn.Module):
         -> ``TokenClassifierOutput(loss=combined, logits=plain logits)``; with ``return_parts`` also a dict: ``loss``
         (plain), ``cutoff_loss``, ``js`` (unweighted, detached), ``cutoff_logits`` -- None where a term was not computed."""
         w_ce, w_js = _arg(self.args, "aug_ce_loss", 1.0), _arg(self.args, "aug_js_loss", 1.0)
+        # args.fused_accumulation (opt-in, DESIGN.md 4.21): the two encoder nodes of this step share the flat gradient buffers -- the first
+        # one the backward runs writes them, the second adds into them -- instead of sending both to the allocate-and-accumulate
+        # fallback.  The sink goes back to its setting when that backward ends, or here if anything below raises.
+        sink = self.bert.encoder.grad_sink if (_arg(self.args, "fused_accumulation") and torch.is_grad_enabled()
+                                               and (w_ce > 0 or w_js > 0)) else None
+        if sink is None:
+            return self._cutoff_passes(w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
+                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts)
+        sink.begin_two_node_pass()
+        try:
+            return self._cutoff_passes(w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
+                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts)
+        except BaseException:
+            sink.end_two_node_pass()
+            raise
+
+    def _cutoff_passes(self, w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
+                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts):
         prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True)
         batch = (prompt_attention_mask, input_ids, attention_mask, token_type_ids, start_positions, end_positions,
                  span_starts, span_ends, polarity_labels, label_masks)

@@ -210,7 +210,14 @@ class GradSink:
     ``param.grad is None`` -- AccumulateGrad only runs once both edges have arrived -- so the flat buffer must not be
     handed to both: the second node would overwrite the views already sitting in autograd's input buffer.  Nodes are
     therefore counted when they are created (``node_created``) and the flat buffers are used only while a single one
-    is outstanding; the count is cleared when the backward pass that consumed them ends."""
+    is outstanding; the count is cleared when the backward pass that consumed them ends.
+
+    Fused accumulation (opt-in: ``accumulate_passes = k`` >= 1, ``nodes_per_pass``) replaces that fallback
+    for a caller that can ADD into the flat buffers and installs them as ``.grad`` itself (``acquire(params, can_accumulate=True)``:
+    the native backward with zero-copy gradients).  A node that finds every ``.grad`` None writes the buffers; a node that finds
+    every ``.grad`` to be exactly its flat view adds into them (``accumulate``) and hands autograd None -- the later micro-batches
+    of a step, or the second of the cutoff step's two nodes; anything else is the fallback above.  ``layer_done`` then reports a
+    layer only from the last node of pass k (``final``).  With ``accumulate_passes == 0`` (default) nothing of this applies."""
 
     def __init__(self, stores: List[_LayerStore]):
         self.stores = stores
@@ -222,6 +229,16 @@ class GradSink:
         self.optimizer = None  # the mtvaf_amd.optim.AdamW attached to this encoder, if any (GradSync re-wires through it)
         self.live_nodes = 0
         self._reset_armed = False
+        # fused accumulation (opt-in).  accumulate_passes = k >= 1: the gradients of a step are complete after k
+        # backward passes of nodes_per_pass encoder nodes each, and every node after the first ADDS into the flat buffers
+        # (mtvaf_layer_grads_t::accumulate) instead of sending the pass to the fallback.  0: off, acquire() is what it always was.
+        self.accumulate_passes = 0
+        self.nodes_per_pass = 1
+        self.accumulate = False  # acquire()'s word to the engine for the node in hand: add into the flat buffers
+        self.final = True        # ... and: this node completes the step's gradients (layer_done reports them)
+        self._pass = 0           # backward passes completed since the last reset_passes()
+        self._nodes_run = 0      # encoder nodes that have run in the backward pass in flight
+        self._two_node_saved = None  # (accumulate_passes, nodes_per_pass) from before begin_two_node_pass()
 
     def node_created(self):
         self.live_nodes += 1
@@ -229,15 +246,76 @@ class GradSink:
     def _pass_done(self):
         self.live_nodes = 0
         self._reset_armed = False
+        if self.accumulate_passes:
+            self._pass += 1
+            self._nodes_run = 0
+        self.end_two_node_pass()  # (a two-node setting lasts for the one pass it was made for)
 
-    def acquire(self, params):
+    def reset_passes(self):
+        """A new step begins (optimizer.step() / zero_grad): the next backward pass is the first of its accumulation."""
+        self._pass = 0
+        self._nodes_run = 0
+
+    def last_pass(self) -> bool:
+        """Is the backward pass in flight (or, between passes, the next one) the one that completes the step's gradients?"""
+        return self.accumulate_passes <= 1 or self._pass >= self.accumulate_passes - 1
+
+    def begin_two_node_pass(self):
+        """The next backward pass holds TWO encoder nodes (TVNetSAModel.forward_with_cutoff): the first one the engine runs
+        writes the flat buffers, the second adds into them.  The previous setting comes back when that pass ends
+        (``_pass_done``) or with ``end_two_node_pass``; accumulation over passes, if on, stays on."""
+        if self._two_node_saved is None:
+            self._two_node_saved = (self.accumulate_passes, self.nodes_per_pass)
+            self.accumulate_passes, self.nodes_per_pass = max(1, self.accumulate_passes), 2
+
+    def end_two_node_pass(self):
+        if self._two_node_saved is not None:
+            self.accumulate_passes, self.nodes_per_pass = self._two_node_saved
+            self._two_node_saved = None
+
+    def _flat_state(self, params):
+        """'none': every .grad is None; 'flat': every .grad is exactly its view of the flat gradient buffers (same storage, offset,
+        shape, contiguous -- checked, not assumed); 'other': anything else."""
+        if all(p.grad is None for p in params):
+            return "none"
+        i = 0
+        for st in self.stores:
+            if st.grad is None:
+                return "other"
+            for v in st.grad_views():
+                g = params[i].grad
+                if (g is None or g.data_ptr() != v.data_ptr() or g.shape != v.shape or g.dtype != v.dtype or not g.is_contiguous()
+                        or g.untyped_storage().data_ptr() != v.untyped_storage().data_ptr()):
+                    return "other"
+                i += 1
+        return "flat" if i == len(params) else "other"
+
+    def acquire(self, params, can_accumulate=False):
+        """can_accumulate: the caller can add into the flat buffers and installs them as ``.grad`` itself (the native executor with
+        zero-copy gradients); without it -- and with ``accumulate_passes`` 0 -- this is the rule it always was."""
         if not self._reset_armed:  # (always called from inside a backward pass)
             self._reset_armed = True
             torch.autograd.Variable._execution_engine.queue_callback(self._pass_done)
-        self.fast = (self.live_nodes <= 1 and all(p.requires_grad for p in params)
-                     and all(p.grad is None for p in params))
+        self.accumulate, self.final = False, True
+        if not (self.accumulate_passes and can_accumulate):
+            self.fast = (self.live_nodes <= 1 and all(p.requires_grad for p in params)
+                         and all(p.grad is None for p in params))
+            if not self.fast:
+                return None
+            views = []
+            for st in self.stores:
+                views.extend(st.grad_views())
+            return views
+        node = self._nodes_run
+        self._nodes_run += 1
+        state = self._flat_state(params) if (self.live_nodes <= self.nodes_per_pass and all(p.requires_grad for p in params)) else "other"
+        if state == "none" and node == 0 and self._pass > 0:
+            self._pass = 0  # (gradients were cleared without a word to the sink: a new accumulation begins here)
+        self.fast = state != "other"
         if not self.fast:
             return None
+        self.accumulate = state == "flat"
+        self.final = self.last_pass() and node + 1 >= self.nodes_per_pass
         views = []
         for st in self.stores:
             views.extend(st.grad_views())
@@ -248,6 +326,8 @@ class GradSink:
 
     def layer_done(self, li):
         if self.on_layer_done is not None:
+            if self.fast and not self.final:
+                return  # (fused accumulation: the layer's gradients are not complete yet -- nobody is told)
             self.on_layer_done(li, self.stores[li].grad if self.fast else None)
 
 
@@ -275,6 +355,7 @@ class BertEncoder(nn.Module):
                 self._sink.on_layer_done, self._sink.settle_params = old.on_layer_done, old.settle_params
                 self._sink.raw_stream_hook = old.raw_stream_hook
                 self._sink.optimizer = old.optimizer
+                self._sink.accumulate_passes, self._sink.nodes_per_pass = old.accumulate_passes, old.nodes_per_pass
         return self._stores, self._sink
 
     @property

@@ -96,7 +96,9 @@ class AdamW(torch.optim.Optimizer):
     the next backward (the reference trainer's flow with gradient_accumulation_steps = 1, modules/train.py:620-625);
     a second backward without a ``step()`` raises -- with or without ``zero_grad`` in between, so gradient accumulation
     (gradient_accumulation_steps > 1, train.py:616-625) cannot silently train the encoder on one micro-batch: use
-    ``overlap=False`` for it (``build_optimizer`` does).  ``step()`` then only updates what is left (embeddings, heads,
+    ``overlap=False`` for it (``build_optimizer`` does), or ``accumulation_steps=k`` (fused accumulation, DESIGN.md 4.21: the first k - 1
+    backward passes add into the flat gradient buffers and update nothing, pass k updates each layer from inside its backward, a
+    (k + 1)-th pass without ``step()`` raises; with ``overlap=False`` the k passes simply share the flat buffers).  ``step()`` then only updates what is left (embeddings, heads,
     prompt generator) and layers that could not take the fast path.
 
     ``max_grad_norm > 0``: gradients are clipped by their global L2 norm (``torch.nn.utils.clip_grad_norm_``'s rule) INSIDE the
@@ -129,7 +131,8 @@ class AdamW(torch.optim.Optimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None, max_grad_norm: float = 0.0,
-                 track_grad_norm: bool = False, skip_nonfinite: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True):
+                 track_grad_norm: bool = False, skip_nonfinite: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True,
+                 accumulation_steps: int = 1):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
         max_grad_norm = float(max_grad_norm or 0.0)
@@ -153,6 +156,12 @@ class AdamW(torch.optim.Optimizer):
         self.skipped_steps = None   # device int32: steps whose norm was not finite (skip_nonfinite)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.overlap = overlap
+        accumulation_steps = int(accumulation_steps or 1)
+        if accumulation_steps < 1:
+            raise ValueError("accumulation_steps must be >= 1")
+        if accumulation_steps > 1 and model is None:
+            raise ValueError("mtvaf_amd.optim.AdamW: accumulation_steps > 1 is the encoder's fused accumulation and needs `model`")
+        self.accumulation_steps = accumulation_steps
         self._encoder = None
         self._layer_group: Dict[int, Optional[dict]] = {}
         self._early = set()
@@ -174,6 +183,13 @@ class AdamW(torch.optim.Optimizer):
         self._background_ok = grad_sync is None
         sink = enc.grad_sink
         sink.optimizer = self  # (a GradSync constructed later re-wires the hook through this, parallel.py)
+        if self.accumulation_steps > 1:
+            # fused accumulation: passes 1 .. k-1 add into the flat gradient buffers and report nothing; pass k reports every layer
+            # with its complete gradient, so the in-backward update (overlap=True) and step() see final gradients only
+            sink.accumulate_passes = self.accumulation_steps
+            sink.reset_passes()
+            if grad_sync is not None:
+                grad_sync.accumulation_steps = self.accumulation_steps
         if self.overlap:
             sink.settle_params = True  # the hook's stream must also be behind the layer's last dX product (engine.py)
             if grad_sync is not None:
@@ -441,12 +457,22 @@ class AdamW(torch.optim.Optimizer):
         hip.grad_clip_finalize(part, self.max_grad_norm, self._clip_state, self.skipped_steps, self.skip_nonfinite)
         return self._clip_state
 
+    def _new_accumulation(self):
+        sink = getattr(self._encoder, "_sink", None) if self._encoder is not None else None
+        if sink is not None and sink.accumulate_passes:
+            sink.reset_passes()
+
+    def zero_grad(self, set_to_none: bool = True):
+        super().zero_grad(set_to_none=set_to_none)
+        self._new_accumulation()
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._new_accumulation()
         self._refuse_swapped("step() was called")
         clipping = self.max_grad_norm > 0.0 or self.track_grad_norm
         ema_on = self.ema_decay > 0.0
@@ -603,6 +629,25 @@ def linear_schedule_with_warmup(optimizer, num_warmup_steps: float, num_training
     return torch.optim.lr_scheduler.LambdaLR(optimizer, factor)
 
 
+def accumulation_plan(args):
+    """-> (overlap, fused accumulation steps): the ONE rule that picks how ``build_optimizer`` trains the encoder under
+    ``args.gradient_accumulation_steps`` (train.py:616-625 steps every `accum` backward passes).
+
+    * accum == 1: layers are updated from inside the backward pass (overlap) unless ``args.overlap_optimizer`` is off or a global
+      gradient norm is wanted (it exists only once the whole backward pass has ended: clipping / tracking step after it).
+    * accum > 1 without ``args.fused_accumulation``: (False, 1) -- the fallback: fresh gradient tensors per micro-batch, autograd adds
+      them, ``step()`` updates.
+    * accum > 1 with ``args.fused_accumulation``: (overlap under the conditions above, accum) -- the micro-batches add into the
+      encoder's flat gradient buffers and, with overlap, the last one updates each layer from inside its backward
+      (``AdamW(accumulation_steps=accum)``)."""
+    accum = int(getattr(args, "gradient_accumulation_steps", 1) or 1)
+    max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    fused = bool(getattr(args, "fused_accumulation", False)) and accum > 1
+    overlap = (bool(getattr(args, "overlap_optimizer", True)) and (accum == 1 or fused)
+               and not (max_grad_norm > 0.0 or bool(getattr(args, "track_grad_norm", False))))
+    return overlap, (accum if fused else 1)
+
+
 def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
     """-> (optimizer, scheduler) as SATrainer2.train() sets them up (train.py:574-578, 887-926)."""
     use_prefix = bool(getattr(args, "use_prefix", False))
@@ -627,11 +672,10 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
     if on_gpu:
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
-        accum = int(getattr(args, "gradient_accumulation_steps", 1) or 1)
-        # a global gradient norm exists only once the whole backward pass has ended: clipping / tracking steps after it
-        overlap = bool(getattr(args, "overlap_optimizer", True)) and accum == 1 and not (max_grad_norm > 0.0 or track_grad_norm)
+        overlap, fused_steps = accumulation_plan(args)
         opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
-                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                    **({"accumulation_steps": fused_steps} if fused_steps > 1 else {}))
     else:
         if max_grad_norm > 0.0:
             raise ValueError("build_optimizer: max_grad_norm is implemented by the gfx950 AdamW kernels; the CPU fallback "

@@ -74,7 +74,7 @@ def balanced_shards(lengths, world: int):
 class GradSync:
     def __init__(self, model: torch.nn.Module, process_group=None, force: bool = False, big_numel: int = 1 << 20,
                  compress: Optional[str] = "auto", seed_per_rank: bool = True, layer_buckets: Optional[int] = None,
-                 check_every: Optional[int] = None):
+                 check_every: Optional[int] = None, accumulation_steps: int = 1):
         if not dist.is_initialized():
             raise RuntimeError("GradSync needs an initialised process group (backend 'nccl' = RCCL on ROCm)")
         self.model = model
@@ -108,6 +108,12 @@ class GradSync:
                 self._bucket_size[b] = self._bucket_size.get(b, 0) + 1
         sink = self.encoder.grad_sink
         sink.on_layer_done = self._layer_done
+        # fused accumulation over k backward passes (the sink's pass count; mtvaf_amd.optim.AdamW(accumulation_steps=k) sets the same):
+        # nothing is exchanged before the last pass, one flat buffer per layer (and the parameters outside the encoder) on it
+        self.accumulation_steps = max(1, int(accumulation_steps or 1))
+        if self.accumulation_steps > 1:
+            sink.accumulate_passes = self.accumulation_steps
+            sink.reset_passes()
         # this hook records events and switches to the communication stream with torch's stream context: it must be
         # called under torch.cuda.stream(side), never through the raw-stream shortcut an optimizer attached EARLIER may
         # have asked for (engine._native_backward; otherwise the all-reduce could start before the layer's dW kernels end)
@@ -395,6 +401,10 @@ class GradSync:
     def _param_ready(self, p):
         if not self.enabled or (self.world == 1 and not self.force) or p.grad is None:
             return
+        if self.accumulation_steps > 1:
+            sink = self.encoder._sink
+            if sink is not None and sink.accumulate_passes and not sink.last_pass():
+                return  # (fused accumulation: this gradient is still a partial sum -- exchanged on the last pass)
         self._arm()
         self._submit(("P", self._outer_idx[id(p)]), self._param_issue(p, p.grad))
 
