@@ -416,8 +416,9 @@ int mtvaf_mean_l_bwd(const float* dmean, float* denc, long n, int L, int W4, mtv
  * H <= 1024).  `index` is a device int32 block of mtvaf_span_index_ints(B,S,M) entries that mtvaf_span_index fills
  * (valid-token compaction, per-span offsets/widths, text length and JR = widest span, clamped to S) -- the sizes
  * the reference reads back to the host stay on the device.  pooled [B*M,H], stats [B*M,2].
- * Contract: 0 <= span_starts, span widths <= S (wider spans are clamped; the reference would index past S only
- * for spans that leave the sentence). */
+ * Contract: 0 <= span_starts, span widths <= S.  A wider span is truncated: JR = min(widest span, S), and pooled is
+ * what the reference returns with every span's end cut to start + S - 1 (the reference would index past S only for
+ * spans that leave the sentence).  rowmap is specified in its first text_length entries only. */
 size_t mtvaf_span_index_ints(int B, int S, int M);
 int mtvaf_span_index(const uint8_t* mask, const int64_t* span_starts, const int64_t* span_ends, int* index, int B,
                      int S, int M, mtvaf_stream_t stream);
@@ -432,7 +433,8 @@ int mtvaf_span_pool_bwd(const float* dpooled, const float* pooled, const float* 
                         size_t ws_bytes, mtvaf_stream_t stream);
 /* loss (+)= scale * -mean_b( sum_s pos log_softmax(logits)_s / sum_s pos );  logits element (b,s) at
  * logits[(b*S+s)*ld] (the start / end logits are the two columns of the binary_affine output, ld = 2);
- * positions [B,S] fp32 multi-hot; row_ws [B,3] is kept for the backward. */
+ * positions [B,S] fp32 multi-hot; row_ws [B,3] = (row value, log sum_s exp(logit - row max), sum_s pos) is kept for
+ * the backward, which finds the row maximum again: a common offset of a row's logits does not cost precision. */
 int mtvaf_distant_ce_fwd(const float* logits, int ld, const float* positions, float* loss, float* row_ws, int B,
                          int S, float scale, int accumulate, mtvaf_stream_t stream);
 int mtvaf_distant_ce_bwd(const float* grad_out, float scale, const float* logits, int ld, const float* positions,

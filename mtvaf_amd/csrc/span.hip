@@ -230,28 +230,34 @@ __global__ __launch_bounds__(256) void span_pool_bwd_token_kernel(
 
 // distant_cross_entropy (:181-190): row value = sum_s pos log_softmax(z)_s / sum_s pos; loss = -mean_b.
 // One wave per row; logits may be strided (start / end logits are the two columns of the binary_affine output).
-// row_ws[b] = (value, lse, den)
+// The row maximum m is subtracted before anything is summed, and m and log e = log sum exp(z - m) are never added up: a
+// common offset of the logits then costs nothing (sum pos z against den (m + log e) would cancel two sums of its size).
+// row_ws[b] = (value, log e, den); the backward finds m again.
+__device__ __forceinline__ float distant_ce_row_max(const float* zr, int ldz, int S, int lane) {
+  float m = -3.0e38f;
+  for (int s = lane; s < S; s += 64) m = fmaxf(m, zr[(long)s * ldz]);
+  return wave_max(m);
+}
+
 __global__ __launch_bounds__(64) void distant_ce_fwd_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ pos,
                                                            float* __restrict__ row_ws, int S) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const float* zr = z + (long)b * S * ldz;
-  float m = -3.0e38f;
-  for (int s = lane; s < S; s += 64) m = fmaxf(m, zr[(long)s * ldz]);
-  m = wave_max(m);
+  const float m = distant_ce_row_max(zr, ldz, S, lane);
   float e = 0.f, num = 0.f, den = 0.f;
   for (int s = lane; s < S; s += 64) {
-    const float v = zr[(long)s * ldz], p = pos[(long)b * S + s];
-    e += expf(v - m);
-    num += p * v;
+    const float d = zr[(long)s * ldz] - m, p = pos[(long)b * S + s];
+    e += expf(d);
+    num += p * d;
     den += p;
   }
   e = wave_sum(e);
   num = wave_sum(num);
   den = wave_sum(den);
-  const float lse = m + logf(e);
+  const float loge = logf(e);
   if (lane == 0) {
-    row_ws[3 * b] = (num - den * lse) / den;
-    row_ws[3 * b + 1] = lse;
+    row_ws[3 * b] = (num - den * loge) / den;
+    row_ws[3 * b + 1] = loge;
     row_ws[3 * b + 2] = den;
   }
 }
@@ -265,17 +271,19 @@ __global__ __launch_bounds__(64) void distant_ce_mean_kernel(const float* __rest
   if (threadIdx.x == 0) *loss = (accumulate ? *loss : 0.f) - scale * s / B;
 }
 
-// dz_s = -(g scale / B) (pos_s - softmax_s den) / den
+// dz_s = -(g scale / B) (pos_s - softmax_s den) / den,  softmax_s = exp((z_s - m) - log e)
 __global__ __launch_bounds__(64) void distant_ce_bwd_kernel(const float* __restrict__ gout, float scale, const float* __restrict__ z,
                                                            int ldz, const float* __restrict__ pos,
                                                            const float* __restrict__ row_ws, float* __restrict__ dz, int lddz,
                                                            int B, int S) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const float lse = row_ws[3 * b + 1], den = row_ws[3 * b + 2];
+  const float* zr = z + (long)b * S * ldz;
+  const float m = distant_ce_row_max(zr, ldz, S, lane);
+  const float loge = row_ws[3 * b + 1], den = row_ws[3 * b + 2];
   const float g = -(*gout) * scale / B / den;
   for (int s = lane; s < S; s += 64) {
-    const float v = z[((long)b * S + s) * ldz], p = pos[(long)b * S + s];
-    dz[((long)b * S + s) * lddz] = g * (p - expf(v - lse) * den);
+    const float v = zr[(long)s * ldz], p = pos[(long)b * S + s];
+    dz[((long)b * S + s) * lddz] = g * (p - expf((v - m) - loge) * den);
   }
 }
 
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(64) void ce_fwd_kernel(const float* __restrict__ z,
     const float m = wave_max(v);
     const float e = wave_sum(lane < C ? expf(v - m) : 0.f);
     const float zl = __shfl(v, (int)lab, 64);
-    tot += m + logf(e) - zl;
+    tot += (m - zl) + logf(e);  // the two logits first: their difference does not carry the size of a common offset
     cnt += 1.f;
   }
   if (lane == 0) {
