@@ -985,6 +985,44 @@ int mtvaf_adamw_planes_seg(float* p, const float* g, float* m, float* v, long n,
                            int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols, void* const* mat_img,
                            int max_blocks, float* ema, float ema_omd, const float* clip_state, mtvaf_stream_t stream);
 
+/* ---- the step's own hyper-parameters on the device: an optimizer step that a graph capture can contain (new functionality: the
+ * reference steps eagerly, modules/train.py:620-625).  Every entry point above takes lr, bc1, bc2_sqrt and ema_omd as host floats,
+ * which a capture would freeze.  Here the host uploads ONE table for the whole run, a row of 24 bytes per optimizer step t = 1 .. rows:
+ *   { double lr_factor;  float bc1, bc2_sqrt, ema_omd;  int32 pad; }
+ * (lr_factor: what the lr schedule's lambda returns for the step whose lr update t uses; the floats exactly as the entry points above
+ * would have been handed them at step t), and the update kernels read the row of the step being taken from a fixed 32-byte block:
+ *   { double lr_factor;  float bc1, bc2_sqrt, ema_omd;  int32 overrun;  int64 step; }
+ * mtvaf_adamw_sched_advance (one block, plain stores from one lane): *counter += 1 (device int64), row min(*counter, rows) - 1 ->
+ * current, current.step = *counter, current.overrun = 1 when *counter lies outside 1 .. rows, else 0.  table, counter and current
+ * 8-byte aligned (MTVAF_ERR_ALIGN), rows >= 1 (MTVAF_ERR_ARG).
+ * mtvaf_adamw_sched / _planes_sched / _multi_sched / _seg_sched / _planes_seg_sched are mtvaf_adamw / _planes / _multi / _seg /
+ * _planes_seg with
+ *   lr = (float)(base_lr * current.lr_factor)   -- base_lr (per segment: seg_lr[k]) a DOUBLE: the product and the single rounding to
+ *                                                  float of a LambdaLR followed by the float argument above, so the same bits
+ *   bc1, bc2_sqrt, ema_omd                      -- read from current
+ * and the same update otherwise, bit for bit.  current.overrun != 0: the launch writes nothing, exactly as clip_state[2] == 0.
+ * Their options are nullable arguments as in mtvaf_adamw_seg: ema (mtvaf_adamw_multi_sched: a host array of device pointers) NULL: no
+ * average; clip_state NULL: grad_scale alone; p_bf16 NULL: no shadow.  Shapes, alignments and error codes are those of the
+ * counterparts; current NULL: MTVAF_ERR_ARG.  No argument changes from step to step. */
+int mtvaf_adamw_sched_advance(const void* table, long rows, long* counter, void* current, mtvaf_stream_t stream);
+int mtvaf_adamw_sched(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2, float eps,
+                      float weight_decay, float grad_scale, void* p_bf16, int max_blocks, float* ema, const float* clip_state,
+                      const void* current, mtvaf_stream_t stream);
+int mtvaf_adamw_planes_sched(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2,
+                             float eps, float weight_decay, float grad_scale, int nmat, const long* mat_begin, const int* mat_rows,
+                             const int* mat_cols, void* const* mat_img, int max_blocks, float* ema, const float* clip_state,
+                             const void* current, mtvaf_stream_t stream);
+int mtvaf_adamw_multi_sched(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                            double base_lr, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                            float* const* ema, const float* clip_state, const void* current, mtvaf_stream_t stream);
+int mtvaf_adamw_seg_sched(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const double* seg_lr,
+                          const float* seg_wd, double beta1, double beta2, float eps, float grad_scale, void* p_bf16, int max_blocks,
+                          float* ema, const float* clip_state, const void* current, mtvaf_stream_t stream);
+int mtvaf_adamw_planes_seg_sched(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end,
+                                 const double* seg_lr, const float* seg_wd, double beta1, double beta2, float eps, float grad_scale,
+                                 int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols, void* const* mat_img,
+                                 int max_blocks, float* ema, const float* clip_state, const void* current, mtvaf_stream_t stream);
+
 /* ---- bf16 gradient wire format of the data-parallel exchange (mtvaf_amd/parallel.py; new functionality, the
  * reference never synchronises gradients: MTVAF_training.py:305-309).  pack: dst[i] = bf16(src[i]), zero padding up to
  * npad (npad % 8 == 0); reduce: out[c] = bf16(scale * sum_r recv[r*chunk + c]) with fp32 accumulation in rank order;

@@ -23,6 +23,13 @@
 //   The *_seg forms (mtvaf_adamw_seg, mtvaf_adamw_planes_seg) take lr and weight decay per segment of the flat buffer from a table
 //   passed by value -- parameter groups that differ inside an encoder layer, still one launch.  Same adamw1 / ema1; their options
 //   (clip state, average, bf16 shadow) are nullable arguments of one entry point each.
+//
+//   The *_sched forms read the step's own hyper-parameters from the device: a 32-byte block {lr_factor (double), bc1, bc2_sqrt,
+//   ema_omd, overrun, step} that mtvaf_adamw_sched_advance copies out of a host-built table, one row per optimizer step.  The
+//   learning rate is (float)(base_lr * lr_factor) -- base_lr travels as a double, so this is the product and the one rounding a
+//   LambdaLR followed by the C ABI's float argument performs on the host -- and nothing per-step is left in the kernel arguments:
+//   the launches can be captured into a graph and replayed.  Same adamw1 / ema1, same bodies; a set overrun word (the counter has
+//   passed the table) makes a launch write nothing, like a non-finite clip state.
 #include <climits>
 
 #include "common.h"
@@ -255,12 +262,10 @@ __device__ __forceinline__ f32x4 adamw_vec4(float* __restrict__ p, const float* 
 }
 
 // the flat form: n % 4 elements of a scalar tail, which lie in the last segment (every other end is a multiple of 4)
-template <bool EMA, bool DEV>
-__global__ __launch_bounds__(256) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, float* __restrict__ e, float ema_omd,
-                                                        __bf16* __restrict__ ph, long n, AdamHyper h, AdamSegTable t,
-                                                        const float* __restrict__ clip) {
-  if (!clip_apply<DEV>(h, clip)) return;
+template <bool EMA>
+__device__ __forceinline__ void adamw_seg_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, float* __restrict__ e, float ema_omd, __bf16* __restrict__ ph,
+                                               long n, AdamHyper h, const AdamSegTable& t) {
   const long i0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
   const long n4 = n >> 2;
   for (long i = i0; i < n4; i += stride) {
@@ -281,14 +286,20 @@ __global__ __launch_bounds__(256) void adamw_seg_kernel(float* __restrict__ p, c
     if (ph) ph[i] = (__bf16)P;
   }
 }
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ e, float ema_omd,
+                                                        __bf16* __restrict__ ph, long n, AdamHyper h, AdamSegTable t,
+                                                        const float* __restrict__ clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  adamw_seg_body<EMA>(p, g, m, v, e, ema_omd, ph, n, h, t);
+}
 
 // the plane-image form (n % 4 == 0): the matrices of AdamSegs are independent of the segments, a matrix may lie across their ends
-template <bool EMA, bool DEV>
-__global__ __launch_bounds__(256) void adamw_planes_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4,
-                                                               AdamHyper h, AdamSegTable t, AdamSegs sg,
-                                                               const float* __restrict__ clip) {
-  if (!clip_apply<DEV>(h, clip)) return;
+template <bool EMA>
+__device__ __forceinline__ void adamw_planes_seg_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4, AdamHyper h,
+                                                      const AdamSegTable& t, const AdamSegs& sg) {
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     seg_hyper(t, (int)i, h);
@@ -302,6 +313,14 @@ __global__ __launch_bounds__(256) void adamw_planes_seg_kernel(float* __restrict
       }
     }
   }
+}
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_planes_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4,
+                                                               AdamHyper h, AdamSegTable t, AdamSegs sg,
+                                                               const float* __restrict__ clip) {
+  if (!clip_apply<DEV>(h, clip)) return;
+  adamw_planes_seg_body<EMA>(p, g, m, v, e, ema_omd, n4, h, t, sg);
 }
 
 // several tensors of one parameter group in one launch: blockIdx.x -> (tensor, block within tensor) through a prefix table
@@ -335,6 +354,117 @@ template <bool DEV>
 __global__ __launch_bounds__(256) void adamw_multi_ema_kernel(AdamMulti t, AdamHyper h, float ema_omd, const float* clip) {
   if (!clip_apply<DEV>(h, clip)) return;
   adamw_multi_body<true>(t, h, ema_omd);
+}
+
+// ---- the schedule on the device (mtvaf_adamw_sched_advance and the *_sched updates) ------------------------------------------------
+struct SchedRow {      // one optimizer step of the host's table
+  double lr_factor;    // what the LambdaLR lambda returns for the step whose lr this update uses
+  float bc1, bc2_sqrt, ema_omd;
+  int pad;
+};
+struct SchedCurrent {  // the row of the step being taken, at a fixed address
+  double lr_factor;
+  float bc1, bc2_sqrt, ema_omd;
+  int overrun;         // != 0: the counter is outside 1 .. rows -- every *_sched update returns before its first load
+  long step;           // the counter's value, for readers
+};
+static_assert(sizeof(SchedRow) == 24 && sizeof(SchedCurrent) == 32, "the layout mtvaf_amd/optim.py writes");
+
+// one lane: ++counter, row min(counter, rows) - 1 -> current.  (The row index is clamped on both sides: a counter the caller has
+// set below 0 reads row 0 and raises overrun too.)
+__global__ void sched_advance_kernel(const SchedRow* __restrict__ table, long rows, long* __restrict__ counter,
+                                     SchedCurrent* __restrict__ cur) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long c = *counter + 1;
+  *counter = c;
+  long r = (c < rows ? c : rows) - 1;
+  if (r < 0) r = 0;
+  const SchedRow row = table[r];
+  cur->lr_factor = row.lr_factor;
+  cur->bc1 = row.bc1;
+  cur->bc2_sqrt = row.bc2_sqrt;
+  cur->ema_omd = row.ema_omd;
+  cur->overrun = (c < 1 || c > rows) ? 1 : 0;
+  cur->step = c;
+}
+
+// what a *_sched kernel does before its body (block-uniform): the step's lr, bias corrections and 1 - decay from `cur`, then the clip
+// state as in the *_dev forms.  false: write nothing
+template <bool DEV>
+__device__ __forceinline__ bool sched_apply(AdamHyper& h, float& ema_omd, double base_lr, const SchedCurrent* __restrict__ cur,
+                                            const float* __restrict__ clip) {
+  if (cur->overrun != 0) return false;
+  h.lr = (float)(base_lr * cur->lr_factor);  // one IEEE double product, one rounding to float: the host's group["lr"] -> c_float
+  h.bc1 = cur->bc1;
+  h.bc2_sqrt = cur->bc2_sqrt;
+  ema_omd = cur->ema_omd;
+  return clip_apply<DEV>(h, clip);
+}
+
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_sched_kernel(float* p, const float* g, float* m, float* v, float* e, __bf16* ph, long n,
+                                                          AdamHyper h, double base_lr, const SchedCurrent* cur, const float* clip) {
+  float ema_omd;
+  if (!sched_apply<DEV>(h, ema_omd, base_lr, cur, clip)) return;
+  adamw_span<EMA>(p, g, m, v, e, ema_omd, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, h);
+}
+
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_planes_sched_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                 float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
+                                                                 long n4, AdamHyper h, AdamSegs sg, double base_lr,
+                                                                 const SchedCurrent* __restrict__ cur, const float* __restrict__ clip) {
+  float ema_omd;
+  if (!sched_apply<DEV>(h, ema_omd, base_lr, cur, clip)) return;
+  adamw_planes_body<EMA>(p, g, m, v, e, ema_omd, n4, h, sg);
+}
+
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_multi_sched_kernel(AdamMulti t, AdamHyper h, double base_lr, const SchedCurrent* cur,
+                                                                const float* clip) {
+  float ema_omd;
+  if (!sched_apply<DEV>(h, ema_omd, base_lr, cur, clip)) return;
+  adamw_multi_body<EMA>(t, h, ema_omd);
+}
+
+// the segmented forms: the table carries every segment's BASE lr as a double; the step's table of floats is made from it here
+struct AdamSegTableD {
+  int end4[ADAM_MAXSEG];
+  double lr[ADAM_MAXSEG];
+  float wd[ADAM_MAXSEG];
+  int n;
+};
+__device__ __forceinline__ AdamSegTable seg_table_at(const AdamSegTableD& s, double lr_factor) {
+  AdamSegTable t;
+#pragma unroll
+  for (int k = 0; k < ADAM_MAXSEG; ++k) {
+    t.end4[k] = s.end4[k];
+    t.lr[k] = (float)(s.lr[k] * lr_factor);
+    t.wd[k] = s.wd[k];
+  }
+  t.n = s.n;
+  return t;
+}
+
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_seg_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, float* __restrict__ e, __bf16* __restrict__ ph,
+                                                              long n, AdamHyper h, AdamSegTableD td,
+                                                              const SchedCurrent* __restrict__ cur, const float* __restrict__ clip) {
+  float ema_omd;
+  if (!sched_apply<DEV>(h, ema_omd, 0.0, cur, clip)) return;
+  adamw_seg_body<EMA>(p, g, m, v, e, ema_omd, ph, n, h, seg_table_at(td, cur->lr_factor));
+}
+
+template <bool EMA, bool DEV>
+__global__ __launch_bounds__(256) void adamw_planes_seg_sched_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                     float* __restrict__ m, float* __restrict__ v,
+                                                                     float* __restrict__ e, long n4, AdamHyper h, AdamSegTableD td,
+                                                                     AdamSegs sg, const SchedCurrent* __restrict__ cur,
+                                                                     const float* __restrict__ clip) {
+  float ema_omd;
+  if (!sched_apply<DEV>(h, ema_omd, 0.0, cur, clip)) return;
+  adamw_planes_seg_body<EMA>(p, g, m, v, e, ema_omd, n4, h, seg_table_at(td, cur->lr_factor), sg);
 }
 
 // exchange of up to 48 pairs of fp32 buffers, bit for bit (the parameters against their averages): the prefix table of AdamMulti
@@ -608,6 +738,147 @@ static int adamw_multi_launch(int count, float* const* p, const float* const* g,
   return MTVAF_OK;
 }
 
+// ---- the *_sched launches: base lr as a double, everything per-step behind `cur`; ema / clip nullable as in the segmented forms ----
+static inline bool sched_ptrs_ok(const void* cur, const float* clip) { return cur && !((uintptr_t)cur & 7) && !((uintptr_t)clip & 3); }
+
+// the plane images of up to four matrices inside a buffer of n elements (the conditions of mtvaf_adamw_planes)
+static int planes_mats(AdamSegs& sg, long n, int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols,
+                       void* const* mat_img) {
+  if (nmat < 0 || nmat > 4 || (nmat && (!mat_begin || !mat_rows || !mat_cols || !mat_img))) return MTVAF_ERR_ARG;
+  sg = AdamSegs{};
+  sg.n = nmat;
+  for (int s = 0; s < nmat; ++s) {
+    const long cnt = (long)mat_rows[s] * mat_cols[s];
+    if (mat_rows[s] <= 0 || mat_cols[s] <= 0 || mat_cols[s] % 32 || mat_begin[s] < 0 || (mat_begin[s] & 3) || mat_begin[s] + cnt > n ||
+        !mat_img[s] || (((uintptr_t)mat_img[s]) & 15))
+      return MTVAF_ERR_SHAPE;
+    sg.b4[s] = mat_begin[s] / 4; sg.e4[s] = (mat_begin[s] + cnt) / 4;
+    sg.rows[s] = mat_rows[s]; sg.cols[s] = mat_cols[s];
+    sg.img[s] = static_cast<unsigned char*>(mat_img[s]);
+  }
+  return MTVAF_OK;
+}
+
+static int seg_table_d(AdamSegTableD& td, long n, int nseg, const long* seg_end, const double* seg_lr, const float* seg_wd) {
+  if (!seg_lr) return MTVAF_ERR_ARG;
+  float lr32[ADAM_MAXSEG] = {};
+  AdamSegTable t;
+  if (const int rc = seg_table(t, n, nseg, seg_end, lr32, seg_wd)) return rc;  // (the checks and the ends; lr comes from seg_lr)
+  td.n = t.n;
+  for (int k = 0; k < ADAM_MAXSEG; ++k) {
+    td.end4[k] = t.end4[k];
+    td.lr[k] = k < nseg ? seg_lr[k] : 0.0;
+    td.wd[k] = t.wd[k];
+  }
+  return MTVAF_OK;
+}
+
+static int adamw_sched_launch(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2,
+                              float eps, float weight_decay, float grad_scale, void* p_bf16, int max_blocks, float* ema,
+                              const float* clip, const void* cur, hipStream_t stream) {
+  if (!p || !g || !m || !v || n <= 0 || !cur) return MTVAF_ERR_ARG;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 3) || !sched_ptrs_ok(cur, clip)) return MTVAF_ERR_ALIGN;
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale);  // (lr, bc1, bc2_sqrt: from cur)
+  int grid = stream_grid((n + 3) / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_sched_kernel<true, true>, adamw_sched_kernel<true, false>, adamw_sched_kernel<false, true>,
+             adamw_sched_kernel<false, false>, ema != nullptr, clip != nullptr, grid, stream, p, g, m, v, ema,
+             static_cast<__bf16*>(p_bf16), n, h, base_lr, static_cast<const SchedCurrent*>(cur), clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int adamw_planes_sched_launch(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2,
+                                     float eps, float weight_decay, float grad_scale, int nmat, const long* mat_begin,
+                                     const int* mat_rows, const int* mat_cols, void* const* mat_img, int max_blocks, float* ema,
+                                     const float* clip, const void* cur, hipStream_t stream) {
+  if (!p || !g || !m || !v || n <= 0 || !cur) return MTVAF_ERR_ARG;
+  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || !sched_ptrs_ok(cur, clip))
+    return MTVAF_ERR_ALIGN;
+  AdamSegs sg;
+  if (const int rc = planes_mats(sg, n, nmat, mat_begin, mat_rows, mat_cols, mat_img)) return rc;
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale);
+  int grid = stream_grid(n / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_planes_sched_kernel<true, true>, adamw_planes_sched_kernel<true, false>, adamw_planes_sched_kernel<false, true>,
+             adamw_planes_sched_kernel<false, false>, ema != nullptr, clip != nullptr, grid, stream, p, g, m, v, ema, n / 4, h, sg,
+             base_lr, static_cast<const SchedCurrent*>(cur), clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int adamw_multi_sched_launch(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                                    double base_lr, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                                    float* const* ema, const float* clip, const void* cur, hipStream_t stream) {
+  if (count < 0 || (count && (!p || !g || !m || !v || !n)) || !cur) return MTVAF_ERR_ARG;
+  if (!sched_ptrs_ok(cur, clip)) return MTVAF_ERR_ALIGN;
+  // every tensor is checked before the first launch: a refused call has written nothing
+  for (int i = 0; i < count; ++i) {
+    if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] <= 0 || (ema && !ema[i])) return MTVAF_ERR_ARG;
+    if (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (uintptr_t)(ema ? ema[i] : nullptr)) & 3) return MTVAF_ERR_ALIGN;
+  }
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale);
+  for (int base = 0; base < count; base += ADAM_MAXT) {
+    AdamMulti t;
+    t.count = count - base < ADAM_MAXT ? count - base : ADAM_MAXT;
+    int blocks = 0;
+    for (int k = 0; k < t.count; ++k) {
+      const int i = base + k;
+      t.p[k] = p[i]; t.g[k] = g[i]; t.m[k] = m[i]; t.v[k] = v[i]; t.n[k] = n[i];
+      t.e[k] = ema ? ema[i] : nullptr;
+      t.blk0[k] = blocks;
+      long b = ((n[i] + 3) / 4 + 255) / 256;
+      blocks += (int)(b > 1024 ? 1024 : b);
+    }
+    t.blk0[t.count] = blocks;
+    seg_launch(adamw_multi_sched_kernel<true, true>, adamw_multi_sched_kernel<true, false>, adamw_multi_sched_kernel<false, true>,
+               adamw_multi_sched_kernel<false, false>, ema != nullptr, clip != nullptr, blocks, stream, t, h, base_lr,
+               static_cast<const SchedCurrent*>(cur), clip);
+    MTVAF_LAUNCH_CHECK();
+  }
+  return MTVAF_OK;
+}
+
+static int adamw_seg_sched_launch(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end,
+                                  const double* seg_lr, const float* seg_wd, double beta1, double beta2, float eps, float grad_scale,
+                                  void* p_bf16, int max_blocks, float* ema, const float* clip, const void* cur, hipStream_t stream) {
+  if (!p || !g || !m || !v || !cur) return MTVAF_ERR_ARG;
+  AdamSegTableD td;
+  if (const int rc = seg_table_d(td, n, nseg, seg_end, seg_lr, seg_wd)) return rc;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || ((uintptr_t)p_bf16 & 7) || !sched_ptrs_ok(cur, clip))
+    return MTVAF_ERR_ALIGN;
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, 0.f, 1.f, 1.f, grad_scale);
+  int grid = stream_grid((n + 3) / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_seg_sched_kernel<true, true>, adamw_seg_sched_kernel<true, false>, adamw_seg_sched_kernel<false, true>,
+             adamw_seg_sched_kernel<false, false>, ema != nullptr, clip != nullptr, grid, stream, p, g, m, v, ema,
+             static_cast<__bf16*>(p_bf16), n, h, td, static_cast<const SchedCurrent*>(cur), clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int adamw_planes_seg_sched_launch(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end,
+                                         const double* seg_lr, const float* seg_wd, double beta1, double beta2, float eps,
+                                         float grad_scale, int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols,
+                                         void* const* mat_img, int max_blocks, float* ema, const float* clip, const void* cur,
+                                         hipStream_t stream) {
+  if (!p || !g || !m || !v || !cur) return MTVAF_ERR_ARG;
+  AdamSegTableD td;
+  if (const int rc = seg_table_d(td, n, nseg, seg_end, seg_lr, seg_wd)) return rc;
+  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) || !sched_ptrs_ok(cur, clip))
+    return MTVAF_ERR_ALIGN;
+  AdamSegs sg;
+  if (const int rc = planes_mats(sg, n, nmat, mat_begin, mat_rows, mat_cols, mat_img)) return rc;
+  const AdamHyper h = make_hyper(0.f, beta1, beta2, eps, 0.f, 1.f, 1.f, grad_scale);
+  int grid = stream_grid(n / 4);
+  if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
+  seg_launch(adamw_planes_seg_sched_kernel<true, true>, adamw_planes_seg_sched_kernel<true, false>,
+             adamw_planes_seg_sched_kernel<false, true>, adamw_planes_seg_sched_kernel<false, false>, ema != nullptr, clip != nullptr,
+             grid, stream, p, g, m, v, ema, n / 4, h, td, sg, static_cast<const SchedCurrent*>(cur), clip);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
 static int swap_multi_launch(int count, float* const* a, float* const* b, const long* n, hipStream_t stream) {
   if (count < 0 || (count && (!a || !b || !n))) return MTVAF_ERR_ARG;
   // every pair is checked before the first launch: a refused call has written nothing
@@ -742,6 +1013,55 @@ int mtvaf_adamw_planes_seg(float* p, const float* g, float* m, float* v, long n,
                            int max_blocks, float* ema, float ema_omd, const float* clip_state, hipStream_t stream) {
   return adamw_planes_seg_launch(p, g, m, v, n, nseg, seg_end, seg_lr, seg_wd, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, nmat,
                                  mat_begin, mat_rows, mat_cols, mat_img, max_blocks, ema, ema_omd, clip_state, stream);
+}
+
+// ++*counter (device int64) and the table's row for that step -> current (32 bytes, 8-byte aligned); rows of 24 bytes.  One block.
+int mtvaf_adamw_sched_advance(const void* table, long rows, long* counter, void* current, hipStream_t stream) {
+  if (!table || rows < 1 || !counter || !current) return MTVAF_ERR_ARG;
+  if (((uintptr_t)table | (uintptr_t)counter | (uintptr_t)current) & 7) return MTVAF_ERR_ALIGN;
+  hipLaunchKernelGGL(sched_advance_kernel, dim3(1), dim3(64), 0, stream, static_cast<const SchedRow*>(table), rows, counter,
+                     static_cast<SchedCurrent*>(current));
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+// The five updates with lr = (float)(base_lr * current.lr_factor) and bc1, bc2_sqrt, ema_omd read from `current`; ema, clip_state
+// (and p_bf16) nullable as in mtvaf_adamw_seg.  current.overrun != 0: nothing is written.
+int mtvaf_adamw_sched(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2, float eps,
+                      float weight_decay, float grad_scale, void* p_bf16, int max_blocks, float* ema, const float* clip_state,
+                      const void* current, hipStream_t stream) {
+  return adamw_sched_launch(p, g, m, v, n, base_lr, beta1, beta2, eps, weight_decay, grad_scale, p_bf16, max_blocks, ema, clip_state,
+                            current, stream);
+}
+
+int mtvaf_adamw_planes_sched(float* p, const float* g, float* m, float* v, long n, double base_lr, double beta1, double beta2,
+                             float eps, float weight_decay, float grad_scale, int nmat, const long* mat_begin, const int* mat_rows,
+                             const int* mat_cols, void* const* mat_img, int max_blocks, float* ema, const float* clip_state,
+                             const void* current, hipStream_t stream) {
+  return adamw_planes_sched_launch(p, g, m, v, n, base_lr, beta1, beta2, eps, weight_decay, grad_scale, nmat, mat_begin, mat_rows,
+                                   mat_cols, mat_img, max_blocks, ema, clip_state, current, stream);
+}
+
+int mtvaf_adamw_multi_sched(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
+                            double base_lr, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                            float* const* ema, const float* clip_state, const void* current, hipStream_t stream) {
+  return adamw_multi_sched_launch(count, p, g, m, v, n, base_lr, beta1, beta2, eps, weight_decay, grad_scale, ema, clip_state, current,
+                                  stream);
+}
+
+int mtvaf_adamw_seg_sched(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end, const double* seg_lr,
+                          const float* seg_wd, double beta1, double beta2, float eps, float grad_scale, void* p_bf16, int max_blocks,
+                          float* ema, const float* clip_state, const void* current, hipStream_t stream) {
+  return adamw_seg_sched_launch(p, g, m, v, n, nseg, seg_end, seg_lr, seg_wd, beta1, beta2, eps, grad_scale, p_bf16, max_blocks, ema,
+                                clip_state, current, stream);
+}
+
+int mtvaf_adamw_planes_seg_sched(float* p, const float* g, float* m, float* v, long n, int nseg, const long* seg_end,
+                                 const double* seg_lr, const float* seg_wd, double beta1, double beta2, float eps, float grad_scale,
+                                 int nmat, const long* mat_begin, const int* mat_rows, const int* mat_cols, void* const* mat_img,
+                                 int max_blocks, float* ema, const float* clip_state, const void* current, hipStream_t stream) {
+  return adamw_planes_seg_sched_launch(p, g, m, v, n, nseg, seg_end, seg_lr, seg_wd, beta1, beta2, eps, grad_scale, nmat, mat_begin,
+                                       mat_rows, mat_cols, mat_img, max_blocks, ema, clip_state, current, stream);
 }
 
 // a[i] <-> b[i], n[i] floats each, bit for bit; host arrays of device pointers, any count (48 pairs per launch).  A pair whose two

@@ -17,13 +17,24 @@ What makes the path capturable:
   * gradients live at fixed addresses (the encoder's flat per-layer buffers, the graph's private pool for the rest);
     ``param.grad`` is re-attached after every replay, so ``optimizer.zero_grad(set_to_none=True)`` stays legal.
 
-The optimizer step stays eager (its learning rate changes per step): use ``mtvaf_amd.optim.AdamW(..., overlap=False)``
-or any torch optimizer.  Shapes are frozen: one object per (batch, seq_len) -- the reference's last, smaller batch of an
-epoch (modules/train.py:596-650) runs through the plain eager path.
+The optimizer step joins the graph when its per-step hyper-parameters live on the device: with
+``optimizer=mtvaf_amd.optim.AdamW(..., device_schedule=optim.schedule_table(...))`` the capture also holds the clip launches (if
+clipping is on), the advance of the device's step counter and every update -- the ``*_sched`` kernels take no argument that changes
+from step to step -- so one replay is one whole training step, and each call runs the optimizer's host-only
+bookkeeping (``AdamW.host_step()``: counters, no launch) behind it.  The warm-up passes before the capture launch the updates
+with the device block's overrun word raised: the kernels are loaded and every state buffer is allocated, nothing is written and no
+counter moves -- the FIRST replay is update number 1.  ``optimizer.step()`` then raises (the step would run twice); a call past the
+schedule table's end raises on the host and launches nothing.  Without ``optimizer`` the step stays eager, as before: use
+``mtvaf_amd.optim.AdamW(..., overlap=False)`` or any torch optimizer.  Shapes are frozen: one object per (batch, seq_len) -- the
+reference's last, smaller batch of an epoch (modules/train.py:596-650) runs through the plain eager path.
 
     step = GraphedTrainStep(model, batch)      # batch: dict of forward() keyword tensors on the device
     out = step(**batch2)                        # same shapes; TokenClassifierOutput(loss, logits) as model(**batch2)
     optimizer.step(); optimizer.zero_grad(set_to_none=True)
+
+    step = GraphedTrainStep(model, batch, optimizer=opt)   # opt: AdamW(..., device_schedule=table)
+    out = step(**batch2)                                    # forward, backward, clipping, schedule advance and every update
+    opt.zero_grad(set_to_none=True)                         # (optional)
 """
 from __future__ import annotations
 
@@ -37,22 +48,45 @@ from .modules.crf import DeferredTags
 
 
 class GraphedTrainStep:
-    def __init__(self, model: torch.nn.Module, batch: Dict[str, torch.Tensor], warmup: int = 3):
+    def __init__(self, model: torch.nn.Module, batch: Dict[str, torch.Tensor], warmup: int = 3, optimizer=None):
         tens = {k: v for k, v in batch.items() if torch.is_tensor(v)}
         if not tens or not all(v.is_cuda for v in tens.values()):
             raise RuntimeError("GraphedTrainStep needs the batch on the MI355X (no CPU fallback)")
         if "labels" not in tens:
             raise ValueError("a training step needs labels (loss.backward() is part of the graph)")
+        self.optimizer = None
+        if optimizer is not None:
+            self._check_optimizer(model, optimizer)
         # padding-free execution (engine.UNPAD) reads the packed row count on the host once per step, which a capture cannot
         # contain: it steps aside -- the warm-up passes and the captured step run the padded layout (same loss, tags and
         # parameter gradients; tests/test_unpad_gpu.py), the switch is restored for eager steps afterwards
         unpad_was, engine.UNPAD = engine.UNPAD, False
         try:
-            self._build(model, batch, tens, warmup)
+            self._build(model, batch, tens, warmup, optimizer)
         finally:
             engine.UNPAD = unpad_was
 
-    def _build(self, model, batch, tens, warmup):
+    @staticmethod
+    def _check_optimizer(model, optimizer):
+        """What a captured optimizer step needs; refused before anything runs."""
+        from .optim import AdamW
+        who = "GraphedTrainStep(optimizer=...)"
+        if not isinstance(optimizer, AdamW) or optimizer.device_schedule is None:
+            raise RuntimeError(f"{who} needs a mtvaf_amd.optim.AdamW with device_schedule=optim.schedule_table(...): host-fed "
+                               "learning rates and bias corrections would be frozen by the capture")
+        if optimizer.overlap:
+            raise RuntimeError(f"{who}: AdamW(overlap=True) updates layers from inside the backward pass; build it with overlap=False")
+        if optimizer.accumulation_steps > 1:
+            raise RuntimeError(f"{who}: accumulation_steps > 1 is not captured (one replay is one backward pass and one update)")
+        enc = getattr(getattr(model, "bert", model), "encoder", None)
+        if optimizer._encoder is not None and optimizer._encoder is not enc:
+            raise RuntimeError(f"{who}: the optimizer is attached to another model's encoder")
+        if optimizer._graphed is not None:
+            raise RuntimeError(f"{who}: this optimizer's step is already part of a captured GraphedTrainStep")
+        if optimizer.ema_swapped:
+            raise RuntimeError(f"{who}: the averaged weights are swapped in (swap_ema): swap the training weights back first")
+
+    def _build(self, model, batch, tens, warmup, optimizer=None):
         enc = getattr(getattr(model, "bert", model), "encoder", None)
         sink = getattr(enc, "_sink", None)
         if sink is not None and sink.on_layer_done is not None:
@@ -79,6 +113,11 @@ class GraphedTrainStep:
             out.loss.backward()
             return out
 
+        def updates(suppress):
+            # every launch of the optimizer step; the warm-up passes run it with the updates suppressed on the device
+            if optimizer is not None and not optimizer._schedule_launch(suppress=suppress):
+                raise RuntimeError("GraphedTrainStep(optimizer=...): the backward pass left no gradient for the optimizer")
+
         # warm-up on a side stream (allocator, lazily built buffers, kernel attributes), as torch's graph recipe does
         cur = torch.cuda.current_stream()
         s = torch.cuda.Stream()
@@ -88,6 +127,7 @@ class GraphedTrainStep:
                 for p in params:
                     p.grad = None
                 out = one_step()
+                updates(suppress=True)
                 if isinstance(out.logits, DeferredTags):
                     out.logits._release = None  # the buffer is ours, not the pool's
                 del out
@@ -103,8 +143,12 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.graph):
                 hip._ck(hip.lib().mtvaf_rng_epoch_advance(self.epoch.data_ptr(), hip._st()), "mtvaf_rng_epoch_advance")
                 out = one_step()
+                updates(suppress=False)
         finally:
             engine.FORCE_SHADOW_REFRESH = False
+        if optimizer is not None:
+            self.optimizer = optimizer
+            optimizer._graphed = self
         self.loss = out.loss.detach()
         self._S = S
         self._tags_host = None
@@ -122,6 +166,8 @@ class GraphedTrainStep:
     def __call__(self, **batch) -> TokenClassifierOutput:
         if self.epoch is None:
             raise RuntimeError("GraphedTrainStep was closed")
+        if self.optimizer is not None:
+            self.optimizer._schedule_refuse_end()  # (first: past the schedule table's end nothing is launched, not even a copy)
         for k, v in batch.items():
             if torch.is_tensor(v):
                 dst = self.static.get(k)
@@ -132,6 +178,9 @@ class GraphedTrainStep:
         self.graph.replay()
         for p, g in self.grads:
             p.grad = g
+        if self.optimizer is not None:
+            self.optimizer.host_step()
+            engine.invalidate_weight_images()  # (the masters moved without an optimizer.step(): eager passes rebuild their images)
         logits = None
         if self._tags_host is not None:
             ev = torch.cuda.Event()
@@ -142,6 +191,9 @@ class GraphedTrainStep:
     def close(self):
         """Unregister the device-side dropout epoch (the word is owned by this object: the library must not keep its
         address once the object dies)."""
+        opt = getattr(self, "optimizer", None)
+        if opt is not None and opt._graphed is self:
+            opt._graphed = None
         if getattr(self, "epoch", None) is not None:
             hip._ck(hip.lib().mtvaf_rng_set_epoch_ptr(None), "mtvaf_rng_set_epoch_ptr")
             self.epoch = None

@@ -167,6 +167,12 @@ _SIGS = {
     "mtvaf_swap_f32_multi": (c_int, [I, P, P, P, P]),
     "mtvaf_adamw_seg": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, F, F, P, I, P, F, P, P]),
     "mtvaf_adamw_planes_seg": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, F, F, I, P, P, P, P, I, P, F, P, P]),
+    "mtvaf_adamw_sched_advance": (c_int, [P, L, P, P, P]),
+    "mtvaf_adamw_sched": (c_int, [P, P, P, P, L, c_double, c_double, c_double, F, F, F, P, I, P, P, P, P]),
+    "mtvaf_adamw_planes_sched": (c_int, [P, P, P, P, L, c_double, c_double, c_double, F, F, F, I, P, P, P, P, I, P, P, P, P]),
+    "mtvaf_adamw_multi_sched": (c_int, [I, P, P, P, P, P, c_double, c_double, c_double, F, F, F, P, P, P, P]),
+    "mtvaf_adamw_seg_sched": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, P, I, P, P, P, P]),
+    "mtvaf_adamw_planes_seg_sched": (c_int, [P, P, P, P, L, I, P, P, P, c_double, c_double, F, F, I, P, P, P, P, I, P, P, P, P]),
     "mtvaf_grad_pack_bf16": (c_int, [P, P, L, L, P]),
     "mtvaf_grad_reduce_bf16": (c_int, [P, P, I, L, F, P]),
     "mtvaf_grad_unpack_bf16": (c_int, [P, P, L, P]),
@@ -1597,6 +1603,92 @@ def adamw_planes_seg(p, g, m, v, segments, beta1, beta2, eps, step, mats, grad_s
                                      (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]),
                                      int(max_blocks), None if ema is None else _ema_arg(ema, p), float(ema_omd),
                                      None if clip is None else _clip_ptr(clip), _st()), "mtvaf_adamw_planes_seg")
+
+
+# ---- the schedule on the device: the *_sched updates read lr factor, bias corrections and 1 - decay from `current` -------------------
+SCHED_ROW_BYTES = 24      # {double lr_factor; float bc1, bc2_sqrt, ema_omd; int32 pad}
+SCHED_CURRENT_BYTES = 32  # {double lr_factor; float bc1, bc2_sqrt, ema_omd; int32 overrun; int64 step}
+
+
+def _sched_ptr(current):
+    """The 32-byte block mtvaf_adamw_sched_advance writes: four int64 on the device."""
+    assert current.is_cuda and current.dtype == torch.int64 and current.numel() == 4 and current.is_contiguous(), \
+        (current.device, current.dtype, current.shape)
+    return current.data_ptr()
+
+
+def adamw_sched_advance(table, counter, current):
+    """counter (device int64, one element) += 1 and the table's row for that step -> current.  table: uint8 on the device, 24 bytes
+    per step (optim.schedule_table); past its end current's overrun word is set and every *_sched update writes nothing."""
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.numel() % SCHED_ROW_BYTES == 0 \
+        and table.numel() > 0, (table.device, table.dtype, table.shape)
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1, (counter.device, counter.dtype, counter.shape)
+    _ck(lib().mtvaf_adamw_sched_advance(table.data_ptr(), table.numel() // SCHED_ROW_BYTES, counter.data_ptr(), _sched_ptr(current),
+                                        _st()), "mtvaf_adamw_sched_advance")
+
+
+def _opt(t, fn=_p, *a):
+    return None if t is None else fn(t, *a)
+
+
+def adamw_sched(p, g, m, v, base_lr, beta1, beta2, eps, weight_decay, current, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None,
+                ema=None):
+    """adamw whose lr is float(base_lr * current.lr_factor) and whose bias corrections and 1 - decay come from `current`: no argument
+    changes from step to step.  p_bf16, max_blocks, clip, ema: see adamw."""
+    _ck(lib().mtvaf_adamw_sched(_p(p), _p(g), _p(m), _p(v), p.numel(), float(base_lr), float(beta1), float(beta2), float(eps),
+                                float(weight_decay), float(grad_scale), _p(p_bf16), int(max_blocks), _opt(ema, _ema_arg, p),
+                                _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_sched")
+
+
+def _mat_args(mats):
+    n = len(mats)
+    return (n, (ctypes.c_long * n)(*[s[0] for s in mats]), (ctypes.c_int * n)(*[s[1] for s in mats]),
+            (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]))
+
+
+def adamw_planes_sched(p, g, m, v, base_lr, beta1, beta2, eps, weight_decay, current, mats, grad_scale=1.0, max_blocks=0, clip=None,
+                       ema=None):
+    """adamw_planes on the device's schedule (adamw_sched); mats as adamw_planes' segs."""
+    _f32(p, g, m, v)
+    _ck(lib().mtvaf_adamw_planes_sched(_p(p), _p(g), _p(m), _p(v), p.numel(), float(base_lr), float(beta1), float(beta2), float(eps),
+                                       float(weight_decay), float(grad_scale), *_mat_args(mats), int(max_blocks),
+                                       _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()),
+        "mtvaf_adamw_planes_sched")
+
+
+def adamw_multi_sched(ps, gs, ms, vs, base_lr, beta1, beta2, eps, weight_decay, current, grad_scale=1.0, clip=None, ema=None):
+    """adamw_multi on the device's schedule (adamw_sched): any number of tensors, 48 per launch; ema: a list parallel to ps, or None."""
+    k = len(ps)
+    if k == 0:
+        return
+    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
+    assert ema is None or len(ema) == k
+    es = None if ema is None else (ctypes.c_void_p * k)(*[_ema_arg(e, t) for e, t in zip(ema, ps)])
+    _ck(lib().mtvaf_adamw_multi_sched(k, arr(ps), arr(gs), arr(ms), arr(vs), (ctypes.c_long * k)(*[t.numel() for t in ps]),
+                                      float(base_lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale),
+                                      es, _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_multi_sched")
+
+
+def _seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale):
+    """segments = [(end element, BASE lr, weight_decay), ...]: the lr column travels as doubles."""
+    _f32(p, g, m, v)
+    k = len(segments)
+    return (_p(p), _p(g), _p(m), _p(v), p.numel(), k, (ctypes.c_long * k)(*[int(s[0]) for s in segments]),
+            (ctypes.c_double * k)(*[float(s[1]) for s in segments]), (ctypes.c_float * k)(*[float(s[2]) for s in segments]),
+            float(beta1), float(beta2), float(eps), float(grad_scale))
+
+
+def adamw_seg_sched(p, g, m, v, segments, beta1, beta2, eps, current, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None):
+    """adamw_seg on the device's schedule: segments = [(end element, base lr, weight_decay), ...]."""
+    _ck(lib().mtvaf_adamw_seg_sched(*_seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale), _p(p_bf16), int(max_blocks),
+                                    _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_seg_sched")
+
+
+def adamw_planes_seg_sched(p, g, m, v, segments, beta1, beta2, eps, current, mats, grad_scale=1.0, max_blocks=0, clip=None, ema=None):
+    """adamw_planes_seg on the device's schedule."""
+    _ck(lib().mtvaf_adamw_planes_seg_sched(*_seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale), *_mat_args(mats),
+                                           int(max_blocks), _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()),
+        "mtvaf_adamw_planes_seg_sched")
 
 
 def swap_f32(a_list, b_list):

@@ -44,6 +44,74 @@ def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
+class ScheduleTable:
+    """What ``schedule_table`` returns: the per-step hyper-parameters of a whole run, as the bytes the device reads.
+
+    ``rows`` is a numpy record array, one 24-byte row per optimizer step 1 .. T (``lr_factor`` float64; ``bc1``, ``bc2_sqrt``,
+    ``ema_omd`` float32; ``pad``) -- row ``t - 1`` is update ``t``.  ``lr_factors`` are the T + 1 values ``factor(0) .. factor(T)`` on the
+    host (``factor(t)`` is what ``group["lr"]`` shows after update ``t``); ``num_steps`` is the T that was asked for."""
+    FIELDS = [("lr_factor", "<f8"), ("bc1", "<f4"), ("bc2_sqrt", "<f4"), ("ema_omd", "<f4"), ("pad", "<i4")]
+
+    def __init__(self, rows, lr_factors, num_steps, betas, ema_decay, ema_warmup):
+        self.rows, self.lr_factors, self.num_steps = rows, lr_factors, int(num_steps)
+        self.betas, self.ema_decay, self.ema_warmup = (float(betas[0]), float(betas[1])), float(ema_decay), bool(ema_warmup)
+
+    def __len__(self):
+        return len(self.rows)
+
+
+def schedule_table(factor, num_steps: int, betas=(0.9, 0.999), ema_decay: float = 0.0, ema_warmup: bool = True) -> ScheduleTable:
+    """The table behind ``AdamW(device_schedule=...)``: everything of optimizer steps 1 .. ``num_steps`` that changes from step to
+    step, computed here with the host's own expressions so that the device reads the host's bits.
+
+    ``factor`` is the function a ``LambdaLR`` would be given.  In the loop ``opt.step(); sched.step()`` update ``t`` runs at
+    ``base_lr * factor(t - 1)`` (the scheduler's constructor applies ``factor(0)``, its ``t``-th ``step()`` applies ``factor(t)`` for
+    the NEXT update), so row ``t`` holds ``factor(t - 1)``; ``bc1 = 1 - beta1 ** t`` and ``bc2_sqrt = (1 - beta2 ** t) ** 0.5`` rounded
+    to float once, as ``mtvaf_amd.hip`` hands them to the kernels; ``ema_omd = 1 - ema_decay_at(t - 1, ema_decay, ema_warmup)``
+    likewise (``AdamW._ema_omd``)."""
+    import numpy as np
+    T = int(num_steps)
+    if T < 1:
+        raise ValueError("schedule_table: num_steps must be >= 1")
+    b1, b2 = betas
+    lr_factors = [float(factor(t)) for t in range(T + 1)]
+    rows = np.zeros(T, dtype=ScheduleTable.FIELDS)
+    for t in range(1, T + 1):
+        rows[t - 1] = (lr_factors[t - 1], float(1.0 - b1 ** t), float((1.0 - b2 ** t) ** 0.5),
+                       float(1.0 - ema_decay_at(t - 1, ema_decay, ema_warmup)), 0)
+    return ScheduleTable(rows, lr_factors, T, betas, ema_decay, ema_warmup)
+
+
+class ScheduleMirror:
+    """The scheduler ``build_optimizer`` returns beside an ``AdamW(device_schedule=...)``: the kernels take their learning rate from
+    the device's table, so ``step()`` launches and computes nothing -- it advances a host count and shows readers of
+    ``group["lr"]`` the table's value for the next update (``base_lr * factor(count)``, what a ``LambdaLR`` would have written)."""
+
+    def __init__(self, optimizer):
+        self.optimizer = optimizer
+        self.last_epoch = optimizer.schedule_count
+        self._show()
+
+    def _show(self):
+        f = self.optimizer.device_schedule.lr_factors
+        for g in self.optimizer.param_groups:
+            g["lr"] = g["initial_lr"] * f[min(self.last_epoch, len(f) - 1)]
+
+    def step(self):
+        self.last_epoch += 1
+        self._show()
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def state_dict(self):
+        return {"last_epoch": self.last_epoch}
+
+    def load_state_dict(self, state):
+        self.last_epoch = int(state["last_epoch"])
+        self._show()
+
+
 MAX_SEGMENTS = 16  # of one segmented launch (csrc/optim.hip, ADAM_MAXSEG): an encoder layer has 16 parameters
 
 
@@ -126,13 +194,27 @@ class AdamW(torch.optim.Optimizer):
     non-finite skip drops, the average keeps its bits but ``ema_step`` advances like the step counters (same caveat).  At
     ``ema_decay == 0`` (default) nothing is allocated and ``step()`` issues the launches it always did.
 
+    ``device_schedule=schedule_table(...)``: the step's own hyper-parameters -- the lr factor, both bias corrections and the
+    average's ``1 - decay`` -- live on the device.  ``step()`` first launches ``hip.adamw_sched_advance`` (a device
+    step counter += 1, that step's table row -> a fixed 32-byte block) and then the ``*_sched`` form of every update it would have
+    launched, which take the group's BASE lr (``group["initial_lr"]``, as a double) and read the rest from that block: no kernel
+    argument changes from step to step, so ``mtvaf_amd.graph.GraphedTrainStep(model, batch, optimizer=opt)`` captures the whole
+    step.  Same bits as ``AdamW`` + ``LambdaLR(factor)``.  The host keeps a mirror of the counter (``schedule_count``, one increment
+    per ``step()`` or replay -- ``host_step()`` is that bookkeeping alone and launches nothing) and raises BEFORE a step past the
+    table's end; on the device such a step would write nothing.  Limits, checked at construction or at the first step: one
+    ``betas`` for all groups (the bias corrections are the table's), every parameter on one step count (and one EMA update count),
+    ``overlap=False``, and the table's ``ema_decay`` / ``ema_warmup`` are the optimizer's.  ``group["lr"]`` is not read by the
+    kernels any more; a scheduler may still write it for readers (``ScheduleMirror``, or a ``LambdaLR`` with the table's factor)
+    and ``assert_schedule_agrees()`` compares the two on demand.
+
     Checkpoints: ``state_dict()`` / ``load_state_dict()`` are torch.optim's; the flat per-layer moment buffers are
-    rebuilt from the loaded per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step`` entries on the first update."""
+    rebuilt from the loaded per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step`` entries on the first update.  Under a device
+    schedule loading also sets the host mirror and the device counter to the loaded step count."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None, max_grad_norm: float = 0.0,
                  track_grad_norm: bool = False, skip_nonfinite: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 accumulation_steps: int = 1):
+                 accumulation_steps: int = 1, device_schedule: Optional[ScheduleTable] = None):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
         max_grad_norm = float(max_grad_norm or 0.0)
@@ -168,6 +250,10 @@ class AdamW(torch.optim.Optimizer):
         self._param_layer: Dict[int, int] = {}  # id(parameter) -> encoder layer whose flat state its entries are views of
         self._background_ok = True
         self.suspended = False    # True: the backward hook does nothing (backward passes that are not followed by step())
+        self.device_schedule = None  # a ScheduleTable: the *_sched kernels, hyper-parameters of the step read on the device
+        self._graphed = None         # the GraphedTrainStep that has captured this optimizer's step (step() then raises)
+        if device_schedule is not None:
+            self._schedule_init(device_schedule)
         if model is not None:
             self.attach(model, grad_sync)
 
@@ -257,6 +343,10 @@ class AdamW(torch.optim.Optimizer):
             ema = self.ema_decay > 0.0
             if ema:
                 st["ema"], st["ema_step"], st["ema_step_t"] = torch.zeros_like(store.flat), 0, torch.zeros((), dtype=torch.float32)
+            if self.device_schedule is not None:  # one step count for everything: the layers share its two 0-dim tensors (host_step)
+                st["step_t"] = self._sched_step_t
+                if ema:
+                    st["ema_step_t"] = self._sched_ema_step_t
             self._flat_state[key] = st
             steps, ema_steps = set(), set()
             for i, p in enumerate(self._encoder.layer[li].ordered_params()):
@@ -294,6 +384,213 @@ class AdamW(torch.optim.Optimizer):
         self.__dict__["_flat_state"] = {}
         self._param_layer = {}
         self._early = set()
+        if self.device_schedule is not None:
+            counts = {int(s["step"]) for s in self.state.values() if "step" in s}
+            if len(counts) > 1:
+                raise RuntimeError(f"mtvaf_amd.optim.AdamW(device_schedule=...): the loaded parameters carry different step counts "
+                                   f"{sorted(counts)}; the device keeps ONE counter for all of them")
+            self._schedule_set_count(counts.pop() if counts else 0)
+
+    # -- the schedule on the device --------------------------------------------------------------------
+    def _schedule_init(self, table):
+        who = "mtvaf_amd.optim.AdamW(device_schedule=...)"
+        if not isinstance(table, ScheduleTable):
+            raise TypeError(f"{who} takes what optim.schedule_table() returns")
+        if self.overlap:
+            raise ValueError(f"{who} needs overlap=False: updates enqueued from inside the backward pass run before step() has "
+                             "advanced the device's step counter")
+        if len(table.rows) < table.num_steps:
+            raise ValueError(f"{who}: the table holds {len(table.rows)} rows, fewer than the {table.num_steps} steps it was built for")
+        for g in self.param_groups:
+            if tuple(float(b) for b in g["betas"]) != table.betas:
+                raise ValueError(f"{who}: a parameter group has betas {tuple(g['betas'])}, the table was built for {table.betas} -- the "
+                                 "bias corrections of a step are one row of the table, shared by every group")
+        if self.ema_decay > 0.0 and (table.ema_decay, table.ema_warmup) != (self.ema_decay, self.ema_warmup):
+            raise ValueError(f"{who}: the table was built for ema_decay={table.ema_decay}, ema_warmup={table.ema_warmup}, the optimizer "
+                             f"averages with ema_decay={self.ema_decay}, ema_warmup={self.ema_warmup}")
+        for g in self.param_groups:
+            g.setdefault("initial_lr", g["lr"])  # the BASE lr the kernels multiply with the table's factor (a LambdaLR keeps it)
+        self.device_schedule = table
+        self._sched_count = 0      # the host mirror of the device counter: updates taken so far
+        self._sched_dev = None     # {"table", "counter", "current"} on the device, made by the first step
+        self._sched_states = []    # state dicts of the tensors the last launch updated one by one (host_step writes their counts)
+        self._sched_step_t = torch.zeros((), dtype=torch.float32)      # state[p]["step"] of every encoder-layer parameter
+        self._sched_ema_step_t = torch.zeros((), dtype=torch.float32)  # ... and state[p]["ema_step"]
+
+    @property
+    def schedule_count(self) -> int:
+        """Updates taken so far under the device schedule (the host mirror of the device counter)."""
+        return self._sched_count
+
+    def _schedule_set_count(self, count: int):
+        self._sched_count = int(count)
+        self._sched_step_t.fill_(self._sched_count)
+        self._sched_ema_step_t.fill_(self._sched_count)
+        if self._sched_dev is not None:  # (in place: a captured graph holds the counter's address)
+            self._sched_dev["counter"].fill_(self._sched_count)
+
+    def _schedule_device(self, dev):
+        d = self._sched_dev
+        if d is None or d["counter"].device != dev:
+            import numpy as np
+            raw = torch.from_numpy(self.device_schedule.rows.view(np.uint8).copy())
+            d = self._sched_dev = {"table": raw.to(dev), "counter": torch.full((1,), self._sched_count, dtype=torch.int64, device=dev),
+                                   "current": torch.zeros(4, dtype=torch.int64, device=dev)}
+        return d
+
+    def _schedule_refuse_end(self):
+        if self._sched_count + 1 > len(self.device_schedule.rows):
+            raise RuntimeError(f"mtvaf_amd.optim.AdamW(device_schedule=...): update {self._sched_count + 1} lies past the end of the "
+                               f"schedule table ({len(self.device_schedule.rows)} steps); nothing was launched")
+
+    def assert_schedule_agrees(self):
+        """``group["lr"]`` of every group is what the table gives the NEXT update (``initial_lr * factor(schedule_count)``): a
+        scheduler that is stepped beside this optimizer for readers of ``group["lr"]`` has kept pace.  On demand, not per step."""
+        f = self.device_schedule.lr_factors
+        want = f[min(self._sched_count, len(f) - 1)]
+        for i, g in enumerate(self.param_groups):
+            if g["lr"] != g["initial_lr"] * want:
+                raise AssertionError(f"parameter group {i}: lr {g['lr']!r} but the device schedule is at update {self._sched_count}, "
+                                     f"lr {g['initial_lr'] * want!r}")
+
+    def host_step(self):
+        """The host's share of one update under the device schedule, and nothing else: the mirror of the device counter, the step
+        and EMA counts ``state_dict()`` saves.  ``step()`` calls it behind its launches; a replay of a captured step calls it
+        alone.  No launch, no synchronisation.  Raises before a step past the table's end."""
+        self._schedule_refuse_end()
+        c = self._sched_count = self._sched_count + 1
+        ema_on = self.ema_decay > 0.0
+        self._sched_step_t.fill_(c)  # (host tensors, shared by the parameters of every encoder layer)
+        if ema_on:
+            self._sched_ema_step_t.fill_(c)
+        for st in self.__dict__.get("_flat_state", {}).values():
+            st["step"] = c
+            if "ema" in st:
+                st["ema_step"] = c
+        for stt in self._sched_states:
+            stt["step"] = c
+            if ema_on:
+                stt["ema_step"] = c
+
+    def _schedule_count_check(self, what: str, step, ema_step):
+        c = self._sched_count
+        if int(step) != c or (ema_step is not None and int(ema_step) != c):
+            raise RuntimeError(f"mtvaf_amd.optim.AdamW(device_schedule=...): {what} has taken {int(step)} updates"
+                               + ("" if ema_step is None else f" ({int(ema_step)} of its average)")
+                               + f", the schedule is at {c}: the device keeps ONE step counter (and one row of bias corrections and "
+                               "EMA decay) for every parameter")
+
+    def _schedule_collect(self):
+        """What this step updates, as ``step()`` finds it, without touching a counter: -> (layer jobs, group jobs, gradients)."""
+        ema_on = self.ema_decay > 0.0
+        done, layer_jobs = set(), []
+        enc = self._encoder
+        if enc is not None and enc._stores is not None:
+            if len(self._layer_group) != len(enc.layer):
+                self._map_layers()
+            for li, layer in enumerate(enc.layer):
+                store = enc._stores[li]
+                group = self._plan(li, store)
+                if group is None or store.grad is None or not store.valid(layer):
+                    continue
+                ps = layer.ordered_params()
+                lo = store.grad.data_ptr()
+                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
+                       for i, p in enumerate(ps)):
+                    st = self._layer_state(li, store)
+                    self._schedule_count_check(f"encoder layer {li}", st["step"], st.get("ema_step"))
+                    layer_jobs.append((li, group, store))
+                    done.update(id(p) for p in ps)
+        group_jobs, states = [], []
+        for group in self.param_groups:
+            items = []
+            for p in group["params"]:
+                if p.grad is None or id(p) in done:
+                    continue
+                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
+                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
+                if not p.is_contiguous():
+                    raise RuntimeError("non-contiguous parameter")
+                stt = self.state[p]
+                if "exp_avg" not in stt:
+                    stt["exp_avg"], stt["exp_avg_sq"], stt["step"] = torch.zeros_like(p), torch.zeros_like(p), 0
+                if ema_on and "ema" not in stt:
+                    stt["ema"], stt["ema_step"] = torch.zeros_like(p), 0
+                if stt["step"] is not self._sched_step_t:  # (a view of a layer's flat state counts with the layer)
+                    self._schedule_count_check("a parameter", stt["step"], stt["ema_step"] if ema_on else None)
+                    states.append(stt)
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                items.append((p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
+            if items:
+                group_jobs.append((group, items))
+        self._sched_states = states
+        grads = [store.grad for _, _, store in layer_jobs] + [i[1] for _, items in group_jobs for i in items]
+        return layer_jobs, group_jobs, grads
+
+    def _schedule_launch(self, suppress: bool = False) -> bool:
+        """Every launch of one update under the device schedule, on the current stream: the clip state (if wanted), the counter's
+        advance, the ``*_sched`` updates.  No host value of the step enters a kernel argument, so a graph capture may contain the
+        call.  ``suppress``: the warm-up of such a capture -- the advance is left out and the block's overrun word is raised instead,
+        so every update kernel is loaded and every buffer allocated while nothing is written and no counter moves.
+        -> False: no gradient, nothing launched."""
+        self._refuse_swapped("step() was called")
+        if not suppress:
+            self._schedule_refuse_end()
+        layer_jobs, group_jobs, grads = self._schedule_collect()
+        if not grads:
+            return False
+        d = self._schedule_device(grads[0].device)
+        clip = None
+        if self.max_grad_norm > 0.0 or self.track_grad_norm:
+            skipped = None if (not suppress or self.skipped_steps is None) else self.skipped_steps.clone()
+            clip = self._clip_launch(grads)
+            if suppress:  # (a warm-up pass is no step: its non-finite norm is not counted)
+                self.skipped_steps.zero_() if skipped is None else self.skipped_steps.copy_(skipped)
+        overrun = d["current"].view(torch.int32)[5:6]
+        if suppress:
+            overrun.fill_(1)
+        else:
+            hip.adamw_sched_advance(d["table"], d["counter"], d["current"])
+        for li, group, store in layer_jobs:
+            self._update_layer_sched(li, group, store, clip, d["current"], stamp=not suppress)
+        ema_on = self.ema_decay > 0.0
+        for group, items in group_jobs:
+            b1, b2 = group["betas"]
+            hip.adamw_multi_sched([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
+                                  group["initial_lr"], b1, b2, group["eps"], group["weight_decay"], d["current"], clip=clip,
+                                  ema=[i[4] for i in items] if ema_on else None)
+        if suppress:
+            overrun.fill_(0)
+        return True
+
+    def _update_layer_sched(self, li: int, group, store, clip, current, stamp: bool = True):
+        """``_update_layer_flat`` under the device schedule: the same choice of form, the groups' BASE lr, no counter."""
+        st = self._layer_state(li, store)
+        table = [(end, g["initial_lr"], g["weight_decay"]) for end, g in group] if isinstance(group, list) else None
+        if table is not None:
+            group = group[0][1]
+        b1, b2 = group["betas"]
+        from . import engine
+        shadow = engine.shadow_for_update(store.weights)
+        mats = engine.planes_for_update(store.weights) if shadow is None else None
+        kw = dict(clip=clip, ema=st.get("ema"))
+        if mats is not None and store.flat.numel() % 4 == 0:
+            if table is not None:
+                hip.adamw_planes_seg_sched(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], current, mats, **kw)
+            else:
+                hip.adamw_planes_sched(store.flat, store.grad, st["m"], st["v"], group["initial_lr"], b1, b2, group["eps"],
+                                       group["weight_decay"], current, mats, **kw)
+            if stamp:
+                engine.planes_written(store.weights)
+            return
+        if table is not None:
+            hip.adamw_seg_sched(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], current, p_bf16=shadow, **kw)
+        else:
+            hip.adamw_sched(store.flat, store.grad, st["m"], st["v"], group["initial_lr"], b1, b2, group["eps"], group["weight_decay"],
+                            current, p_bf16=shadow, **kw)
+        if shadow is not None and stamp:
+            engine.shadow_written(store.weights)
+        engine.planes_rewrite(store.weights)
 
     # -- averaged weights --------------------------------------------------------------------------------------------
     def _ema_omd(self, t: int) -> float:
@@ -479,6 +776,13 @@ class AdamW(torch.optim.Optimizer):
         if clipping and hip.STREAM_OVERRIDE is not None:
             raise RuntimeError("mtvaf_amd.optim.AdamW: step() with max_grad_norm / track_grad_norm was called from inside a backward "
                                "hook -- the gradient norm would be taken before the pass has produced every gradient")
+        if self.device_schedule is not None:
+            if self._graphed is not None:
+                raise RuntimeError("mtvaf_amd.optim.AdamW: step() was called, but this optimizer's step is part of a captured "
+                                   "GraphedTrainStep -- every call of that object IS the step (close() it to step eagerly again)")
+            if self._schedule_launch():
+                self.host_step()
+            return loss
         done = set()
         layer_jobs = []  # (layer index, group, store): one launch each
         enc = self._encoder
@@ -617,16 +921,21 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
     return groups
 
 
-def linear_schedule_with_warmup(optimizer, num_warmup_steps: float, num_training_steps: int):
-    """transformers.get_linear_schedule_with_warmup restated (the reference passes a float warm-up count,
-    train.py:922-924): lr factor = step / warmup while warming up, then linear decay to 0."""
+def linear_warmup_factor(num_warmup_steps: float, num_training_steps: int):
+    """The lr factor of ``linear_schedule_with_warmup`` as a function of the step (what ``schedule_table`` tabulates)."""
 
     def factor(step: int) -> float:
         if step < num_warmup_steps:
             return float(step) / float(max(1, num_warmup_steps))
         return max(0.0, float(num_training_steps - step) / float(max(1, num_training_steps - num_warmup_steps)))
 
-    return torch.optim.lr_scheduler.LambdaLR(optimizer, factor)
+    return factor
+
+
+def linear_schedule_with_warmup(optimizer, num_warmup_steps: float, num_training_steps: int):
+    """transformers.get_linear_schedule_with_warmup restated (the reference passes a float warm-up count,
+    train.py:922-924): lr factor = step / warmup while warming up, then linear decay to 0."""
+    return torch.optim.lr_scheduler.LambdaLR(optimizer, linear_warmup_factor(num_warmup_steps, num_training_steps))
 
 
 def accumulation_plan(args):
@@ -669,13 +978,27 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
     track_grad_norm = bool(getattr(args, "track_grad_norm", False))
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)  # 0: unchanged, the reference keeps no averaged weights
     ema_warmup = bool(getattr(args, "ema_warmup", True))
+    # args.device_schedule (default off): lr factor, bias corrections and EMA decay of every step as a table on the device, read by
+    # the *_sched kernels -- the optimizer step can then be captured (GraphedTrainStep(model, batch, optimizer=opt)); updates after
+    # the backward pass (overlap=False), and the scheduler returned only mirrors the table for readers of group["lr"]
+    device_schedule = bool(getattr(args, "device_schedule", False))
+    warmup_steps = getattr(args, "warmup_ratio", 0.01) * train_num_steps
+    if device_schedule and not on_gpu:
+        raise ValueError("build_optimizer: device_schedule is implemented by the gfx950 AdamW kernels; the model is not on the GPU")
     if on_gpu:
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
         overlap, fused_steps = accumulation_plan(args)
+        extra = {"accumulation_steps": fused_steps} if fused_steps > 1 else {}
+        if device_schedule:
+            overlap = False
+            extra["device_schedule"] = schedule_table(linear_warmup_factor(warmup_steps, train_num_steps), train_num_steps,
+                                                      (0.9, 0.999), ema_decay, ema_warmup)  # (AdamW's default betas, as below)
         opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
                     max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                    **({"accumulation_steps": fused_steps} if fused_steps > 1 else {}))
+                    **extra)
+        if device_schedule:
+            return opt, ScheduleMirror(opt)
     else:
         if max_grad_norm > 0.0:
             raise ValueError("build_optimizer: max_grad_norm is implemented by the gfx950 AdamW kernels; the CPU fallback "
@@ -684,5 +1007,5 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
             raise ValueError("build_optimizer: ema_decay is implemented by the gfx950 AdamW kernels; the CPU fallback "
                              "(torch.optim.AdamW) would ignore it")
         opt = torch.optim.AdamW(groups, lr=args.lr)
-    sched = linear_schedule_with_warmup(opt, getattr(args, "warmup_ratio", 0.01) * train_num_steps, train_num_steps)
+    sched = linear_schedule_with_warmup(opt, warmup_steps, train_num_steps)
     return opt, sched
