@@ -1032,6 +1032,35 @@ int mtvaf_grad_pack_bf16(const float* src, void* dst, long n, long npad, mtvaf_s
 int mtvaf_grad_reduce_bf16(const void* recv, void* out, int world, long chunk, float scale, mtvaf_stream_t stream);
 int mtvaf_grad_unpack_bf16(const void* src, float* dst, long n, mtvaf_stream_t stream);
 
+/* ---- Adversarial perturbation of the embedding output: one FGM / PGD / FreeLB step (mtvaf_amd/adversarial.py; new
+ * functionality, the reference trainer has no adversarial step).  g [B,S,H] fp32: the gradient at the embedding output;
+ * mask [B,S] u8, non-zero = live, any pattern; delta_in [B,S,H] or NULL; x [B,S,H] or NULL.  A unit u is all live rows
+ * of a sentence (scope SENTENCE) or one live row (scope TOKEN), |.|_u its L2 norm:
+ *   norm L2,   delta_in NULL:  delta_out = eps * g / |g|_u
+ *   norm L2,   delta_in:       d = delta_in + step * g / |g|_u;  if |d|_u > eps: d *= eps / |d|_u;  delta_out = d
+ *   norm LINF, delta_in NULL:  delta_out = eps * sign(g)          (sign(0) = 0)
+ *   norm LINF, delta_in:       delta_out = clamp(delta_in + step * sign(g), -eps, eps)
+ * Rows with mask 0 are exact 0.0f in delta_out whatever g and delta_in hold there (neither is read).  A unit whose |g|_u
+ * is 0, inf or NaN -- as rounded to fp32 -- takes no gradient term: delta_out = 0 without delta_in, the projected (L2) or
+ * clamped (LINF) delta_in with it; a finite delta_in gives a finite delta_out.  out [B,S,H] (optional, needs x) =
+ * x + delta_out, bit for bit the fp32 sum of the stored delta.  stats [B,2] = {|g| over the sentence's live rows,
+ * |delta_out| over the sentence}, for either scope; a non-finite |g| is reported there.  delta_out may be delta_in.
+ * Squares and sums run in double from the first operation and are rounded to fp32 once; per element the fp32 work is one
+ * division and one multiplication, so g * 2^k (nothing underflowing) gives the same bits.  No atomics, no host
+ * synchronisation: the same inputs give the same bits.  workspace: mtvaf_adv_workspace_bytes(B, S) bytes, 8-byte
+ * aligned (MTVAF_ERR_WORKSPACE if short).  B >= 1, 1 <= S <= 512, 1 <= H <= 1024 (MTVAF_ERR_SHAPE); eps, step finite
+ * and >= 0, norm / scope one of the constants (MTVAF_ERR_ARG): checked before any launch.
+ * mtvaf_adv_add: out[i] = x[i] + delta[i], n elements (the embedding tap's forward, engine.EmbeddingTapFunction). */
+#define MTVAF_ADV_NORM_L2 0
+#define MTVAF_ADV_NORM_LINF 1
+#define MTVAF_ADV_SCOPE_SENTENCE 0
+#define MTVAF_ADV_SCOPE_TOKEN 1
+size_t mtvaf_adv_workspace_bytes(int B, int S);
+int mtvaf_adv_perturb(const float* g, const float* delta_in, const float* x, const uint8_t* mask, float* delta_out,
+                      float* out, float* stats, int B, int S, int H, float eps, float step, int norm, int scope,
+                      void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_adv_add(const float* x, const float* delta, float* out, long n, mtvaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,37 @@ class EmbeddingsFunction(torch.autograd.Function):
         return dword, dpos, dtyp, dg, db, None, None, None, None, None, None
 
 
+class EmbeddingTap:
+    """What ``BertModel.embedding_tap`` holds (None by default): ``delta`` [B,S,H] fp32 or None is added to the embedding output,
+    ``capture`` asks the backward for the gradient at that seam, which then sits in ``grad`` (mtvaf_amd.adversarial)."""
+    __slots__ = ("delta", "capture", "grad")
+
+    def __init__(self, delta=None, capture=False):
+        self.delta, self.capture, self.grad = delta, bool(capture), None
+
+
+class EmbeddingTapFunction(torch.autograd.Function):
+    """The seam behind the embeddings.  Forward: ``emb + tap.delta`` (one launch, mtvaf_adv_add), or the
+    input itself when there is no delta (autograd makes it a view: no copy, no launch).  Backward: the incoming gradient -- [B,S,H]
+    in the padded and in the padding-free run, where the encoder scatters its packed rows back -- is kept in ``tap.grad`` by
+    reference when ``tap.capture`` and returned unchanged: ``delta`` is a constant."""
+
+    @staticmethod
+    def forward(ctx, emb, tap):
+        ctx.tap = tap
+        if tap.delta is None:
+            return emb
+        if tap.delta.shape != emb.shape:
+            raise ValueError(f"embedding_tap.delta {tuple(tap.delta.shape)} does not match the embedding output {tuple(emb.shape)}")
+        return hip.adv_add(emb.contiguous(), tap.delta)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.tap.capture:
+            ctx.tap.grad = dout
+        return dout, None
+
+
 # -------------------------------------------------------------------------------------------------
 class LayerWeights:
     """Device pointers of one encoder layer in kernel-ready (QKV-packed) form."""

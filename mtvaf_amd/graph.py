@@ -94,6 +94,9 @@ class GraphedTrainStep:
             # warm-up passes below (and raise on the second), GradSync would enqueue collectives into the capture
             raise RuntimeError("GraphedTrainStep: the encoder has a backward hook attached (AdamW(overlap=True) or GradSync); "
                                "build the optimizer with overlap=False and capture single-GPU steps only")
+        if getattr(getattr(model, "bert", None), "embedding_tap", None) is not None:
+            raise RuntimeError("GraphedTrainStep: the encoder's embedding_tap is set (mtvaf_amd.adversarial): an adversarial step "
+                               "is several eager passes and is not captured")
         self.model = model
         self.static = {k: v.clone() for k, v in tens.items()}
         self.const = {k: v for k, v in batch.items() if not torch.is_tensor(v)}

@@ -176,6 +176,9 @@ _SIGS = {
     "mtvaf_grad_pack_bf16": (c_int, [P, P, L, L, P]),
     "mtvaf_grad_reduce_bf16": (c_int, [P, P, I, L, F, P]),
     "mtvaf_grad_unpack_bf16": (c_int, [P, P, L, P]),
+    "mtvaf_adv_workspace_bytes": (SZ, [I, I]),
+    "mtvaf_adv_perturb": (c_int, [P, P, P, P, P, P, P, I, I, I, F, F, I, I, P, SZ, P]),
+    "mtvaf_adv_add": (c_int, [P, P, P, L, P]),
 }
 
 class LayerStruct(ctypes.Structure):
@@ -1748,3 +1751,60 @@ def grad_reduce_bf16(recv, out, world, chunk, scale):
 
 def grad_unpack_bf16(src, dst, n):
     _ck(lib().mtvaf_grad_unpack_bf16(_p(src), _p(dst), n, _st()), "mtvaf_grad_unpack_bf16")
+
+
+# ---- adversarial perturbation of the embedding output (csrc/adversarial.hip) ----------------------------------------
+ADV_NORMS = {"l2": 0, "linf": 1}          # MTVAF_ADV_NORM_*
+ADV_SCOPES = {"sentence": 0, "token": 1}  # MTVAF_ADV_SCOPE_*
+ADV_MAX_S, ADV_MAX_H = 512, 1024
+
+
+def adv_mask(mask):
+    """[B,S] mask of any dtype -> the contiguous u8 form the kernels read (non-zero = live)."""
+    if mask.dtype == torch.uint8 and mask.is_contiguous():
+        return mask
+    return mask.ne(0).contiguous().view(torch.uint8)
+
+
+def adv_perturb(g, mask, eps, step=0.0, norm="l2", scope="sentence", delta_in=None, x=None, delta_out=None, out=None, stats=None):
+    """One FGM (delta_in None) / PGD step on the gradient g [B,S,H] at the embedding output (include/mtvaf_hip.h,
+    mtvaf_adv_perturb): -> (delta_out [B,S,H], out = x + delta_out or None, stats [B,2] = |g|, |delta_out| per sentence).
+    mask [B,S], non-zero = live, any dtype; ``out`` is made when x is given.  No host sync; the launches go to the current stream.
+    delta_out may be delta_in."""
+    _f32(g, delta_in, x, delta_out, out, stats)
+    if g.dim() != 3:
+        raise ValueError(f"adv_perturb: g {tuple(g.shape)}: expected [B, S, H]")
+    B, S, H = g.shape
+    if norm not in ADV_NORMS or scope not in ADV_SCOPES:
+        raise ValueError(f"adv_perturb: norm {norm!r} / scope {scope!r}: expected one of {sorted(ADV_NORMS)} / {sorted(ADV_SCOPES)}")
+    m8 = adv_mask(mask)
+    if tuple(m8.shape) != (B, S):
+        raise ValueError(f"adv_perturb: mask {tuple(mask.shape)} does not match g {tuple(g.shape)}")
+    for name, t in (("delta_in", delta_in), ("x", x), ("delta_out", delta_out), ("out", out)):
+        if t is not None and t.shape != g.shape:
+            raise ValueError(f"adv_perturb: {name} {tuple(t.shape)} does not match g {tuple(g.shape)}")
+    if delta_out is None:
+        delta_out = torch.empty_like(g)
+    if out is not None and x is None:
+        raise ValueError("adv_perturb: out = x + delta_out needs x")
+    if x is not None and out is None:
+        out = torch.empty_like(g)
+    if stats is None:
+        stats = torch.empty(B, 2, dtype=torch.float32, device=g.device)
+    assert tuple(stats.shape) == (B, 2), stats.shape
+    nbytes = int(lib().mtvaf_adv_workspace_bytes(B, S))
+    ws = workspace(nbytes, g.device)
+    _ck(lib().mtvaf_adv_perturb(_p(g), _p(delta_in), _p(x), _p(m8), _p(delta_out), _p(out), _p(stats), B, S, H,
+                                float(eps), float(step), ADV_NORMS[norm], ADV_SCOPES[scope], _p(ws), ws.numel(), _st()),
+        "mtvaf_adv_perturb")
+    return delta_out, out, stats
+
+
+def adv_add(x, delta, out=None):
+    """out = x + delta (fp32, same shape, contiguous): the forward of the embedding tap."""
+    _f32(x, delta, out)
+    assert x.shape == delta.shape, (x.shape, delta.shape)
+    if out is None:
+        out = torch.empty_like(x)
+    _ck(lib().mtvaf_adv_add(_p(x), _p(delta), _p(out), x.numel(), _st()), "mtvaf_adv_add")
+    return out

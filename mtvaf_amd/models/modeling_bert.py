@@ -518,6 +518,9 @@ class BertModel(nn.Module):
     config_class = BertConfig
     base_model_prefix = "bert"
     embeddings_class = BertEmbeddings
+    # an engine.EmbeddingTap, or None: the embedding output then passes through engine.EmbeddingTapFunction, which can add a constant
+    # perturbation to it and keep the gradient that arrives there (mtvaf_amd.adversarial).  None: no node, no launch
+    embedding_tap = None
 
     def __init__(self, config, add_pooling_layer=True):
         super().__init__()
@@ -643,6 +646,8 @@ class BertModel(nn.Module):
             engine.Packing.begin(ext.view(B, -1), ext.shape[-1] - S, S)
         emb = self.embeddings(input_ids=input_ids, token_type_ids=token_type_ids, position_ids=position_ids,
                               inputs_embeds=inputs_embeds, past_key_values_length=0)
+        if self.embedding_tap is not None:
+            emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
         enc = self.encoder(emb, attention_mask=ext, past_key_values=past_key_values, output_attentions=output_attentions,
                            output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok)
         seq = enc.last_hidden_state
@@ -658,7 +663,10 @@ class BertModel(nn.Module):
     def get_embedding_output(self, input_ids, token_type_ids=None, position_ids=None):
         """reference: models/modeling_bert.py:1117-1125 (Cutoff augmentation entry)"""
         assert input_ids is not None
-        return self.embeddings(input_ids=input_ids, token_type_ids=token_type_ids, position_ids=position_ids)
+        emb = self.embeddings(input_ids=input_ids, token_type_ids=token_type_ids, position_ids=position_ids)
+        if self.embedding_tap is not None:
+            emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
+        return emb
 
     def get_bert_output(self, embedding_output, attention_mask=None, past_key_values=None):
         """reference: models/modeling_bert.py:1127-1157"""

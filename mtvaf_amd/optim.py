@@ -989,6 +989,20 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
         overlap, fused_steps = accumulation_plan(args)
+        # args.adv_eps > 0 (default 0: nothing changes): adversarial training on the embedding output (mtvaf_amd.adversarial,
+        # DESIGN.md 4.23; args.adv_norm, args.adv_steps, args.adv_weight).  One step is 1 + adv_steps backward passes: on the
+        # fallback the update waits for step(); with args.fused_accumulation they are the passes of the fused accumulation.  The
+        # Adversary is left in `optimizer.adversary`; the trainer calls its step(**batch) in place of model(**batch).loss.backward()
+        adv_passes = 1 + int(getattr(args, "adv_steps", 1) or 1) if float(getattr(args, "adv_eps", 0.0) or 0.0) > 0.0 else 0
+        if adv_passes:
+            if int(getattr(args, "gradient_accumulation_steps", 1) or 1) > 1:
+                raise ValueError("build_optimizer: adv_eps > 0 with gradient_accumulation_steps > 1 is not supported")
+            if getattr(args, "grad_sync", None) is not None or device_schedule:
+                raise ValueError("build_optimizer: adv_eps > 0 is single-GPU and eager (no grad_sync, no device_schedule)")
+            if bool(getattr(args, "fused_accumulation", False)):
+                fused_steps = adv_passes  # (overlap stays what the plan gave a step of one micro-batch)
+            else:
+                overlap = False
         extra = {"accumulation_steps": fused_steps} if fused_steps > 1 else {}
         if device_schedule:
             overlap = False
@@ -997,6 +1011,9 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
                     max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
                     **extra)
+        if adv_passes:
+            from .adversarial import from_args
+            opt.adversary = from_args(model, args, optimizer=opt)
         if device_schedule:
             return opt, ScheduleMirror(opt)
     else:
@@ -1006,6 +1023,8 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         if ema_decay > 0.0:
             raise ValueError("build_optimizer: ema_decay is implemented by the gfx950 AdamW kernels; the CPU fallback "
                              "(torch.optim.AdamW) would ignore it")
+        if float(getattr(args, "adv_eps", 0.0) or 0.0) > 0.0:
+            raise ValueError("build_optimizer: adv_eps is implemented by the gfx950 kernels; the model is not on the GPU")
         opt = torch.optim.AdamW(groups, lr=args.lr)
     sched = linear_schedule_with_warmup(opt, warmup_steps, train_num_steps)
     return opt, sched
