@@ -1061,6 +1061,39 @@ int mtvaf_adv_perturb(const float* g, const float* delta_in, const float* x, con
                       void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
 int mtvaf_adv_add(const float* x, const float* delta, float* out, long n, mtvaf_stream_t stream);
 
+/* ---- Sharpness-aware minimisation (SAM, Foret et al. 2021): the ascent step in weight space and the way back
+ * (mtvaf_amd/optim.py AdamW(sam_rho=...), mtvaf_amd/sam.py; new functionality, the reference trainer has nothing like it).
+ * Streaming kernels, no atomics, no host synchronisation: the same inputs give the same bits.
+ * mtvaf_sam_finalize (one block) adds the `count` double partials of mtvaf_grad_sqnorm_multi in index order and writes
+ * sam_state[4] (16-byte aligned):
+ *   [0] norm = fp32(sqrt(sum))   [1] scale = (float)(rho / (sqrt(sum) + 1e-12)), quotient and sum in double
+ *   [2] finite = 1.f / 0.f       [3] 0
+ * A norm that is not finite in fp32: scale = 0, finite = 0 and *skipped (int32, may be NULL) += 1.  rho finite and >= 0.
+ * mtvaf_sam_perturb: for every element  backup = p;  p = fmaf(sam_state[1], g, p)  -- one correctly rounded operation.  Any n,
+ * pointers 4-byte aligned; p_bf16 NULL or the bf16 shadow of the buffer, which receives the new p rounded as mtvaf_adamw rounds it.
+ * With sam_state[2] == 0 p keeps its bits (g is not read), and backup and the shadow are still written, from that unchanged p.
+ * mtvaf_sam_perturb_planes: the same over a flat buffer (n % 4 == 0; p, g, backup 16-byte aligned) that also rewrites the plane
+ * images of the nseg <= 4 matrices inside it; seg_begin / seg_rows / seg_cols / seg_img and the image layout are those of
+ * mtvaf_adamw_planes.  With sam_state[2] == 0 the images are written from the unchanged p.
+ * mtvaf_sam_perturb_multi: `count` tensors per call (host arrays of device pointers and lengths, any count: 48 per launch).
+ * mtvaf_sam_restore / _restore_planes / _restore_multi: p = backup bit for bit; the first two rewrite the shadow / the plane
+ * images from the restored values.  All three perturb forms give a buffer the same bits.
+ * Errors, checked before anything is launched: a NULL pointer (p_bf16 and skipped excepted), n <= 0, a misaligned pointer or
+ * length, p / backup (or g) ranges that overlap: MTVAF_ERR_ARG; a matrix table mtvaf_adamw_planes would refuse:
+ * MTVAF_ERR_ARG / MTVAF_ERR_SHAPE as there. */
+int mtvaf_sam_finalize(const void* partials, long count, float rho, float* sam_state, int* skipped, mtvaf_stream_t stream);
+int mtvaf_sam_perturb(float* p, const float* g, float* backup, long n, const float* sam_state, void* p_bf16,
+                      mtvaf_stream_t stream);
+int mtvaf_sam_perturb_planes(float* p, const float* g, float* backup, long n, const float* sam_state, int nseg,
+                             const long* seg_begin, const int* seg_rows, const int* seg_cols, void* const* seg_img,
+                             mtvaf_stream_t stream);
+int mtvaf_sam_perturb_multi(int count, float* const* p, const float* const* g, float* const* backup, const long* n,
+                            const float* sam_state, mtvaf_stream_t stream);
+int mtvaf_sam_restore(float* p, const float* backup, long n, void* p_bf16, mtvaf_stream_t stream);
+int mtvaf_sam_restore_planes(float* p, const float* backup, long n, int nseg, const long* seg_begin, const int* seg_rows,
+                             const int* seg_cols, void* const* seg_img, mtvaf_stream_t stream);
+int mtvaf_sam_restore_multi(int count, float* const* p, const float* const* backup, const long* n, mtvaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,12 +73,8 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(SqMulti t, double* __r
   if (threadIdx.x == 0) part[b] = s;
 }
 
-// state = {norm, coef, finite (1.f / 0.f), 0.f}.  `finite` is the *_dev kernels' permission to write: with skip_nonfinite == 0
-// it is always 1 and a non-finite norm reaches the update through coef as it does in torch (inf -> 0, NaN -> NaN).
-__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ part, long count, float max_norm,
-                                                                 int skip_nonfinite, float* __restrict__ state,
-                                                                 int* __restrict__ skipped) {
-  __shared__ double sh[256];
+// one block of 256 lanes: the `count` slots added in index order -> lane 0's return value (the other lanes': 0)
+__device__ __forceinline__ double ordered_sum_256(const double* __restrict__ part, long count, double* sh) {
   double sum = 0.0;  // (lane 0's)
   for (long base = 0; base < count; base += 256) {
     const long i = base + threadIdx.x;
@@ -96,6 +92,16 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* _
     }
     __syncthreads();
   }
+  return sum;
+}
+
+// state = {norm, coef, finite (1.f / 0.f), 0.f}.  `finite` is the *_dev kernels' permission to write: with skip_nonfinite == 0
+// it is always 1 and a non-finite norm reaches the update through coef as it does in torch (inf -> 0, NaN -> NaN).
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ part, long count, float max_norm,
+                                                                 int skip_nonfinite, float* __restrict__ state,
+                                                                 int* __restrict__ skipped) {
+  __shared__ double sh[256];
+  const double sum = ordered_sum_256(part, count, sh);
   if (threadIdx.x != 0) return;
   const double nd = sqrt(sum);
   const float norm = (float)nd;
@@ -112,6 +118,24 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* _
   state[2] = (finite || !skip_nonfinite) ? 1.f : 0.f;
   state[3] = 0.f;
   if (!finite && skip_nonfinite && skipped) *skipped += 1;
+}
+
+// The same sum for the SAM ascent step (mtvaf_sam_perturb*, csrc/optim.hip): state = {norm, scale, finite, 0.f} with
+// scale = (float)(rho / (norm + 1e-12)), quotient and sum in double, ONE rounding.  A norm that fp32 cannot hold: scale = 0,
+// finite = 0 -- the perturb launches then leave the parameters alone -- and *skipped += 1.
+__global__ __launch_bounds__(256) void sam_finalize_kernel(const double* __restrict__ part, long count, float rho,
+                                                           float* __restrict__ state, int* __restrict__ skipped) {
+  __shared__ double sh[256];
+  const double sum = ordered_sum_256(part, count, sh);
+  if (threadIdx.x != 0) return;
+  const double nd = sqrt(sum);
+  const float norm = (float)nd;
+  const bool finite = (norm - norm) == 0.f;
+  state[0] = norm;
+  state[1] = finite ? (float)((double)rho / (nd + 1e-12)) : 0.f;
+  state[2] = finite ? 1.f : 0.f;
+  state[3] = 0.f;
+  if (!finite && skipped) *skipped += 1;
 }
 
 }  // namespace mtvaf
@@ -176,6 +200,18 @@ int mtvaf_grad_clip_finalize(const void* partials, long count, float max_norm, i
   if (((uintptr_t)partials & 7) || ((uintptr_t)clip_state & 15) || ((uintptr_t)skipped & 3)) return MTVAF_ERR_ALIGN;
   hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, stream, static_cast<const double*>(partials), count,
                      max_norm, skip_nonfinite, clip_state, skipped);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+// One block: adds `count` partials in index order (double) and writes sam_state = {norm, scale = rho / (norm + 1e-12), finite, 0}
+// (4 floats, 16-byte aligned); rho finite and >= 0.  A norm that is not finite in fp32: scale = 0, finite = 0, *skipped += 1
+// (skipped may be NULL).  Any bad argument: MTVAF_ERR_ARG.
+int mtvaf_sam_finalize(const void* partials, long count, float rho, float* sam_state, int* skipped, hipStream_t stream) {
+  if (count < 0 || (count && !partials) || !sam_state || !(rho >= 0.f) || (rho - rho) != 0.f) return MTVAF_ERR_ARG;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)sam_state & 15) || ((uintptr_t)skipped & 3)) return MTVAF_ERR_ARG;
+  hipLaunchKernelGGL(sam_finalize_kernel, dim3(1), dim3(256), 0, stream, static_cast<const double*>(partials), count, rho, sam_state,
+                     skipped);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

@@ -158,6 +158,17 @@ struct AdamSegs {
   unsigned char* img[4];
   int n;
 };
+// float4 number i of the flat buffer, as it has just been stored: -> the image of the matrix it lies in, if it lies in one
+__device__ __forceinline__ void mats_store4(const AdamSegs& sg, long i, f32x4 P) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (s < sg.n && i >= sg.b4[s] && i < sg.e4[s]) {
+      const long e = (i - sg.b4[s]) * 4;
+      const long row = e / sg.cols[s];
+      planes_store4(sg.img[s], sg.rows[s], row, (int)(e - row * sg.cols[s]), P);
+    }
+  }
+}
 template <bool EMA>
 __device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, float* __restrict__ e, float ema_omd, long n4, AdamHyper h,
@@ -183,6 +194,7 @@ __device__ __forceinline__ void adamw_planes_body(float* __restrict__ p, const f
       for (int j = 0; j < 4; ++j) E[j] = ema1(E[j], P[j], ema_omd);
       __builtin_nontemporal_store(E, reinterpret_cast<f32x4*>(e) + i);
     }
+    // (mats_store4, spelled out: with the table passed by value these kernels compile to other code through the helper)
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if (s < sg.n && i >= sg.b4[s] && i < sg.e4[s]) {
@@ -304,14 +316,7 @@ __device__ __forceinline__ void adamw_planes_seg_body(float* __restrict__ p, con
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     seg_hyper(t, (int)i, h);
     const f32x4 P = adamw_vec4<EMA>(p, g, m, v, e, ema_omd, i, h);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (s < sg.n && i >= sg.b4[s] && i < sg.e4[s]) {
-        const long el = (i - sg.b4[s]) * 4;
-        const long row = el / sg.cols[s];
-        planes_store4(sg.img[s], sg.rows[s], row, (int)(el - row * sg.cols[s]), P);
-      }
-    }
+    mats_store4(sg, i, P);
   }
 }
 template <bool EMA, bool DEV>
@@ -906,6 +911,168 @@ static int swap_multi_launch(int count, float* const* a, float* const* b, const 
   return MTVAF_OK;
 }
 
+// ---- sharpness-aware minimisation: the ascent step in weight space and the way back (mtvaf_sam_*; mtvaf_amd/optim.py) --
+// sam_state = {norm, scale, finite, 0} is written by mtvaf_sam_finalize (csrc/gradnorm.hip) from the partial sums of
+// mtvaf_grad_sqnorm_multi.  Per element
+//     perturb:  backup = p;  p = fmaf(scale, g, p)          12 B read and written per parameter, + 2 B shadow or 6 B plane images
+//     restore:  p = backup                                    8 B
+// fmaf is ONE correctly rounded operation, so the vector body, the scalar body, the plane form and the multi-tensor form give the
+// same bits.  finite == 0 (block-uniform): p is carried over unchanged -- no arithmetic touches it, an inf or NaN in g cannot reach
+// it -- while backup, the bf16 shadow and the plane images are still written, from that unchanged p: after either outcome backup
+// holds the weights to return to and every image matches p, so the caller stamps them fresh without knowing which one it was.
+// RESTORE: g and the state are not read.
+template <bool RESTORE>
+__device__ __forceinline__ f32x4 sam_vec4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ backup, long i,
+                                          float scale, bool apply) {
+  f32x4 P;
+  if constexpr (RESTORE) {
+    P = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(backup) + i);  // (the backup is read once and never again)
+  } else {
+    P = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + i);
+    __builtin_nontemporal_store(P, reinterpret_cast<f32x4*>(backup) + i);
+    if (apply) {
+      const f32x4 G = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) P[j] = fmaf(scale, G[j], P[j]);
+    }
+  }
+  reinterpret_cast<f32x4*>(p)[i] = P;  // (read again by the next forward pass)
+  return P;
+}
+
+template <bool RESTORE>
+__device__ __forceinline__ void sam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ backup,
+                                         __bf16* __restrict__ ph, long n, long i0, long stride, float scale, bool apply) {
+  // vector body on 16-byte bases, scalar otherwise and for the tail: as adamw_span
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)backup) & 15) == 0) && (!ph || ((uintptr_t)ph & 7) == 0);
+  const long n4 = vec ? (n >> 2) : 0;
+  for (long i = i0; i < n4; i += stride) {
+    const f32x4 P = sam_vec4<RESTORE>(p, g, backup, i, scale, apply);
+    if (ph) {
+      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+      bf16x4 o = {(__bf16)P.x, (__bf16)P.y, (__bf16)P.z, (__bf16)P.w};
+      reinterpret_cast<bf16x4*>(ph)[i] = o;
+    }
+  }
+  for (long i = (n4 << 2) + i0; i < n; i += stride) {
+    float P;
+    if constexpr (RESTORE) {
+      P = backup[i];
+    } else {
+      P = p[i];
+      backup[i] = P;
+      if (apply) P = fmaf(scale, g[i], P);
+    }
+    p[i] = P;
+    if (ph) ph[i] = (__bf16)P;
+  }
+}
+
+// the state's two words a perturb launch reads (block-uniform, two scalar loads)
+__device__ __forceinline__ void sam_read(const float* __restrict__ state, float& scale, bool& apply) {
+  scale = state[1];
+  apply = state[2] != 0.f;
+}
+
+template <bool RESTORE>
+__global__ __launch_bounds__(256) void sam_kernel(float* p, const float* g, float* backup, __bf16* ph, long n, const float* state) {
+  float scale = 0.f;
+  bool apply = false;
+  if constexpr (!RESTORE) sam_read(state, scale, apply);
+  sam_span<RESTORE>(p, g, backup, ph, n, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, scale, apply);
+}
+
+template <bool RESTORE>
+__global__ __launch_bounds__(256) void sam_planes_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ backup,
+                                                         long n4, AdamSegs sg, const float* __restrict__ state) {
+  float scale = 0.f;
+  bool apply = false;
+  if constexpr (!RESTORE) sam_read(state, scale, apply);
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) mats_store4(sg, i, sam_vec4<RESTORE>(p, g, backup, i, scale, apply));
+}
+
+struct SamMulti {  // the prefix table of AdamMulti
+  float* p[ADAM_MAXT];
+  const float* g[ADAM_MAXT];
+  float* b[ADAM_MAXT];
+  long n[ADAM_MAXT];
+  int blk0[ADAM_MAXT + 1];
+  int count;
+};
+template <bool RESTORE>
+__global__ __launch_bounds__(256) void sam_multi_kernel(SamMulti t, const float* state) {
+  float scale = 0.f;
+  bool apply = false;
+  if constexpr (!RESTORE) sam_read(state, scale, apply);
+  int k = 0;
+  const int blk = blockIdx.x;
+  while (k + 1 < t.count && blk >= t.blk0[k + 1]) ++k;
+  sam_span<RESTORE>(t.p[k], t.g[k], t.b[k], nullptr, t.n[k], (long)(blk - t.blk0[k]) * 256 + threadIdx.x,
+                    (long)(t.blk0[k + 1] - t.blk0[k]) * 256, scale, apply);
+}
+
+static inline bool ranges_overlap(const void* a, const void* b, long n) {
+  const uintptr_t lo_a = (uintptr_t)a, lo_b = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+  return lo_a < lo_b + bytes && lo_b < lo_a + bytes;
+}
+
+// what every mtvaf_sam_* form checks of one (p, g, backup) triple; g == nullptr with restore.  The family reports a misaligned
+// pointer as MTVAF_ERR_ARG too (include/mtvaf_hip.h)
+static inline bool sam_triple_ok(const float* p, const float* g, const float* backup, long n, bool restore, uintptr_t align_mask) {
+  if (!p || !backup || (!restore && !g) || n <= 0) return false;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)backup) & align_mask) return false;
+  if (ranges_overlap(p, backup, n) || (!restore && (ranges_overlap(g, backup, n) || ranges_overlap(g, p, n)))) return false;
+  return true;
+}
+
+static int sam_launch(float* p, const float* g, float* backup, long n, const float* state, void* p_bf16, bool restore,
+                      hipStream_t stream) {
+  if (!sam_triple_ok(p, g, backup, n, restore, 3) || (!restore && (!state || ((uintptr_t)state & 3))) || ((uintptr_t)p_bf16 & 1))
+    return MTVAF_ERR_ARG;
+  const int grid = stream_grid((n + 3) / 4);
+  hipLaunchKernelGGL(restore ? sam_kernel<true> : sam_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, backup,
+                     static_cast<__bf16*>(p_bf16), n, state);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int sam_planes_launch(float* p, const float* g, float* backup, long n, const float* state, int nmat, const long* mat_begin,
+                             const int* mat_rows, const int* mat_cols, void* const* mat_img, bool restore, hipStream_t stream) {
+  if (!sam_triple_ok(p, g, backup, n, restore, 15) || (n & 3) || (!restore && (!state || ((uintptr_t)state & 3)))) return MTVAF_ERR_ARG;
+  AdamSegs sg;
+  if (const int rc = planes_mats(sg, n, nmat, mat_begin, mat_rows, mat_cols, mat_img)) return rc;
+  hipLaunchKernelGGL(restore ? sam_planes_kernel<true> : sam_planes_kernel<false>, dim3(stream_grid(n / 4)), dim3(256), 0, stream, p, g,
+                     backup, n / 4, sg, state);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+static int sam_multi_launch(int count, float* const* p, const float* const* g, float* const* backup, const long* n, const float* state,
+                            bool restore, hipStream_t stream) {
+  if (count < 0 || (count && (!p || !backup || !n || (!restore && !g))) || (!restore && (!state || ((uintptr_t)state & 3))))
+    return MTVAF_ERR_ARG;
+  // every tensor is checked before the first launch: a refused call has written nothing
+  for (int i = 0; i < count; ++i)
+    if (!sam_triple_ok(p[i], restore ? nullptr : g[i], backup[i], n[i], restore, 3)) return MTVAF_ERR_ARG;
+  for (int base = 0; base < count; base += ADAM_MAXT) {
+    SamMulti t;
+    t.count = count - base < ADAM_MAXT ? count - base : ADAM_MAXT;
+    int blocks = 0;
+    for (int k = 0; k < t.count; ++k) {
+      const int i = base + k;
+      t.p[k] = p[i]; t.g[k] = restore ? nullptr : g[i]; t.b[k] = backup[i]; t.n[k] = n[i];
+      t.blk0[k] = blocks;
+      long nb = ((n[i] + 3) / 4 + 255) / 256;
+      blocks += (int)(nb > 1024 ? 1024 : nb);
+    }
+    t.blk0[t.count] = blocks;
+    hipLaunchKernelGGL(restore ? sam_multi_kernel<true> : sam_multi_kernel<false>, dim3(blocks), dim3(256), 0, stream, t, state);
+    MTVAF_LAUNCH_CHECK();
+  }
+  return MTVAF_OK;
+}
+
 }  // namespace mtvaf
 
 using namespace mtvaf;
@@ -1068,6 +1235,37 @@ int mtvaf_adamw_planes_seg_sched(float* p, const float* g, float* m, float* v, l
 // sides overlap is refused before anything is launched.
 int mtvaf_swap_f32_multi(int count, float* const* a, float* const* b, const long* n, hipStream_t stream) {
   return swap_multi_launch(count, a, b, n, stream);
+}
+
+// The SAM ascent step under the device state of mtvaf_sam_finalize: backup = p, p = fmaf(sam_state[1], g, p); with sam_state[2] == 0
+// p keeps its bits and backup, the shadow and the images are written from it (the head of the sam kernels above).  The restore forms
+// copy backup over p and rewrite the shadow / the images from it.  Any bad argument: MTVAF_ERR_ARG (matrix tables: as
+// mtvaf_adamw_planes), nothing launched.
+int mtvaf_sam_perturb(float* p, const float* g, float* backup, long n, const float* sam_state, void* p_bf16, hipStream_t stream) {
+  return sam_launch(p, g, backup, n, sam_state, p_bf16, false, stream);
+}
+
+int mtvaf_sam_perturb_planes(float* p, const float* g, float* backup, long n, const float* sam_state, int nseg, const long* seg_begin,
+                             const int* seg_rows, const int* seg_cols, void* const* seg_img, hipStream_t stream) {
+  return sam_planes_launch(p, g, backup, n, sam_state, nseg, seg_begin, seg_rows, seg_cols, seg_img, false, stream);
+}
+
+int mtvaf_sam_perturb_multi(int count, float* const* p, const float* const* g, float* const* backup, const long* n,
+                            const float* sam_state, hipStream_t stream) {
+  return sam_multi_launch(count, p, g, backup, n, sam_state, false, stream);
+}
+
+int mtvaf_sam_restore(float* p, const float* backup, long n, void* p_bf16, hipStream_t stream) {
+  return sam_launch(p, nullptr, const_cast<float*>(backup), n, nullptr, p_bf16, true, stream);
+}
+
+int mtvaf_sam_restore_planes(float* p, const float* backup, long n, int nseg, const long* seg_begin, const int* seg_rows,
+                             const int* seg_cols, void* const* seg_img, hipStream_t stream) {
+  return sam_planes_launch(p, nullptr, const_cast<float*>(backup), n, nullptr, nseg, seg_begin, seg_rows, seg_cols, seg_img, true, stream);
+}
+
+int mtvaf_sam_restore_multi(int count, float* const* p, const float* const* backup, const long* n, hipStream_t stream) {
+  return sam_multi_launch(count, p, nullptr, const_cast<float* const*>(backup), n, nullptr, true, stream);
 }
 
 int mtvaf_grad_pack_bf16(const float* src, void* dst, long n, long npad, hipStream_t stream) {

@@ -195,11 +195,12 @@ def shadow_for_update(w: LayerWeights):
     return w._h[1] if (hip.COMPUTE == "bf16" and w._h is not None) else None
 
 
-def shadow_written(w: LayerWeights):
+def shadow_written(w: LayerWeights, epoch_ahead: int = 1):
     """Called from inside ``optimizer.step()`` (or the backward pass preceding it): the image matches the masters as they
-    will be once this step's post-step hook has run."""
+    will be once this step's post-step hook has run.  ``epoch_ahead=0``: the writer is no optimizer step and no post-step hook
+    follows it (``AdamW.perturb``) -- the image matches the masters as they are."""
     if w._h is not None:
-        w._h[0] = shadow_version(w, 1)
+        w._h[0] = shadow_version(w, epoch_ahead)
 
 
 _OPT_EPOCH = [0]
@@ -254,12 +255,16 @@ def _weights_planes(w: "LayerWeights"):
     return c[2]
 
 
-def planes_for_update(w: "LayerWeights"):
+def planes_for_update(w: "LayerWeights", keep_read_mark: bool = False):
     """-> [(first element in w.flat, rows, cols, image), ...] of the layer's four weight matrices when their plane images exist (a
     forward pass on the pre-split path has built them): ``hip.adamw_planes`` rewrites them inside the update; the caller then stamps
-    them with ``planes_written``.  None: no images to maintain."""
+    them with ``planes_written``.  None: no images to maintain.  ``keep_read_mark``: a writer that the step's own update follows
+    (the SAM restore) -- the images are handed out as they stand and the update still finds the forward pass's mark."""
     if w._pl is None or not F32_PLANES or hip.COMPUTE != "fp32":
         return None
+    if keep_read_mark:
+        base = w.flat.data_ptr()
+        return [((t.data_ptr() - base) // 4, t.shape[0], t.shape[1], v) for t, v in zip((w.wqkv, w.wo, w.w1, w.w2), w._pl[2])]
     if not w._pl[3]:
         # no forward pass has read the images since the last update (the run went padded, below F32_PLANES_MIN_ROWS or switched the
         # path off): stop paying 6 bytes per weight per step for them; the next pre-split forward rebuilds them
@@ -272,9 +277,16 @@ def planes_for_update(w: "LayerWeights"):
     return [((t.data_ptr() - base) // 4, t.shape[0], t.shape[1], v) for t, v in zip((w.wqkv, w.wo, w.w1, w.w2), w._pl[2])]
 
 
-def planes_written(w: "LayerWeights"):
+def planes_written(w: "LayerWeights", epoch_ahead: int = 1):
+    """(``epoch_ahead``: as ``shadow_written``)"""
     if w._pl is not None:
-        w._pl[0] = shadow_version(w, 1)
+        w._pl[0] = shadow_version(w, epoch_ahead)
+
+
+def images_left_stale(w: "LayerWeights", shadow, mats) -> bool:
+    """Does the layer hold a cached image that a writer of ``w.flat`` maintaining only ``shadow`` / ``mats`` (what
+    ``shadow_for_update`` / ``planes_for_update`` gave it; None: nothing) leaves behind the masters?"""
+    return (w._h is not None and shadow is None) or (w._pl is not None and mats is None)
 
 
 def planes_rewrite(w: "LayerWeights"):

@@ -71,6 +71,9 @@ class GraphedTrainStep:
         """What a captured optimizer step needs; refused before anything runs."""
         from .optim import AdamW
         who = "GraphedTrainStep(optimizer=...)"
+        if isinstance(optimizer, AdamW) and optimizer.sam_rho > 0.0:
+            raise RuntimeError(f"{who}: AdamW(sam_rho > 0) takes two eager passes with perturb() between them and is not captured; "
+                               "run it through mtvaf_amd.sam.SharpnessAware, or build the optimizer with sam_rho=0")
         if not isinstance(optimizer, AdamW) or optimizer.device_schedule is None:
             raise RuntimeError(f"{who} needs a mtvaf_amd.optim.AdamW with device_schedule=optim.schedule_table(...): host-fed "
                                "learning rates and bias corrections would be frozen by the capture")

@@ -179,6 +179,13 @@ _SIGS = {
     "mtvaf_adv_workspace_bytes": (SZ, [I, I]),
     "mtvaf_adv_perturb": (c_int, [P, P, P, P, P, P, P, I, I, I, F, F, I, I, P, SZ, P]),
     "mtvaf_adv_add": (c_int, [P, P, P, L, P]),
+    "mtvaf_sam_finalize": (c_int, [P, L, F, P, P, P]),
+    "mtvaf_sam_perturb": (c_int, [P, P, P, L, P, P, P]),
+    "mtvaf_sam_perturb_planes": (c_int, [P, P, P, L, P, I, P, P, P, P, P]),
+    "mtvaf_sam_perturb_multi": (c_int, [I, P, P, P, P, P, P]),
+    "mtvaf_sam_restore": (c_int, [P, P, L, P, P]),
+    "mtvaf_sam_restore_planes": (c_int, [P, P, L, I, P, P, P, P, P]),
+    "mtvaf_sam_restore_multi": (c_int, [I, P, P, P, P]),
 }
 
 class LayerStruct(ctypes.Structure):
@@ -1808,3 +1815,80 @@ def adv_add(x, delta, out=None):
         out = torch.empty_like(x)
     _ck(lib().mtvaf_adv_add(_p(x), _p(delta), _p(out), x.numel(), _st()), "mtvaf_adv_add")
     return out
+
+
+# ---- sharpness-aware minimisation: the ascent step in weight space (csrc/optim.hip, csrc/gradnorm.hip) --------------
+def _sam_state_ptr(state):
+    """Device SAM state of sam_finalize for the perturb kernels: 4 floats {norm, scale, finite, 0}."""
+    assert state.is_cuda and state.dtype == torch.float32 and state.numel() >= 4 and state.is_contiguous(), (state.device, state.dtype,
+                                                                                                                state.shape)
+    return state.data_ptr()
+
+
+def _sam_same(p, *others):
+    _f32(p, *others)
+    for t in others:
+        assert t is None or t.numel() == p.numel(), (p.shape, t.shape)
+
+
+def sam_finalize(partials, rho, state, skipped=None):
+    """state (4 floats on the device) <- {norm, scale, finite, 0} from the partial sums of grad_sqnorm, added in index order:
+    scale = float(rho / (norm + 1e-12)) with the quotient in double; a norm that fp32 cannot hold gives scale = 0, finite = 0 and
+    adds 1 to `skipped` (device int32)."""
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+    assert skipped is None or (skipped.is_cuda and skipped.dtype == torch.int32)
+    _ck(lib().mtvaf_sam_finalize(_p(partials), partials.numel(), float(rho), _sam_state_ptr(state), _p(skipped), _st()),
+        "mtvaf_sam_finalize")
+    return state
+
+
+def sam_perturb(p, g, backup, state, p_bf16=None):
+    """backup = p; p = fmaf(scale, g, p) over one flat fp32 tensor, scale read from the device state of sam_finalize (finite == 0: p
+    keeps its bits, backup is written all the same).  p_bf16: the bf16 shadow of p, written from the new p in the same pass."""
+    _sam_same(p, g, backup)
+    _ck(lib().mtvaf_sam_perturb(_p(p), _p(g), _p(backup), p.numel(), _sam_state_ptr(state), _p(p_bf16), _st()), "mtvaf_sam_perturb")
+
+
+def sam_perturb_planes(p, g, backup, state, segs):
+    """sam_perturb over a flat buffer that also rewrites the plane images of the matrices inside it: segs as adamw_planes'."""
+    _sam_same(p, g, backup)
+    _ck(lib().mtvaf_sam_perturb_planes(_p(p), _p(g), _p(backup), p.numel(), _sam_state_ptr(state), *_mat_args(segs), _st()),
+        "mtvaf_sam_perturb_planes")
+
+
+def sam_perturb_multi(ps, gs, backups, state):
+    """sam_perturb over lists of tensors: one launch per 48."""
+    k = len(ps)
+    assert len(gs) == k and len(backups) == k
+    if k == 0:
+        return
+    for t in zip(ps, gs, backups):
+        _sam_same(*t)
+    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
+    _ck(lib().mtvaf_sam_perturb_multi(k, arr(ps), arr(gs), arr(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]),
+                                      _sam_state_ptr(state), _st()), "mtvaf_sam_perturb_multi")
+
+
+def sam_restore(p, backup, p_bf16=None):
+    """p = backup, bit for bit; p_bf16: the bf16 shadow of p, rewritten from the restored values."""
+    _sam_same(p, backup)
+    _ck(lib().mtvaf_sam_restore(_p(p), _p(backup), p.numel(), _p(p_bf16), _st()), "mtvaf_sam_restore")
+
+
+def sam_restore_planes(p, backup, segs):
+    """sam_restore over a flat buffer that also rewrites the plane images of the matrices inside it: segs as adamw_planes'."""
+    _sam_same(p, backup)
+    _ck(lib().mtvaf_sam_restore_planes(_p(p), _p(backup), p.numel(), *_mat_args(segs), _st()), "mtvaf_sam_restore_planes")
+
+
+def sam_restore_multi(ps, backups):
+    """sam_restore over lists of tensors: one launch per 48 (no image is rewritten)."""
+    k = len(ps)
+    assert len(backups) == k
+    if k == 0:
+        return
+    for t in zip(ps, backups):
+        _sam_same(*t)
+    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
+    _ck(lib().mtvaf_sam_restore_multi(k, arr(ps), arr(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]), _st()),
+        "mtvaf_sam_restore_multi")

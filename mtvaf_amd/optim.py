@@ -207,6 +207,20 @@ class AdamW(torch.optim.Optimizer):
     kernels any more; a scheduler may still write it for readers (``ScheduleMirror``, or a ``LambdaLR`` with the table's factor)
     and ``assert_schedule_agrees()`` compares the two on demand.
 
+    ``sam_rho > 0``: sharpness-aware minimisation (Foret et al. 2021).  The loop is: backward, ``perturb()``, forward
+    and backward again, ``step()`` -- ``mtvaf_amd.sam.SharpnessAware`` runs it.  ``perturb()`` moves every parameter the step would
+    update to ``p + sam_rho * g / (|g| + 1e-12)`` (global norm in double on the device, no host synchronisation), keeps the weights
+    aside (4 B per parameter, allocated at the first call) and discards the first pass's gradients; an encoder layer is ONE launch
+    that also rewrites the bf16 shadow or the plane images, so the second pass's GEMMs read the perturbed weights.  ``step()``
+    restores the weights bit for bit and then is the step it always was (clipping, averages, segments); where clipping can drop
+    the step on the device the restore rewrites the images too.  ``last_sam_norm`` (0-dim device view) and ``sam_skipped`` (device
+    int32: a non-finite norm leaves the weights alone) report.  ``step()`` without ``perturb()`` is a plain step; ``unperturb()``
+    restores without one.  Like ``max_grad_norm`` a setting of the optimizer, not in ``defaults``; nothing of it is in
+    ``state_dict()``.  Raises: ``overlap=True``, ``accumulation_steps > 1``, ``device_schedule`` / a ``GraphedTrainStep``, a
+    ``GradSync`` with several ranks, ``perturb()`` while the averages are swapped in or twice without ``step()``,
+    ``load_state_dict`` while perturbed.  At ``sam_rho == 0`` (default) nothing is allocated and ``step()`` issues the launches it
+    always did.
+
     Checkpoints: ``state_dict()`` / ``load_state_dict()`` are torch.optim's; the flat per-layer moment buffers are
     rebuilt from the loaded per-parameter ``exp_avg`` / ``exp_avg_sq`` / ``step`` entries on the first update.  Under a device
     schedule loading also sets the host mirror and the device counter to the loaded step count."""
@@ -214,9 +228,31 @@ class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  model: Optional[torch.nn.Module] = None, overlap: bool = False, grad_sync=None, max_grad_norm: float = 0.0,
                  track_grad_norm: bool = False, skip_nonfinite: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 accumulation_steps: int = 1, device_schedule: Optional[ScheduleTable] = None):
+                 accumulation_steps: int = 1, device_schedule: Optional[ScheduleTable] = None, sam_rho: float = 0.0):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
+        sam_rho = float(sam_rho or 0.0)
+        if not (0.0 <= sam_rho < float("inf")):  # (NaN fails both comparisons)
+            raise ValueError("sam_rho must be finite and >= 0 (0: no sharpness-aware step)")
+        if sam_rho > 0.0:
+            who = "mtvaf_amd.optim.AdamW(sam_rho > 0)"
+            if overlap:
+                raise ValueError(f"{who} needs overlap=False: layers updated from inside the first backward pass would move the "
+                                 "weights before perturb() has read them (build_optimizer arranges it)")
+            if int(accumulation_steps or 1) > 1:
+                raise ValueError(f"{who} with accumulation_steps > 1 is not supported: perturb() discards the first pass's gradients, "
+                                 "fused accumulation would add them to the second pass's; use accumulation_steps=1")
+            if device_schedule is not None:
+                raise ValueError(f"{who} with device_schedule is not supported: a SAM step is two eager passes with perturb() between "
+                                 "them and cannot be captured; use a LambdaLR (linear_schedule_with_warmup) on the host")
+        self.sam_rho = sam_rho
+        self.sam_perturbed = False  # True between perturb() and the step() that restores the weights
+        self.last_sam_norm = None   # 0-dim view of _sam_state[0]: the gradient norm the last perturb() scaled by
+        self.sam_skipped = None     # device int32: perturb() calls whose norm was not finite (the weights were left alone)
+        self._sam_state = None      # device {norm, scale, finite, 0}: written by hip.sam_finalize, read by the perturb kernels
+        self._sam_partials = None
+        self._sam_backup = {}       # ("layer", li) / id(parameter) -> the weights before perturb(): 4 B per parameter, kept
+        self._sam_record = None     # what the last perturb() wrote: ([(store, backup)], [parameters], [backups])
         max_grad_norm = float(max_grad_norm or 0.0)
         if max_grad_norm != max_grad_norm or max_grad_norm < 0.0:
             raise ValueError("max_grad_norm must be >= 0 (0: no clipping)")
@@ -262,6 +298,8 @@ class AdamW(torch.optim.Optimizer):
         enc = getattr(getattr(model, "bert", model), "encoder", None)
         if enc is None or not hasattr(enc, "grad_sink"):
             raise ValueError("AdamW.attach needs a mtvaf_amd model (TVNetSAModel2 / TVNetSAModel / BertModel)")
+        if self.sam_rho > 0.0:
+            self._sam_refuse_parallel(grad_sync)
         self._encoder = enc
         self._map_layers()
         # under GradSync the hook runs on the communication stream, where a slow update would delay the next layer's
@@ -379,6 +417,9 @@ class AdamW(torch.optim.Optimizer):
         return st
 
     def load_state_dict(self, state_dict):
+        if self.sam_perturbed:
+            raise RuntimeError("mtvaf_amd.optim.AdamW.load_state_dict: the weights are perturbed (perturb() without step()); call "
+                               "step() or unperturb() first -- a checkpoint never holds the perturbed weights or their backup")
         super().load_state_dict(state_dict)
         # the flat per-layer buffers are rebuilt from the loaded per-parameter entries by the next _layer_state()
         self.__dict__["_flat_state"] = {}
@@ -738,6 +779,157 @@ class AdamW(torch.optim.Optimizer):
         self._update_layer_flat(li, group, stores[li], background=background, rows=rows)
         self._early.add(li)
 
+    # -- sharpness-aware minimisation ---------------------------------------------------------------------
+    def _sam_refuse_parallel(self, grad_sync=None):
+        who = "mtvaf_amd.optim.AdamW(sam_rho > 0)"
+        sink = getattr(self._encoder, "_sink", None) if self._encoder is not None else None
+        owner = getattr(getattr(sink, "on_layer_done", None), "__self__", None)
+        if grad_sync is None and type(owner).__name__ == "GradSync":
+            grad_sync = owner
+        several = grad_sync is not None and (getattr(grad_sync, "world", 1) > 1 or getattr(grad_sync, "force", False))
+        try:
+            import torch.distributed as dist
+            several = several or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        except Exception:  # pragma: no cover
+            pass
+        if several:
+            raise RuntimeError(f"{who}: data-parallel training (GradSync with several ranks) is not supported -- the perturbation "
+                               "would be scaled by one rank's gradient norm; train on one GPU or build the optimizer with sam_rho=0")
+
+    def _sam_collect(self):
+        """What ``step()`` would update right now, without touching a counter: -> ([(layer index, store)] of the layers on the one-launch
+        path, [(parameter, gradient)] of everything else)."""
+        done, layers = set(), []
+        enc = self._encoder
+        if enc is not None and enc._stores is not None:
+            if len(self._layer_group) != len(enc.layer):
+                self._map_layers()
+            for li, layer in enumerate(enc.layer):
+                store = enc._stores[li]
+                if self._plan(li, store) is None or store.grad is None or not store.valid(layer):
+                    continue
+                ps = layer.ordered_params()
+                lo = store.grad.data_ptr()
+                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
+                       for i, p in enumerate(ps)):
+                    layers.append((li, store))
+                    done.update(id(p) for p in ps)
+        rest = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None or id(p) in done:
+                    continue
+                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
+                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
+                if not p.is_contiguous():
+                    raise RuntimeError("non-contiguous parameter")
+                rest.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous()))
+        return layers, rest
+
+    def _sam_buffer(self, key, like):
+        b = self._sam_backup.get(key)
+        if b is None or b.numel() != like.numel() or b.device != like.device:
+            b = self._sam_backup[key] = torch.empty(like.numel(), dtype=torch.float32, device=like.device)
+        return b
+
+    @torch.no_grad()
+    def perturb(self):
+        """The ascent step of SAM, after the first backward pass: every parameter ``step()`` would update moves to
+        ``p + sam_rho * g / (|g| + 1e-12)`` with ``|g|`` the global L2 norm of those gradients (double on the device, no host
+        synchronisation), the weights it had are kept aside, and the first pass's gradients are discarded -- the second backward
+        pass then leaves the gradient ``step()`` applies, after putting the weights back.  An encoder layer on the one-launch path
+        is one launch that also rewrites the bf16 shadow or the plane images its GEMMs read, so the second forward pass multiplies
+        by the perturbed weights.  A norm that is not finite leaves the weights alone and counts in ``sam_skipped``."""
+        who = "mtvaf_amd.optim.AdamW.perturb"
+        if self.sam_rho <= 0.0:
+            raise RuntimeError(f"{who}: the optimizer was built with sam_rho=0; pass sam_rho > 0 to AdamW (or build_optimizer's args)")
+        if self.sam_perturbed:
+            raise RuntimeError(f"{who} was called twice without optimizer.step(): the weights are already perturbed (step() applies "
+                               "the second pass's gradient and restores them; unperturb() only restores them)")
+        self._refuse_swapped("perturb() was called")
+        self._sam_refuse_parallel()
+        if hip.STREAM_OVERRIDE is not None:
+            raise RuntimeError(f"{who} was called from inside a backward hook -- the pass has not produced every gradient yet")
+        layers, rest = self._sam_collect()
+        grads = [store.grad for _, store in layers] + [g for _, g in rest]
+        if not grads:
+            raise RuntimeError(f"{who}: no parameter has a gradient; call it after the first loss.backward()")
+        dev = grads[0].device
+        if self._sam_state is None or self._sam_state.device != dev:
+            self._sam_state = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.last_sam_norm = self._sam_state[0]
+            self.sam_skipped = torch.zeros((), dtype=torch.int32, device=dev)
+            self._sam_partials = None
+        slots = hip.grad_sqnorm_slots(grads)
+        if self._sam_partials is None or self._sam_partials.numel() < slots:
+            self._sam_partials = torch.empty(slots, dtype=torch.float64, device=dev)
+        state = hip.sam_finalize(hip.grad_sqnorm(grads, self._sam_partials), self.sam_rho, self._sam_state, self.sam_skipped)
+        from . import engine
+        jobs, fast = [], set()
+        for li, store in layers:
+            w = store.weights
+            shadow = engine.shadow_for_update(w)
+            mats = engine.planes_for_update(w) if shadow is None else None
+            if store.flat.numel() % 4:
+                mats = None
+            jobs.append((store, shadow, mats, self._sam_buffer(("layer", li), store.flat)))
+            fast.add(li)
+        enc = self._encoder
+        stale = any(engine.images_left_stale(store.weights, shadow, mats) for store, shadow, mats, _ in jobs)
+        if enc is not None and enc._stores is not None:  # (a layer that goes tensor by tensor below: nothing maintains its images)
+            stale = stale or any(li not in fast and engine.images_left_stale(st.weights, None, None) for li, st in enumerate(enc._stores))
+        if stale:
+            engine.invalidate_weight_images()  # (before the stamps below)
+        for store, shadow, mats, backup in jobs:
+            if mats is not None:
+                hip.sam_perturb_planes(store.flat, store.grad, backup, state, mats)
+                engine.planes_written(store.weights, 0)  # (no optimizer step, no post-step hook: fresh as of now)
+            else:
+                hip.sam_perturb(store.flat, store.grad, backup, state, p_bf16=shadow)
+                if shadow is not None:
+                    engine.shadow_written(store.weights, 0)
+        ps = [p.data for p, _ in rest]
+        bs = [self._sam_buffer(id(p), p) for p, _ in rest]
+        hip.sam_perturb_multi(ps, [g for _, g in rest], bs, state)
+        self._sam_record = ([(store, backup) for store, _, _, backup in jobs], ps, bs)
+        for group in self.param_groups:  # the first pass's gradients: the applied gradient is the second pass's alone
+            for p in group["params"]:
+                p.grad = None
+        sink = getattr(enc, "_sink", None) if enc is not None else None
+        if sink is not None:
+            sink.reset_passes()
+        self.sam_perturbed = True
+
+    def _sam_restore(self, images: bool):
+        """The weights of before ``perturb()`` back, bit for bit.  ``images``: through the forms that rewrite the bf16 shadow / the plane
+        images from the restored values (an update that may write nothing follows, and stamps them); otherwise one multi-tensor copy
+        (the update that follows rewrites them)."""
+        from . import engine
+        layer_jobs, ps, bs = self._sam_record
+        if not images:
+            hip.sam_restore_multi([store.flat for store, _ in layer_jobs] + ps, [b for _, b in layer_jobs] + bs)
+        else:
+            for store, backup in layer_jobs:
+                w = store.weights
+                shadow = engine.shadow_for_update(w)
+                mats = engine.planes_for_update(w, keep_read_mark=True) if shadow is None else None
+                if mats is not None and store.flat.numel() % 4 == 0:
+                    hip.sam_restore_planes(store.flat, backup, mats)
+                else:
+                    hip.sam_restore(store.flat, backup, p_bf16=shadow)
+            hip.sam_restore_multi(ps, bs)
+        self._sam_record = None
+        self.sam_perturbed = False
+
+    @torch.no_grad()
+    def unperturb(self):
+        """Put back the weights of before ``perturb()`` without a step (the second pass raised, or its result is not wanted): one
+        copy, and every cached weight image is declared stale -- the next forward pass rebuilds them."""
+        if self.sam_perturbed:
+            self._sam_restore(images=False)
+            from . import engine
+            engine.invalidate_weight_images()
+
     # -- the step ------------------------------------------------------------------------------------------------
     def _clip_launch(self, grads):
         """Norm + finalize over the gradients this step applies, on the stream of the updates that follow; -> the device state."""
@@ -773,6 +965,10 @@ class AdamW(torch.optim.Optimizer):
         self._refuse_swapped("step() was called")
         clipping = self.max_grad_norm > 0.0 or self.track_grad_norm
         ema_on = self.ema_decay > 0.0
+        if self.sam_perturbed:
+            # the weights of before perturb() first.  Where the update below may write nothing (a non-finite norm under clipping) the
+            # images it stamps fresh must already hold the restored values; otherwise it rewrites them itself and a copy is enough
+            self._sam_restore(images=clipping and self.skip_nonfinite)
         if clipping and hip.STREAM_OVERRIDE is not None:
             raise RuntimeError("mtvaf_amd.optim.AdamW: step() with max_grad_norm / track_grad_norm was called from inside a backward "
                                "hook -- the gradient norm would be taken before the pass has produced every gradient")
@@ -1004,6 +1200,16 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
             else:
                 overlap = False
         extra = {"accumulation_steps": fused_steps} if fused_steps > 1 else {}
+        # args.sam_rho > 0 (default 0: nothing changes): sharpness-aware minimisation.  The update waits for step(),
+        # as under clipping; the trainer calls mtvaf_amd.sam.SharpnessAware(model, opt).step(**batch) in place of its three lines
+        sam_rho = float(getattr(args, "sam_rho", 0.0) or 0.0)
+        if sam_rho > 0.0:
+            if int(getattr(args, "gradient_accumulation_steps", 1) or 1) > 1 or adv_passes:
+                raise ValueError("build_optimizer: sam_rho > 0 with gradient_accumulation_steps > 1 or adv_eps > 0 is not supported")
+            if getattr(args, "grad_sync", None) is not None or device_schedule:
+                raise ValueError("build_optimizer: sam_rho > 0 is single-GPU and eager (no grad_sync, no device_schedule)")
+            overlap = False
+            extra["sam_rho"] = sam_rho
         if device_schedule:
             overlap = False
             extra["device_schedule"] = schedule_table(linear_warmup_factor(warmup_steps, train_num_steps), train_num_steps,
@@ -1025,6 +1231,8 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
                              "(torch.optim.AdamW) would ignore it")
         if float(getattr(args, "adv_eps", 0.0) or 0.0) > 0.0:
             raise ValueError("build_optimizer: adv_eps is implemented by the gfx950 kernels; the model is not on the GPU")
+        if float(getattr(args, "sam_rho", 0.0) or 0.0) > 0.0:
+            raise ValueError("build_optimizer: sam_rho is implemented by the gfx950 AdamW kernels; the model is not on the GPU")
         opt = torch.optim.AdamW(groups, lr=args.lr)
     sched = linear_schedule_with_warmup(opt, warmup_steps, train_num_steps)
     return opt, sched
