@@ -887,7 +887,12 @@ size_t mtvaf_layer_struct_bytes(int which /* 0: mtvaf_layer_t, 1: mtvaf_layer_gr
  * optionally writes the updated parameters rounded to bf16 (the GEMM operand shadow of the bf16 compute mode);
  * max_blocks > 0 caps its grid (a background update that trickles under MFMA-bound kernels instead of taking the whole
  * HBM rate from them for its duration; 0 = full width).
- * mtvaf_adamw_multi updates `count` tensors of one parameter group per launch (host arrays of device pointers). */
+ * mtvaf_adamw_multi updates `count` tensors of one parameter group per launch (host arrays of device pointers); every tensor is
+ * checked before the first launch, so a refused call has written nothing.
+ * The arithmetic of one element is the same in every mtvaf_adamw* entry point, on aligned and unaligned bases, each line ONE fp32
+ * rounding (s = grad_scale, times the clip coefficient in the *_dev forms; omb = (float)(1 - beta); sqrt and / correctly rounded):
+ *   gs = g * s;  d = fma(g, s, -m);  m = fma(omb1, d, m);  v = fma(beta2, v, gs * (omb2 * gs));
+ *   p1 = fma(-(lr * wd), p, p);  den = sqrt(v) / bc2_sqrt + eps;  p = fma(-(lr / bc1), m / den, p1) */
 int mtvaf_adamw(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
                 float weight_decay, float bc1, float bc2_sqrt, float grad_scale, void* p_bf16, int max_blocks,
                 mtvaf_stream_t stream);

@@ -5,6 +5,7 @@ here imports mtvaf_amd: the references are numpy / torch on the host.
 
 Every case is the smallest shape at which its kernel can still go wrong; the ids name the branch a case is there for."""
 import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -146,8 +147,9 @@ def adamw_ref(p, g, m, v, lr, wd, step, grad_scale=1.0):
 
 
 def adamw_f32(p, g, m, v, lr, wd, step, grad_scale=1.0):
-    """The five lines of adamw1 (csrc/optim.hip) in fp32 on the host, every operation rounded, no contraction; the
-    hyper-parameters rounded as make_hyper and the wrapper round them."""
+    """The update of adamw1 (csrc/optim.hip) in fp32 on the host, every operation rounded on its own, no fused multiply-add (the
+    device's own sequence, with its fmas, is adamw_pinned below); the hyper-parameters rounded as make_hyper and the wrapper round
+    them."""
     f = lambda x: torch.tensor(x, dtype=torch.float32)
     bc1, bc2s = f(1.0 - BETA1 ** step), f((1.0 - BETA2 ** step) ** 0.5)
     lr_, wd_, gs = f(lr), f(wd), f(grad_scale)
@@ -159,6 +161,62 @@ def adamw_f32(p, g, m, v, lr, wd, step, grad_scale=1.0):
     denom = v.sqrt() / bc2s + eps
     p = p - (lr_ / bc1) * (m / denom)
     return p, m, v
+
+
+def _round32(x):
+    """Fraction -> the nearest float32 (ties to even; gradual underflow), as a Fraction."""
+    if x == 0:
+        return x
+    n, d = abs(x.numerator), x.denominator
+    e = n.bit_length() - d.bit_length()
+    if Fraction(n, d) < Fraction(2) ** e:
+        e -= 1  # 2^e <= |x| < 2^(e + 1)
+    quantum = Fraction(2) ** (max(e, -126) - 23)
+    return round(x / quantum) * quantum  # (round() of a Fraction: half to even)
+
+
+PINNED_N = 64  # elements of the bit-for-bit device tests: one block, 16 float4s; the exact arithmetic below takes ~10 ms per element
+
+
+def pinned_inputs(seed, n=PINNED_N):
+    """adam_inputs without the planted elements (no denormal, no 1e-20 gradient: flushing is not part of the pinned contract)."""
+    g = gen(seed)
+    p = torch.randn(n, generator=g)
+    g1, g2 = torch.randn(n, generator=g) * 0.1, torch.randn(n, generator=g) * 0.1
+    m, v = torch.randn(n, generator=g) * 0.01, torch.rand(n, generator=g) * 0.01
+    return p, m, v, (g1, g2)
+
+
+def adamw_pinned(p, g, m, v, lr, wd, step, grad_scale=1.0):
+    """The rounding sequence adamw1 (csrc/optim.hip) pins, in exact rational arithmetic with ONE correctly rounded conversion to
+    float32 per line; hyper-parameters rounded as make_hyper and the wrapper round them.  fp32 in, fp32 out -- the device's bits.
+        gs  = g * s
+        d   = fma(g, s, -m)                     (not gs - m)
+        m   = fma(omb1, d, m)
+        v   = fma(beta2, v, gs * (omb2 * gs))
+        p1  = fma(-(lr * wd), p, p)
+        den = sqrt(v) / bc2_sqrt + eps
+        p   = fma(-(lr / bc1), m / den, p1)"""
+    f = lambda x: Fraction(float(torch.tensor(x, dtype=torch.float32)))
+    r = _round32
+    s, lr_, wd_, eps = f(grad_scale), f(lr), f(wd), f(EPS)
+    omb1, omb2, b2 = f(1.0 - BETA1), f(1.0 - BETA2), f(BETA2)
+    bc1, bc2s = f(1.0 - BETA1 ** step), f((1.0 - BETA2 ** step) ** 0.5)
+    lrwd, lrbc = r(lr_ * wd_), r(lr_ / bc1)
+    out = [], [], []
+    for pi, gi, mi, vi in zip(*(t.double().tolist() for t in (p, g, m, v))):
+        pi, gi, mi, vi = Fraction(pi), Fraction(gi), Fraction(mi), Fraction(vi)
+        gs = r(gi * s)
+        d = r(gi * s - mi)
+        mi = r(omb1 * d + mi)
+        vi = r(b2 * vi + r(gs * r(omb2 * gs)))
+        p1 = r(-lrwd * pi + pi)
+        root = Fraction(float(torch.tensor(math.sqrt(float(vi)), dtype=torch.float32)))  # (float64 sqrt of a float32, rounded: exact)
+        den = r(r(root / bc2s) + eps)
+        pi = r(-lrbc * r(mi / den) + p1)
+        for o, x in zip(out, (pi, mi, vi)):
+            o.append(float(x))
+    return tuple(torch.tensor(o, dtype=torch.float64).float() for o in out)  # (every value is a float32: the conversion is exact)
 
 
 def adam_errors(got, ref, p_old, m_old, g, lr, grad_scale=1.0):

@@ -283,3 +283,168 @@ def test_adamw_rewrites_the_plane_images_of_the_weights_inside_a_flat_buffer():
         want = torch.empty_like(img)
         hip.split_planes_blocked(pa[o:o + r * c].view(r, c), want)
         assert torch.equal(img, want), (o, r, c)
+
+
+# ---- one arithmetic in every form (csrc/optim.hip: adamw1 pins its roundings) ---------------------------------------------------
+import stream_cases as SC  # noqa: E402
+
+B1, B2, EPS = SC.BETA1, SC.BETA2, SC.EPS
+LR, WD, STEP0, DECAY = 1e-3, 1e-2, 3, 0.99
+GRAD_SCALES = [1.0, 1.0 / 1024, 0.3]  # 0.3 is no power of two: g * grad_scale rounds, and gs - m differs from fma(g, s, -m)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _dev(x, shift=0):
+    """x on the device, its base `shift` floats past a 16-byte boundary."""
+    return torch.cat([torch.zeros(shift), x]).to(DEV)[shift:]
+
+
+class _Const:
+    """A device schedule of constant lr factor 1 whose row for update STEP0 + k holds the host's bias corrections of that step."""
+
+    def __init__(self):
+        import numpy as np
+        from mtvaf_amd import hip
+        from mtvaf_amd.optim import schedule_table
+        rows = schedule_table(lambda t: 1.0, STEP0 + 4, (B1, B2), ema_decay=DECAY).rows
+        self.table = torch.from_numpy(rows.view(np.uint8).copy()).to(DEV)
+        self.counter = torch.full((1,), STEP0 - 1, dtype=torch.int64, device=DEV)
+        self.current = torch.zeros(4, dtype=torch.int64, device=DEV)
+        self.advance = lambda: hip.adamw_sched_advance(self.table, self.counter, self.current)
+
+    def omd(self):
+        return float(self.current.view(torch.float32)[4])  # {double lr_factor, float bc1, bc2_sqrt, ema_omd, ...}
+
+
+def _steps(form, feed, ema, tensors, grad_scale, uniform_seg=None):
+    """Two updates of `tensors` = [(p, m, v, e, (g1, g2))] by one form (flat / multi / seg) fed one way (host / dev / sched);
+    -> [(p, m, v, e)] clones after each step."""
+    from mtvaf_amd import hip
+    sched, out = _Const(), []
+    clip = torch.tensor([1.0, 1.0, 1.0, 0.0], device=DEV) if feed == "dev" else None
+    for k in range(2):
+        sched.advance()
+        kw = dict(grad_scale=grad_scale, clip=clip)
+        if feed != "sched" and ema:
+            kw["ema_omd"] = sched.omd()
+        if form == "multi":
+            ps, ms, vs, es = ([t[i] for t in tensors] for i in range(4))
+            gs = [t[4][k] for t in tensors]
+            if feed == "sched":
+                hip.adamw_multi_sched(ps, gs, ms, vs, LR, B1, B2, EPS, WD, sched.current, ema=es if ema else None, **kw)
+            else:
+                hip.adamw_multi(ps, gs, ms, vs, LR, B1, B2, EPS, WD, STEP0 + k, ema=es if ema else None, **kw)
+        else:
+            for p, m, v, e, gs in tensors:
+                kw["ema"] = e if ema else None
+                segs = [(end, LR, WD) for end in (uniform_seg or ())]
+                if form == "flat" and feed == "sched":
+                    hip.adamw_sched(p, gs[k], m, v, LR, B1, B2, EPS, WD, sched.current, **kw)
+                elif form == "flat":
+                    hip.adamw(p, gs[k], m, v, LR, B1, B2, EPS, WD, STEP0 + k, **kw)
+                elif feed == "sched":
+                    hip.adamw_seg_sched(p, gs[k], m, v, segs, B1, B2, EPS, sched.current, **kw)
+                else:
+                    hip.adamw_seg(p, gs[k], m, v, segs, B1, B2, EPS, STEP0 + k, **kw)
+        out.append([tuple(x.clone() for x in t[:4]) for t in tensors])
+    return out
+
+
+def _tensors(sizes_shifts, seed):
+    """[(p, m, v, e, (g1, g2))] on the device; shift: the base of p in floats past a 16-byte boundary (the scalar body)."""
+    out = []
+    for i, (n, shift) in enumerate(sizes_shifts):
+        p, m, v, gs = SC.adam_inputs(n, False, seed + i)
+        e = torch.randn(n, generator=SC.gen(seed + 1000 + i))
+        out.append((_dev(p, shift), _dev(m), _dev(v), _dev(e), tuple(_dev(g) for g in gs)))
+    return out
+
+
+# (id, [(n, shift of p)], forms, ends of the uniform segment table)
+FORM_CASES = [
+    ("n1023-vector-body-and-3-element-tail", [(1023, 0)], ("flat", "multi", "seg"), (512, 1023)),
+    ("n5-p-shifted-scalar-body", [(5, 1)], ("flat", "multi"), None),  # (the segmented entry points refuse an unaligned base)
+    ("49-tensors-one-unaligned", [((1, 2, 5, 64, 1000)[i % 5], 1 if i == 7 else 0) for i in range(49)], ("flat", "multi"), None),
+]
+
+
+@pytest.mark.parametrize("grad_scale", GRAD_SCALES, ids=["gs1", "gs2^-10", "gs0.3"])
+@pytest.mark.parametrize("case", FORM_CASES, ids=[c[0] for c in FORM_CASES])
+def test_every_form_and_feed_gives_the_same_bits_at_any_grad_scale(case, grad_scale):
+    """flat, multi and seg (uniform table) x host scalars, clip state with coef 1, device schedule x average on / off: p, m, v
+    identical bit for bit, and e among the runs that keep it.  (With grad_scale != 1 this separates fma(g, s, -m) from g * s - m.)"""
+    _, sizes_shifts, forms, seg_ends = case
+    want, want_e = None, None
+    for form in forms:
+        for feed in ("host", "dev", "sched"):
+            for ema in (False, True):
+                if form == "flat" and len(sizes_shifts) > 1 and (feed != "host" or ema):
+                    continue  # (49 flat launches per variant: the flat forms agree among themselves in the cases above)
+                got = _steps(form, feed, ema, _tensors(sizes_shifts, seed=5), grad_scale, seg_ends)
+                want = want or got
+                if ema:
+                    want_e = want_e or got
+                for k in range(2):
+                    for i, (a, b) in enumerate(zip(got[k], want[k])):
+                        for name, x, y in zip("pmv", a, b):
+                            assert torch.equal(_bits(x), _bits(y)), (form, feed, ema, k, i, name)
+                        if ema:
+                            assert torch.equal(_bits(a[3]), _bits(want_e[k][i][3])), (form, feed, ema, k, i, "e")
+    first = _tensors(sizes_shifts, seed=5)
+    assert not torch.equal(want[1][0][0], first[0][0]) and want_e is not None
+
+
+@pytest.fixture(scope="module")
+def pinned_reference():
+    """grad_scale -> the inputs and SC.adamw_pinned's p, m, v after each of two steps (computed once, never written)."""
+    ref = {}
+    for gscale in (1.0, 0.3):
+        p, m, v, gs = SC.pinned_inputs(seed=64)
+        steps, state = [], (p, m, v)
+        for k, g in enumerate(gs):
+            state = SC.adamw_pinned(*state[:1], g, *state[1:], LR, WD, STEP0 + k, gscale)
+            steps.append(state)
+        ref[gscale] = ((p, m, v, gs), steps)
+    return ref
+
+
+@pytest.mark.parametrize("grad_scale", [1.0, 0.3])
+@pytest.mark.parametrize("form,shift", [("flat", 0), ("flat", 1), ("multi", 0), ("seg", 0)],
+                         ids=["flat-aligned", "flat-shifted", "multi", "seg"])
+def test_device_update_equals_the_pinned_sequence_bit_for_bit(form, shift, grad_scale, pinned_reference):
+    """64 elements, two consecutive steps: the kernels' p, m, v ARE SC.adamw_pinned's (exact arithmetic, one rounding per line of
+    adamw1).  A mismatch is a finding about that listing, not a tolerance to add."""
+    (p, m, v, gs), steps = pinned_reference[grad_scale]
+    e = torch.zeros_like(p)
+    if form == "multi":  # three tensors, the second off the boundary: both bodies
+        cuts = [(0, 20, 0), (20, 41, 1), (41, 64, 0)]
+        tensors = [(_dev(p[a:b], s), _dev(m[a:b]), _dev(v[a:b]), _dev(e[a:b]), tuple(_dev(g[a:b]) for g in gs)) for a, b, s in cuts]
+    else:
+        tensors = [(_dev(p, shift), _dev(m), _dev(v), _dev(e), tuple(_dev(g) for g in gs))]
+    got = _steps(form, "host", False, tensors, grad_scale, (32, 64))
+    for k in range(2):
+        for name, i in zip("pmv", range(3)):
+            dev = torch.cat([t[i] for t in got[k]]).cpu()
+            bad = (_bits(dev) != _bits(steps[k][i])).nonzero().flatten().tolist()
+            assert not bad, (form, shift, grad_scale, k, name, bad[:4], dev[bad[:4]].tolist(), steps[k][i][bad[:4]].tolist())
+
+
+def test_multi_update_refuses_a_bad_49th_tensor_before_the_first_launch():
+    import ctypes
+    from mtvaf_amd import hip
+    tensors = _tensors([(5, 0)] * 49, seed=9)
+    before = [tuple(x.clone() for x in t[:3]) for t in tensors]
+    arr = lambda col: (ctypes.c_void_p * 49)(*[t[col].data_ptr() for t in tensors])
+    ps = arr(0)
+    ps[48] = None
+    gs = (ctypes.c_void_p * 49)(*[t[4][0].data_ptr() for t in tensors])
+    rc = hip.lib().mtvaf_adamw_multi(49, ps, gs, arr(1), arr(2), (ctypes.c_long * 49)(*[5] * 49), LR, B1, B2, EPS, WD,
+                                     1.0 - B1 ** STEP0, (1.0 - B2 ** STEP0) ** 0.5, 1.0, hip._st())
+    torch.cuda.synchronize()
+    assert rc == -3, rc  # MTVAF_ERR_ARG
+    for t, b in zip(tensors, before):
+        for x, y in zip(t[:3], b):
+            assert torch.equal(_bits(x), _bits(y))

@@ -68,6 +68,33 @@ def test_adamw_fp32_restatement_error_is_the_recorded_one():
         assert rec / 1.25 <= worst[name] <= rec, (name, worst[name], rec)
 
 
+def test_adamw_pinned_restatement_stays_inside_the_recorded_fp32_error():
+    """The sequence the kernels pin (SC.adamw_pinned: exact arithmetic, one rounding per line) has fewer roundings than adamw_f32, so
+    it stays inside adamw_f32's recorded error against float64; and the fmas make a difference -- it is not adamw_f32's bits."""
+    differs = False
+    for gscale in (1.0, 0.3):
+        p, m, v, gs = SC.pinned_inputs(seed=64)
+        for k, g in enumerate(gs):
+            ref = SC.adamw_ref(p, g, m, v, 1e-3, 1e-2, 3 + k, gscale)
+            got = SC.adamw_pinned(p, g, m, v, 1e-3, 1e-2, 3 + k, gscale)
+            errs = SC.adam_errors(got, ref, p, m, g, 1e-3, gscale)
+            print("adamw pinned restatement, grad_scale", gscale, "step", 3 + k, {n: round(e, 4) for n, e in errs.items()})
+            for name, e in errs.items():
+                assert e <= SC.ADAM_F32_ERR[name], (gscale, k, name, e)
+            differs = differs or any(not torch.equal(a, b) for a, b in zip(got, SC.adamw_f32(p, g, m, v, 1e-3, 1e-2, 3 + k, gscale)))
+            p, m, v = got
+    assert differs
+
+
+def test_round32_is_round_to_nearest_even_float32():
+    from fractions import Fraction
+    tie = Fraction(1) + Fraction(1, 2 ** 24)  # halfway between 1 and 1 + 2^-23: to even, 1
+    assert SC._round32(tie) == 1 and SC._round32(tie + Fraction(1, 2 ** 60)) == 1 + Fraction(1, 2 ** 23)
+    assert SC._round32(Fraction(3, 2 ** 150)) == Fraction(1, 2 ** 148)  # 1.5 denormal quanta: to even, 2 of them
+    for x in (0.1, -2.5e-3, 3.4e38, 1e-40, 0.3):
+        assert float(SC._round32(Fraction(x))) == float(torch.tensor(x, dtype=torch.float32)), x
+
+
 def test_adam_inputs_plant_the_edge_elements():
     p, m, v, (g1, g2) = SC.adam_inputs(4097, False, seed=4097)
     assert g1[0] == 0 and g1[-1] == 0 and m[1] == 0 and v[1] == 0 and abs(p[3]) == 1e4 and abs(p[-4]) == 1e4
