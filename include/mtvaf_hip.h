@@ -1099,6 +1099,36 @@ int mtvaf_sam_restore_planes(float* p, const float* backup, long n, int nseg, co
                              const int* seg_cols, void* const* seg_img, mtvaf_stream_t stream);
 int mtvaf_sam_restore_multi(int count, float* const* p, const float* const* backup, const long* n, mtvaf_stream_t stream);
 
+/* ---- Word-level tagging head: the word axis of a batch, piece-to-word pooling and its backward (mtvaf_amd/words.py,
+ * engine.WordPoolFunction; new functionality, the reference tags word pieces).  No atomics, no host synchronisation, every
+ * element of every output written: the same inputs give the same bits.
+ * mtvaf_word_index: attention_mask [B,S] u8, a prefix mask (len = its leading non-zero entries); token_to_word [B,S] int32, -1
+ * outside the map (mtvaf_amd.spans.batch_token_to_word).  Token s < len OPENS a column iff s == 0, map[s] < 0 or
+ * map[s] != map[s-1]; map entries at s >= len are never read.  For the caller's width W >= 1 (S always suffices):
+ *   col_start [B,W] int32  first token of the column (0 for a dead column)     col_len [B,W] int32  its tokens, 0 = no column
+ *   col_of_token [B,S] int32  the token's column; -1 for s >= len and for tokens of columns >= W
+ *   word_mask [B,W] u8  1 on live columns (a prefix mask)     word_id [B,W] int32  the column's map value, -1 if unmapped / dead
+ *   n_cols [B] int32  the true column count: it may exceed W, the columns beyond W are dropped
+ * B >= 1, 1 <= S <= 512, W >= 1 (MTVAF_ERR_SHAPE); int32 pointers 4-byte aligned (MTVAF_ERR_ALIGN).
+ * mtvaf_word_pool_fwd: x [B,S,H] fp32 -> y [B,W,H] fp32.  FIRST / LAST: the column's first / last piece, copied.  MEAN: the
+ * pieces added one after the other in ascending token order in fp32, then one correctly rounded division by (float)col_len (no
+ * reciprocal, no contraction).  Dead columns (col_len 0, or a start / length outside the sentence) are exact zeros; x is read
+ * only inside live columns.
+ * mtvaf_word_pool_bwd: dy [B,W,H] -> dx [B,S,H], a gather: the selected piece gets its column's dy (FIRST / LAST), every piece
+ * dy / (float)col_len (MEAN, the same division); tokens with col_of_token < 0 and unselected pieces get exact zeros; dy is
+ * read only at live columns.
+ * Both: 16-byte accesses when H % 4 == 0 and x, y (dy, dx) are 16-byte aligned, scalar accesses otherwise, the same values.
+ * B, S, W, H >= 1 (MTVAF_ERR_SHAPE); a NULL pointer or an unknown mode: MTVAF_ERR_ARG; 4-byte alignment: MTVAF_ERR_ALIGN. */
+#define MTVAF_WORD_POOL_FIRST 0
+#define MTVAF_WORD_POOL_LAST 1
+#define MTVAF_WORD_POOL_MEAN 2
+int mtvaf_word_index(const uint8_t* attention_mask, const int* token_to_word, int* col_start, int* col_len, int* col_of_token,
+                     uint8_t* word_mask, int* word_id, int* n_cols, int B, int S, int W, mtvaf_stream_t stream);
+int mtvaf_word_pool_fwd(const float* x, const int* col_start, const int* col_len, float* y, int B, int S, int W, int H, int mode,
+                        mtvaf_stream_t stream);
+int mtvaf_word_pool_bwd(const float* dy, const int* col_start, const int* col_len, const int* col_of_token, float* dx, int B,
+                        int S, int W, int H, int mode, mtvaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

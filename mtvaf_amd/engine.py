@@ -1583,6 +1583,23 @@ class MeanLFunction(torch.autograd.Function):
         return denc
 
 
+class WordPoolFunction(torch.autograd.Function):
+    """Piece vectors x [B,S,H] -> one vector per column of the word axis [B,W,H] (csrc/wordpool.hip; `index`: a
+    `mtvaf_amd.words.WordIndex`; mode first | last | mean).  The backward is a gather of dy by col_of_token: the node saves the
+    index only, not x."""
+
+    @staticmethod
+    def forward(ctx, x, index, mode):
+        y = hip.word_pool_fwd(x.contiguous(), index.col_start, index.col_len, mode)
+        ctx.stash = (index, mode)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        index, mode = ctx.stash
+        return hip.word_pool_bwd(dy.contiguous(), index.col_start, index.col_len, index.col_of_token, mode), None, None
+
+
 class KLFunction(torch.autograd.Function):
     """KLDivLoss(reduction='batchmean')(log_softmax(logits), target) -> 0-dim tensor."""
 

@@ -160,6 +160,7 @@ class GraphedTrainStep:
         self._tags_host = None
         if isinstance(out.logits, DeferredTags):
             self._tags_host = out.logits._packed
+            self._S = out.logits._S  # (the tag axis: the word axis of a model with args.word_pooling may be narrower than S)
             out.logits._packed, out.logits._release = None, None  # never filled from the capture-time event
         self.grads = [(p, p.grad) for p in params if p.grad is not None]
         if crf is not None:

@@ -186,6 +186,9 @@ _SIGS = {
     "mtvaf_sam_restore": (c_int, [P, P, L, P, P]),
     "mtvaf_sam_restore_planes": (c_int, [P, P, L, I, P, P, P, P, P]),
     "mtvaf_sam_restore_multi": (c_int, [I, P, P, P, P]),
+    "mtvaf_word_index": (c_int, [P, P, P, P, P, P, P, P, I, I, I, P]),
+    "mtvaf_word_pool_fwd": (c_int, [P, P, P, P, I, I, I, I, I, P]),
+    "mtvaf_word_pool_bwd": (c_int, [P, P, P, P, P, I, I, I, I, I, P]),
 }
 
 class LayerStruct(ctypes.Structure):
@@ -1892,3 +1895,101 @@ def sam_restore_multi(ps, backups):
     arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
     _ck(lib().mtvaf_sam_restore_multi(k, arr(ps), arr(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]), _st()),
         "mtvaf_sam_restore_multi")
+
+
+# ---- word-level tagging head: the word axis, piece-to-word pooling and its backward (csrc/wordpool.hip) -------------
+WORD_POOL_MODES = {"first": 0, "last": 1, "mean": 2}  # MTVAF_WORD_POOL_*
+WORD_MAX_S = 512
+
+
+def _word_out(t, shape, dtype, device, name):
+    """An output the caller may bring (tests pre-fill it): checked, or allocated."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on the device, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _word_i32(t, shape, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous int32 tensor of shape {tuple(shape)} on the device, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def word_index(attention_mask, token_to_word, max_words=None, out=None):
+    """The word axis of a batch (include/mtvaf_hip.h, mtvaf_word_index): attention_mask [B,S], a prefix mask of any dtype
+    (non-zero = live); token_to_word [B,S] int32, -1 outside the map.  -> dict of col_start, col_len [B,W] int32, col_of_token
+    [B,S] int32, word_mask [B,W] uint8, word_id [B,W] int32, n_cols [B] int32, with W = max_words or S.  ``out``: a dict holding
+    any of those tensors to write into.  No host sync; the launch goes to the current stream."""
+    if attention_mask.dim() != 2:
+        raise ValueError(f"word_index: attention_mask {tuple(attention_mask.shape)}: expected [B, S]")
+    B, S = attention_mask.shape
+    W = S if max_words is None else int(max_words)
+    if W < 1:
+        raise ValueError(f"word_index: max_words {max_words}: expected a width >= 1")
+    m8 = adv_mask(attention_mask)
+    _word_i32(token_to_word, (B, S), "word_index: token_to_word")
+    out = dict(out or {})
+    dev = m8.device
+    res = {}
+    for name, shape, dtype in (("col_start", (B, W), torch.int32), ("col_len", (B, W), torch.int32),
+                               ("col_of_token", (B, S), torch.int32), ("word_mask", (B, W), torch.uint8),
+                               ("word_id", (B, W), torch.int32), ("n_cols", (B,), torch.int32)):
+        res[name] = _word_out(out.pop(name, None), shape, dtype, dev, f"word_index: {name}")
+    if out:
+        raise ValueError(f"word_index: unknown outputs {sorted(out)}")
+    _ck(lib().mtvaf_word_index(_p(m8), _p(token_to_word), _p(res["col_start"]), _p(res["col_len"]), _p(res["col_of_token"]),
+                               _p(res["word_mask"]), _p(res["word_id"]), _p(res["n_cols"]), B, S, W, _st()), "mtvaf_word_index")
+    return res
+
+
+def _word_mode(mode, who):
+    if mode not in WORD_POOL_MODES:
+        raise ValueError(f"{who}: mode {mode!r}: expected one of {sorted(WORD_POOL_MODES)}")
+    return WORD_POOL_MODES[mode]
+
+
+def _word_rows(t, name):
+    """[B,N,H] fp32 on the device whose rows lie one behind the other (a view that starts off a 16-byte boundary is fine: the
+    kernels then take their scalar path)."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a contiguous fp32 [B, N, H] tensor on the device, got {t.dtype} {tuple(t.shape)} on "
+                         f"{t.device}")
+    return t
+
+
+def word_pool_fwd(x, col_start, col_len, mode="first", out=None):
+    """y [B,W,H] = the pieces of every column of x [B,S,H] pooled (first | last | mean; mtvaf_word_pool_fwd); dead columns are
+    exact zeros.  col_start / col_len [B,W] int32 from word_index."""
+    _word_rows(x, "word_pool_fwd: x")
+    B, S, H = x.shape
+    if col_start.dim() != 2 or col_start.shape[0] != B:
+        raise ValueError(f"word_pool_fwd: col_start {tuple(col_start.shape)} does not match x {tuple(x.shape)}")
+    W = col_start.shape[1]
+    _word_i32(col_start, (B, W), "word_pool_fwd: col_start")
+    _word_i32(col_len, (B, W), "word_pool_fwd: col_len")
+    m = _word_mode(mode, "word_pool_fwd")
+    out = _word_out(out, (B, W, H), torch.float32, x.device, "word_pool_fwd: out")
+    _ck(lib().mtvaf_word_pool_fwd(_p(x), _p(col_start), _p(col_len), _p(out), B, S, W, H, m, _st()), "mtvaf_word_pool_fwd")
+    return out
+
+
+def word_pool_bwd(dy, col_start, col_len, col_of_token, mode="first", out=None):
+    """dx [B,S,H] from dy [B,W,H]: every token row gathers its column's dy (mtvaf_word_pool_bwd); masked tokens, tokens of
+    dropped columns and unselected pieces get exact zeros."""
+    _word_rows(dy, "word_pool_bwd: dy")
+    B, W, H = dy.shape
+    if col_of_token.dim() != 2 or col_of_token.shape[0] != B:
+        raise ValueError(f"word_pool_bwd: col_of_token {tuple(col_of_token.shape)} does not match dy {tuple(dy.shape)}")
+    S = col_of_token.shape[1]
+    _word_i32(col_start, (B, W), "word_pool_bwd: col_start")
+    _word_i32(col_len, (B, W), "word_pool_bwd: col_len")
+    _word_i32(col_of_token, (B, S), "word_pool_bwd: col_of_token")
+    m = _word_mode(mode, "word_pool_bwd")
+    out = _word_out(out, (B, S, H), torch.float32, dy.device, "word_pool_bwd: out")
+    _ck(lib().mtvaf_word_pool_bwd(_p(dy), _p(col_start), _p(col_len), _p(col_of_token), _p(out), B, S, W, H, m, _st()),
+        "mtvaf_word_pool_bwd")
+    return out

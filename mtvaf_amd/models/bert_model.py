@@ -187,6 +187,9 @@ class TVNetSAModel2(nn.Module):
         self.last_crf_risk = None  # detached device scalar after a forward with labels and args.crf_risk_weight > 0
         self.last_crf_entropy = None  # detached device scalar after a forward with a loss and args.crf_entropy_weight != 0
         self.last_crf_mrt = None  # detached device scalar after a forward with labels and args.crf_mrt_weight > 0
+        self.last_word_index = None  # mtvaf_amd.words.WordIndex of the last call that ran on the word axis (args.word_pooling)
+        if _arg(args, "word_pooling", None) not in (None, "first", "last", "mean"):
+            raise ValueError(f"args.word_pooling={args.word_pooling!r}: expected None, 'first', 'last' or 'mean'")
         hidden = self.bert.config.hidden_size
         self.num_labels = len(label_list) + 1
 
@@ -222,11 +225,18 @@ class TVNetSAModel2(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
-                images=None, aux_imgs=None, allowed_tags=None):
+                images=None, aux_imgs=None, allowed_tags=None, token_to_word=None):
         """reference: models/bert_model.py:480-532.  ``allowed_tags`` int64 [B,S] (`mtvaf_amd.constraints`: per-column tag sets of a
         partly annotated batch), given with ``labels=None``: the loss is ``-CRF.partial_llh`` -- the marginal likelihood of the
         paths the sets permit -- with args.crf_reduction, plus the same ``alpha * img_tag_loss`` term.  Without it the method runs
-        the code it always ran."""
+        the code it always ran.
+        args.word_pooling ("first" | "last" | "mean") with ``token_to_word`` int32 [B,S] (`mtvaf_amd.spans.batch_token_to_word`): the
+        head runs over WORDS (`mtvaf_amd.words`) -- last_hidden_state is pooled onto the word axis [B,W,H]
+        (W = args.max_words or S), and dropout, fc, decoding, the scorer, the marginals and every loss term run there with the
+        index' word_mask; ``labels`` / ``allowed_tags`` arrive piece-level and are taken at every word's first piece; ``logits``
+        are the tags of the word columns and ``self.last_word_index`` keeps the index.  Without args.word_pooling the map is not
+        read and the method runs the code it always ran."""
+        word_mode = self._word_mode(token_to_word)
         bsz = input_ids.size(0)
         img_tag_loss = 0
         if _arg(self.args, "use_prefix"):
@@ -250,7 +260,18 @@ class TVNetSAModel2(nn.Module):
                                 output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
                                 return_dict=True)
         self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
-        sequence_output = engine.dropout(bert_output["last_hidden_state"], self.dropout.p, self.training)
+        hidden = bert_output["last_hidden_state"]
+        if word_mode is not None:
+            # the word axis: one launch builds the index, one pools (fp32, the dtype fc reads in every compute mode); from here on
+            # the mask, the labels and the constraint sets are those of the word columns
+            from ..words import build_word_index, word_allowed, word_labels
+            index = build_word_index(attention_mask, token_to_word, _arg(self.args, "max_words", None))
+            self.last_word_index = index
+            hidden = engine.WordPoolFunction.apply(hidden, index, word_mode)
+            attention_mask = index.word_mask
+            labels = None if labels is None else word_labels(labels, index)
+            allowed_tags = None if allowed_tags is None else word_allowed(allowed_tags, index)
+        sequence_output = engine.dropout(hidden, self.dropout.p, self.training)
         emissions = engine.LinearFunction.apply(sequence_output, self.fc.weight, self.fc.bias, False)
         mask_u8 = attention_mask.to(torch.uint8)
         # Viterbi paths: device kernel + async packed copy; the list materialises on first use (no mid-step sync).
@@ -337,6 +358,32 @@ class TVNetSAModel2(nn.Module):
         return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
 
     # ------------------------------------------------------------------------------------------------
+    def _word_mode(self, token_to_word):
+        """args.word_pooling when this call runs on the word axis (`mtvaf_amd.words`), else None: the head then reads pieces, as it
+        always did.  The switch without a map at call time is an error, not a quiet piece-level run."""
+        mode = _arg(self.args, "word_pooling", None)
+        if mode is None:
+            return None
+        if token_to_word is None:
+            raise ValueError(f"args.word_pooling={mode!r}: this model's head runs over words and needs token_to_word [B,S] "
+                             "(mtvaf_amd.spans.batch_token_to_word, or spans.word_starts_from_labels) with every call")
+        return mode
+
+    def _word_axis(self, hidden, attention_mask, token_to_word, word_mask=None):
+        """The prologue's last step of the ``predict*`` methods: (hidden, attention_mask) as they are, or -- args.word_pooling and
+        a map -- the pooled hidden states [B,W,H] and the word axis' mask.  ``word_mask`` picks word columns on the piece axis:
+        on the word axis every column is one, so it is refused together with ``token_to_word``."""
+        mode = self._word_mode(token_to_word)
+        if mode is None:
+            return hidden, attention_mask
+        if word_mask is not None:
+            raise ValueError("word_mask marks the word columns of the piece axis: with token_to_word every column is a word; "
+                             "pass one of the two")
+        from ..words import build_word_index
+        index = build_word_index(attention_mask, token_to_word, _arg(self.args, "max_words", None))
+        self.last_word_index = index
+        return engine.WordPoolFunction.apply(hidden, index, mode), index.word_mask
+
     def _entity_tables(self, device):
         """The tagging scheme of `predict` on ``device`` (args.entity_scheme, default "seqeval") over the trainer's label map
         (label_list enumerated from 1, MTVAF_training.py:369), plus the lookup of the structural predicted labels: built once."""
@@ -351,13 +398,16 @@ class TVNetSAModel2(nn.Module):
             self._predict_tables = (key, t)
         return self._predict_tables[1]
 
-    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None):
+    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, token_to_word=None):
         """Inference end to end with no host sync, in eval mode whatever mode the module is in: visual prompt -> encoder -> fc ->
         Viterbi -> `CRF.entities`.  Chunked columns: the run of attention_mask from column 1, minus the columns whose PREDICTED
         label is structural (`mtvaf_amd.metrics.structural_labels`: PAD, X, [CLS], [SEP]), and only those of ``word_mask``
         [B,S] when it is given (e.g. first sub-tokens).  args.entity_scheme ("seqeval" | "reference"), args.max_entities (32).
         -> the dict of `CRF.entities` (tags, lengths, entities, log_confidence, confidence, count) plus ``types``, the type
         names the entities' type indices refer to; `mtvaf_amd.metrics.entities_to_lists` turns it into Python lists.
+        With args.word_pooling, ``token_to_word`` int32 [B,S] (as in `forward`) puts fc, the decoder and `CRF.entities` on the word
+        axis: tags [B,W] and entity columns are WORD columns (``self.last_word_index``); ``word_mask`` is refused beside it.  The
+        other ``predict_*`` methods take it the same way.
         This and the other ``predict_*`` methods read the weights the module holds: to evaluate the averaged weights of a run with
         ``args.ema_decay``, call them inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         # (an eval pass still reserves dropout offsets: the counter is put back, so a training run draws the same masks with or
@@ -378,7 +428,8 @@ class TVNetSAModel2(nn.Module):
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
                                         return_dict=True)
-                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 tags, _ = self.crf.decode_packed(emissions, mask_u8)
                 t = self._entity_tables(emissions.device)
@@ -397,7 +448,7 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_constrained(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                            allowed=None):
+                            allowed=None, token_to_word=None):
         """`predict` with the decoder searching only among the tag sequences that the input's layout permits, instead of decoding
         freely and dropping the columns whose predicted label is structural afterwards: the same prologue (visual prompt ->
         encoder -> fc, eval mode, no host sync, dropout counter put back), then `CRF.decode_constrained` over ``allowed`` int64
@@ -422,7 +473,8 @@ class TVNetSAModel2(nn.Module):
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
                                         return_dict=True)
-                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 if allowed is None:
                     from ..constraints import structural_sets
@@ -444,7 +496,7 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_posteriors(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                           threshold=0.5):
+                           threshold=0.5, token_to_word=None):
         """`predict_constrained` plus the posterior of every chunk EVENT (`CRF.chunk_posteriors`): the same prologue and the same
         layout sets (`structural_sets` of the trainer's label map, the attention mask and ``word_mask``), the posteriors
         conditional on them.  Kept columns: the word columns between [CLS] and [SEP] (columns 1 .. L-2, and only those of
@@ -474,7 +526,8 @@ class TVNetSAModel2(nn.Module):
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
                                         return_dict=True)
-                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 from ..constraints import structural_sets
                 allowed = structural_sets({label: i for i, label in enumerate(self.label_list, 1)}, attention_mask,
@@ -507,7 +560,8 @@ class TVNetSAModel2(nn.Module):
         return {"decoded": decoded, "log_post": log_post, "logz_a": logz_a, "keep": keep_w, "selected": selected,
                 "types": t["types"]}
 
-    def predict_nbest(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, nbest=None):
+    def predict_nbest(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, nbest=None,
+                      token_to_word=None):
         """`predict` with the ``nbest`` best tag sequences of every sentence instead of the best one (args.nbest, default 4; 1..8):
         the same prologue (visual prompt -> encoder -> fc, eval mode, no host sync, dropout counter put back), then
         `CRF.decode_nbest`, then every hypothesis through `CRF.entities` as one batch of B * K rows against the repeated emissions
@@ -533,7 +587,8 @@ class TVNetSAModel2(nn.Module):
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
                                         return_dict=True)
-                emissions = engine.LinearFunction.apply(bert_output["last_hidden_state"], self.fc.weight, self.fc.bias, False)
+                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 out = self.crf.decode_nbest(emissions, mask_u8, nbest=K)
                 B, _, S = out["tags"].shape

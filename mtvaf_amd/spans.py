@@ -24,6 +24,20 @@ def batch_token_to_word(maps: Sequence[Mapping[int, int]], seq_len: int) -> torc
     return torch.stack([token_to_word(m, seq_len) for m in maps])
 
 
+def word_starts_from_labels(labels: torch.Tensor, x_id: int, attention_mask: torch.Tensor) -> torch.Tensor:
+    """A synthetic ``token_to_word`` [B,S] int32 for callers who hold only ``X``-labelled features (`mtvaf_amd.words`): a token
+    continues the previous word iff its label is ``x_id``.  Every other unmasked token -- [CLS] and [SEP] too -- starts a word,
+    numbered from 0 along the sentence; masked tokens get -1.  The columns it gives are those of the tokenizer's map whenever the
+    continuation pieces are exactly the ``X``-labelled ones (the word numbers differ: [CLS] counts as word 0 here)."""
+    if tuple(labels.shape) != tuple(attention_mask.shape) or labels.dim() != 2:
+        raise ValueError(f"labels {tuple(labels.shape)} and attention_mask {tuple(attention_mask.shape)}: expected two [B, S] tensors")
+    live = torch.cumprod((attention_mask != 0).to(torch.int64), dim=1) != 0  # the leading ones
+    starts = live & (labels != x_id)
+    starts[:, 0] = live[:, 0]  # the first token opens a word whatever its label
+    word = torch.cumsum(starts.to(torch.int64), dim=1) - 1
+    return torch.where(live, word, torch.full_like(word, -1)).to(torch.int32)
+
+
 def word_keys(sentences: Sequence[Sequence[str]], vocab: Optional[Dict[str, int]] = None):
     """Ids of the lower-cased word strings: equal strings (across sentences too) get equal ids, numbered from 0 in order of first
     appearance.  -> (one list of ids per sentence, the string -> id dict; pass it back in to keep numbering a further batch)."""
