@@ -1129,6 +1129,34 @@ int mtvaf_word_pool_fwd(const float* x, const int* col_start, const int* col_len
 int mtvaf_word_pool_bwd(const float* dy, const int* col_start, const int* col_len, const int* col_of_token, float* dx, int B,
                         int S, int W, int H, int mode, mtvaf_stream_t stream);
 
+/* ---- Layer mix: a learned weighted sum of hidden states for the heads (mtvaf_amd/modules/layer_mix.py,
+ * engine.EncoderMixFunction; new functionality, the reference's heads read the last layer).  states: a HOST array of K device
+ * pointers, each [rows,H] fp32 (the residual-stream states of the chosen layers, in ascending layer order); scalars [K] and
+ * gamma [1] fp32 ON THE DEVICE.  No atomics, no host synchronisation, a launch geometry that depends on (rows, H, K) alone: the
+ * same inputs give the same bits.
+ * mtvaf_layer_mix_fwd: y[r,c] = gamma * sum_j s_j h_j[r,c] with s = softmax(scalars): e_j = expf(scalars_j - max), their sum
+ * taken in the order j = 0 .. K-1, s_j = e_j / sum (one correctly rounded division); the weighted sum is
+ * fmaf(s_j, h_j, acc) from acc = 0 in the order j = 0 .. K-1, multiplied by gamma once at the end.  Rows are independent.
+ * mtvaf_layer_mix_dots: with t_j = sum_{r,c} dy h_j, accumulated in double in two deterministic stages (one partial per block
+ * and state in `workspace`, then a fixed-order sum), writes
+ *   dgamma [1] = sum_j s_j t_j     dscalars [K]: gamma s_j (t_j - sum_i s_i t_i)     coef [K]: c_j = gamma * s_j (fp32),
+ * the coefficient of dy in the gradient of state j.  workspace: at least MTVAF_LAYER_MIX_WORKSPACE_BYTES, 8-byte aligned.
+ * mtvaf_layer_mix_inject: dh = fmaf(coef[j], dy, dh) (accumulate != 0) or dh = coef[j] * dy (accumulate == 0, dh is not read),
+ * [rows,H] each; coef is read on the device.
+ * Errors, checked before anything is launched: K outside 1 .. MTVAF_LAYER_MIX_MAX_K, j outside 0 .. K-1, a NULL pointer (an entry
+ * of `states` included) or H % 4 != 0: MTVAF_ERR_ARG; rows < 1 or H < 4: MTVAF_ERR_SHAPE; a short workspace:
+ * MTVAF_ERR_WORKSPACE; states, y, dy, dh not 16-byte aligned (the small vectors: 4-byte): MTVAF_ERR_ALIGN. */
+#define MTVAF_LAYER_MIX_MAX_K 32
+#define MTVAF_LAYER_MIX_DOT_BLOCKS 1024
+#define MTVAF_LAYER_MIX_WORKSPACE_BYTES 262144 /* MAX_K x DOT_BLOCKS doubles */
+int mtvaf_layer_mix_fwd(const float* const* states, int K, const float* scalars, const float* gamma, float* y, long rows, int H,
+                        mtvaf_stream_t stream);
+int mtvaf_layer_mix_dots(const float* const* states, int K, const float* dy, const float* scalars, const float* gamma, long rows,
+                         int H, void* workspace, long workspace_bytes, float* dscalars, float* dgamma, float* coef,
+                         mtvaf_stream_t stream);
+int mtvaf_layer_mix_inject(const float* coef, int j, int K, const float* dy, float* dh, long rows, int H, int accumulate,
+                           mtvaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -344,7 +344,8 @@ DIRECT_GRADS = os.environ.get("MTVAF_DIRECT_GRADS", "1") != "0"
 # zeros at the masked positions (only for callers that set BertModel.allow_unpad: TVNetSAModel2, whose CRF head is
 # masked; the span model's position softmax reads every position, so it stays padded).  Loss, decoded tags and every parameter gradient are those of the padded run (a masked
 # key contributes exp(-10000) = 0 there, a masked query feeds nothing); hidden states AT masked positions are zeros
-# instead of the reference's don't-care values, and the intermediate hidden states are handed out lazily / detached.
+# instead of the reference's don't-care values, and the intermediate hidden states are handed out lazily / detached (a head that
+# trains on them goes through EncoderMixFunction, whose gradient enters the backward at the layer boundaries, on packed rows too).
 UNPAD = os.environ.get("MTVAF_UNPAD", "1") != "0"
 
 
@@ -670,6 +671,8 @@ def _native_forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, params):
     ctx.stash = (offs, weights, pkv, addmask, cfg, seed, (B, S, H, Pn), grad_sink, params)
     ctx.native = (use_h, pkv_k if (use_h and Pn) else None)
     ctx.pack = pack
+    if getattr(ctx, "mix", None) is not None:  # (EncoderMixFunction: the fp32 residual-stream states, packed rows in a packed run)
+        ctx.mix_states = [x] + [a[o_h2:o_h2 + M * H * 4].view(torch.float32).view(M, H) for a in arenas]
     global LAST_PACK
     LAST_PACK = pack
     if pack is not None and L > 1:
@@ -799,22 +802,32 @@ def _native_backward(ctx, douts):
             kcnt.record_stream(side)
     keep = []  # temporaries the second stream still reads: alive until the join below
     dh = None
+    inject = getattr(ctx, "mix_inject", None)  # (EncoderMixFunction.backward: adds gamma s_j dy at the boundary of state k_j)
     for li in range(L - 1, -1, -1):
         w = weights[li]
         g_out = douts[li]
         if dh is None:
             if g_out is None:
-                if Pn:
-                    dpkv[li].zero_()  # layers above the last used hidden state get no gradient
-                continue
-            if pack is not None:
-                dh = pack.pack(g_out.contiguous().view(B * S, H))  # (a fresh buffer; zero rows pad the image)
+                if inject is not None:
+                    dh = inject(li + 1, None)
+                if dh is None:
+                    if Pn:
+                        dpkv[li].zero_()  # layers above the last used hidden state get no gradient
+                    continue
             else:
-                dh = g_out.contiguous().view(M, H)
-                if dh.data_ptr() == g_out.data_ptr():
-                    dh = dh.clone()  # we modify / free it
-        elif g_out is not None:
-            dh = dh + g_out.reshape(M, H)
+                if pack is not None:
+                    dh = pack.pack(g_out.contiguous().view(B * S, H))  # (a fresh buffer; zero rows pad the image)
+                else:
+                    dh = g_out.contiguous().view(M, H)
+                    if dh.data_ptr() == g_out.data_ptr():
+                        dh = dh.clone()  # we modify / free it
+                if inject is not None:
+                    dh = inject(li + 1, dh)
+        else:
+            if g_out is not None:
+                dh = dh + g_out.reshape(M, H)
+            if inject is not None:
+                dh = inject(li + 1, dh)
         base_i = li * N_LAYER_PARAMS
         if gviews is not None:
             G = gviews[base_i:base_i + N_LAYER_PARAMS]
@@ -887,6 +900,8 @@ def _native_backward(ctx, douts):
     if side is not None:
         main.wait_stream(side)  # join: gradients (and every buffer the second stream read) are settled from here on
     del keep
+    if inject is not None:
+        dh = inject(0, dh)  # the embedding output's term
     if dh is not None and pack is not None:
         dh = pack.unpack(dh)
     dh0_out = dh.view(B, S, H) if dh is not None else None
@@ -984,7 +999,10 @@ class EncoderFunction(torch.autograd.Function):
             x = h2
         # activations go through save_for_backward so that autograd releases them as soon as the backward has run
         # (a python attribute would keep ~3 GB per layer at B=128, S=512 alive until the loss tensor dies)
-        ctx.save_for_backward(*saved, *saved_t)
+        mix_on = getattr(ctx, "mix", None) is not None
+        ctx.save_for_backward(*saved, *saved_t, *((x,) if mix_on else ()))  # (EncoderMixFunction: the last state too)
+        if mix_on:
+            ctx.mix_states = [saved[13 * li] for li in range(L)] + [x]
         ctx.stash = (offs, weights, pkv, addmask, cfg, seed, (B, S, H, Pn), grad_sink, params)
         ctx.wh = wh
         ctx.pkv16 = pkv16
@@ -1047,6 +1065,7 @@ class EncoderFunction(torch.autograd.Function):
                     t_.record_stream(side)
 
         dh = None  # gradient wrt the current layer's OUTPUT, [M,H], owned by us
+        inject = getattr(ctx, "mix_inject", None)  # (EncoderMixFunction.backward: adds gamma s_j dy at the boundary of state k_j)
         for li in range(L - 1, -1, -1):
             x, qkv, cx, lse, a, h1, mean1, rstd1, pre, act, f, mean2, rstd2 = flat[13 * li:13 * li + 13]
             off = offs[li]
@@ -1055,14 +1074,23 @@ class EncoderFunction(torch.autograd.Function):
             g_out = douts[li]
             if dh is None:
                 if g_out is None:
-                    if Pn:
-                        dpkv[li].zero_()  # layers above the last used hidden state get no gradient
-                    continue
-                dh = g_out.contiguous().view(M, H)
-                if dh.data_ptr() == g_out.data_ptr():
-                    dh = dh.clone()  # we modify / free it
-            elif g_out is not None:
-                dh = dh + g_out.reshape(M, H)
+                    if inject is not None:
+                        dh = inject(li + 1, None)
+                    if dh is None:
+                        if Pn:
+                            dpkv[li].zero_()  # layers above the last used hidden state get no gradient
+                        continue
+                else:
+                    dh = g_out.contiguous().view(M, H)
+                    if dh.data_ptr() == g_out.data_ptr():
+                        dh = dh.clone()  # we modify / free it
+                    if inject is not None:
+                        dh = inject(li + 1, dh)
+            else:
+                if g_out is not None:
+                    dh = dh + g_out.reshape(M, H)
+                if inject is not None:
+                    dh = inject(li + 1, dh)
             base = li * N_LAYER_PARAMS
             if gviews is not None:
                 G = gviews[base:base + N_LAYER_PARAMS]
@@ -1182,10 +1210,108 @@ class EncoderFunction(torch.autograd.Function):
                     grad_sink.layer_done(li)
         if side is not None:
             main.wait_stream(side)  # join: gradients (and every buffer the side stream read) are settled from here on
+        if inject is not None:
+            dh = inject(0, dh)  # the embedding output's term
         dh0_out = dh.view(B, S, H) if dh is not None else None
         if not need_param_grads:
             pgrads = [None] * len(params)
         return (dh0_out, dpkv, None, None, None, None, *pgrads)
+
+
+def resolve_mix_layers(layers, num_states: int):
+    """The hidden states a layer mix reads -> a sorted tuple of indices into (embedding output, layer 1, ..., layer L),
+    ``num_states`` = L + 1 of them.  ``"all"`` (or None): every state; otherwise an iterable of integers, negative ones counting from
+    the end.  ValueError: an index outside the states, one state named twice, none, or more than 32 (hip.LAYER_MIX_MAX_K)."""
+    n = int(num_states)
+    if n < 1:
+        raise ValueError(f"layer mix: {num_states} hidden states")
+    if layers is None or (isinstance(layers, str) and layers == "all"):
+        idx = list(range(n))
+    elif isinstance(layers, (str, bytes)) or not hasattr(layers, "__iter__"):
+        raise ValueError(f"layer mix: layers={layers!r}: expected 'all' or a list of state indices")
+    else:
+        idx = []
+        for k in layers:
+            if isinstance(k, bool) or int(k) != k:
+                raise ValueError(f"layer mix: layer index {k!r} is not an integer")
+            k = int(k)
+            if not -n <= k < n:
+                raise ValueError(f"layer mix: layer index {k} outside the {n} hidden states (0 = embedding output ... {n - 1})")
+            idx.append(k % n)
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"layer mix: layers={list(layers)!r} names a hidden state twice")
+        idx.sort()
+    if not 1 <= len(idx) <= hip.LAYER_MIX_MAX_K:
+        raise ValueError(f"layer mix: {len(idx)} layers chosen: expected 1 .. {hip.LAYER_MIX_MAX_K}")
+    return tuple(idx)
+
+
+class EncoderMixFunction(torch.autograd.Function):
+    """EncoderFunction with a layer mix inside the node (csrc/layermix.hip).
+
+    inputs : h0, pkv, addmask, cfg, weights, grad_sink as EncoderFunction's, then scalars [K], gamma [1] (fp32 parameters on the
+             device), layers (a sorted tuple of K state indices, 0 = h0, l = layer l's output), then the 16*L layer parameters.
+    outputs: EncoderFunction's L hidden states, then mixed [B,S,H] = gamma * sum_j softmax(scalars)_j * state k_j.
+
+    Both executions (native, Python-orchestrated) run EncoderFunction's own code; it hands the fp32 residual-stream states out
+    (``ctx.mix_states``) and calls ``ctx.mix_inject`` at every layer boundary of its backward.  A padding-free run mixes the packed
+    rows and scatters the result once (zeros at masked positions); its backward packs the mixed state's gradient once.  The K
+    hidden-state gradients are never materialised: gamma s_j dy is added into the running dh where layer k_j's backward starts."""
+
+    @staticmethod
+    def forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, scalars, gamma, layers, *params):
+        B, S, H = h0.shape
+        if H % 4 or max(layers) > len(weights) or min(layers) < 0 or scalars.numel() != len(layers):
+            raise ValueError(f"layer mix: layers {layers} / {scalars.numel()} scalars / H {H} do not fit {len(weights)} encoder layers")
+        ctx.mix = (scalars, gamma, layers)
+        outs = EncoderFunction.forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, *params)
+        states = ctx.mix_states
+        del ctx.mix_states
+        y = hip.layer_mix_fwd([states[k] for k in layers], scalars, gamma)
+        pack = getattr(ctx, "pack", None) if ctx.native is not None else None
+        mixed = (pack.unpack(y) if pack is not None else y).view(B, S, H)
+        return (*outs, mixed)
+
+    @staticmethod
+    def _saved_states(ctx):
+        """The L + 1 states as [M,H] views of what the forward saved."""
+        saved = ctx.saved_tensors
+        (B, S, H, Pn), L = ctx.stash[6], len(ctx.stash[1])
+        if ctx.native is None:
+            return [saved[13 * li] for li in range(L)] + [saved[-1]]
+        use_h = ctx.native[0]
+        planes = bool(getattr(ctx, "planes", False))
+        arenas = saved[2:] if (use_h or planes) else saved[1:]
+        M = saved[0].shape[0]
+        NH = ctx.stash[4][0]
+        I = ctx.stash[1][0].w1.shape[0]
+        o_h2 = dict(_fwd_layout(M, H, I, B, NH, S, use_h, planes)[0])["h2"]
+        return [saved[0]] + [a[o_h2:o_h2 + M * H * 4].view(torch.float32).view(M, H) for a in arenas]
+
+    @staticmethod
+    def backward(ctx, *douts):
+        scalars, gamma, layers = ctx.mix
+        dmix = douts[-1]
+        dscalars = dgamma = None
+        ctx.mix_inject = None
+        if dmix is not None:
+            B, S, H, _ = ctx.stash[6]
+            pack = getattr(ctx, "pack", None) if ctx.native is not None else None
+            dy = dmix.contiguous().view(B * S, H)
+            if pack is not None:
+                dy = pack.pack(dy)  # (zero rows pad the image; the dots read the live rows only)
+            states = EncoderMixFunction._saved_states(ctx)
+            dscalars, dgamma, coef = hip.layer_mix_dots([states[k] for k in layers], dy, scalars, gamma,
+                                                        rows=pack.Mv if pack is not None else None)
+            slot = {k: j for j, k in enumerate(layers)}
+
+            def inject(state, dh):
+                j = slot.get(state)
+                return dh if j is None else hip.layer_mix_inject(coef, j, dy, dh)
+            ctx.mix_inject = inject
+        res = EncoderFunction.backward(ctx, *douts[:-1])
+        ctx.mix_inject = None
+        return (*res[:6], dscalars, dgamma, None, *res[6:])
 
 
 # -------------------------------------------------------------------------------------------------

@@ -15,7 +15,9 @@ What makes the path capturable:
   * bf16 weight images -- rebuilt by a cast inside the graph (one kernel per layer), so ANY optimizer may update the fp32
     masters between replays;
   * gradients live at fixed addresses (the encoder's flat per-layer buffers, the graph's private pool for the rest);
-    ``param.grad`` is re-attached after every replay, so ``optimizer.zero_grad(set_to_none=True)`` stays legal.
+    ``param.grad`` is re-attached after every replay, so ``optimizer.zero_grad(set_to_none=True)`` stays legal;
+  * a model with ``args.layer_mix`` -- the softmax of the mix, its parameter gradients and the coefficients of the
+    injection are computed and read on the device, their buffers allocated at capture: nothing there reaches the host.
 
 The optimizer step joins the graph when its per-step hyper-parameters live on the device: with
 ``optimizer=mtvaf_amd.optim.AdamW(..., device_schedule=optim.schedule_table(...))`` the capture also holds the clip launches (if

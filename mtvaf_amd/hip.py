@@ -189,6 +189,9 @@ _SIGS = {
     "mtvaf_word_index": (c_int, [P, P, P, P, P, P, P, P, I, I, I, P]),
     "mtvaf_word_pool_fwd": (c_int, [P, P, P, P, I, I, I, I, I, P]),
     "mtvaf_word_pool_bwd": (c_int, [P, P, P, P, P, I, I, I, I, I, P]),
+    "mtvaf_layer_mix_fwd": (c_int, [P, I, P, P, P, L, I, P]),
+    "mtvaf_layer_mix_dots": (c_int, [P, I, P, P, P, L, I, P, L, P, P, P, P]),
+    "mtvaf_layer_mix_inject": (c_int, [P, I, I, P, P, L, I, I, P]),
 }
 
 class LayerStruct(ctypes.Structure):
@@ -1993,3 +1996,69 @@ def word_pool_bwd(dy, col_start, col_len, col_of_token, mode="first", out=None):
     _ck(lib().mtvaf_word_pool_bwd(_p(dy), _p(col_start), _p(col_len), _p(col_of_token), _p(out), B, S, W, H, m, _st()),
         "mtvaf_word_pool_bwd")
     return out
+
+
+# ---- layer mix: a learned weighted sum of hidden states, its parameter gradients and the injection (csrc/layermix.hip) ---------
+LAYER_MIX_MAX_K = 32                  # MTVAF_LAYER_MIX_MAX_K
+LAYER_MIX_WORKSPACE_BYTES = 262144    # MTVAF_LAYER_MIX_WORKSPACE_BYTES
+
+
+def _mix_states(states, who):
+    """The K states as the host array of device pointers the entry points take -> (array, K, rows, H)."""
+    K = len(states)
+    if not 1 <= K <= LAYER_MIX_MAX_K:
+        raise ValueError(f"{who}: {K} states: expected 1 .. {LAYER_MIX_MAX_K}")
+    shape = tuple(states[0].shape)
+    for t in states:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.dim() >= 2):
+            raise ValueError(f"{who}: every state must be a contiguous fp32 [..., H] tensor of one shape on the device, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    H = shape[-1]
+    return (ctypes.c_void_p * K)(*[t.data_ptr() for t in states]), K, states[0].numel() // H, H
+
+
+def _mix_vec(t, n, name):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"{name}: expected {n} contiguous fp32 value(s) on the device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def layer_mix_fwd(states, scalars, gamma, out=None):
+    """y = gamma * sum_j softmax(scalars)_j * states[j] (mtvaf_layer_mix_fwd): states a list of K fp32 tensors of one shape
+    [..., H], H % 4 == 0; scalars [K] and gamma [1] on the device (no host read)."""
+    arr, K, rows, H = _mix_states(states, "layer_mix_fwd")
+    _mix_vec(scalars, K, "layer_mix_fwd: scalars")
+    _mix_vec(gamma, 1, "layer_mix_fwd: gamma")
+    out = _word_out(out, states[0].shape, torch.float32, states[0].device, "layer_mix_fwd: out")
+    _ck(lib().mtvaf_layer_mix_fwd(arr, K, _p(scalars), _p(gamma), _p(out), rows, H, _st()), "mtvaf_layer_mix_fwd")
+    return out
+
+
+def layer_mix_dots(states, dy, scalars, gamma, rows=None):
+    """-> (dscalars [K], dgamma [1], coef [K]) of the mix for the upstream gradient dy (mtvaf_layer_mix_dots); coef[j] = gamma * s_j
+    is what `layer_mix_inject` multiplies dy by.  rows: take only the leading rows of every tensor (a packed image's live rows)."""
+    arr, K, all_rows, H = _mix_states(states, "layer_mix_dots")
+    rows = all_rows if rows is None else int(rows)
+    if not (dy.is_cuda and dy.dtype == torch.float32 and dy.is_contiguous() and dy.numel() == states[0].numel()) or not 1 <= rows <= all_rows:
+        raise ValueError(f"layer_mix_dots: dy {dy.dtype} {tuple(dy.shape)} / rows {rows} do not match the states {tuple(states[0].shape)}")
+    _mix_vec(scalars, K, "layer_mix_dots: scalars")
+    _mix_vec(gamma, 1, "layer_mix_dots: gamma")
+    dev = dy.device
+    ws = torch.empty(LAYER_MIX_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+    dscalars, dgamma, coef = (torch.empty(n, dtype=torch.float32, device=dev) for n in (K, 1, K))
+    _ck(lib().mtvaf_layer_mix_dots(arr, K, _p(dy), _p(scalars), _p(gamma), rows, H, _p(ws), ws.numel(), _p(dscalars), _p(dgamma),
+                                   _p(coef), _st()), "mtvaf_layer_mix_dots")
+    return dscalars, dgamma, coef
+
+
+def layer_mix_inject(coef, j, dy, dh=None):
+    """dh = fmaf(coef[j], dy, dh) in place, or a new dh = coef[j] * dy where none exists yet (mtvaf_layer_mix_inject)."""
+    if not (dy.is_cuda and dy.dtype == torch.float32 and dy.is_contiguous() and dy.dim() >= 2):
+        raise ValueError(f"layer_mix_inject: dy {dy.dtype} {tuple(dy.shape)} on {dy.device}: expected contiguous fp32 [..., H] on the device")
+    K = coef.numel()
+    _mix_vec(coef, K, "layer_mix_inject: coef")
+    H = dy.shape[-1]
+    acc = dh is not None
+    dh = _word_out(dh, dy.shape, torch.float32, dy.device, "layer_mix_inject: dh")
+    _ck(lib().mtvaf_layer_mix_inject(_p(coef), int(j), K, _p(dy), _p(dh), dy.numel() // H, H, int(acc), _st()), "mtvaf_layer_mix_inject")
+    return dh

@@ -59,6 +59,22 @@ def _span_scorer(args):
     return SpanScorer() if want is True else SpanScorer(classes=want)
 
 
+def _layer_mix(args, bert):
+    """args.layer_mix (None | "all" | a list of hidden-state indices, 0 = the embedding output) -> a `LayerMix` over the
+    encoder's L + 1 hidden states, or None: no module, no parameter, no state-dict key, no launch.
+    args.layer_mix_init_last is added to the last chosen state's scalar."""
+    spec = _arg(args, "layer_mix", None)
+    if spec is None:
+        return None
+    from ..modules.layer_mix import LayerMix
+    return LayerMix(bert.config.num_hidden_layers + 1, spec, _arg(args, "layer_mix_init_last", 0.0) or 0.0)
+
+
+def _head_state(bert_output, mix):
+    """What the heads read: the last hidden state, or -- with a layer mix -- the mixed state."""
+    return bert_output["last_hidden_state"] if mix is None else bert_output.mixed_hidden_state
+
+
 def _mask_word_map(attention_mask, device):
     """The word map without a tokenizer's: every token with ``attention_mask`` 1 is its own word, the others are outside."""
     pos = torch.arange(attention_mask.shape[1], device=device, dtype=torch.int32).expand(attention_mask.shape[0], -1)
@@ -188,6 +204,7 @@ class TVNetSAModel2(nn.Module):
         self.last_crf_entropy = None  # detached device scalar after a forward with a loss and args.crf_entropy_weight != 0
         self.last_crf_mrt = None  # detached device scalar after a forward with labels and args.crf_mrt_weight > 0
         self.last_word_index = None  # mtvaf_amd.words.WordIndex of the last call that ran on the word axis (args.word_pooling)
+        self.layer_mix = _layer_mix(args, self.bert)  # args.layer_mix: the head reads a learned mix of the hidden states
         if _arg(args, "word_pooling", None) not in (None, "first", "last", "mean"):
             raise ValueError(f"args.word_pooling={args.word_pooling!r}: expected None, 'first', 'last' or 'mean'")
         hidden = self.bert.config.hidden_size
@@ -258,9 +275,9 @@ class TVNetSAModel2(nn.Module):
         bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
                                 token_type_ids=token_type_ids, past_key_values=prefix_guids,
                                 output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
-                                return_dict=True)
+                                return_dict=True, layer_mix=self.layer_mix)
         self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
-        hidden = bert_output["last_hidden_state"]
+        hidden = _head_state(bert_output, self.layer_mix)
         if word_mode is not None:
             # the word axis: one launch builds the index, one pools (fp32, the dtype fc reads in every compute mode); from here on
             # the mask, the labels and the constraint sets are those of the word columns
@@ -427,8 +444,9 @@ class TVNetSAModel2(nn.Module):
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True)
-                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                                        return_dict=True, layer_mix=self.layer_mix)
+                hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
+                                                         word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 tags, _ = self.crf.decode_packed(emissions, mask_u8)
@@ -472,8 +490,9 @@ class TVNetSAModel2(nn.Module):
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True)
-                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                                        return_dict=True, layer_mix=self.layer_mix)
+                hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
+                                                         word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 if allowed is None:
@@ -525,8 +544,9 @@ class TVNetSAModel2(nn.Module):
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True)
-                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                                        return_dict=True, layer_mix=self.layer_mix)
+                hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
+                                                         word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 from ..constraints import structural_sets
@@ -586,8 +606,9 @@ class TVNetSAModel2(nn.Module):
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True)
-                hidden, attention_mask = self._word_axis(bert_output["last_hidden_state"], attention_mask, token_to_word, word_mask)
+                                        return_dict=True, layer_mix=self.layer_mix)
+                hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
+                                                         word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
                 out = self.crf.decode_nbest(emissions, mask_u8, nbest=K)
@@ -719,6 +740,7 @@ class TVNetSAModel(nn.Module):
         bert_config = _arg(args, "bert_config", None)
         self.bert = enc_cls(bert_config) if bert_config is not None else enc_cls.from_pretrained(args.bert_name)
         self.bert.skip_pooler = True  # pooler_output only feeds the (unbuilt) GCN branch (:349)
+        self.layer_mix = _layer_mix(args, self.bert)  # args.layer_mix: the heads read a learned mix of the hidden states
         hidden = self.bert.config.hidden_size
         self.dense = nn.Linear(hidden, hidden)
         self.activation = nn.Tanh()
@@ -854,13 +876,13 @@ class TVNetSAModel(nn.Module):
             # and throws its output away; only hidden_states[7] of it feeds the unbuilt probe)
             from ..modules.augument import Cutoff
             cutoff = Cutoff(input_ids=input_ids, token_type_ids=token_type_ids, attention_masks=prompt_attention_mask,
-                            prefix_guids=prefix_guids, args=self.args, model=self.bert)
-            last_hidden = cutoff._training_step_with_cutoff(self.args.aug_type)[0]
+                            prefix_guids=prefix_guids, args=self.args, model=self.bert, layer_mix=self.layer_mix)
+            last_hidden = cutoff._training_step_with_cutoff(self.args.aug_type)[0 if self.layer_mix is None else 2]
         else:
-            last_hidden = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
-                                    token_type_ids=token_type_ids, past_key_values=prefix_guids,
-                                    output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
-                                    return_dict=True)["last_hidden_state"]
+            last_hidden = _head_state(self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
+                                                token_type_ids=token_type_ids, past_key_values=prefix_guids,
+                                                output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
+                                                return_dict=True, layer_mix=self.layer_mix), self.layer_mix)
         sequence_output = engine.dropout(last_hidden, self.dropout.p, self.training)
         ae_logits = engine.LinearFunction.apply(sequence_output, self.binary_affine.weight, self.binary_affine.bias, False)
         return ae_logits, sequence_output

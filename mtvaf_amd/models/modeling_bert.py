@@ -364,9 +364,11 @@ class BertEncoder(nn.Module):
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, encoder_hidden_states=None,
                 encoder_attention_mask=None, past_key_values=None, use_cache=None, output_attentions=False,
-                output_hidden_states=False, return_dict=True, unpad_ok=False):
+                output_hidden_states=False, return_dict=True, unpad_ok=False, layer_mix=None):
         """``attention_mask`` is the additive extended mask [B,1,1,T] (or [B,T]) as in the reference.  ``unpad_ok``: the
-        caller does not read hidden states at masked positions (padding-free execution may zero them, engine.UNPAD)."""
+        caller does not read hidden states at masked positions (padding-free execution may zero them, engine.UNPAD).
+        ``layer_mix``: a `modules.layer_mix.LayerMix` -- the output then carries ``mixed_hidden_state`` [B,S,H], the learned
+        weighted sum of the chosen hidden states, computed (and differentiated) inside the encoder's node; None: nothing new."""
         if encoder_hidden_states is not None or (head_mask is not None and any(h is not None for h in head_mask)):
             raise NotImplementedError("cross-attention / head_mask are not on the MTVAF path")
         if not hidden_states.is_cuda:
@@ -386,8 +388,18 @@ class BertEncoder(nn.Module):
         ecfg = (cfg.num_attention_heads, cfg.layer_norm_eps, cfg.hidden_dropout_prob if tr else 0.0,
                 cfg.attention_probs_dropout_prob if tr else 0.0, getattr(past_key_values, "ready_event", None), bool(unpad_ok))
         params = [p for l in self.layer for p in l.ordered_params()]
-        outs = engine.EncoderFunction.apply(hidden_states, pkv, addmask, ecfg, [st.weights for st in stores],
-                                            sink if torch.is_grad_enabled() else None, *params)
+        mixed = None
+        if layer_mix is None:
+            outs = engine.EncoderFunction.apply(hidden_states, pkv, addmask, ecfg, [st.weights for st in stores],
+                                                sink if torch.is_grad_enabled() else None, *params)
+        else:
+            if layer_mix.num_states != len(self.layer) + 1:
+                raise ValueError(f"layer_mix was built for {layer_mix.num_states} hidden states, this encoder has {len(self.layer) + 1}")
+            if not return_dict:
+                raise ValueError("layer_mix: the mixed state is an attribute of the output object (return_dict=True)")
+            *outs, mixed = engine.EncoderMixFunction.apply(hidden_states, pkv, addmask, ecfg, [st.weights for st in stores],
+                                                           sink if torch.is_grad_enabled() else None, layer_mix.scalars,
+                                                           layer_mix.gamma, layer_mix.layers, *params)
         all_hidden = (hidden_states,) + tuple(outs) if output_hidden_states else None
         if all_hidden is not None and len(outs) > 1 and outs[0].dim() == 2:
             all_hidden = _LazyHiddenStates(all_hidden, engine.LAST_PACK)  # padding-free run: intermediate states are packed
@@ -398,9 +410,12 @@ class BertEncoder(nn.Module):
             attn, self.last_prefix_mass = self._attention_maps(hidden_states, outs, stores, pkv, addmask, layers, want_mass)
         if not return_dict:
             return tuple(v for v in [outs[-1], all_hidden, attn] if v is not None)
-        return BaseModelOutputWithPastAndCrossAttentions(last_hidden_state=outs[-1], past_key_values=None,
-                                                         hidden_states=all_hidden, attentions=attn,
-                                                         cross_attentions=None)
+        out = BaseModelOutputWithPastAndCrossAttentions(last_hidden_state=outs[-1], past_key_values=None,
+                                                        hidden_states=all_hidden, attentions=attn,
+                                                        cross_attentions=None)
+        if mixed is not None:
+            out.mixed_hidden_state = mixed
+        return out
 
     def _attention_maps(self, h0, outs, stores, pkv, addmask, layers, want_mass):
         """-> (attentions: a tuple of L entries, [B,NH,S,P+S] for the requested ``layers`` and None elsewhere, or None when no
@@ -628,7 +643,9 @@ class BertModel(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, past_key_values=None,
-                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, layer_mix=None):
+        """``layer_mix``: a `modules.layer_mix.LayerMix` or None.  With one, the output object has the extra attribute
+        ``mixed_hidden_state`` [B,S,H]; ``last_hidden_state`` (and the pooler, which reads it) is what it is without."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids (inputs_embeds is not on the MTVAF path)")
         if head_mask is not None or encoder_hidden_states is not None:
@@ -649,16 +666,21 @@ class BertModel(nn.Module):
         if self.embedding_tap is not None:
             emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
         enc = self.encoder(emb, attention_mask=ext, past_key_values=past_key_values, output_attentions=output_attentions,
-                           output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok)
+                           output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok, layer_mix=layer_mix)
         seq = enc.last_hidden_state
+        if layer_mix is not None and not return_dict:
+            raise ValueError("layer_mix: the mixed state is an attribute of the output object (return_dict=True)")
         # the pooler output is consumed only by the span model's DualGCN head; TVNetSAModel2 never reads it
         # (models/bert_model.py:496-506) and sets `skip_pooler` so the [B,H]x[H,H] product is not launched
         pooled = self.pooler(seq) if (self.pooler is not None and not getattr(self, "skip_pooler", False)) else None
         if not return_dict:
             return (seq, pooled) + tuple(v for v in (enc.hidden_states, enc.attentions) if v is not None)
-        return BaseModelOutputWithPoolingAndCrossAttentions(last_hidden_state=seq, pooler_output=pooled,
-                                                            past_key_values=None, hidden_states=enc.hidden_states,
-                                                            attentions=enc.attentions, cross_attentions=None)
+        out = BaseModelOutputWithPoolingAndCrossAttentions(last_hidden_state=seq, pooler_output=pooled,
+                                                           past_key_values=None, hidden_states=enc.hidden_states,
+                                                           attentions=enc.attentions, cross_attentions=None)
+        if layer_mix is not None:
+            out.mixed_hidden_state = enc.mixed_hidden_state
+        return out
 
     def get_embedding_output(self, input_ids, token_type_ids=None, position_ids=None):
         """reference: models/modeling_bert.py:1117-1125 (Cutoff augmentation entry)"""
@@ -668,12 +690,13 @@ class BertModel(nn.Module):
             emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
         return emb
 
-    def get_bert_output(self, embedding_output, attention_mask=None, past_key_values=None):
-        """reference: models/modeling_bert.py:1127-1157"""
+    def get_bert_output(self, embedding_output, attention_mask=None, past_key_values=None, layer_mix=None):
+        """reference: models/modeling_bert.py:1127-1157.  ``layer_mix`` (a `LayerMix`): the tuple gets a third entry, the mixed
+        state."""
         assert attention_mask.dim() == 2
         ext = self.get_extended_attention_mask(attention_mask)
         enc = self.encoder(embedding_output, attention_mask=ext, past_key_values=past_key_values, return_dict=True,
-                           unpad_ok=bool(getattr(self, "allow_unpad", False)))
+                           unpad_ok=bool(getattr(self, "allow_unpad", False)), layer_mix=layer_mix)
         seq = enc.last_hidden_state
         pooled = self.pooler(seq) if (self.pooler is not None and not getattr(self, "skip_pooler", False)) else None
-        return (seq, pooled)
+        return (seq, pooled) if layer_mix is None else (seq, pooled, enc.mixed_hidden_state)

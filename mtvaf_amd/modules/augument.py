@@ -26,7 +26,8 @@ from .. import engine
 
 
 class Cutoff:
-    def __init__(self, input_ids, token_type_ids, attention_masks, prefix_guids, args, model):
+    def __init__(self, input_ids, token_type_ids, attention_masks, prefix_guids, args, model, layer_mix=None):
+        self.layer_mix = layer_mix  # a `LayerMix` or None: with one, the cut pass returns the mixed state as a third entry
         self.input_ids = input_ids
         self.token_type_ids = token_type_ids
         self.attention_masks = attention_masks
@@ -82,7 +83,8 @@ class Cutoff:
         return engine.MaskMulFunction.apply(embeds, None, keep.contiguous()), masks
 
     def _training_step_with_cutoff(self, aug_type):
-        """reference: modules/augument.py:54-77 -> (sequence_output, pooled_output) of the cut input."""
+        """reference: modules/augument.py:54-77 -> (sequence_output, pooled_output) of the cut input (with ``layer_mix``:
+        and the mixed state)."""
         dev = self.args.device
         input_ids = self.input_ids.to(dev)
         token_type_ids = self.token_type_ids.to(dev)
@@ -98,4 +100,4 @@ class Cutoff:
         else:
             raise NotImplementedError
         return self.model.get_bert_output(embedding_output=input_embeds, attention_mask=input_masks,
-                                          past_key_values=self.prefix_guids)
+                                          past_key_values=self.prefix_guids, layer_mix=self.layer_mix)

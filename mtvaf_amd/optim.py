@@ -1061,16 +1061,27 @@ class AdamW(torch.optim.Optimizer):
         return loss
 
 
+def _is_layer_mix(name: str) -> bool:
+    """The two parameters of a model's `LayerMix` (args.layer_mix): softmax logits and one scale, never weight-decayed."""
+    return name.startswith("layer_mix.") or ".layer_mix." in name
+
+
 def reference_param_groups(model: torch.nn.Module, lr: float, use_prefix: bool = True) -> List[Dict]:
-    """The parameter groups of modules/train.py:887-916 (by parameter name, in the reference's order)."""
+    """The parameter groups of modules/train.py:887-916 (by parameter name, in the reference's order).  A model with args.layer_mix
+    (not the reference's) gets one more group behind them: the mix's two parameters, at the head's lr (``lr`` without a prefix),
+    weight decay 0."""
     named = list(model.named_parameters())
+    mix = [p for n, p in named if _is_layer_mix(n)]
+    named = [(n, p) for n, p in named if not _is_layer_mix(n)]
     if not use_prefix:  # bert_before_train: every parameter, one group
-        return [{"params": [p for _, p in named], "lr": lr}]
+        return [{"params": [p for _, p in named], "lr": lr}] + ([{"params": mix, "lr": lr, "weight_decay": 0.0}] if mix else [])
     groups = [
         {"lr": lr, "weight_decay": 1e-2, "params": [p for n, p in named if "bert" in n]},
         {"lr": lr, "weight_decay": 1e-2, "params": [p for n, p in named if "encoder_conv" in n or "gates" in n]},
         {"lr": 5e-2, "weight_decay": 1e-2, "params": [p for n, p in named if "crf" in n or n.startswith("fc")]},
     ]
+    if mix:
+        groups.append({"lr": 5e-2, "weight_decay": 0.0, "params": mix})
     return groups
 
 
@@ -1089,6 +1100,8 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
         decay 0, the others ``weight_decay``), and
       * the encoder is split by depth: layer ``l`` of ``L`` (``encoder.layer.<l>.``) trains at ``lr * layer_lr_decay ** (L - 1 - l)``,
         the embeddings at ``lr * layer_lr_decay ** L``, whatever sits above the last layer (the pooler) at ``lr``.
+    The two parameters of a `LayerMix` (``layer_mix.scalars``, ``layer_mix.gamma``; args.layer_mix) belong to the head partition and
+    are always exempt from weight decay, whatever ``no_decay`` names.
     Groups come in the order their first parameter has in ``named_parameters()``.  With ``no_decay=()`` and ``layer_lr_decay=1`` these
     are the reference groups.  An encoder layer then holds two groups; ``AdamW`` still updates it with one launch (``layer_segments``)."""
     import re
@@ -1097,7 +1110,7 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
     if use_prefix:
         parts = [(lr, [(n, p) for n, p in named if "bert" in n], True),
                  (lr, [(n, p) for n, p in named if "encoder_conv" in n or "gates" in n], False),
-                 (head_lr, [(n, p) for n, p in named if "crf" in n or n.startswith("fc")], False)]
+                 (head_lr, [(n, p) for n, p in named if "crf" in n or n.startswith("fc") or _is_layer_mix(n)], False)]
     else:
         parts = [(lr, named, True)]
     layer_of = lambda n: re.search(r"encoder\.layer\.(\d+)\.", n)
@@ -1109,7 +1122,7 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
             power = 0
             if by_depth and layer_lr_decay != 1.0:
                 power = L - 1 - int(layer_of(n).group(1)) if layer_of(n) else (L if "embeddings." in n else 0)
-            split.setdefault((power, any(s in n for s in no_decay)), []).append(p)
+            split.setdefault((power, any(s in n for s in no_decay) or _is_layer_mix(n)), []).append(p)
         if not split:  # (the reference keeps its empty second group too)
             split[(0, False)] = []
         groups.extend({"lr": base_lr * layer_lr_decay ** power, "weight_decay": 0.0 if exempt else weight_decay, "params": ps}
