@@ -1513,7 +1513,8 @@ def colsum_small(part, out, accumulate=False):
 
 # ---- optimizer / gradient wire format (csrc/optim.hip, csrc/gradnorm.hip) -------------------------------------------
 def _clip_ptr(clip):
-    """Device clip state of grad_clip_finalize for the *_dev update kernels: 4 floats {norm, coef, finite, 0}."""
+    """Device state of a gradient norm: 4 floats, {norm, coef, finite, 0} of grad_clip_finalize for the *_dev update kernels or
+    {norm, scale, finite, 0} of sam_finalize for the perturb kernels."""
     assert clip.is_cuda and clip.dtype == torch.float32 and clip.numel() >= 4 and clip.is_contiguous(), (clip.device, clip.dtype, clip.shape)
     return clip.data_ptr()
 
@@ -1525,25 +1526,69 @@ def _ema_arg(ema, like):
     return ema.data_ptr()
 
 
+def _opt(t, fn=_p, *a):
+    return None if t is None else fn(t, *a)
+
+
+# The pieces every update's argument list is made of, in the order of the C ABI: the flat buffers, then the hyper-parameters of a
+# uniform launch (_uniform_args) or the segment table of a segmented one (_seg_table) -- with the host's bias corrections in front
+# of grad_scale when `step` is given, without them on the device's schedule --, then what the form adds (_mat_args, the shadow,
+# max_blocks) and its optional pointers.
+def _flat_args(p, g, m, v, check=True):
+    if check:
+        _f32(p, g, m, v)
+    return _p(p), _p(g), _p(m), _p(v), p.numel()
+
+
+def _ptr_array(ts, fn=_p):
+    return (ctypes.c_void_p * len(ts))(*[fn(t) for t in ts])
+
+
+def _multi_args(ps, gs, ms, vs):
+    return len(ps), _ptr_array(ps), _ptr_array(gs), _ptr_array(ms), _ptr_array(vs), (ctypes.c_long * len(ps))(*[t.numel() for t in ps])
+
+
+def _bias_corrections(beta1, beta2, step):
+    """(1 - beta1^t, sqrt(1 - beta2^t)) of the 1-based step t, in Python doubles: the C ABI rounds each to float once."""
+    return 1.0 - beta1 ** step, (1.0 - beta2 ** step) ** 0.5
+
+
+def _uniform_args(lr, beta1, beta2, eps, weight_decay, grad_scale, step=None):
+    bc = () if step is None else _bias_corrections(beta1, beta2, step)
+    return (float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), *bc, float(grad_scale))
+
+
+def _seg_table(segments, beta1, beta2, eps, grad_scale, lr_type, step=None):
+    """segments = [(end element, lr, weight_decay), ...] in buffer order; the lr column as `lr_type` (float: this step's lr; double:
+    the BASE lr of the device's schedule)."""
+    k = len(segments)
+    bc = () if step is None else _bias_corrections(beta1, beta2, step)
+    return (k, (ctypes.c_long * k)(*[int(s[0]) for s in segments]), (lr_type * k)(*[float(s[1]) for s in segments]),
+            (ctypes.c_float * k)(*[float(s[2]) for s in segments]), float(beta1), float(beta2), float(eps), *bc, float(grad_scale))
+
+
+def _mat_args(mats):
+    n = len(mats)
+    return (n, (ctypes.c_long * n)(*[s[0] for s in mats]), (ctypes.c_int * n)(*[s[1] for s in mats]),
+            (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]))
+
+
+def _uniform_update(name, args, ema_arg, ema_omd, clip):
+    """The three entry points of a uniform update on host scalars: `name`, `name`_dev (clip state) and `name`_ema (the average; the
+    clip state optional)."""
+    if ema_arg is not None:
+        name, args = name + "_ema", (*args, ema_arg, float(ema_omd), _opt(clip, _clip_ptr))
+    elif clip is not None:
+        name, args = name + "_dev", (*args, _clip_ptr(clip))
+    _ck(getattr(lib(), name)(*args, _st()), name)
+
+
 def adamw_planes(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, segs, grad_scale=1.0, max_blocks=0, clip=None, ema=None,
                  ema_omd=0.0):
     """adamw over a flat buffer that also rewrites the plane images of the matrices inside it: segs = [(begin element, rows, cols,
     image uint8 tensor), ...] (at most four).  clip, ema, ema_omd: see adamw."""
-    _f32(p, g, m, v)
-    n = len(segs)
-    bc1 = 1.0 - beta1 ** step
-    bc2_sqrt = (1.0 - beta2 ** step) ** 0.5
-    args = (_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-            float(bc1), float(bc2_sqrt), float(grad_scale), n, (ctypes.c_long * n)(*[s[0] for s in segs]),
-            (ctypes.c_int * n)(*[s[1] for s in segs]), (ctypes.c_int * n)(*[s[2] for s in segs]),
-            (ctypes.c_void_p * n)(*[_p(s[3]) for s in segs]), int(max_blocks))
-    if ema is not None:
-        _ck(lib().mtvaf_adamw_planes_ema(*args, _ema_arg(ema, p), float(ema_omd), None if clip is None else _clip_ptr(clip), _st()),
-            "mtvaf_adamw_planes_ema")
-    elif clip is None:
-        _ck(lib().mtvaf_adamw_planes(*args, _st()), "mtvaf_adamw_planes")
-    else:
-        _ck(lib().mtvaf_adamw_planes_dev(*args, _clip_ptr(clip), _st()), "mtvaf_adamw_planes_dev")
+    _uniform_update("mtvaf_adamw_planes", (*_flat_args(p, g, m, v), *_uniform_args(lr, beta1, beta2, eps, weight_decay, grad_scale, step),
+                                           *_mat_args(segs), int(max_blocks)), _opt(ema, _ema_arg, p), ema_omd, clip)
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None,
@@ -1554,71 +1599,41 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0,
     state whose `finite` is 0 makes the launch write nothing.
     ema: an fp32 tensor as long as p that the same launch averages the new parameter into, ema += ema_omd * (p_new - ema) with
     ema_omd = 1 - decay (1: ema becomes p_new exactly); None: the launch without it."""
-    n = p.numel()
-    bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    if ema is not None:
-        _ck(lib().mtvaf_adamw_ema(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
-                                  _p(p_bf16), int(max_blocks), _ema_arg(ema, p), float(ema_omd),
-                                  None if clip is None else _clip_ptr(clip), _st()), "mtvaf_adamw_ema")
-    elif clip is None:
-        _ck(lib().mtvaf_adamw(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
-                              _p(p_bf16), int(max_blocks), _st()), "mtvaf_adamw")
-    else:
-        _ck(lib().mtvaf_adamw_dev(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, bc1, bc2 ** 0.5, grad_scale,
-                                  _p(p_bf16), int(max_blocks), _clip_ptr(clip), _st()), "mtvaf_adamw_dev")
+    _uniform_update("mtvaf_adamw", (*_flat_args(p, g, m, v, check=False),
+                                    *_uniform_args(lr, beta1, beta2, eps, weight_decay, grad_scale, step), _p(p_bf16), int(max_blocks)),
+                    _opt(ema, _ema_arg, p), ema_omd, clip)
+
+
+def _ema_array(ema, ps):
+    assert ema is None or len(ema) == len(ps)
+    return None if ema is None else (ctypes.c_void_p * len(ps))(*[_ema_arg(e, t) for e, t in zip(ema, ps)])
 
 
 def adamw_multi(ps, gs, ms, vs, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_omd=0.0):
     """One launch per 48 tensors of a parameter group sharing hyper-parameters and step count.  clip: see adamw; ema: a list of
     averages parallel to ps (one ema_omd for all of them), None: without."""
-    k = len(ps)
-    if k == 0:
+    if len(ps) == 0:
         return
-    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
-    ns = (ctypes.c_long * k)(*[t.numel() for t in ps])
-    bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
-    if ema is not None:
-        assert len(ema) == k
-        es = (ctypes.c_void_p * k)(*[_ema_arg(e, t) for e, t in zip(ema, ps)])
-        _ck(lib().mtvaf_adamw_multi_ema(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
-                                        bc2 ** 0.5, grad_scale, es, float(ema_omd), None if clip is None else _clip_ptr(clip), _st()),
-            "mtvaf_adamw_multi_ema")
-    elif clip is None:
-        _ck(lib().mtvaf_adamw_multi(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
-                                    bc2 ** 0.5, grad_scale, _st()), "mtvaf_adamw_multi")
-    else:
-        _ck(lib().mtvaf_adamw_multi_dev(k, arr(ps), arr(gs), arr(ms), arr(vs), ns, lr, beta1, beta2, eps, weight_decay, bc1,
-                                        bc2 ** 0.5, grad_scale, _clip_ptr(clip), _st()), "mtvaf_adamw_multi_dev")
-
-
-def _seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale):
-    """The leading arguments of the two segmented updates: segments = [(end element, lr, weight_decay), ...] in buffer order."""
-    _f32(p, g, m, v)
-    k = len(segments)
-    return (_p(p), _p(g), _p(m), _p(v), p.numel(), k, (ctypes.c_long * k)(*[int(s[0]) for s in segments]),
-            (ctypes.c_float * k)(*[float(s[1]) for s in segments]), (ctypes.c_float * k)(*[float(s[2]) for s in segments]),
-            float(beta1), float(beta2), float(eps), float(1.0 - beta1 ** step), float((1.0 - beta2 ** step) ** 0.5), float(grad_scale))
+    _uniform_update("mtvaf_adamw_multi", (*_multi_args(ps, gs, ms, vs), *_uniform_args(lr, beta1, beta2, eps, weight_decay, grad_scale, step)),
+                    _ema_array(ema, ps), ema_omd, clip)
 
 
 def adamw_seg(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None, ema_omd=0.0):
     """adamw with lr and weight decay per segment of the flat buffer: segments = [(end element, lr, weight_decay), ...], at most 16,
     ends strictly increasing, the last one p.numel(), every other one a multiple of 4.  One launch; each element gets the bits
     adamw gives it on its segment alone.  p_bf16, max_blocks, clip, ema, ema_omd: see adamw (all optional, one entry point)."""
-    _ck(lib().mtvaf_adamw_seg(*_seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale), _p(p_bf16), int(max_blocks),
-                              None if ema is None else _ema_arg(ema, p), float(ema_omd), None if clip is None else _clip_ptr(clip),
-                              _st()), "mtvaf_adamw_seg")
+    _ck(lib().mtvaf_adamw_seg(*_flat_args(p, g, m, v), *_seg_table(segments, beta1, beta2, eps, grad_scale, ctypes.c_float, step),
+                              _p(p_bf16), int(max_blocks), _opt(ema, _ema_arg, p), float(ema_omd), _opt(clip, _clip_ptr), _st()),
+        "mtvaf_adamw_seg")
 
 
 def adamw_planes_seg(p, g, m, v, segments, beta1, beta2, eps, step, mats, grad_scale=1.0, max_blocks=0, clip=None, ema=None,
                      ema_omd=0.0):
     """adamw_seg that also rewrites the plane images of the matrices inside the buffer: mats = [(begin element, rows, cols, image
     uint8 tensor), ...] (at most four, as adamw_planes' segs; a matrix may lie across segment ends)."""
-    n = len(mats)
-    _ck(lib().mtvaf_adamw_planes_seg(*_seg_args(p, g, m, v, segments, beta1, beta2, eps, step, grad_scale), n,
-                                     (ctypes.c_long * n)(*[s[0] for s in mats]), (ctypes.c_int * n)(*[s[1] for s in mats]),
-                                     (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]),
-                                     int(max_blocks), None if ema is None else _ema_arg(ema, p), float(ema_omd),
-                                     None if clip is None else _clip_ptr(clip), _st()), "mtvaf_adamw_planes_seg")
+    _ck(lib().mtvaf_adamw_planes_seg(*_flat_args(p, g, m, v), *_seg_table(segments, beta1, beta2, eps, grad_scale, ctypes.c_float, step),
+                                     *_mat_args(mats), int(max_blocks), _opt(ema, _ema_arg, p), float(ema_omd), _opt(clip, _clip_ptr),
+                                     _st()), "mtvaf_adamw_planes_seg")
 
 
 # ---- the schedule on the device: the *_sched updates read lr factor, bias corrections and 1 - decay from `current` -------------------
@@ -1643,68 +1658,45 @@ def adamw_sched_advance(table, counter, current):
                                         _st()), "mtvaf_adamw_sched_advance")
 
 
-def _opt(t, fn=_p, *a):
-    return None if t is None else fn(t, *a)
+def _sched_update(name, args, ema_arg, clip, current):
+    """Every *_sched entry point ends alike: the average, the clip state (both optional), the schedule block, the stream."""
+    _ck(getattr(lib(), name)(*args, ema_arg, _opt(clip, _clip_ptr), _sched_ptr(current), _st()), name)
 
 
 def adamw_sched(p, g, m, v, base_lr, beta1, beta2, eps, weight_decay, current, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None,
                 ema=None):
     """adamw whose lr is float(base_lr * current.lr_factor) and whose bias corrections and 1 - decay come from `current`: no argument
     changes from step to step.  p_bf16, max_blocks, clip, ema: see adamw."""
-    _ck(lib().mtvaf_adamw_sched(_p(p), _p(g), _p(m), _p(v), p.numel(), float(base_lr), float(beta1), float(beta2), float(eps),
-                                float(weight_decay), float(grad_scale), _p(p_bf16), int(max_blocks), _opt(ema, _ema_arg, p),
-                                _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_sched")
-
-
-def _mat_args(mats):
-    n = len(mats)
-    return (n, (ctypes.c_long * n)(*[s[0] for s in mats]), (ctypes.c_int * n)(*[s[1] for s in mats]),
-            (ctypes.c_int * n)(*[s[2] for s in mats]), (ctypes.c_void_p * n)(*[_p(s[3]) for s in mats]))
+    _sched_update("mtvaf_adamw_sched", (*_flat_args(p, g, m, v, check=False),
+                                        *_uniform_args(base_lr, beta1, beta2, eps, weight_decay, grad_scale), _p(p_bf16), int(max_blocks)),
+                  _opt(ema, _ema_arg, p), clip, current)
 
 
 def adamw_planes_sched(p, g, m, v, base_lr, beta1, beta2, eps, weight_decay, current, mats, grad_scale=1.0, max_blocks=0, clip=None,
                        ema=None):
     """adamw_planes on the device's schedule (adamw_sched); mats as adamw_planes' segs."""
-    _f32(p, g, m, v)
-    _ck(lib().mtvaf_adamw_planes_sched(_p(p), _p(g), _p(m), _p(v), p.numel(), float(base_lr), float(beta1), float(beta2), float(eps),
-                                       float(weight_decay), float(grad_scale), *_mat_args(mats), int(max_blocks),
-                                       _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()),
-        "mtvaf_adamw_planes_sched")
+    _sched_update("mtvaf_adamw_planes_sched", (*_flat_args(p, g, m, v), *_uniform_args(base_lr, beta1, beta2, eps, weight_decay, grad_scale),
+                                               *_mat_args(mats), int(max_blocks)), _opt(ema, _ema_arg, p), clip, current)
 
 
 def adamw_multi_sched(ps, gs, ms, vs, base_lr, beta1, beta2, eps, weight_decay, current, grad_scale=1.0, clip=None, ema=None):
     """adamw_multi on the device's schedule (adamw_sched): any number of tensors, 48 per launch; ema: a list parallel to ps, or None."""
-    k = len(ps)
-    if k == 0:
+    if len(ps) == 0:
         return
-    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
-    assert ema is None or len(ema) == k
-    es = None if ema is None else (ctypes.c_void_p * k)(*[_ema_arg(e, t) for e, t in zip(ema, ps)])
-    _ck(lib().mtvaf_adamw_multi_sched(k, arr(ps), arr(gs), arr(ms), arr(vs), (ctypes.c_long * k)(*[t.numel() for t in ps]),
-                                      float(base_lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale),
-                                      es, _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_multi_sched")
-
-
-def _seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale):
-    """segments = [(end element, BASE lr, weight_decay), ...]: the lr column travels as doubles."""
-    _f32(p, g, m, v)
-    k = len(segments)
-    return (_p(p), _p(g), _p(m), _p(v), p.numel(), k, (ctypes.c_long * k)(*[int(s[0]) for s in segments]),
-            (ctypes.c_double * k)(*[float(s[1]) for s in segments]), (ctypes.c_float * k)(*[float(s[2]) for s in segments]),
-            float(beta1), float(beta2), float(eps), float(grad_scale))
+    _sched_update("mtvaf_adamw_multi_sched", (*_multi_args(ps, gs, ms, vs), *_uniform_args(base_lr, beta1, beta2, eps, weight_decay, grad_scale)),
+                  _ema_array(ema, ps), clip, current)
 
 
 def adamw_seg_sched(p, g, m, v, segments, beta1, beta2, eps, current, grad_scale=1.0, p_bf16=None, max_blocks=0, clip=None, ema=None):
     """adamw_seg on the device's schedule: segments = [(end element, base lr, weight_decay), ...]."""
-    _ck(lib().mtvaf_adamw_seg_sched(*_seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale), _p(p_bf16), int(max_blocks),
-                                    _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()), "mtvaf_adamw_seg_sched")
+    _sched_update("mtvaf_adamw_seg_sched", (*_flat_args(p, g, m, v), *_seg_table(segments, beta1, beta2, eps, grad_scale, ctypes.c_double),
+                                            _p(p_bf16), int(max_blocks)), _opt(ema, _ema_arg, p), clip, current)
 
 
 def adamw_planes_seg_sched(p, g, m, v, segments, beta1, beta2, eps, current, mats, grad_scale=1.0, max_blocks=0, clip=None, ema=None):
     """adamw_planes_seg on the device's schedule."""
-    _ck(lib().mtvaf_adamw_planes_seg_sched(*_seg_sched_args(p, g, m, v, segments, beta1, beta2, eps, grad_scale), *_mat_args(mats),
-                                           int(max_blocks), _opt(ema, _ema_arg, p), _opt(clip, _clip_ptr), _sched_ptr(current), _st()),
-        "mtvaf_adamw_planes_seg_sched")
+    _sched_update("mtvaf_adamw_planes_seg_sched", (*_flat_args(p, g, m, v), *_seg_table(segments, beta1, beta2, eps, grad_scale, ctypes.c_double),
+                                                   *_mat_args(mats), int(max_blocks)), _opt(ema, _ema_arg, p), clip, current)
 
 
 def swap_f32(a_list, b_list):
@@ -1824,13 +1816,6 @@ def adv_add(x, delta, out=None):
 
 
 # ---- sharpness-aware minimisation: the ascent step in weight space (csrc/optim.hip, csrc/gradnorm.hip) --------------
-def _sam_state_ptr(state):
-    """Device SAM state of sam_finalize for the perturb kernels: 4 floats {norm, scale, finite, 0}."""
-    assert state.is_cuda and state.dtype == torch.float32 and state.numel() >= 4 and state.is_contiguous(), (state.device, state.dtype,
-                                                                                                                state.shape)
-    return state.data_ptr()
-
-
 def _sam_same(p, *others):
     _f32(p, *others)
     for t in others:
@@ -1843,7 +1828,7 @@ def sam_finalize(partials, rho, state, skipped=None):
     adds 1 to `skipped` (device int32)."""
     assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
     assert skipped is None or (skipped.is_cuda and skipped.dtype == torch.int32)
-    _ck(lib().mtvaf_sam_finalize(_p(partials), partials.numel(), float(rho), _sam_state_ptr(state), _p(skipped), _st()),
+    _ck(lib().mtvaf_sam_finalize(_p(partials), partials.numel(), float(rho), _clip_ptr(state), _p(skipped), _st()),
         "mtvaf_sam_finalize")
     return state
 
@@ -1852,13 +1837,13 @@ def sam_perturb(p, g, backup, state, p_bf16=None):
     """backup = p; p = fmaf(scale, g, p) over one flat fp32 tensor, scale read from the device state of sam_finalize (finite == 0: p
     keeps its bits, backup is written all the same).  p_bf16: the bf16 shadow of p, written from the new p in the same pass."""
     _sam_same(p, g, backup)
-    _ck(lib().mtvaf_sam_perturb(_p(p), _p(g), _p(backup), p.numel(), _sam_state_ptr(state), _p(p_bf16), _st()), "mtvaf_sam_perturb")
+    _ck(lib().mtvaf_sam_perturb(_p(p), _p(g), _p(backup), p.numel(), _clip_ptr(state), _p(p_bf16), _st()), "mtvaf_sam_perturb")
 
 
 def sam_perturb_planes(p, g, backup, state, segs):
     """sam_perturb over a flat buffer that also rewrites the plane images of the matrices inside it: segs as adamw_planes'."""
     _sam_same(p, g, backup)
-    _ck(lib().mtvaf_sam_perturb_planes(_p(p), _p(g), _p(backup), p.numel(), _sam_state_ptr(state), *_mat_args(segs), _st()),
+    _ck(lib().mtvaf_sam_perturb_planes(_p(p), _p(g), _p(backup), p.numel(), _clip_ptr(state), *_mat_args(segs), _st()),
         "mtvaf_sam_perturb_planes")
 
 
@@ -1870,9 +1855,8 @@ def sam_perturb_multi(ps, gs, backups, state):
         return
     for t in zip(ps, gs, backups):
         _sam_same(*t)
-    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
-    _ck(lib().mtvaf_sam_perturb_multi(k, arr(ps), arr(gs), arr(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]),
-                                      _sam_state_ptr(state), _st()), "mtvaf_sam_perturb_multi")
+    _ck(lib().mtvaf_sam_perturb_multi(k, _ptr_array(ps), _ptr_array(gs), _ptr_array(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]),
+                                      _clip_ptr(state), _st()), "mtvaf_sam_perturb_multi")
 
 
 def sam_restore(p, backup, p_bf16=None):
@@ -1895,8 +1879,7 @@ def sam_restore_multi(ps, backups):
         return
     for t in zip(ps, backups):
         _sam_same(*t)
-    arr = lambda ts: (ctypes.c_void_p * k)(*[_p(t) for t in ts])
-    _ck(lib().mtvaf_sam_restore_multi(k, arr(ps), arr(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]), _st()),
+    _ck(lib().mtvaf_sam_restore_multi(k, _ptr_array(ps), _ptr_array(backups), (ctypes.c_long * k)(*[t.numel() for t in ps]), _st()),
         "mtvaf_sam_restore_multi")
 
 

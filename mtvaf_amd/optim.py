@@ -284,6 +284,7 @@ class AdamW(torch.optim.Optimizer):
         self._layer_group: Dict[int, Optional[dict]] = {}
         self._early = set()
         self._param_layer: Dict[int, int] = {}  # id(parameter) -> encoder layer whose flat state its entries are views of
+        self._flat_state: Dict[tuple, dict] = {}  # ("layer", li) -> the layer's flat moment buffers and counters (_layer_state)
         self._background_ok = True
         self.suspended = False    # True: the backward hook does nothing (backward passes that are not followed by step())
         self.device_schedule = None  # a ScheduleTable: the *_sched kernels, hyper-parameters of the step read on the device
@@ -374,7 +375,7 @@ class AdamW(torch.optim.Optimizer):
     def _layer_state(self, li: int, store):
         """Flat moment buffers of layer li; the per-parameter state entries are views of them."""
         key = ("layer", li)
-        st = self.__dict__.setdefault("_flat_state", {}).get(key)
+        st = self._flat_state.get(key)
         if st is None or st["m"].numel() != store.flat.numel() or st["m"].device != store.flat.device:
             st = {"m": torch.zeros_like(store.flat), "v": torch.zeros_like(store.flat), "step": 0,
                   "step_t": torch.zeros((), dtype=torch.float32)}
@@ -422,7 +423,7 @@ class AdamW(torch.optim.Optimizer):
                                "step() or unperturb() first -- a checkpoint never holds the perturbed weights or their backup")
         super().load_state_dict(state_dict)
         # the flat per-layer buffers are rebuilt from the loaded per-parameter entries by the next _layer_state()
-        self.__dict__["_flat_state"] = {}
+        self._flat_state = {}
         self._param_layer = {}
         self._early = set()
         if self.device_schedule is not None:
@@ -504,7 +505,7 @@ class AdamW(torch.optim.Optimizer):
         self._sched_step_t.fill_(c)  # (host tensors, shared by the parameters of every encoder layer)
         if ema_on:
             self._sched_ema_step_t.fill_(c)
-        for st in self.__dict__.get("_flat_state", {}).values():
+        for st in self._flat_state.values():
             st["step"] = c
             if "ema" in st:
                 st["ema_step"] = c
@@ -521,53 +522,6 @@ class AdamW(torch.optim.Optimizer):
                                + f", the schedule is at {c}: the device keeps ONE step counter (and one row of bias corrections and "
                                "EMA decay) for every parameter")
 
-    def _schedule_collect(self):
-        """What this step updates, as ``step()`` finds it, without touching a counter: -> (layer jobs, group jobs, gradients)."""
-        ema_on = self.ema_decay > 0.0
-        done, layer_jobs = set(), []
-        enc = self._encoder
-        if enc is not None and enc._stores is not None:
-            if len(self._layer_group) != len(enc.layer):
-                self._map_layers()
-            for li, layer in enumerate(enc.layer):
-                store = enc._stores[li]
-                group = self._plan(li, store)
-                if group is None or store.grad is None or not store.valid(layer):
-                    continue
-                ps = layer.ordered_params()
-                lo = store.grad.data_ptr()
-                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
-                       for i, p in enumerate(ps)):
-                    st = self._layer_state(li, store)
-                    self._schedule_count_check(f"encoder layer {li}", st["step"], st.get("ema_step"))
-                    layer_jobs.append((li, group, store))
-                    done.update(id(p) for p in ps)
-        group_jobs, states = [], []
-        for group in self.param_groups:
-            items = []
-            for p in group["params"]:
-                if p.grad is None or id(p) in done:
-                    continue
-                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
-                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
-                if not p.is_contiguous():
-                    raise RuntimeError("non-contiguous parameter")
-                stt = self.state[p]
-                if "exp_avg" not in stt:
-                    stt["exp_avg"], stt["exp_avg_sq"], stt["step"] = torch.zeros_like(p), torch.zeros_like(p), 0
-                if ema_on and "ema" not in stt:
-                    stt["ema"], stt["ema_step"] = torch.zeros_like(p), 0
-                if stt["step"] is not self._sched_step_t:  # (a view of a layer's flat state counts with the layer)
-                    self._schedule_count_check("a parameter", stt["step"], stt["ema_step"] if ema_on else None)
-                    states.append(stt)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                items.append((p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
-            if items:
-                group_jobs.append((group, items))
-        self._sched_states = states
-        grads = [store.grad for _, _, store in layer_jobs] + [i[1] for _, items in group_jobs for i in items]
-        return layer_jobs, group_jobs, grads
-
     def _schedule_launch(self, suppress: bool = False) -> bool:
         """Every launch of one update under the device schedule, on the current stream: the clip state (if wanted), the counter's
         advance, the ``*_sched`` updates.  No host value of the step enters a kernel argument, so a graph capture may contain the
@@ -577,7 +531,21 @@ class AdamW(torch.optim.Optimizer):
         self._refuse_swapped("step() was called")
         if not suppress:
             self._schedule_refuse_end()
-        layer_jobs, group_jobs, grads = self._schedule_collect()
+        ema_on = self.ema_decay > 0.0
+        layers, rest = self._collect()
+        for li, _, store in layers:
+            st = self._layer_state(li, store)
+            self._schedule_count_check(f"encoder layer {li}", st["step"], st.get("ema_step"))
+        group_jobs, states = {}, []  # id(group) -> (group, [(p, g, exp_avg, exp_avg_sq, ema), ...]); states: what host_step counts
+        for group, p, g in rest:
+            stt = self._tensor_state(p)
+            if stt["step"] is not self._sched_step_t:  # (a view of a layer's flat state counts with the layer)
+                self._schedule_count_check("a parameter", stt["step"], stt["ema_step"] if ema_on else None)
+                states.append(stt)
+            group_jobs.setdefault(id(group), (group, []))[1].append(
+                (p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
+        self._sched_states = states
+        grads = [store.grad for _, _, store in layers] + [g for _, _, g in rest]
         if not grads:
             return False
         d = self._schedule_device(grads[0].device)
@@ -592,10 +560,9 @@ class AdamW(torch.optim.Optimizer):
             overrun.fill_(1)
         else:
             hip.adamw_sched_advance(d["table"], d["counter"], d["current"])
-        for li, group, store in layer_jobs:
-            self._update_layer_sched(li, group, store, clip, d["current"], stamp=not suppress)
-        ema_on = self.ema_decay > 0.0
-        for group, items in group_jobs:
+        for li, plan, store in layers:
+            self._update_layer(li, plan, store, clip=clip, current=d["current"], stamp=not suppress)
+        for group, items in group_jobs.values():
             b1, b2 = group["betas"]
             hip.adamw_multi_sched([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
                                   group["initial_lr"], b1, b2, group["eps"], group["weight_decay"], d["current"], clip=clip,
@@ -603,35 +570,6 @@ class AdamW(torch.optim.Optimizer):
         if suppress:
             overrun.fill_(0)
         return True
-
-    def _update_layer_sched(self, li: int, group, store, clip, current, stamp: bool = True):
-        """``_update_layer_flat`` under the device schedule: the same choice of form, the groups' BASE lr, no counter."""
-        st = self._layer_state(li, store)
-        table = [(end, g["initial_lr"], g["weight_decay"]) for end, g in group] if isinstance(group, list) else None
-        if table is not None:
-            group = group[0][1]
-        b1, b2 = group["betas"]
-        from . import engine
-        shadow = engine.shadow_for_update(store.weights)
-        mats = engine.planes_for_update(store.weights) if shadow is None else None
-        kw = dict(clip=clip, ema=st.get("ema"))
-        if mats is not None and store.flat.numel() % 4 == 0:
-            if table is not None:
-                hip.adamw_planes_seg_sched(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], current, mats, **kw)
-            else:
-                hip.adamw_planes_sched(store.flat, store.grad, st["m"], st["v"], group["initial_lr"], b1, b2, group["eps"],
-                                       group["weight_decay"], current, mats, **kw)
-            if stamp:
-                engine.planes_written(store.weights)
-            return
-        if table is not None:
-            hip.adamw_seg_sched(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], current, p_bf16=shadow, **kw)
-        else:
-            hip.adamw_sched(store.flat, store.grad, st["m"], st["v"], group["initial_lr"], b1, b2, group["eps"], group["weight_decay"],
-                            current, p_bf16=shadow, **kw)
-        if shadow is not None and stamp:
-            engine.shadow_written(store.weights)
-        engine.planes_rewrite(store.weights)
 
     # -- averaged weights --------------------------------------------------------------------------------------------
     def _ema_omd(self, t: int) -> float:
@@ -641,11 +579,10 @@ class AdamW(torch.optim.Optimizer):
     def _ema_pairs(self):
         """-> (parameter side, average side): one pair per encoder layer whose flat buffers hold both, one per remaining tensor."""
         a, b, seen = [], [], set()
-        flat_state = self.__dict__.get("_flat_state", {})
         enc = self._encoder
         if enc is not None and enc._stores is not None:
             for li, layer in enumerate(enc.layer):
-                st, store = flat_state.get(("layer", li)), enc._stores[li]
+                st, store = self._flat_state.get(("layer", li)), enc._stores[li]
                 if st is None or "ema" not in st or not store.valid(layer) or st["ema"].numel() != store.flat.numel():
                     continue
                 ps = layer.ordered_params()
@@ -722,43 +659,70 @@ class AdamW(torch.optim.Optimizer):
     BACKGROUND_BLOCKS_SHORT = 256
     BACKGROUND_SHORT_ROWS = 4096
 
-    def _update_layer_flat(self, li: int, group: dict, store, background: bool = False, rows: int = 0, clip=None):
-        st = self._layer_state(li, store)
-        st["step"] += 1
-        st["step_t"].fill_(st["step"])  # the 16 per-parameter state entries share this 0-dim tensor
-        ema, omd = None, 0.0
-        if "ema" in st:
-            ema, omd = st["ema"], self._ema_omd(st["ema_step"])
-            st["ema_step"] += 1
-            st["ema_step_t"].fill_(st["ema_step"])
-        # a segmented plan ([(end element, group), ...]): lr and weight decay per segment, read now; betas and eps are the launch's
-        table = [(end, float(g["lr"]), g["weight_decay"]) for end, g in group] if isinstance(group, list) else None
-        if table is not None:
-            group = group[0][1]
-        b1, b2 = group["betas"]
+    @staticmethod
+    def _images(store, keep_read_mark: bool = False):
+        """The image rule, once: -> (shadow, mats), the GEMM-operand image of the layer's weights that a kernel writing
+        ``store.flat`` rewrites in the same pass.  ``shadow``: the bf16 image (bf16 compute mode, once a forward pass has built it);
+        else ``mats``: the plane images of the four matrices (fp32 mode, pre-split operands) -- None as well when the buffer is no
+        multiple of 4 elements, which the planes forms need.  At most one of the two is not None.
+
+        The order and number of the two engine calls are part of the behaviour: ``planes_for_update`` is asked only where there is
+        no shadow, exactly once per layer and writer, and it CLEARS the forward pass's read mark (and drops images no forward pass
+        has read since the last update) unless ``keep_read_mark`` -- the writer the step's own update still follows (the SAM
+        restore) passes it, so that the update finds the mark."""
         from . import engine
-        shadow = engine.shadow_for_update(store.weights)  # bf16 compute mode: the GEMM operand image, written in the same pass
-        segs = engine.planes_for_update(store.weights) if shadow is None else None
-        ema_kw = {} if ema is None else dict(ema=ema, ema_omd=omd)
-        if segs is not None and store.flat.numel() % 4 == 0:
-            # fp32 mode, pre-split operands: the weights' plane images are rewritten by the update kernel itself
-            blocks = self.BACKGROUND_BLOCKS_PLANES if background else 0
-            if table is not None:
-                hip.adamw_planes_seg(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], st["step"], segs,
-                                     max_blocks=blocks, clip=clip, **ema_kw)
-            else:
-                hip.adamw_planes(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                                 st["step"], segs, max_blocks=blocks, clip=clip, **ema_kw)
-            engine.planes_written(store.weights)
-            return
-        blocks = ((self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS) if background else 0)
-        if table is not None:
-            hip.adamw_seg(store.flat, store.grad, st["m"], st["v"], table, b1, b2, group["eps"], st["step"], p_bf16=shadow,
-                          max_blocks=blocks, clip=clip, **ema_kw)
+        shadow = engine.shadow_for_update(store.weights)
+        mats = None
+        if shadow is None:
+            mats = engine.planes_for_update(store.weights, keep_read_mark=True) if keep_read_mark else engine.planes_for_update(store.weights)
+        return shadow, (None if store.flat.numel() % 4 else mats)
+
+    # the wrapper of mtvaf_amd.hip for a layer's one launch, by (plane images, segmented plan, device schedule)
+    _LAYER_FORMS = {(planes, seg, sched): "adamw" + ("_planes" if planes else "") + ("_seg" if seg else "") + ("_sched" if sched else "")
+                    for planes in (False, True) for seg in (False, True) for sched in (False, True)}
+
+    def _update_layer(self, li: int, plan, store, *, clip=None, background: bool = False, rows: int = 0, current=None, stamp: bool = True):
+        """The ONE launch that updates encoder layer ``li``.  ``current`` (the device schedule's block): the groups' BASE lr, no
+        counter moves (``host_step`` does that).  Without it: the layer's step and EMA counters advance and lr / 1 - decay are the
+        host's values of now.  ``stamp=False``: the images are not declared fresh (a launch that writes nothing)."""
+        st = self._layer_state(li, store)
+        sched = current is not None
+        kw = dict(clip=clip)
+        if sched:
+            kw["ema"] = st.get("ema")
+            lr_key, count = "initial_lr", current  # (the BASE lr: the kernel multiplies it with the block's factor)
         else:
-            hip.adamw(store.flat, store.grad, st["m"], st["v"], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
-                      st["step"], p_bf16=shadow, max_blocks=blocks, clip=clip, **ema_kw)
-        if shadow is not None:
+            st["step"] += 1
+            st["step_t"].fill_(st["step"])  # the 16 per-parameter state entries share this 0-dim tensor
+            if "ema" in st:
+                kw.update(ema=st["ema"], ema_omd=self._ema_omd(st["ema_step"]))
+                st["ema_step"] += 1
+                st["ema_step_t"].fill_(st["ema_step"])
+            lr_key, count = "lr", st["step"]
+        # a segmented plan ([(end element, group), ...]): lr and weight decay per segment, read now; betas and eps are the launch's
+        segmented = isinstance(plan, list)
+        group = plan[0][1] if segmented else plan
+        b1, b2 = group["betas"]
+        if segmented:
+            hyper = ([(end, float(g[lr_key]), g["weight_decay"]) for end, g in plan], b1, b2, group["eps"], count)
+        else:
+            hyper = (float(group[lr_key]), b1, b2, group["eps"], group["weight_decay"], count)
+        from . import engine
+        shadow, mats = self._images(store)
+        update = getattr(hip, self._LAYER_FORMS[mats is not None, segmented, sched])
+        if mats is not None:
+            # fp32 mode, pre-split operands: the weights' plane images are rewritten by the update kernel itself
+            if not sched:
+                kw["max_blocks"] = self.BACKGROUND_BLOCKS_PLANES if background else 0
+            update(store.flat, store.grad, st["m"], st["v"], *hyper, mats, **kw)
+            if stamp:
+                engine.planes_written(store.weights)
+            return
+        if not sched:
+            kw["max_blocks"] = ((self.BACKGROUND_BLOCKS_SHORT if 0 < rows < self.BACKGROUND_SHORT_ROWS else self.BACKGROUND_BLOCKS)
+                                if background else 0)
+        update(store.flat, store.grad, st["m"], st["v"], *hyper, p_bf16=shadow, **kw)  # (shadow: written in the same pass)
+        if shadow is not None and stamp:
             engine.shadow_written(store.weights)
         engine.planes_rewrite(store.weights)  # (images exist but the fused form does not apply: rebuilt behind the update)
 
@@ -776,7 +740,7 @@ class AdamW(torch.optim.Optimizer):
         rows = getattr(self._encoder._sink, "token_rows", 0)
         # (layer 0 is the last one of the pass: nothing left to hide behind)
         background = self._background_ok and li > 0 and rows >= self.BACKGROUND_MIN_ROWS
-        self._update_layer_flat(li, group, stores[li], background=background, rows=rows)
+        self._update_layer(li, group, stores[li], background=background, rows=rows)
         self._early.add(li)
 
     # -- sharpness-aware minimisation ---------------------------------------------------------------------
@@ -795,36 +759,6 @@ class AdamW(torch.optim.Optimizer):
         if several:
             raise RuntimeError(f"{who}: data-parallel training (GradSync with several ranks) is not supported -- the perturbation "
                                "would be scaled by one rank's gradient norm; train on one GPU or build the optimizer with sam_rho=0")
-
-    def _sam_collect(self):
-        """What ``step()`` would update right now, without touching a counter: -> ([(layer index, store)] of the layers on the one-launch
-        path, [(parameter, gradient)] of everything else)."""
-        done, layers = set(), []
-        enc = self._encoder
-        if enc is not None and enc._stores is not None:
-            if len(self._layer_group) != len(enc.layer):
-                self._map_layers()
-            for li, layer in enumerate(enc.layer):
-                store = enc._stores[li]
-                if self._plan(li, store) is None or store.grad is None or not store.valid(layer):
-                    continue
-                ps = layer.ordered_params()
-                lo = store.grad.data_ptr()
-                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
-                       for i, p in enumerate(ps)):
-                    layers.append((li, store))
-                    done.update(id(p) for p in ps)
-        rest = []
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None or id(p) in done:
-                    continue
-                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
-                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
-                if not p.is_contiguous():
-                    raise RuntimeError("non-contiguous parameter")
-                rest.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous()))
-        return layers, rest
 
     def _sam_buffer(self, key, like):
         b = self._sam_backup.get(key)
@@ -850,29 +784,16 @@ class AdamW(torch.optim.Optimizer):
         self._sam_refuse_parallel()
         if hip.STREAM_OVERRIDE is not None:
             raise RuntimeError(f"{who} was called from inside a backward hook -- the pass has not produced every gradient yet")
-        layers, rest = self._sam_collect()
-        grads = [store.grad for _, store in layers] + [g for _, g in rest]
+        layers, rest = self._collect()
+        grads = [store.grad for _, _, store in layers] + [g for _, _, g in rest]
         if not grads:
             raise RuntimeError(f"{who}: no parameter has a gradient; call it after the first loss.backward()")
-        dev = grads[0].device
-        if self._sam_state is None or self._sam_state.device != dev:
-            self._sam_state = torch.zeros(4, dtype=torch.float32, device=dev)
-            self.last_sam_norm = self._sam_state[0]
-            self.sam_skipped = torch.zeros((), dtype=torch.int32, device=dev)
-            self._sam_partials = None
-        slots = hip.grad_sqnorm_slots(grads)
-        if self._sam_partials is None or self._sam_partials.numel() < slots:
-            self._sam_partials = torch.empty(slots, dtype=torch.float64, device=dev)
-        state = hip.sam_finalize(hip.grad_sqnorm(grads, self._sam_partials), self.sam_rho, self._sam_state, self.sam_skipped)
+        partials, state, skipped = self._grad_sqnorm("sam", grads)
+        hip.sam_finalize(partials, self.sam_rho, state, skipped)
         from . import engine
         jobs, fast = [], set()
-        for li, store in layers:
-            w = store.weights
-            shadow = engine.shadow_for_update(w)
-            mats = engine.planes_for_update(w) if shadow is None else None
-            if store.flat.numel() % 4:
-                mats = None
-            jobs.append((store, shadow, mats, self._sam_buffer(("layer", li), store.flat)))
+        for li, _, store in layers:
+            jobs.append((store, *self._images(store), self._sam_buffer(("layer", li), store.flat)))
             fast.add(li)
         enc = self._encoder
         stale = any(engine.images_left_stale(store.weights, shadow, mats) for store, shadow, mats, _ in jobs)
@@ -888,9 +809,9 @@ class AdamW(torch.optim.Optimizer):
                 hip.sam_perturb(store.flat, store.grad, backup, state, p_bf16=shadow)
                 if shadow is not None:
                     engine.shadow_written(store.weights, 0)
-        ps = [p.data for p, _ in rest]
-        bs = [self._sam_buffer(id(p), p) for p, _ in rest]
-        hip.sam_perturb_multi(ps, [g for _, g in rest], bs, state)
+        ps = [p.data for _, p, _ in rest]
+        bs = [self._sam_buffer(id(p), p) for _, p, _ in rest]
+        hip.sam_perturb_multi(ps, [g for _, _, g in rest], bs, state)
         self._sam_record = ([(store, backup) for store, _, _, backup in jobs], ps, bs)
         for group in self.param_groups:  # the first pass's gradients: the applied gradient is the second pass's alone
             for p in group["params"]:
@@ -904,16 +825,13 @@ class AdamW(torch.optim.Optimizer):
         """The weights of before ``perturb()`` back, bit for bit.  ``images``: through the forms that rewrite the bf16 shadow / the plane
         images from the restored values (an update that may write nothing follows, and stamps them); otherwise one multi-tensor copy
         (the update that follows rewrites them)."""
-        from . import engine
         layer_jobs, ps, bs = self._sam_record
         if not images:
             hip.sam_restore_multi([store.flat for store, _ in layer_jobs] + ps, [b for _, b in layer_jobs] + bs)
         else:
             for store, backup in layer_jobs:
-                w = store.weights
-                shadow = engine.shadow_for_update(w)
-                mats = engine.planes_for_update(w, keep_read_mark=True) if shadow is None else None
-                if mats is not None and store.flat.numel() % 4 == 0:
+                shadow, mats = self._images(store, keep_read_mark=True)
+                if mats is not None:
                     hip.sam_restore_planes(store.flat, backup, mats)
                 else:
                     hip.sam_restore(store.flat, backup, p_bf16=shadow)
@@ -931,20 +849,81 @@ class AdamW(torch.optim.Optimizer):
             engine.invalidate_weight_images()
 
     # -- the step ------------------------------------------------------------------------------------------------
+    def _collect(self):
+        """What a step updates right now, found ONCE for ``step()``, the device-schedule path and ``perturb()`` (so that all three
+        mean the same tensors): -> (layers, rest).  ``layers``: ``(li, plan, store)`` of every encoder layer on the one-launch path
+        -- it has a plan, its store is valid, and every parameter's ``.grad`` is its view of the store's flat gradient buffer.
+        ``rest``: ``(group, parameter, contiguous gradient)`` of every other parameter with a gradient, in group order.  Layers a
+        backward pass has already updated (``_early``; only with ``overlap=True``) are in neither.  Touches no optimizer state and no
+        counter; what happens with the result is the caller's."""
+        done, layers = set(), []
+        enc = self._encoder
+        if enc is not None and enc._stores is not None:
+            if len(self._layer_group) != len(enc.layer):
+                self._map_layers()
+            for li, layer in enumerate(enc.layer):
+                ps = layer.ordered_params()
+                if li in self._early:
+                    done.update(id(p) for p in ps)
+                    continue
+                store = enc._stores[li]
+                plan = self._plan(li, store)
+                if plan is None or store.grad is None or not store.valid(layer):
+                    continue
+                lo = store.grad.data_ptr()
+                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
+                       for i, p in enumerate(ps)):
+                    layers.append((li, plan, store))
+                    done.update(id(p) for p in ps)
+        rest = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None or id(p) in done:
+                    continue
+                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
+                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
+                if not p.is_contiguous():
+                    raise RuntimeError("non-contiguous parameter")
+                rest.append((group, p, p.grad if p.grad.is_contiguous() else p.grad.contiguous()))
+        return layers, rest
+
+    def _tensor_state(self, p):
+        """``state[p]`` of a tensor updated on its own, its moments (and average) made at the first update."""
+        stt = self.state[p]
+        if "exp_avg" not in stt:
+            stt["exp_avg"], stt["exp_avg_sq"], stt["step"] = torch.zeros_like(p), torch.zeros_like(p), 0
+        if self.ema_decay > 0.0 and "ema" not in stt:  # (with exp_avg, or behind a checkpoint written without averages: they start now)
+            stt["ema"], stt["ema_step"] = torch.zeros_like(p), 0
+        return stt
+
+    _NORM_ATTRS = {"clip": ("_clip_state", "last_grad_norm", "skipped_steps", "_clip_partials"),
+                   "sam": ("_sam_state", "last_sam_norm", "sam_skipped", "_sam_partials")}
+
+    def _grad_sqnorm(self, which: str, grads):
+        """The device norm state of clipping ("clip") or of perturb() ("sam") -- 4 floats a finalize kernel writes, a 0-dim view of
+        the norm in them, an int32 counter of non-finite norms, doubles for the partial sums: made on the gradients' device, the
+        partials grown as needed -- and the sums of squares of ``grads`` launched into it.
+        -> (partial sums, state, counter): what ``hip.grad_clip_finalize`` / ``hip.sam_finalize`` take."""
+        s_state, s_norm, s_count, s_part = self._NORM_ATTRS[which]
+        dev = grads[0].device
+        state = getattr(self, s_state)
+        if state is None or state.device != dev:
+            state = torch.zeros(4, dtype=torch.float32, device=dev)
+            setattr(self, s_state, state)
+            setattr(self, s_norm, state[0])
+            setattr(self, s_count, torch.zeros((), dtype=torch.int32, device=dev))
+            setattr(self, s_part, None)
+        slots = hip.grad_sqnorm_slots(grads)
+        partials = getattr(self, s_part)
+        if partials is None or partials.numel() < slots:
+            partials = torch.empty(slots, dtype=torch.float64, device=dev)
+            setattr(self, s_part, partials)
+        return hip.grad_sqnorm(grads, partials), state, getattr(self, s_count)
+
     def _clip_launch(self, grads):
         """Norm + finalize over the gradients this step applies, on the stream of the updates that follow; -> the device state."""
-        dev = grads[0].device
-        if self._clip_state is None or self._clip_state.device != dev:
-            self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
-            self.last_grad_norm = self._clip_state[0]
-            self.skipped_steps = torch.zeros((), dtype=torch.int32, device=dev)
-            self._clip_partials = None
-        slots = hip.grad_sqnorm_slots(grads)
-        if self._clip_partials is None or self._clip_partials.numel() < slots or self._clip_partials.device != dev:
-            self._clip_partials = torch.empty(slots, dtype=torch.float64, device=dev)
-        part = hip.grad_sqnorm(grads, self._clip_partials)
-        hip.grad_clip_finalize(part, self.max_grad_norm, self._clip_state, self.skipped_steps, self.skip_nonfinite)
-        return self._clip_state
+        partials, state, skipped = self._grad_sqnorm("clip", grads)
+        return hip.grad_clip_finalize(partials, self.max_grad_norm, state, skipped, self.skip_nonfinite)
 
     def _new_accumulation(self):
         sink = getattr(self._encoder, "_sink", None) if self._encoder is not None else None
@@ -979,80 +958,48 @@ class AdamW(torch.optim.Optimizer):
             if self._schedule_launch():
                 self.host_step()
             return loss
-        done = set()
-        layer_jobs = []  # (layer index, group, store): one launch each
-        enc = self._encoder
-        if enc is not None and enc._stores is not None:
-            if len(self._layer_group) != len(enc.layer):
-                self._map_layers()
-            for li, layer in enumerate(enc.layer):
-                ps = layer.ordered_params()
-                if li in self._early:
-                    done.update(id(p) for p in ps)
-                    continue
-                store = enc._stores[li]
-                group = self._plan(li, store)
-                if group is None or store.grad is None or not store.valid(layer):
-                    continue
-                lo = store.grad.data_ptr()
-                if all(p.grad is not None and p.grad.data_ptr() == lo + 4 * store.offsets[i] and p.grad.is_contiguous()
-                       for i, p in enumerate(ps)):
-                    layer_jobs.append((li, group, store))
-                    done.update(id(p) for p in ps)
+        layers, rest = self._collect()
         self._early = set()
         touched = set()  # layers updated tensor by tensor this step: ONE step counter per layer, shared with the flat path
-        flat_state = self.__dict__.get("_flat_state", {})
-        group_jobs = []  # (group, (step number, EMA update number), [(p, g, exp_avg, exp_avg_sq, ema), ...]): one launch per 48 tensors each
-        for group in self.param_groups:
-            buckets: Dict[int, list] = {}
-            for p in group["params"]:
-                if p.grad is None or id(p) in done:
-                    continue
-                if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
-                    raise RuntimeError("mtvaf_amd.optim.AdamW updates dense fp32 parameters on the MI355X only")
-                stt = self.state[p]
-                if "exp_avg" not in stt:
-                    stt["exp_avg"], stt["exp_avg_sq"], stt["step"] = torch.zeros_like(p), torch.zeros_like(p), 0
-                if ema_on and "ema" not in stt:  # (with exp_avg, or behind a checkpoint written without averages: they start now)
-                    stt["ema"], stt["ema_step"] = torch.zeros_like(p), 0
-                li = self._param_layer.get(id(p))
-                fst = flat_state.get(("layer", li)) if li is not None else None
-                ema_no = -1
-                if fst is not None and stt["step"] is fst["step_t"]:
-                    # moments live in the layer's flat buffers (views): this tensor-by-tensor update advances the layer's counter
-                    step_no = fst["step"] + 1
-                    if ema_on:
-                        ema_no = fst["ema_step"]
-                    touched.add(li)
-                else:
-                    if torch.is_tensor(stt["step"]):
-                        stt["step"] = int(stt["step"])
-                    stt["step"] += 1
-                    step_no = stt["step"]
-                    if ema_on:
-                        ema_no = stt["ema_step"] = int(stt["ema_step"])
-                        stt["ema_step"] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                if not p.is_contiguous():
-                    raise RuntimeError("non-contiguous parameter")
-                buckets.setdefault((step_no, ema_no), []).append((p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
-            group_jobs.extend((group, nos, items) for nos, items in buckets.items())
+        # (id(group), step number, EMA update number) -> (group, [(p, g, exp_avg, exp_avg_sq, ema), ...]): one launch per 48 tensors each
+        group_jobs: Dict[tuple, tuple] = {}
+        for group, p, g in rest:
+            stt = self._tensor_state(p)
+            li = self._param_layer.get(id(p))
+            fst = self._flat_state.get(("layer", li)) if li is not None else None
+            ema_no = -1
+            if fst is not None and stt["step"] is fst["step_t"]:
+                # moments live in the layer's flat buffers (views): this tensor-by-tensor update advances the layer's counter
+                step_no = fst["step"] + 1
+                if ema_on:
+                    ema_no = fst["ema_step"]
+                touched.add(li)
+            else:
+                if torch.is_tensor(stt["step"]):
+                    stt["step"] = int(stt["step"])
+                stt["step"] += 1
+                step_no = stt["step"]
+                if ema_on:
+                    ema_no = stt["ema_step"] = int(stt["ema_step"])
+                    stt["ema_step"] += 1
+            group_jobs.setdefault((id(group), step_no, ema_no), (group, []))[1].append(
+                (p, g, stt["exp_avg"], stt["exp_avg_sq"], stt["ema"] if ema_on else None))
         clip = None
         if clipping:
             # every gradient about to be applied, each once: a layer's flat gradient buffer stands for its 16 views.  The launches
             # go to the stream of the updates below, behind the producers of every gradient
-            grads = [store.grad for _, _, store in layer_jobs] + [i[1] for _, _, items in group_jobs for i in items]
+            grads = [store.grad for _, _, store in layers] + [g for _, _, g in rest]
             if grads:
                 clip = self._clip_launch(grads)
-        for li, group, store in layer_jobs:
-            self._update_layer_flat(li, group, store, clip=clip)
-        for group, (step_no, ema_no), items in group_jobs:
+        for li, plan, store in layers:
+            self._update_layer(li, plan, store, clip=clip)
+        for (_, step_no, ema_no), (group, items) in group_jobs.items():
             b1, b2 = group["betas"]
             hip.adamw_multi([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
                             float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], step_no, clip=clip,
                             **(dict(ema=[i[4] for i in items], ema_omd=self._ema_omd(ema_no)) if ema_on else {}))
         for li in touched:
-            fst = flat_state[("layer", li)]
+            fst = self._flat_state[("layer", li)]
             fst["step"] += 1
             fst["step_t"].fill_(fst["step"])
             if ema_on:
@@ -1183,14 +1130,21 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
             if "image_model" in n:
                 p.requires_grad = False
     on_gpu = any(p.is_cuda for g in groups for p in g["params"])
-    max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)  # 0: unchanged, the reference does not clip (train.py:620-625)
+    number = lambda name, default=0.0: float(getattr(args, name, default) or default)
+    max_grad_norm = number("max_grad_norm")  # 0: unchanged, the reference does not clip (train.py:620-625)
     track_grad_norm = bool(getattr(args, "track_grad_norm", False))
-    ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)  # 0: unchanged, the reference keeps no averaged weights
+    ema_decay = number("ema_decay")  # 0: unchanged, the reference keeps no averaged weights
     ema_warmup = bool(getattr(args, "ema_warmup", True))
     # args.device_schedule (default off): lr factor, bias corrections and EMA decay of every step as a table on the device, read by
     # the *_sched kernels -- the optimizer step can then be captured (GraphedTrainStep(model, batch, optimizer=opt)); updates after
     # the backward pass (overlap=False), and the scheduler returned only mirrors the table for readers of group["lr"]
     device_schedule = bool(getattr(args, "device_schedule", False))
+    # args.adv_eps > 0 (default 0: nothing changes): adversarial training on the embedding output (mtvaf_amd.adversarial,
+    # DESIGN.md 4.23; args.adv_norm, args.adv_steps, args.adv_weight).  args.sam_rho > 0 (default 0: nothing changes):
+    # sharpness-aware minimisation
+    adv_eps, sam_rho = number("adv_eps"), number("sam_rho")
+    accum = int(getattr(args, "gradient_accumulation_steps", 1) or 1)
+    grad_sync = getattr(args, "grad_sync", None)
     warmup_steps = getattr(args, "warmup_ratio", 0.01) * train_num_steps
     if device_schedule and not on_gpu:
         raise ValueError("build_optimizer: device_schedule is implemented by the gfx950 AdamW kernels; the model is not on the GPU")
@@ -1198,28 +1152,26 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         # the path's own optimizer kernels.  Updates from inside the backward pass only when every backward is followed by a
         # step (gradient_accumulation_steps == 1: train.py:616-625 steps every `accum` backward passes)
         overlap, fused_steps = accumulation_plan(args)
-        # args.adv_eps > 0 (default 0: nothing changes): adversarial training on the embedding output (mtvaf_amd.adversarial,
-        # DESIGN.md 4.23; args.adv_norm, args.adv_steps, args.adv_weight).  One step is 1 + adv_steps backward passes: on the
-        # fallback the update waits for step(); with args.fused_accumulation they are the passes of the fused accumulation.  The
-        # Adversary is left in `optimizer.adversary`; the trainer calls its step(**batch) in place of model(**batch).loss.backward()
-        adv_passes = 1 + int(getattr(args, "adv_steps", 1) or 1) if float(getattr(args, "adv_eps", 0.0) or 0.0) > 0.0 else 0
+        # One adversarial step is 1 + adv_steps backward passes: on the fallback the update waits for step(); with
+        # args.fused_accumulation they are the passes of the fused accumulation.  The Adversary is left in `optimizer.adversary`;
+        # the trainer calls its step(**batch) in place of model(**batch).loss.backward()
+        adv_passes = 1 + int(getattr(args, "adv_steps", 1) or 1) if adv_eps > 0.0 else 0
         if adv_passes:
-            if int(getattr(args, "gradient_accumulation_steps", 1) or 1) > 1:
+            if accum > 1:
                 raise ValueError("build_optimizer: adv_eps > 0 with gradient_accumulation_steps > 1 is not supported")
-            if getattr(args, "grad_sync", None) is not None or device_schedule:
+            if grad_sync is not None or device_schedule:
                 raise ValueError("build_optimizer: adv_eps > 0 is single-GPU and eager (no grad_sync, no device_schedule)")
             if bool(getattr(args, "fused_accumulation", False)):
                 fused_steps = adv_passes  # (overlap stays what the plan gave a step of one micro-batch)
             else:
                 overlap = False
         extra = {"accumulation_steps": fused_steps} if fused_steps > 1 else {}
-        # args.sam_rho > 0 (default 0: nothing changes): sharpness-aware minimisation.  The update waits for step(),
-        # as under clipping; the trainer calls mtvaf_amd.sam.SharpnessAware(model, opt).step(**batch) in place of its three lines
-        sam_rho = float(getattr(args, "sam_rho", 0.0) or 0.0)
+        # Under SAM the update waits for step(), as under clipping; the trainer calls
+        # mtvaf_amd.sam.SharpnessAware(model, opt).step(**batch) in place of its three lines
         if sam_rho > 0.0:
-            if int(getattr(args, "gradient_accumulation_steps", 1) or 1) > 1 or adv_passes:
+            if accum > 1 or adv_passes:
                 raise ValueError("build_optimizer: sam_rho > 0 with gradient_accumulation_steps > 1 or adv_eps > 0 is not supported")
-            if getattr(args, "grad_sync", None) is not None or device_schedule:
+            if grad_sync is not None or device_schedule:
                 raise ValueError("build_optimizer: sam_rho > 0 is single-GPU and eager (no grad_sync, no device_schedule)")
             overlap = False
             extra["sam_rho"] = sam_rho
@@ -1227,9 +1179,8 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
             overlap = False
             extra["device_schedule"] = schedule_table(linear_warmup_factor(warmup_steps, train_num_steps), train_num_steps,
                                                       (0.9, 0.999), ema_decay, ema_warmup)  # (AdamW's default betas, as below)
-        opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=getattr(args, "grad_sync", None),
-                    max_grad_norm=max_grad_norm, track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                    **extra)
+        opt = AdamW(groups, lr=args.lr, model=model, overlap=overlap, grad_sync=grad_sync, max_grad_norm=max_grad_norm,
+                    track_grad_norm=track_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup, **extra)
         if adv_passes:
             from .adversarial import from_args
             opt.adversary = from_args(model, args, optimizer=opt)
@@ -1242,9 +1193,9 @@ def build_optimizer(model: torch.nn.Module, args, train_num_steps: int):
         if ema_decay > 0.0:
             raise ValueError("build_optimizer: ema_decay is implemented by the gfx950 AdamW kernels; the CPU fallback "
                              "(torch.optim.AdamW) would ignore it")
-        if float(getattr(args, "adv_eps", 0.0) or 0.0) > 0.0:
+        if adv_eps > 0.0:
             raise ValueError("build_optimizer: adv_eps is implemented by the gfx950 kernels; the model is not on the GPU")
-        if float(getattr(args, "sam_rho", 0.0) or 0.0) > 0.0:
+        if sam_rho > 0.0:
             raise ValueError("build_optimizer: sam_rho is implemented by the gfx950 AdamW kernels; the model is not on the GPU")
         opt = torch.optim.AdamW(groups, lr=args.lr)
     sched = linear_schedule_with_warmup(opt, warmup_steps, train_num_steps)

@@ -12,6 +12,7 @@ import torch
 
 import ema_cases as EC
 import params as P
+from optim_trace import recorded_updates as _recorded_updates
 from test_model_gpu import DEV, LABELS, _prompt_inputs, hf_config, make_args
 
 pytestmark = pytest.mark.gpu
@@ -301,27 +302,6 @@ def _mode(mode):
     finally:
         engine.F32_PLANES = was_p
         hip.set_compute_dtype(was_c)
-
-
-@contextlib.contextmanager
-def _recorded_updates():
-    """The wrappers the optimizer calls, recorded as (wrapper, with average, with shadow, with clip state)."""
-    from mtvaf_amd import hip
-    calls = []
-    real = {k: getattr(hip, k) for k in ("adamw", "adamw_planes", "adamw_multi", "swap_f32")}
-
-    def wrap(name):
-        def f(*a, **k):
-            calls.append((name, k.get("ema") is not None, k.get("p_bf16") is not None, k.get("clip") is not None, "ema" in k))
-            return real[name](*a, **k)
-        return f
-    try:
-        for k in real:
-            setattr(hip, k, wrap(k))
-        yield calls
-    finally:
-        for k, f in real.items():
-            setattr(hip, k, f)
 
 
 def _model():

@@ -1,6 +1,5 @@
 """Sharpness-aware minimisation on the GPU: the mtvaf_sam_* kernels against the float64 restatement of tests/sam_cases.py, the
 weight-image cache under AdamW.perturb() / step(), and SharpnessAware.step against the same step built from public pieces."""
-import contextlib
 import ctypes
 
 import numpy as np
@@ -8,6 +7,7 @@ import pytest
 import torch
 
 import sam_cases as C
+from optim_trace import recorded as _recorded
 from test_ema_gpu import _batch, _mode, _model
 from test_js_consistency_gpu import _batch as span_batch, _build as span_build
 from test_ops_gpu import DEV, hip  # noqa: F401  (fixture)
@@ -469,28 +469,6 @@ def test_refusals():
         build_optimizer(m, args, 10)
     args.gradient_accumulation_steps, args.sam_rho = 1, 0.0
     assert build_optimizer(m, args, 10)[0].sam_rho == 0.0
-
-
-@contextlib.contextmanager
-def _recorded(hip_mod):
-    """Every wrapper of mtvaf_amd.hip that launches for the optimizer, recorded by name."""
-    names = [k for k in dir(hip_mod) if k.startswith(("adamw", "sam_", "grad_sqnorm", "grad_clip", "swap_f32"))
-             and callable(getattr(hip_mod, k)) and k != "grad_sqnorm_slots"]
-    real = {k: getattr(hip_mod, k) for k in names}
-    calls = []
-
-    def wrap(name):
-        def f(*a, **k):
-            calls.append(name)
-            return real[name](*a, **k)
-        return f
-    try:
-        for k in real:
-            setattr(hip_mod, k, wrap(k))
-        yield calls
-    finally:
-        for k, f in real.items():
-            setattr(hip_mod, k, f)
 
 
 def test_default_is_the_step_it_was(hip):
