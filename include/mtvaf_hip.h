@@ -463,6 +463,31 @@ int mtvaf_js_consistency_fwd(const float* x, const float* y, const uint8_t* mask
                              int M, int C, float scale, mtvaf_stream_t stream);
 int mtvaf_js_consistency_bwd(const float* grad_out, float scale, const float* x, const float* y, const uint8_t* mask,
                              float* dx, float* dy, int B, int M, int C, mtvaf_stream_t stream);
+/* Token-level divergence between the emissions of two passes over one batch -- the consistency term of R-Drop and of a
+ * plain / cut pair for the tagger (csrc/consistency.hip).  x, y [N,C] fp32 contiguous, N = B*S rows
+ * (they may be the same buffer: the value is then exactly 0); mask [N] u8 (non-zero = live) or NULL = every row live.  Per
+ * live row, with u = x/T, v = y/T (T = temperature), lp = log_softmax(u), lq = log_softmax(v), p = exp(lp), q = exp(lq):
+ *   kind 0 (symmetric KL)     L = 1/2 sum_c (p_c - q_c)(lp_c - lq_c)                      >= 0, unbounded
+ *   kind 1 (Jensen-Shannon)   L = 1/2 sum_c p_c (lp_c - lm_c) + 1/2 sum_c q_c (lq_c - lm_c),  lm = log((p + q) / 2);  0 <= L <= log 2
+ *   loss[0] = scale * (sum of L over the live rows) / D
+ * reduction 0 (token mean): D = the number of live rows, counted on the device; D = 0 gives loss 0 and all-zero gradients.
+ * reduction 1 (batch mean): D = B (B is read in this mode only).  row_ws [N] receives every row's L, 0 on masked rows.
+ * The backward recomputes everything from x, y and mask (nothing is kept from the forward) and writes every element of
+ * dx, dy [N,C], exact zeros on masked rows:  with d = lp - lq, A = sum_c p_c d_c, a = lp - lm, Abar = sum_c p_c a_c
+ *   kind 0   dL/du_c = 1/2 [p_c (d_c - A) + p_c - q_c]        kind 1   dL/du_c = 1/2 p_c (a_c - Abar)
+ *   dL/dx = dL/du / T, the y side with the roles swapped, all of it times *grad_out (device) * scale / D.
+ * Contract: evaluated in log space with the row maximum removed -- logits of magnitude 1e4 and rows whose two distributions
+ * put all mass on different tags give a finite value and finite gradients (kind 0), a value <= log 2 (kind 1); masked rows
+ * are never read and may hold NaN; no floating-point atomics -- the row values are added in double in a fixed order by one
+ * finishing block, so the same inputs give the same bits; no host sync, no read-back.  N >= 1, 1 <= C <= 64
+ * (MTVAF_ERR_SHAPE); kind and reduction 0 or 1, finite temperature > 0, B >= 1 with reduction 1, no NULL but mask
+ * (MTVAF_ERR_ARG); all checked before any launch. */
+int mtvaf_token_divergence_fwd(const float* x, const float* y, const uint8_t* mask, float* loss, float* row_ws, int N,
+                               int C, int kind, float temperature, int reduction, int B, float scale,
+                               mtvaf_stream_t stream);
+int mtvaf_token_divergence_bwd(const float* grad_out, const float* x, const float* y, const uint8_t* mask, float* dx,
+                               float* dy, int N, int C, int kind, float temperature, int reduction, int B, float scale,
+                               mtvaf_stream_t stream);
 /* Candidate spans at eval / predict time: the eval branch of models/utils.py::span_annotate_candidates (:451-521) and
  * the host round trip around it (modules/train.py:382-410) as one launch, no host read-back.  Start logit of (b,s) at
  * logits[(b*S+s)*ld], end logit one element later (the binary_affine output, ld = 2).  word_index [B,S] int32: token

@@ -1848,6 +1848,42 @@ class JSConsistencyFunction(torch.autograd.Function):
         return dx.to(tx), dy.to(ty), None, None
 
 
+class TokenDivergenceFunction(torch.autograd.Function):
+    """The token-level divergence between the emissions of two passes over one batch (include/mtvaf_hip.h,
+    mtvaf_token_divergence_*): ``x``, ``y`` [B,S,C] or [N,C], ``mask`` [B,S] / [N] (non-zero = live) or
+    None; per live token the symmetric KL (``kind="sym_kl"``, R-Drop's term) or the Jensen-Shannon divergence (``"js"``, at most
+    log 2) between softmax(x / temperature) and softmax(y / temperature); ``reduction="token_mean"`` divides the sum by the live
+    tokens (counted on the device; none: 0), ``"batch_mean"`` by B (1 for [N,C]); times ``scale`` -> 0-dim fp32.  Gradients to both
+    inputs in their own dtypes, recomputed from the inputs; masked rows are never read and get exact zeros."""
+
+    @staticmethod
+    def forward(ctx, x, y, mask=None, kind="sym_kl", temperature=1.0, reduction="token_mean", scale=1.0):
+        if x.dim() not in (2, 3) or x.shape != y.shape:
+            raise ValueError(f"TokenDivergenceFunction: x {tuple(x.shape)} and y {tuple(y.shape)} must be the same [B,S,C] or [N,C]")
+        if kind not in hip.TOKEN_DIVERGENCE_KINDS or reduction not in hip.TOKEN_DIVERGENCE_REDUCTIONS:
+            raise ValueError(f"TokenDivergenceFunction: kind={kind!r} (expected one of {sorted(hip.TOKEN_DIVERGENCE_KINDS)}), "
+                             f"reduction={reduction!r} (expected one of {sorted(hip.TOKEN_DIVERGENCE_REDUCTIONS)})")
+        C = x.shape[-1]
+        B = x.shape[0] if x.dim() == 3 else 1
+        xc, yc = x.contiguous().float().view(-1, C), y.contiguous().float().view(-1, C)
+        N = xc.shape[0]
+        if mask is not None and mask.numel() != N:
+            raise ValueError(f"TokenDivergenceFunction: mask {tuple(mask.shape)} does not fit x {tuple(x.shape)}")
+        m8 = None if mask is None else mask.ne(0).contiguous().view(torch.uint8).view(-1)
+        loss, row = _empty(1, like=xc), _empty(N, like=xc)
+        how = (hip.TOKEN_DIVERGENCE_KINDS[kind], float(temperature), hip.TOKEN_DIVERGENCE_REDUCTIONS[reduction], B, float(scale))
+        hip.token_divergence_fwd(xc, yc, m8, loss, row, *how)
+        ctx.stash = (xc, yc, m8, how, x.shape, x.dtype, y.dtype)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        xc, yc, m8, how, shape, tx, ty = ctx.stash
+        dx, dy = torch.empty_like(xc), torch.empty_like(yc)
+        hip.token_divergence_bwd(gout.contiguous().view(1).float(), xc, yc, m8, dx, dy, *how)
+        return dx.view(shape).to(tx), dy.view(shape).to(ty), None, None, None, None, None
+
+
 class MaskMulFunction(torch.autograd.Function):
     """Cutoff augmentation apply (modules/augument.py:99-159): x * row_keep[b,s] * col_keep[b,:]."""
 

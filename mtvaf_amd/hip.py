@@ -111,6 +111,8 @@ _SIGS = {
     "mtvaf_ce_bwd": (c_int, [P, P, P, P, P, I, I, P]),
     "mtvaf_js_consistency_fwd": (c_int, [P, P, P, P, P, I, I, I, F, P]),
     "mtvaf_js_consistency_bwd": (c_int, [P, F, P, P, P, P, P, I, I, I, P]),
+    "mtvaf_token_divergence_fwd": (c_int, [P, P, P, P, P, I, I, I, F, I, I, F, P]),
+    "mtvaf_token_divergence_bwd": (c_int, [P, P, P, P, P, P, I, I, I, F, I, I, F, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_span_counts": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
@@ -829,6 +831,35 @@ def js_consistency_bwd(gout, scale, x, y, mask_u8, dx, dy):
            tuple(mask_u8.shape) == (B, M) and mask_u8.is_contiguous())), (x.shape, y.shape, dx.shape, dy.shape)
     _ck(lib().mtvaf_js_consistency_bwd(_p(gout), float(scale), _p(x), _p(y), _p(mask_u8), _p(dx), _p(dy), B, M, C, _st()),
         "mtvaf_js_consistency_bwd")
+
+
+TOKEN_DIVERGENCE_KINDS = {"sym_kl": 0, "js": 1}
+TOKEN_DIVERGENCE_REDUCTIONS = {"token_mean": 0, "batch_mean": 1}
+
+
+def _token_divergence_mask(mask_u8, N):
+    assert mask_u8 is None or (mask_u8.dtype == torch.uint8 and mask_u8.numel() == N and mask_u8.is_contiguous()
+                               and mask_u8.is_cuda), (None if mask_u8 is None else (mask_u8.dtype, tuple(mask_u8.shape)), N)
+
+
+def token_divergence_fwd(x, y, mask_u8, loss, row_ws, kind, temperature, reduction, B, scale):
+    """x, y [N,C] fp32 contiguous, mask_u8 [N] or None; kind / reduction are the ABI's integers (TOKEN_DIVERGENCE_*), B the
+    divisor of the batch mean; loss [1] and row_ws [N] are written."""
+    _f32(x, y, loss, row_ws)
+    N, C = x.shape
+    assert y.shape == x.shape and row_ws.numel() >= N, (x.shape, y.shape, row_ws.shape)
+    _token_divergence_mask(mask_u8, N)
+    _ck(lib().mtvaf_token_divergence_fwd(_p(x), _p(y), _p(mask_u8), _p(loss), _p(row_ws), N, C, int(kind), float(temperature),
+                                         int(reduction), int(B), float(scale), _st()), "mtvaf_token_divergence_fwd")
+
+
+def token_divergence_bwd(gout, x, y, mask_u8, dx, dy, kind, temperature, reduction, B, scale):
+    _f32(gout, x, y, dx, dy)
+    N, C = x.shape
+    assert y.shape == x.shape == dx.shape == dy.shape, (x.shape, y.shape, dx.shape, dy.shape)
+    _token_divergence_mask(mask_u8, N)
+    _ck(lib().mtvaf_token_divergence_bwd(_p(gout), _p(x), _p(y), _p(mask_u8), _p(dx), _p(dy), N, C, int(kind), float(temperature),
+                                         int(reduction), int(B), float(scale), _st()), "mtvaf_token_divergence_bwd")
 
 
 SPAN_PROPOSE_MAX_S, SPAN_PROPOSE_MAX_N = 512, 32

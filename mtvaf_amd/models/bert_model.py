@@ -39,6 +39,22 @@ def _crf_reduction(args):
     return reduction
 
 
+def _consistency_options(args):
+    """The switches of TVNetSAModel2.forward_consistent, checked: args.consistency_weight (0), consistency_ce (True),
+    consistency_level ("token" | "chain"), consistency_kind ("sym_kl" | "js"), consistency_temperature (1.0), consistency_aug
+    (None | "span_cutoff" | "token_cutoff" | "dim_cutoff")."""
+    opt = {"weight": float(_arg(args, "consistency_weight", 0.0) or 0.0), "ce": bool(_arg(args, "consistency_ce", True)),
+           "level": _arg(args, "consistency_level", "token"), "kind": _arg(args, "consistency_kind", "sym_kl"),
+           "temperature": float(_arg(args, "consistency_temperature", 1.0)), "aug": _arg(args, "consistency_aug", None)}
+    for name, allowed in (("level", ("token", "chain")), ("kind", ("sym_kl", "js")),
+                          ("aug", (None, "span_cutoff", "token_cutoff", "dim_cutoff"))):
+        if opt[name] not in allowed:
+            raise ValueError(f"args.consistency_{name}={opt[name]!r}: expected one of {allowed}")
+    if not opt["temperature"] > 0:
+        raise ValueError(f"args.consistency_temperature={opt['temperature']!r}: expected a positive number")
+    return opt
+
+
 def _entity_scorer(args, label_list):
     """args.score_entities: True (the "seqeval" scheme) or a scheme name -> an `mtvaf_amd.metrics.EntityScorer` over the
     trainer's label map (label_list enumerated from 1, MTVAF_training.py:369); unset / False -> None."""
@@ -231,6 +247,7 @@ class TVNetSAModel2(nn.Module):
         self.fc = nn.Linear(hidden, self.num_labels)
         self.dropout = nn.Dropout(0.1)
         _crf_reduction(args)  # (a misspelt reduction is an error here, not at the first step)
+        _consistency_options(args)  # (the same for the switches of forward_consistent)
         # args.score_entities: every forward with labels adds its entity counts to model.entity_scorer on the device (one small
         # launch behind the Viterbi kernel, on its tags); without the switch nothing is launched
         self.entity_scorer = _entity_scorer(args, label_list)
@@ -254,19 +271,8 @@ class TVNetSAModel2(nn.Module):
         are the tags of the word columns and ``self.last_word_index`` keeps the index.  Without args.word_pooling the map is not
         read and the method runs the code it always ran."""
         word_mode = self._word_mode(token_to_word)
-        bsz = input_ids.size(0)
-        img_tag_loss = 0
-        if _arg(self.args, "use_prefix"):
-            prefix_guids, img_tag_loss, aux_img_tag_loss = _on_second_stream(
-                lambda: self.get_visual_prompt(images, aux_imgs, imagelabel), (images, aux_imgs, imagelabel),
-                join=_arg(self.args, "vao"))  # the VAO losses are consumed on the main stream right away
-            img_tag_loss = img_tag_loss if _arg(self.args, "noauxloss") else img_tag_loss + sum(aux_img_tag_loss)
-            prefix_len = prefix_guids[0][0].shape[2]
-            prefix_mask = torch.ones((bsz, prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
-            prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
-        else:
-            prefix_guids = None
-            prompt_attention_mask = attention_mask
+        prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
+                                                                                  aux_imgs)
         # The attention maps are made on request only (the reference hard-codes output_attentions=True, bert_model.py:496-502, and
         # never reads them): args.output_attentions (True or layer indices) fills TokenClassifierOutput.attentions,
         # args.output_prefix_mass fills self.last_prefix_mass [L,B,NH,S] -- each token's attention on the visual slots --
@@ -278,22 +284,64 @@ class TVNetSAModel2(nn.Module):
                                 return_dict=True, layer_mix=self.layer_mix)
         self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
         hidden = _head_state(bert_output, self.layer_mix)
+        index = None
         if word_mode is not None:
-            # the word axis: one launch builds the index, one pools (fp32, the dtype fc reads in every compute mode); from here on
-            # the mask, the labels and the constraint sets are those of the word columns
-            from ..words import build_word_index, word_allowed, word_labels
-            index = build_word_index(attention_mask, token_to_word, _arg(self.args, "max_words", None))
-            self.last_word_index = index
-            hidden = engine.WordPoolFunction.apply(hidden, index, word_mode)
-            attention_mask = index.word_mask
-            labels = None if labels is None else word_labels(labels, index)
-            allowed_tags = None if allowed_tags is None else word_allowed(allowed_tags, index)
-        sequence_output = engine.dropout(hidden, self.dropout.p, self.training)
-        emissions = engine.LinearFunction.apply(sequence_output, self.fc.weight, self.fc.bias, False)
+            index, attention_mask, labels, allowed_tags = self._word_targets(attention_mask, token_to_word, labels, allowed_tags)
+        emissions = self._emissions(hidden, index, word_mode)
         mask_u8 = attention_mask.to(torch.uint8)
-        # Viterbi paths: device kernel + async packed copy; the list materialises on first use (no mid-step sync).
-        # One wavefront per sentence is all the parallelism Viterbi and the CRF forward algorithm have, so the two
-        # run side by side (second stream) instead of back to back.
+        logits, decoded = self._decode(emissions, mask_u8, labels)
+        # args.output_tag_marginals fills self.last_tag_marginals [B,S,num_labels] -- posterior tag probabilities, zeros on
+        # padding -- from the marginals kernels; without the switch the step launches nothing for them.
+        self.last_tag_marginals = self.crf.marginals(emissions.detach(), mask_u8) \
+            if _arg(self.args, "output_tag_marginals") else None
+        loss = None
+        if labels is not None or allowed_tags is not None:
+            loss = self._crf_nll(emissions, mask_u8, labels, allowed_tags)
+            extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
+            if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
+                loss = loss + extra
+        loss = self._posterior_terms(loss, emissions, mask_u8, labels, logits, decoded)
+        if decoded is not None:
+            # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
+            # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)
+            torch.cuda.current_stream().wait_event(decoded)
+        return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
+
+    # ---- the pieces of `forward`, shared with `forward_consistent` -----------------------------------------------------
+    def _prompt_prologue(self, input_ids, attention_mask, imagelabel, images, aux_imgs):
+        """-> (prefix_guids, img_tag_loss, prompt_attention_mask): the visual prompt, its VAO loss (args.vao; else 0) and the attention
+        mask extended over the prompt's slots; (None, 0, attention_mask) without ``use_prefix``."""
+        if not _arg(self.args, "use_prefix"):
+            return None, 0, attention_mask
+        prefix_guids, img_tag_loss, aux_img_tag_loss = _on_second_stream(
+            lambda: self.get_visual_prompt(images, aux_imgs, imagelabel), (images, aux_imgs, imagelabel),
+            join=_arg(self.args, "vao"))  # the VAO losses are consumed on the main stream right away
+        img_tag_loss = img_tag_loss if _arg(self.args, "noauxloss") else img_tag_loss + sum(aux_img_tag_loss)
+        prefix_len = prefix_guids[0][0].shape[2]
+        prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
+        return prefix_guids, img_tag_loss, torch.cat((prefix_mask, attention_mask), dim=1)
+
+    def _word_targets(self, attention_mask, token_to_word, labels, allowed_tags):
+        """The word axis: one launch builds the index; from here on the mask, the labels and the constraint sets are those of the
+        word columns.  -> (index, word mask, word labels, word constraint sets)"""
+        from ..words import build_word_index, word_allowed, word_labels
+        index = build_word_index(attention_mask, token_to_word, _arg(self.args, "max_words", None))
+        self.last_word_index = index
+        return (index, index.word_mask, None if labels is None else word_labels(labels, index),
+                None if allowed_tags is None else word_allowed(allowed_tags, index))
+
+    def _emissions(self, hidden, index, word_mode):
+        """The head of one pass: [pool onto the word axis (one launch; fp32, the dtype fc reads in every compute mode) ->] dropout
+        -> fc."""
+        if index is not None:
+            hidden = engine.WordPoolFunction.apply(hidden, index, word_mode)
+        sequence_output = engine.dropout(hidden, self.dropout.p, self.training)
+        return engine.LinearFunction.apply(sequence_output, self.fc.weight, self.fc.bias, False)
+
+    def _decode(self, emissions, mask_u8, labels):
+        """Viterbi paths: device kernel + async packed copy; the list materialises on first use (no mid-step sync).
+        One wavefront per sentence is all the parallelism Viterbi and the CRF forward algorithm have, so the two
+        run side by side (second stream) instead of back to back.  -> (paths, the event behind them on the second stream or None)"""
         if emissions.is_cuda and engine.DW_SIDE_STREAM and emissions.shape[0] * emissions.shape[1] >= 1024:  # host-bound below
             main, side = torch.cuda.current_stream(), engine._side_stream(emissions.device)
             side.wait_stream(main)
@@ -306,28 +354,27 @@ class TVNetSAModel2(nn.Module):
                 decoded.record(side)
             emissions.record_stream(side)
             mask_u8.record_stream(side)
-        else:
-            logits = self.crf.decode_deferred(emissions, mask_u8)
-            if self.entity_scorer is not None and labels is not None:
-                self.entity_scorer.update(logits.device_tags, labels, mask_u8)
-            decoded = None
-        # args.output_tag_marginals fills self.last_tag_marginals [B,S,num_labels] -- posterior tag probabilities, zeros on
-        # padding -- from the marginals kernels; without the switch the step launches nothing for them.
-        self.last_tag_marginals = self.crf.marginals(emissions.detach(), mask_u8) \
-            if _arg(self.args, "output_tag_marginals") else None
-        loss = None
+            return logits, decoded
+        logits = self.crf.decode_deferred(emissions, mask_u8)
+        if self.entity_scorer is not None and labels is not None:
+            self.entity_scorer.update(logits.device_tags, labels, mask_u8)
+        return logits, None
+
+    def _crf_nll(self, emissions, mask_u8, labels, allowed_tags):
+        """-llh of the labels, or without them of the paths ``allowed_tags`` permit (`CRF.partial_llh`), under args.crf_reduction."""
+        reduction = _crf_reduction(self.args)
+        if labels is None:
+            return -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=reduction)
+        if reduction == "mean":
+            return self.crf.nll_mean(emissions, labels, mask=mask_u8)  # = -1 * crf(..., reduction='mean'), bert_model.py:521
+        return -self.crf(emissions, labels, mask=mask_u8, reduction=reduction)
+
+    def _posterior_terms(self, loss, emissions, mask_u8, labels, logits, decoded):
+        """``loss`` plus the weighted risk / MRT / entropy terms of one pass' posterior; fills self.last_crf_*."""
         self.last_crf_risk = None
         self.last_crf_entropy = None
         self.last_crf_mrt = None
         if labels is not None:
-            reduction = _crf_reduction(self.args)
-            if reduction == "mean":
-                loss = self.crf.nll_mean(emissions, labels, mask=mask_u8)  # = -1 * crf(..., reduction='mean'), bert_model.py:521
-            else:
-                loss = -self.crf(emissions, labels, mask=mask_u8, reduction=reduction)
-            extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
-            if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
-                loss = loss + extra
             # args.crf_risk_weight > 0 adds the expected rate of wrong tags under the posterior (CRF.hamming_risk, token_mean) to
             # the loss and keeps it in self.last_crf_risk; at the default 0 the step launches nothing for it.
             risk_weight = _arg(self.args, "crf_risk_weight", 0.0)
@@ -355,11 +402,6 @@ class TVNetSAModel2(nn.Module):
                                                 reduction="mean")
                 self.last_crf_mrt = crf_mrt.detach()
                 loss = loss + mrt_weight * crf_mrt
-        elif allowed_tags is not None:
-            loss = -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=_crf_reduction(self.args))
-            extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
-            if torch.is_tensor(extra) or extra != 0:
-                loss = loss + extra
         # args.crf_entropy_weight != 0 adds weight * the posterior's sequence entropy per unmasked column (CRF.entropy, token_mean)
         # wherever a loss is formed -- positive minimises entropy, negative is a confidence penalty -- and keeps it in
         # self.last_crf_entropy; at the default 0 the step launches nothing for it.
@@ -368,11 +410,108 @@ class TVNetSAModel2(nn.Module):
             crf_entropy = self.crf.entropy(emissions, mask=mask_u8, reduction="token_mean")
             self.last_crf_entropy = crf_entropy.detach()
             loss = loss + entropy_weight * crf_entropy
+        return loss
+
+    # ------------------------------------------------------------------------------------------------
+    def forward_consistent(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
+                           images=None, aux_imgs=None, allowed_tags=None, token_to_word=None, return_parts=False):
+        """One training step's loss with a two-pass consistency term: the same batch goes through the encoder
+        twice -- under two independent dropout masks (R-Drop), or once plain and once cut -- both passes are trained and a
+        divergence between their predictive distributions joins the loss:
+
+            1/2 (nll_1 + nll_2)   [args.consistency_ce = False: nll_1]
+              + args.consistency_weight * divergence  +  alpha * img_tag_loss
+
+        Arguments as ``forward``; ``labels`` or ``allowed_tags`` is required (the nll is ``forward``'s, under args.crf_reduction).
+        The visual prompt -- with args.vao its losses -- is computed once and serves both passes; ``alpha * img_tag_loss`` enters
+        once.  Pass 1 is ``forward``'s pass.  Pass 2 runs the encoder again on the same prompt: in train mode under dropout masks
+        of its own (as two ``forward`` calls draw them), and with args.consistency_aug ("span_cutoff" | "token_cutoff" |
+        "dim_cutoff"; None = plain R-Drop) through `modules.augument.Cutoff` (args.aug_cutoff_ratio): the encoder sees the cut
+        attention mask, while the head, the CRF and the divergence keep ``attention_mask`` -- a CRF needs its prefix mask and a
+        cut column still has a label.
+        args.consistency_level "token" (default): `engine.TokenDivergenceFunction` on the two emission tensors, args.consistency_kind
+        ("sym_kl" | "js"), args.consistency_temperature (1.0), mean over the unmasked tokens.  "chain": `CRF.symmetric_kl` between
+        the two posteriors over whole paths, 'token_mean'.  args.consistency_weight <= 0 (the default 0) skips the divergence; with
+        args.consistency_ce = False as well pass 2 is not run.
+        With args.word_pooling both passes pool onto the word axis and the divergence runs there; with args.layer_mix both read the
+        mix; with args.fused_accumulation the two encoder nodes share the flat gradient buffers.  The Viterbi
+        paths, ``entity_scorer.update``, ``last_*`` and the risk / MRT / entropy terms (args.crf_*_weight) come from pass 1 only.
+        -> ``TokenClassifierOutput(loss, logits=pass-1 paths)``; with ``return_parts`` also a dict: ``nll`` (pass 1), ``nll_2``,
+        ``divergence`` (unweighted, detached), ``emissions``, ``emissions_2`` -- None where a term was not computed."""
+        if labels is None and allowed_tags is None:
+            raise ValueError("forward_consistent forms a loss: it needs labels or allowed_tags")
+        opt = _consistency_options(self.args)
+        two = opt["weight"] > 0 or opt["ce"]
+        # args.fused_accumulation: the two encoder nodes write / add into the flat gradient buffers, as in
+        # TVNetSAModel.forward_with_cutoff; the sink goes back to its setting when that backward ends, or here if anything raises
+        sink = self.bert.encoder.grad_sink if (_arg(self.args, "fused_accumulation") and torch.is_grad_enabled() and two) else None
+        batch = (input_ids, attention_mask, token_type_ids, labels, imagelabel, images, aux_imgs, allowed_tags, token_to_word,
+                 return_parts)
+        if sink is None:
+            return self._consistent_passes(opt, two, *batch)
+        sink.begin_two_node_pass()
+        try:
+            return self._consistent_passes(opt, two, *batch)
+        except BaseException:
+            sink.end_two_node_pass()
+            raise
+
+    def _consistent_passes(self, opt, two, input_ids, attention_mask, token_type_ids, labels, imagelabel, images, aux_imgs, allowed_tags,
+                           token_to_word, return_parts):
+        word_mode = self._word_mode(token_to_word)
+        prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
+                                                                                  aux_imgs)
+        self.bert.encoder.output_prefix_mass = bool(_arg(self.args, "output_prefix_mass"))
+        bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
+                                token_type_ids=token_type_ids, past_key_values=prefix_guids,
+                                output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
+                                return_dict=True, layer_mix=self.layer_mix)
+        self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
+        index = None
+        if word_mode is not None:
+            index, attention_mask, labels, allowed_tags = self._word_targets(attention_mask, token_to_word, labels, allowed_tags)
+        emissions = self._emissions(_head_state(bert_output, self.layer_mix), index, word_mode)
+        mask_u8 = attention_mask.to(torch.uint8)
+        logits, decoded = self._decode(emissions, mask_u8, labels)
+        self.last_tag_marginals = self.crf.marginals(emissions.detach(), mask_u8) \
+            if _arg(self.args, "output_tag_marginals") else None
+        nll = self._crf_nll(emissions, mask_u8, labels, allowed_tags)
+        parts = {"nll": nll, "nll_2": None, "divergence": None, "emissions": emissions, "emissions_2": None}
+        loss = nll
+        if two:
+            self.bert.encoder.output_prefix_mass = False  # (pass 1 filled last_prefix_mass)
+            if opt["aug"] is None:
+                hidden_2 = _head_state(self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
+                                                 token_type_ids=token_type_ids, past_key_values=prefix_guids,
+                                                 output_hidden_states=True, return_dict=True, layer_mix=self.layer_mix),
+                                       self.layer_mix)
+            else:
+                from ..modules.augument import Cutoff
+                cutoff = Cutoff(input_ids=input_ids, token_type_ids=token_type_ids, attention_masks=prompt_attention_mask,
+                                prefix_guids=prefix_guids, args=self.args, model=self.bert, layer_mix=self.layer_mix)
+                hidden_2 = cutoff._training_step_with_cutoff(opt["aug"])[0 if self.layer_mix is None else 2]
+            emissions_2 = self._emissions(hidden_2, index, word_mode)
+            parts["emissions_2"] = emissions_2
+            if opt["ce"]:
+                parts["nll_2"] = self._crf_nll(emissions_2, mask_u8, labels, allowed_tags)
+                loss = 0.5 * (nll + parts["nll_2"])
+            if opt["weight"] > 0:
+                if opt["level"] == "token":  # the weight rides in the kernel
+                    div = engine.TokenDivergenceFunction.apply(emissions, emissions_2, mask_u8, opt["kind"], opt["temperature"],
+                                                               "token_mean", opt["weight"])
+                else:
+                    div = opt["weight"] * self.crf.symmetric_kl(emissions, emissions_2, mask_u8, reduction="token_mean")
+                loss = loss + div
+                if return_parts:
+                    parts["divergence"] = div.detach() / opt["weight"]
+        extra = _arg(self.args, "alpha", 0.0) * img_tag_loss
+        if torch.is_tensor(extra) or extra != 0:
+            loss = loss + extra
+        loss = self._posterior_terms(loss, emissions, mask_u8, labels, logits, decoded)
         if decoded is not None:
-            # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
-            # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)
-            torch.cuda.current_stream().wait_event(decoded)
-        return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
+            torch.cuda.current_stream().wait_event(decoded)  # (as in `forward`: the decode reads the CRF parameters)
+        out = TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
+        return (out, parts) if return_parts else out
 
     # ------------------------------------------------------------------------------------------------
     def _word_mode(self, token_to_word):

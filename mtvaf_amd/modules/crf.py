@@ -612,6 +612,29 @@ class CRF(nn.Module):
                                         q.start_transitions, q.end_transitions, q.transitions, mask)
         return self.reduce_risk(kl, mask.to(kl.dtype).sum(), reduction)
 
+    def symmetric_kl(self, emissions_a, emissions_b, mask: Optional[torch.Tensor] = None, reduction: str = "mean"):
+        """``KL(p_a || p_b)[b] + KL(p_b || p_a)[b]`` over whole tag sequences between this chain's posteriors on two emission
+        tensors -- the chain-level consistency term between two passes over one batch.  Both sides share the transitions, so with
+        ``D = emissions_a - emissions_b`` the difference of the two path scores is column-additive, ``score_a(y) - score_b(y) =
+        sum_t D[t,y_t]``, and ``KL(p_a || p_b) = E_a[sum_t D[t,y_t]] - logZ_a + logZ_b``, ``KL(p_b || p_a) = -E_b[sum_t D[t,y_t]] +
+        logZ_a - logZ_b``: both ``logZ`` cancel in the sum,
+
+            symKL = E_{p_a}[sum_t D[t,y_t]] - E_{p_b}[sum_t D[t,y_t]]
+
+        which is two ``expected_cost`` calls with cost ``D`` (against four risk launches and two ``logZ`` for two ``kl_divergence``
+        calls).  Gradients reach both emission tensors -- through the posteriors and through the cost -- and the chain
+        parameters.  Exactly 0 when both arguments are one tensor.  The limits of ``expected_cost``: at most 64 tags and 512
+        columns, ``mask`` a prefix mask.  Reductions as ``forward``: 'none' [B], 'sum', 'mean' (over sentences), 'token_mean'."""
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"invalid reduction: {reduction}")
+        if tuple(emissions_a.shape) != tuple(emissions_b.shape):
+            raise ValueError(f"CRF.symmetric_kl: emissions_b {tuple(emissions_b.shape)} does not fit emissions_a "
+                             f"{tuple(emissions_a.shape)}")
+        delta = emissions_a.float() - emissions_b.float()
+        skl = self.expected_cost(emissions_a, delta, mask, "none") - self.expected_cost(emissions_b, delta, mask, "none")
+        columns = emissions_a.shape[0] * emissions_a.shape[1] if mask is None else mask.ne(0).sum().to(skl.dtype)
+        return self.reduce_risk(skl, columns, reduction)
+
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
         tags, lens = self.decode_packed(emissions, mask)
