@@ -488,6 +488,46 @@ int mtvaf_token_divergence_fwd(const float* x, const float* y, const uint8_t* ma
 int mtvaf_token_divergence_bwd(const float* grad_out, const float* x, const float* y, const uint8_t* mask, float* dx,
                                float* dy, int N, int C, int kind, float temperature, int reduction, int B, float scale,
                                mtvaf_stream_t stream);
+/* Token-level cross entropy over the tagger's emissions -- the loss of a softmax tagging head and the auxiliary term beside
+ * the CRF, with class weights, label smoothing and the focal factor (csrc/token_ce.hip).
+ * logits [N,C] fp32 contiguous, N = B*S rows; labels [N] int64; mask [N] u8 (non-zero = live) or NULL; class_weight w [C]
+ * fp32 or NULL = all ones.  A row is LIVE iff its mask byte is non-zero (or mask is NULL), its label is not ignore_index
+ * and its label lies in [0, C); a label outside [0, C) that is not ignore_index on an unmasked row makes the row dead and is
+ * counted in stats[1] (the label of a masked row is not looked at).  Per live row with label y, lp = log_softmax(z),
+ * p = exp(lp), eps = smoothing, g = gamma:
+ *   a_c = (1 - eps) w_y [c = y] + (eps / C) w_c          A = sum_c a_c
+ *   ce  = -sum_c a_c lp_c       om = sum_{c != y} p_c  (= 1 - p_y, formed as this sum)       L = om^g ce   (g = 0: L = ce)
+ *   dL/dz_k = om^g (A p_k - a_k) - ce g om^(g-1) p_y ([k = y] - p_k)
+ *   loss[0] = scale * (sum of L over the live rows) / D
+ * reduction 0 (mean): D = sum of w_y over the live rows -- at g = 0 torch.nn.functional.cross_entropy(weight=,
+ * label_smoothing=, ignore_index=); D = 0 gives loss 0 and all-zero gradients.  reduction 1 (batch mean): D = B (read in
+ * this mode only; commensurable with the CRF's mean NLL).  reduction 2 (sum): D = 1.  row_ws [N] receives every row's L,
+ * exactly 0 on dead rows; stats [2] int32 receives the number of live rows and of out-of-range labels.
+ * The backward recomputes everything from its inputs (nothing is kept from the forward) and writes every element of
+ * dlogits [N,C], exact zeros on dead rows: dL/dz times *grad_out (device) * scale / D -- or, with grad_rows [N] in place of
+ * grad_out (exactly one of the two is given), times scale * grad_rows[row], the per-row upstream gradient of the rows
+ * themselves (reduction and B are then not read; grad_rows is not read on dead rows).
+ * Contract: log space with the row maximum removed -- logits of magnitude 1e4 give finite values and gradients, and a row
+ * whose other tags all underflow has om = 0 exactly, so its focal value and gradient are exact zeros; dead rows are never
+ * read and may hold NaN; no floating-point atomics -- one finishing block adds the rows and D in double in a fixed order
+ * (the backward forms D the same way in every block), so the same inputs give the same bits; no host sync, no read-back,
+ * no LDS opt-in.  N >= 1, 1 <= C <= 64 (MTVAF_ERR_SHAPE); smoothing in [0, 1), gamma 0 or in [1, 8], reduction 0..2,
+ * B >= 1 with reduction 1, no NULL but mask, class_weight and one of grad_out / grad_rows (MTVAF_ERR_ARG); all checked
+ * before any launch. */
+int mtvaf_token_ce_fwd(const float* logits, const int64_t* labels, const uint8_t* mask, const float* class_weight,
+                       float* loss, float* row_ws, int* stats, int N, int C, long ignore_index, float smoothing,
+                       float gamma, int reduction, int B, float scale, mtvaf_stream_t stream);
+int mtvaf_token_ce_bwd(const float* grad_out, const float* grad_rows, const float* logits, const int64_t* labels,
+                       const uint8_t* mask, const float* class_weight, float* dlogits, int N, int C, long ignore_index,
+                       float smoothing, float gamma, int reduction, int B, float scale, mtvaf_stream_t stream);
+/* Per-token decoding of a softmax head (csrc/token_ce.hip).  tags [N] int64 = the first maximum of each live row of
+ * logits [N,C]; logp [N] = log_softmax at it, taken over all C tags.  mask [N] u8 or NULL; masked rows are not read and get
+ * tag 0 and logp 0.  allowed [N] int64 or NULL: tag sets in the format of the constrained CRF entry points (bit j = tag j
+ * permitted; a word without any of the low C bits = no constraint): the maximum runs over the permitted tags only, logp
+ * stays the unconstrained log-probability.  N >= 1, 1 <= C <= 64 (MTVAF_ERR_SHAPE); no NULL but mask and allowed
+ * (MTVAF_ERR_ARG). */
+int mtvaf_token_argmax(const float* logits, const uint8_t* mask, const int64_t* allowed, int64_t* tags, float* logp, int N,
+                       int C, mtvaf_stream_t stream);
 /* Candidate spans at eval / predict time: the eval branch of models/utils.py::span_annotate_candidates (:451-521) and
  * the host round trip around it (modules/train.py:382-410) as one launch, no host read-back.  Start logit of (b,s) at
  * logits[(b*S+s)*ld], end logit one element later (the binary_affine output, ld = 2).  word_index [B,S] int32: token

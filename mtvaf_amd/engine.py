@@ -1884,6 +1884,59 @@ class TokenDivergenceFunction(torch.autograd.Function):
         return dx.view(shape).to(tx), dy.view(shape).to(ty), None, None, None, None, None
 
 
+class TokenCEFunction(torch.autograd.Function):
+    """Token-level cross entropy with class weights, label smoothing and the focal factor (include/mtvaf_hip.h, mtvaf_token_ce_*;
+    DESIGN.md section 4.28): ``logits`` [B,S,C] or [N,C] (the only differentiable input), ``labels`` [B,S] / [N] integer ids,
+    ``mask`` [B,S] / [N] (non-zero = live) or None, ``class_weight`` [C] or None.  A row is live iff its mask is non-zero, its label
+    is not ``ignore_index`` and lies in [0, C).  ``reduction`` "mean" divides the sum by the live rows' class weights (torch's
+    rule; none: 0), "batch_mean" by B (1 for [N,C]), "sum" by 1; all times ``scale``.  -> (loss 0-dim fp32; rows [N] fp32, detached:
+    every row's value, 0 on dead rows; stats int32 [2] on the device: live rows, out-of-range labels).  ``reduction="none"``:
+    the rows (times nothing) are the differentiable output and take a per-row upstream gradient; the loss returned beside them is
+    their detached sum.  The gradient is recomputed from the inputs; dead rows are never read and get exact zeros."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mask=None, class_weight=None, ignore_index=-100, smoothing=0.0, gamma=0.0, reduction="mean",
+                scale=1.0):
+        if logits.dim() not in (2, 3) or labels.shape != logits.shape[:-1]:
+            raise ValueError(f"TokenCEFunction: logits {tuple(logits.shape)} must be [B,S,C] or [N,C] and labels "
+                             f"{tuple(labels.shape)} their leading shape")
+        if reduction != "none" and reduction not in hip.TOKEN_CE_REDUCTIONS:
+            raise ValueError(f"TokenCEFunction: reduction={reduction!r} (expected 'none' or one of {sorted(hip.TOKEN_CE_REDUCTIONS)})")
+        if not 0.0 <= smoothing < 1.0 or not (gamma == 0.0 or 1.0 <= gamma <= 8.0):
+            raise ValueError(f"TokenCEFunction: smoothing={smoothing!r} (expected [0, 1)), gamma={gamma!r} (expected 0 or [1, 8])")
+        C = logits.shape[-1]
+        B = logits.shape[0] if logits.dim() == 3 else 1
+        zc = logits.contiguous().float().view(-1, C)
+        N = zc.shape[0]
+        if mask is not None and mask.numel() != N:
+            raise ValueError(f"TokenCEFunction: mask {tuple(mask.shape)} does not fit logits {tuple(logits.shape)}")
+        if class_weight is not None and class_weight.numel() != C:
+            raise ValueError(f"TokenCEFunction: class_weight {tuple(class_weight.shape)} does not fit {C} tags")
+        # (the kernels read "non-zero = live": a u8 mask goes in as it is)
+        m8 = None if mask is None else (mask if mask.dtype == torch.uint8 else mask.ne(0).view(torch.uint8)).contiguous().view(-1)
+        lab = labels.contiguous().view(-1).long()
+        cw = None if class_weight is None else class_weight.detach().contiguous().float().view(-1)
+        loss, rows, stats = _empty(1, like=zc), _empty(N, like=zc), _empty(2, like=zc, dtype=torch.int32)
+        per_row = reduction == "none"
+        how = (int(ignore_index), float(smoothing), float(gamma), hip.TOKEN_CE_REDUCTIONS["sum" if per_row else reduction], B,
+               1.0 if per_row else float(scale))
+        hip.token_ce_fwd(zc, lab, m8, cw, loss, rows, stats, *how)
+        ctx.stash = (zc, lab, m8, cw, how, per_row, logits.shape, logits.dtype)
+        loss = loss.view(())
+        ctx.mark_non_differentiable(loss if per_row else rows, stats)
+        return loss, rows, stats
+
+    @staticmethod
+    def backward(ctx, gloss, grows, _gstats):
+        zc, lab, m8, cw, how, per_row, shape, dtype = ctx.stash
+        dz = torch.empty_like(zc)
+        if per_row:
+            hip.token_ce_bwd(None, grows.contiguous().float().view(-1), zc, lab, m8, cw, dz, *how)
+        else:
+            hip.token_ce_bwd(gloss.contiguous().view(1).float(), None, zc, lab, m8, cw, dz, *how)
+        return dz.view(shape).to(dtype), None, None, None, None, None, None, None, None
+
+
 class MaskMulFunction(torch.autograd.Function):
     """Cutoff augmentation apply (modules/augument.py:99-159): x * row_keep[b,s] * col_keep[b,:]."""
 

@@ -113,6 +113,9 @@ _SIGS = {
     "mtvaf_js_consistency_bwd": (c_int, [P, F, P, P, P, P, P, I, I, I, P]),
     "mtvaf_token_divergence_fwd": (c_int, [P, P, P, P, P, I, I, I, F, I, I, F, P]),
     "mtvaf_token_divergence_bwd": (c_int, [P, P, P, P, P, P, I, I, I, F, I, I, F, P]),
+    "mtvaf_token_ce_fwd": (c_int, [P, P, P, P, P, P, P, I, I, L, F, F, I, I, F, P]),
+    "mtvaf_token_ce_bwd": (c_int, [P, P, P, P, P, P, P, I, I, L, F, F, I, I, F, P]),
+    "mtvaf_token_argmax": (c_int, [P, P, P, P, P, I, I, P]),
     "mtvaf_span_propose": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "mtvaf_entity_counts": (c_int, [P, I, P, P, P, P, P, P, I, I, I, I, P, P]),
     "mtvaf_span_counts": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P]),
@@ -860,6 +863,52 @@ def token_divergence_bwd(gout, x, y, mask_u8, dx, dy, kind, temperature, reducti
     _token_divergence_mask(mask_u8, N)
     _ck(lib().mtvaf_token_divergence_bwd(_p(gout), _p(x), _p(y), _p(mask_u8), _p(dx), _p(dy), N, C, int(kind), float(temperature),
                                          int(reduction), int(B), float(scale), _st()), "mtvaf_token_divergence_bwd")
+
+
+TOKEN_CE_REDUCTIONS = {"mean": 0, "batch_mean": 1, "sum": 2}
+
+
+def _token_ce_inputs(logits, labels, mask_u8, class_weight):
+    _f32(logits, class_weight)
+    N, C = logits.shape
+    assert labels.is_cuda and labels.dtype == torch.int64 and labels.numel() == N and labels.is_contiguous(), \
+        (labels.device, labels.dtype, tuple(labels.shape), N)
+    assert class_weight is None or class_weight.numel() == C, (tuple(class_weight.shape), C)
+    _token_divergence_mask(mask_u8, N)
+    return N, C
+
+
+def token_ce_fwd(logits, labels, mask_u8, class_weight, loss, row_ws, stats, ignore_index, smoothing, gamma, reduction, B, scale):
+    """logits [N,C] fp32 contiguous, labels [N] int64, mask_u8 [N] or None, class_weight [C] fp32 or None; reduction is the ABI's
+    integer (TOKEN_CE_REDUCTIONS), B the divisor of the batch mean; loss [1], row_ws [N] and stats [2] int32 are written."""
+    _f32(loss, row_ws)
+    N, C = _token_ce_inputs(logits, labels, mask_u8, class_weight)
+    assert row_ws.numel() >= N and stats.is_cuda and stats.dtype == torch.int32 and stats.numel() >= 2 and stats.is_contiguous()
+    _ck(lib().mtvaf_token_ce_fwd(_p(logits), _p(labels), _p(mask_u8), _p(class_weight), _p(loss), _p(row_ws), _p(stats), N, C,
+                                 int(ignore_index), float(smoothing), float(gamma), int(reduction), int(B), float(scale), _st()),
+        "mtvaf_token_ce_fwd")
+
+
+def token_ce_bwd(gout, grows, logits, labels, mask_u8, class_weight, dlogits, ignore_index, smoothing, gamma, reduction, B, scale):
+    """Exactly one of gout [1] (the gradient of the reduced loss) and grows [N] (per-row gradients of row_ws) is given."""
+    _f32(gout, grows, dlogits)
+    N, C = _token_ce_inputs(logits, labels, mask_u8, class_weight)
+    assert dlogits.shape == logits.shape and (grows is None or grows.numel() == N), (dlogits.shape, logits.shape)
+    _ck(lib().mtvaf_token_ce_bwd(_p(gout), _p(grows), _p(logits), _p(labels), _p(mask_u8), _p(class_weight), _p(dlogits), N, C,
+                                 int(ignore_index), float(smoothing), float(gamma), int(reduction), int(B), float(scale), _st()),
+        "mtvaf_token_ce_bwd")
+
+
+def token_argmax(logits, mask_u8, allowed, tags, logp):
+    """logits [N,C] fp32 contiguous, mask_u8 [N] or None, allowed [N] int64 tag sets (mtvaf_amd.constraints) or None; tags [N]
+    int64 and logp [N] fp32 are written (0 on masked rows)."""
+    _f32(logits, logp)
+    N, C = logits.shape
+    _token_divergence_mask(mask_u8, N)
+    assert allowed is None or (allowed.is_cuda and allowed.dtype == torch.int64 and allowed.numel() == N and
+                               allowed.is_contiguous()), (None if allowed is None else (allowed.dtype, tuple(allowed.shape)), N)
+    assert tags.is_cuda and tags.dtype == torch.int64 and tags.numel() >= N and tags.is_contiguous() and logp.numel() >= N
+    _ck(lib().mtvaf_token_argmax(_p(logits), _p(mask_u8), _p(allowed), _p(tags), _p(logp), N, C, _st()), "mtvaf_token_argmax")
 
 
 SPAN_PROPOSE_MAX_S, SPAN_PROPOSE_MAX_N = 512, 32

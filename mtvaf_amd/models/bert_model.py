@@ -55,6 +55,43 @@ def _consistency_options(args):
     return opt
 
 
+_CHAIN_ONLY = ("crf_risk_weight", "crf_mrt_weight", "crf_entropy_weight")
+
+
+def _token_head_options(args, num_labels):
+    """The switches of the token cross entropy, checked: args.tag_head ("crf" | "softmax"), token_ce_weight
+    (0: the auxiliary term beside the CRF), token_ce_reduction ("batch_mean" | "mean" | "sum": the softmax head's loss),
+    token_ce_smoothing (0), token_ce_focal_gamma (0, or 1..8), token_ce_class_weights (None | num_labels floats >= 0).  What
+    needs a real chain is refused beside the softmax head here, not at the first step."""
+    weights = _arg(args, "token_ce_class_weights", None)
+    opt = {"head": _arg(args, "tag_head", "crf"), "weight": float(_arg(args, "token_ce_weight", 0.0) or 0.0),
+           "reduction": _arg(args, "token_ce_reduction", "batch_mean"), "smoothing": float(_arg(args, "token_ce_smoothing", 0.0) or 0.0),
+           "gamma": float(_arg(args, "token_ce_focal_gamma", 0.0) or 0.0),
+           "class_weights": None if weights is None else [float(w) for w in weights]}
+    if opt["head"] not in ("crf", "softmax"):
+        raise ValueError(f"args.tag_head={opt['head']!r}: expected 'crf' or 'softmax'")
+    if opt["reduction"] not in ("batch_mean", "mean", "sum"):
+        raise ValueError(f"args.token_ce_reduction={opt['reduction']!r}: expected 'batch_mean', 'mean' or 'sum'")
+    if opt["weight"] < 0:
+        raise ValueError(f"args.token_ce_weight={opt['weight']!r}: expected a number >= 0")
+    if not 0.0 <= opt["smoothing"] < 1.0:
+        raise ValueError(f"args.token_ce_smoothing={opt['smoothing']!r}: expected a number in [0, 1)")
+    if not (opt["gamma"] == 0.0 or 1.0 <= opt["gamma"] <= 8.0):
+        raise ValueError(f"args.token_ce_focal_gamma={opt['gamma']!r}: expected 0 or a number in [1, 8]")
+    if opt["class_weights"] is not None and (len(opt["class_weights"]) != num_labels or min(opt["class_weights"]) < 0):
+        raise ValueError(f"args.token_ce_class_weights: expected {num_labels} weights >= 0 (one per label id, PAD = 0 first), got "
+                         f"{weights!r}")
+    if opt["head"] == "softmax":
+        on = [n for n in _CHAIN_ONLY if _arg(args, n, 0.0)]
+        if _arg(args, "crf_reduction", "mean") != "mean":
+            on.append("crf_reduction")
+        if _arg(args, "consistency_level", "token") == "chain":
+            on.append("consistency_level='chain'")
+        if on:
+            raise ValueError(f"args.tag_head='softmax' has no chain: {', '.join('args.' + n for n in on)} need args.tag_head='crf'")
+    return opt
+
+
 def _entity_scorer(args, label_list):
     """args.score_entities: True (the "seqeval" scheme) or a scheme name -> an `mtvaf_amd.metrics.EntityScorer` over the
     trainer's label map (label_list enumerated from 1, MTVAF_training.py:369); unset / False -> None."""
@@ -243,7 +280,21 @@ class TVNetSAModel2(nn.Module):
             self.aux_img_classifier = nn.ModuleList([nn.Linear(4 * 2 * hidden, 2089) for _ in range(3)])
             self._packed_proj: Optional[_PackedLinears] = None
 
-        self.crf = CRF(self.num_labels, batch_first=True)
+        # args.tag_head = "softmax": no trainable chain -- the loss is the token cross entropy, the tags are per-token maxima, and
+        # self.crf is a chain of zero buffers for the code that reports posteriors (`predict`); args.token_ce_weight > 0 adds the
+        # same cross entropy beside the CRF's loss.  Without either nothing is built and nothing is launched.
+        self.token_opt = _token_head_options(args, self.num_labels)
+        self.token_ce = None
+        self.last_token_ce = None  # detached device scalar after a forward with labels and args.token_ce_weight > 0
+        if self.token_opt["head"] == "softmax" or self.token_opt["weight"] > 0:
+            from ..modules.token_head import TokenCrossEntropy
+            self.token_ce = TokenCrossEntropy(self.num_labels, self.token_opt["class_weights"], self.token_opt["smoothing"],
+                                              self.token_opt["gamma"])
+        if self.token_opt["head"] == "softmax":
+            from ..modules.token_head import zero_chain
+            self.crf = zero_chain(self.num_labels)
+        else:
+            self.crf = CRF(self.num_labels, batch_first=True)
         self.fc = nn.Linear(hidden, self.num_labels)
         self.dropout = nn.Dropout(0.1)
         _crf_reduction(args)  # (a misspelt reduction is an error here, not at the first step)
@@ -269,7 +320,12 @@ class TVNetSAModel2(nn.Module):
         (W = args.max_words or S), and dropout, fc, decoding, the scorer, the marginals and every loss term run there with the
         index' word_mask; ``labels`` / ``allowed_tags`` arrive piece-level and are taken at every word's first piece; ``logits``
         are the tags of the word columns and ``self.last_word_index`` keeps the index.  Without args.word_pooling the map is not
-        read and the method runs the code it always ran."""
+        read and the method runs the code it always ran.
+        args.tag_head = "softmax" (DESIGN.md 4.28): the loss is the token cross entropy of the emissions (args.token_ce_reduction,
+        default "batch_mean"; args.token_ce_smoothing / _focal_gamma / _class_weights) plus the same ``alpha * img_tag_loss``, and
+        ``logits`` are the per-token first maxima (mtvaf_token_argmax); ``allowed_tags`` raises.  args.token_ce_weight > 0 with
+        the CRF head adds ``weight * CE(batch_mean)`` of the same emissions; ``self.last_token_ce`` keeps the unweighted value."""
+        self._chain_only(allowed_tags is not None, "allowed_tags")
         word_mode = self._word_mode(token_to_word)
         prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
                                                                                   aux_imgs)
@@ -341,7 +397,13 @@ class TVNetSAModel2(nn.Module):
     def _decode(self, emissions, mask_u8, labels):
         """Viterbi paths: device kernel + async packed copy; the list materialises on first use (no mid-step sync).
         One wavefront per sentence is all the parallelism Viterbi and the CRF forward algorithm have, so the two
-        run side by side (second stream) instead of back to back.  -> (paths, the event behind them on the second stream or None)"""
+        run side by side (second stream) instead of back to back.  -> (paths, the event behind them on the second stream or None)
+        args.tag_head = "softmax": the per-token maxima in the same packed form, on the main stream (one row launch)."""
+        if self.token_opt["head"] == "softmax":
+            logits = self.crf.defer_packed(*self._token_tags(emissions.detach(), mask_u8))
+            if self.entity_scorer is not None and labels is not None:
+                self.entity_scorer.update(logits.device_tags, labels, mask_u8)
+            return logits, None
         if emissions.is_cuda and engine.DW_SIDE_STREAM and emissions.shape[0] * emissions.shape[1] >= 1024:  # host-bound below
             main, side = torch.cuda.current_stream(), engine._side_stream(emissions.device)
             side.wait_stream(main)
@@ -360,8 +422,21 @@ class TVNetSAModel2(nn.Module):
             self.entity_scorer.update(logits.device_tags, labels, mask_u8)
         return logits, None
 
+    def _token_tags(self, emissions, mask_u8):
+        """The softmax head's tags in `CRF.decode_packed`'s form -> (tags int32 [B,S], -1 on masked columns; lengths int32 [B])"""
+        tags, _ = self.token_ce.decode(emissions, mask_u8)
+        return (torch.where(mask_u8 != 0, tags, torch.full_like(tags, -1)).to(torch.int32),
+                mask_u8.sum(dim=1, dtype=torch.int32))
+
+    def _chain_only(self, asked, what):
+        if asked and self.token_opt["head"] == "softmax":
+            raise ValueError(f"args.tag_head='softmax' has no chain: {what} needs args.tag_head='crf'")
+
     def _crf_nll(self, emissions, mask_u8, labels, allowed_tags):
-        """-llh of the labels, or without them of the paths ``allowed_tags`` permit (`CRF.partial_llh`), under args.crf_reduction."""
+        """-llh of the labels, or without them of the paths ``allowed_tags`` permit (`CRF.partial_llh`), under args.crf_reduction.
+        args.tag_head = "softmax": the token cross entropy of the labels under args.token_ce_reduction."""
+        if self.token_opt["head"] == "softmax":
+            return self.token_ce(emissions, labels, mask_u8, self.token_opt["reduction"])
         reduction = _crf_reduction(self.args)
         if labels is None:
             return -self.crf.partial_llh(emissions, allowed_tags, mask=mask_u8, reduction=reduction)
@@ -374,7 +449,15 @@ class TVNetSAModel2(nn.Module):
         self.last_crf_risk = None
         self.last_crf_entropy = None
         self.last_crf_mrt = None
+        self.last_token_ce = None
         if labels is not None:
+            # args.token_ce_weight > 0 adds the token cross entropy of the emissions the CRF sees (TokenCrossEntropy, batch_mean:
+            # the divisor of the CRF's mean NLL) to the loss and keeps it in self.last_token_ce; at the default 0 the step
+            # launches nothing for it.
+            if self.token_opt["weight"] > 0 and self.token_opt["head"] == "crf":
+                token_ce = self.token_ce(emissions, labels, mask_u8, "batch_mean")
+                self.last_token_ce = token_ce.detach()
+                loss = loss + self.token_opt["weight"] * token_ce
             # args.crf_risk_weight > 0 adds the expected rate of wrong tags under the posterior (CRF.hamming_risk, token_mean) to
             # the loss and keeps it in self.last_crf_risk; at the default 0 the step launches nothing for it.
             risk_weight = _arg(self.args, "crf_risk_weight", 0.0)
@@ -440,7 +523,9 @@ class TVNetSAModel2(nn.Module):
         ``divergence`` (unweighted, detached), ``emissions``, ``emissions_2`` -- None where a term was not computed."""
         if labels is None and allowed_tags is None:
             raise ValueError("forward_consistent forms a loss: it needs labels or allowed_tags")
+        self._chain_only(allowed_tags is not None, "allowed_tags")
         opt = _consistency_options(self.args)
+        self._chain_only(opt["level"] == "chain", "args.consistency_level='chain'")
         two = opt["weight"] > 0 or opt["ce"]
         # args.fused_accumulation: the two encoder nodes write / add into the flat gradient buffers, as in
         # TVNetSAModel.forward_with_cutoff; the sink goes back to its setting when that backward ends, or here if anything raises
@@ -588,7 +673,10 @@ class TVNetSAModel2(nn.Module):
                                                          word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
                 mask_u8 = attention_mask.to(torch.uint8)
-                tags, _ = self.crf.decode_packed(emissions, mask_u8)
+                # (the softmax head: per-token maxima; self.crf is then the chain of zero buffers, whose segment posteriors are
+                # the sums of the token log-probabilities)
+                tags, _ = self._token_tags(emissions, mask_u8) if self.token_opt["head"] == "softmax" \
+                    else self.crf.decode_packed(emissions, mask_u8)
                 t = self._entity_tables(emissions.device)
                 keep = torch.zeros_like(mask_u8, dtype=torch.bool)
                 keep[:, 1:] = torch.cumprod(mask_u8[:, 1:], dim=1).bool()  # from column 1 up to the first 0
@@ -613,6 +701,7 @@ class TVNetSAModel2(nn.Module):
         -- [CLS] / [SEP] at the ends, X on the columns outside ``word_mask``, no structural tag on a word column), then
         `CRF.entities` on those tags by `predict`'s column rule.  -> `predict`'s dict.  The reported confidence stays the
         posterior of the decoded segment under the UNCONSTRAINED chain, p(y_b..y_e | x), not conditioned on the sets."""
+        self._chain_only(True, "predict_constrained")
         # (the prologue is `predict`'s, restated: that method is left as it is)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
         self.eval()
@@ -667,6 +756,7 @@ class TVNetSAModel2(nn.Module):
         then start (`CRF.chunks_above`; args.max_entities); ``types``.  Two overlapping chunks exclude each other, so with
         ``threshold > 0.5`` the selected spans of a sentence cannot overlap.  `mtvaf_amd.metrics.posteriors_to_lists` makes
         Python lists of it."""
+        self._chain_only(True, "predict_posteriors")
         # (the prologue is `predict`'s, restated: that method is left as it is)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
         self.eval()
@@ -728,6 +818,7 @@ class TVNetSAModel2(nn.Module):
         -> dict: tags [B,K,S], scores / logprob [B,K], n_paths [B] (`CRF.decode_nbest`); lengths / count [B,K], entities
         [B,K,E,3], log_confidence / confidence [B,K,E] (`CRF.entities`), ``types``.  Hypothesis 0 is `predict`'s answer; ranks >=
         n_paths have no entities."""
+        self._chain_only(True, "predict_nbest")
         K = int(_arg(self.args, "nbest", 4) if nbest is None else nbest)
         # (the prologue is `predict`'s, restated: that method is left as it is)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset

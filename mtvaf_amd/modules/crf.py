@@ -637,7 +637,11 @@ class CRF(nn.Module):
 
     def decode_deferred(self, emissions, mask: Optional[torch.Tensor] = None) -> DeferredTags:
         """Viterbi on device + asynchronous packed copy to pinned host memory; no host sync here."""
-        tags, lens = self.decode_packed(emissions, mask)
+        return self.defer_packed(*self.decode_packed(emissions, mask))
+
+    def defer_packed(self, tags, lens) -> DeferredTags:
+        """``decode_deferred``'s second half for tags that are on the device already: tags int32 [B,S] (-1 beyond each length) and
+        lens int32 [B] -> the list that fills itself from an asynchronous packed copy."""
         S = tags.shape[1]
         packed = torch.cat([tags, lens[:, None]], dim=1)
         need = packed.numel()
