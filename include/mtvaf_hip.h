@@ -676,7 +676,10 @@ int mtvaf_colsum_small(const float* part, int rows, int cols, float* out, int ac
  * below 2^-26 |a||b|: accuracy of the fp32 pipe; operands and results stay fp32 in memory).  Same arguments as
  * mtvaf_gemm_f32 (modeling_bert.py:266, 283-284, 353, 420-421, 433 and their autograd backward); shapes it does not cover
  * (not whole 64x64 tiles, K % 32 != 0, unaligned operands) run the fp32 pipe.  mtvaf_f32_split(1 / 0): mtvaf_gemm_f32 and
- * mtvaf_gemm_f32_ktiles use it everywhere they can / never (default: 1; MTVAF_F32_SPLIT=0 in the environment: 0); -1 queries. */
+ * mtvaf_gemm_f32_ktiles use it everywhere they can / never (default: 1; MTVAF_F32_SPLIT=0 in the environment: 0); -1 queries.
+ * Domain: operands at or above 2^127 (2 - 2^-8) ~ 3.396e38 in magnitude round to an infinite first plane and give non-finite
+ * results on the split arithmetic (here and from plane images), while the fp32 pipe stays finite; inf and NaN operands give
+ * non-finite results on both. */
 int mtvaf_gemm_f32x3(int layout_a, int layout_b, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                      int M, int N, int K, const float* bias, int epi, float* aux, int ldaux, int accumulate,
                      int allow_split, void* workspace, size_t workspace_bytes, int cfg, int splits,
@@ -718,7 +721,9 @@ int mtvaf_f32x3_trace(void* buf);
  * 433).  mtvaf_f32_split_planes writes the three bf16 planes x = x1 + x2 + x3 of an fp32 matrix [rows][cols] (the split of
  * csrc/gemm_f32x3.hip, bit for bit) as a plane image addressed by three BYTE strides: plane -> plane, row -> row, 32-column
  * k-tile -> k-tile (natural form: cols * 2 * rows / ld * 2 / 64; tile-blocked form [k-tile][plane][rows][32]: rows * 64 / 64 /
- * 3 * rows * 64).  mtvaf_gemm_f32p: C[M,N] = A[M,K] . op(B) (+ bias, epilogue, accumulate) from the plane images of both
+ * 3 * rows * 64).  An element at or above 2^127 (2 - 2^-8) in magnitude has an infinite first plane (RNE to bf16 overflows), then an
+ * infinite and a NaN plane: operands from there on give non-finite results on the split arithmetic, while the fp32 pipe stays finite.
+ * mtvaf_gemm_f32p: C[M,N] = A[M,K] . op(B) (+ bias, epilogue, accumulate) from the plane images of both
  * operands on v_mfma_f32_16x16x32_bf16, nothing split inside the k-loop; layout_b 0: B [N][K] (forward), 1: B [K][N] (the dX
  * products: natural plane image, b_row = N * 2, b_kt = 32 * N * 2, b_col = 256); layout_a 1 (with layout_b 1): A [K][M] too, the
  * weight-gradient products; M, N % 128 == 0, K % 32 == 0; splits > 1 = deterministic

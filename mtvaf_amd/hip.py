@@ -464,6 +464,24 @@ def gemm_planes(a: Planes, b: Planes, out, bias=None, epi=EPI_NONE, aux=None, ac
     return out
 
 
+def gemm_planes_slabs(a: Planes, b: Planes, out, ws, bias=None, accumulate=False, splits=1, layout_b=KC) -> int:
+    """mtvaf_gemm_f32p_slabs: gemm_planes with a plain epilogue that leaves a split-K plan's slabs unreduced in the caller's fp32
+    workspace `ws` (None: no workspace).  -> the number of slabs s: 1 = `out` holds the result (+ bias, accumulate); s > 1 = ws holds s
+    slabs [M][N], neither bias nor accumulate applied, `out` untouched (the LayerNorm kernel behind the product adds them)."""
+    if layout_b == KM:
+        M, N, K = a.rows, b.cols, a.cols
+        bs = _km_strides(b)
+    else:
+        M, N, K = a.rows, b.rows, a.cols
+        bs = (b.s_plane, b.s_row, b.s_kt, 0)
+    ns = ctypes.c_int(0)
+    _ck(lib().mtvaf_gemm_f32p_slabs(KC, _p(a.img), a.s_plane, a.s_row, a.s_kt, 0, layout_b, _p(b.img), bs[0], bs[1], bs[2], bs[3], _p(out),
+                                    out.stride(0), M, N, K, _p(bias), int(accumulate), splits, _p(ws),
+                                    ws.numel() * ws.element_size() if ws is not None else 0, ctypes.byref(ns), _st()),
+        "mtvaf_gemm_f32p_slabs")
+    return ns.value
+
+
 def split_planes_blocked(x: torch.Tensor, out: torch.Tensor):
     """fp32 [rows, cols] (contiguous) -> its tile-blocked plane image [cols / 32][3][rows][32] bf16 in `out` (6 rows cols bytes)."""
     rows, cols = x.shape
