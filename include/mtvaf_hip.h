@@ -140,6 +140,21 @@ int mtvaf_prefix_attn_varlen_bwd_planes(const float* dctx, const float* qkv, con
                                         const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv, int B,
                                         int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
                                         void* dqkv_planes, int rows, mtvaf_stream_t st);
+/* The packed-row attention with a per-sentence PREFIX-SLOT MASK: pmask [B, P] fp32 additive, 0 = sentence b owns slot p, -10000 = it
+ * does not -- the prefix columns of the padded layout's addmask, indexed by the sentence and added at the same place of the
+ * arithmetic, so a packed run with a mask equals the padded run with the same mask to the degree the unmasked runs agree.  A masked
+ * slot has probability exactly 0 (exp2 underflows, as in the padded layout) and its rows of dpk / dpv are exactly 0; a sentence
+ * with all P slots masked attends to its own text keys.  No tile is skipped (same products, same order).  pmask_len: the element
+ * count of pmask, B * P -- anything else, or a pmask with P == 0, is MTVAF_ERR_ARG.  pmask == NULL (pmask_len ignored): the launch
+ * of mtvaf_prefix_attn_varlen_fwd / _bwd.  ctx_planes / dqkv_planes with rows: as the _planes forms, or NULL for none. */
+int mtvaf_prefix_attn_varlen_fwd_pm(const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
+                                    const float* pmask, long pmask_len, float* ctx, float* lse, int B, int S, int P, int NH,
+                                    int head_dim, float p_drop, uint64_t seed, uint64_t offset, void* ctx_planes, int rows,
+                                    mtvaf_stream_t st);
+int mtvaf_prefix_attn_varlen_bwd_pm(const float* dctx, const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
+                                    const float* pmask, long pmask_len, const float* ctx, const float* lse, float* delta, float* dqkv,
+                                    float* dpk, float* dpv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
+                                    uint64_t offset, void* dqkv_planes, int rows, mtvaf_stream_t st);
 /* dst[r][:] = map[r] >= 0 ? src[map[r]][:] : 0  (rows_dst rows of H floats): packs / unpacks token rows. */
 int mtvaf_gather_rows(const float* src, const int* map, float* dst, int rows_dst, int H, mtvaf_stream_t stream);
 /* Token packing of a batch from its additive mask [B, T = P + S] (text keys at columns P..; kept: > -5000): cu [B+1] row
@@ -404,6 +419,13 @@ int mtvaf_prompt_mix_bwd_enc(const float* gate, const float* dpkv, const float* 
                              int L, int W, int NL, mtvaf_stream_t stream);
 int mtvaf_kl_logsoftmax_fwd(const float* logits, const float* target, float* loss, float* row_ws, int B, int N,
                             mtvaf_stream_t stream);
+/* The same loss over the rows that are PRESENT (present [B] fp32, 1 / 0: the sentences that have this image): loss[0] = sum over
+ * present rows of the row's KL term / the number of present rows (0 when none is); an absent row adds nothing and gets a zero
+ * gradient.  All rows present: the bits of mtvaf_kl_logsoftmax_fwd / _bwd (the same sums in the same order, factor B / B = 1). */
+int mtvaf_kl_logsoftmax_masked_fwd(const float* logits, const float* target, const float* present, float* loss, float* row_ws,
+                                   int B, int N, mtvaf_stream_t stream);
+int mtvaf_kl_logsoftmax_masked_bwd(const float* grad_out, float gscale, const float* logits, const float* target,
+                                   const float* present, float* dlogits, int B, int N, mtvaf_stream_t stream);
 int mtvaf_kl_logsoftmax_bwd(const float* grad_out, float gscale, const float* logits, const float* target,
                             float* dlogits, int B, int N, mtvaf_stream_t stream);
 int mtvaf_mean_l_fwd(const float* enc, float* out, long n, int L, int W4, mtvaf_stream_t stream);
@@ -864,6 +886,15 @@ int mtvaf_prefix_attn_bf16_varlen_bwd(const void* dctx16, const void* qkv16, con
                                       int pad_rows, const void* ctx16, const float* lse, void* dqkv16, float* dpk, float* dpv, float* partq,
                                       float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
                                       uint64_t offset, mtvaf_stream_t stream);
+/* ... with a per-sentence prefix-slot mask (see mtvaf_prefix_attn_varlen_fwd_pm): pmask [B, P] fp32 additive, pmask_len = B * P;
+ * pmask == NULL: the launch of mtvaf_prefix_attn_bf16_varlen_fwd / _bwd. */
+int mtvaf_prefix_attn_bf16_varlen_fwd_pm(const void* qkv16, const void* pk16, const void* pv16, const int* cu, int pad_rows,
+                                         const float* pmask, long pmask_len, void* ctx16, float* lse, int B, int S, int P, int NH,
+                                         int head_dim, float p_drop, uint64_t seed, uint64_t offset, mtvaf_stream_t stream);
+int mtvaf_prefix_attn_bf16_varlen_bwd_pm(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16, const int* cu,
+                                         int pad_rows, const float* pmask, long pmask_len, const void* ctx16, const float* lse,
+                                         void* dqkv16, float* dpk, float* dpv, float* partq, float* partkv, int B, int S, int P, int NH,
+                                         int head_dim, float p_drop, uint64_t seed, uint64_t offset, mtvaf_stream_t stream);
 int mtvaf_cast_bf16(const float* x, int ldx, void* out, int ldo, void* outT, int ldt, int R, int C,
                     mtvaf_stream_t stream);
 
@@ -909,6 +940,9 @@ typedef struct {
    * gradients then run on the pre-split kernels of csrc/gemm_f32p.hip (nothing split inside their k-loops). */
   const void* x_p;
   void *cx_p, *h1_p, *act_p, *h2_p;
+  /* packed rows, optional: the per-sentence prefix-slot mask [B, P] (mtvaf_prefix_attn_varlen_fwd_pm; the prefix columns of
+   * addmask, which packed rows do not read) or NULL -- every sentence owns all P slots.  Ignored in the padded layout. */
+  const float* pmask;
 } mtvaf_layer_t;
 
 typedef struct {

@@ -222,6 +222,24 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_kernel(AttnArgs a, int nq) { 
   attn_bwd_body<PipeF32>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot);
 }
 
+// The packed-row kernels with a per-sentence prefix-slot mask (mask_at<PM>): the same bodies, LDS and launch bounds; pmask is an
+// argument of its own, so the kernels above keep their argument block and their code.
+__global__ __launch_bounds__(256) void attn_fwd_pm_kernel(AttnArgs a, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) float Ks[KT * PipeF32::LDK];
+  __shared__ __attribute__((aligned(16))) float Vs[KT * PipeF32::LDT];
+  __shared__ __attribute__((aligned(16))) float Ms[KT];
+  __shared__ int t_eff_slot;
+  attn_fwd_body<PipeF32, true>(a, PipeF32::RowTile{Ks}, PipeF32::ColTile{Vs}, Ms, &t_eff_slot, pmask);
+}
+
+__global__ __launch_bounds__(256, 3) void attn_bwd_pm_kernel(AttnArgs a, int nq, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) float tile0[KT * PipeF32::LDK];
+  __shared__ __attribute__((aligned(16))) float tile1[KT * PipeF32::LDK];
+  __shared__ __attribute__((aligned(16))) float small[3 * KT];
+  __shared__ int t_eff_slot;
+  attn_bwd_body<PipeF32, true>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot, pmask);
+}
+
 }  // namespace mtvaf
 
 using namespace mtvaf;
@@ -234,7 +252,7 @@ static bool attn_split_on() { return mtvaf_f32_split(-1) != 0; }
 
 static int attn_fwd_launch(const float* qkv, const float* pk, const float* pv, const float* addmask, const int* cu, int pad_rows,
                            float* ctx, float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
-                           uint64_t offset, hipStream_t st, void* ctx_planes = nullptr, long rows = 0) {
+                           uint64_t offset, hipStream_t st, void* ctx_planes = nullptr, long rows = 0, const float* pmask = nullptr) {
   if (head_dim != D) return MTVAF_ERR_SHAPE;
   if (!cu && !addmask) return MTVAF_ERR_ARG;
   AttnArgs a{};
@@ -246,8 +264,9 @@ static int attn_fwd_launch(const float* qkv, const float* pk, const float* pv, c
   if (rc) return rc;
   if (pad_rows < 0 || (pad_rows && !cu)) return MTVAF_ERR_ARG;
   const dim3 grid((S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0));
-  if (attn_split_on()) return launch_attn_f32s_fwd(a, grid, st);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, a);
+  if (attn_split_on()) return launch_attn_f32s_fwd(a, grid, st, pmask);
+  if (pmask) hipLaunchKernelGGL(attn_fwd_pm_kernel, grid, dim3(256), 0, st, a, pmask);
+  else hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, a);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -255,7 +274,7 @@ static int attn_fwd_launch(const float* qkv, const float* pk, const float* pv, c
 static int attn_bwd_launch(const float* dctx, const float* qkv, const float* pk, const float* pv, const float* addmask,
                            const int* cu, int pad_rows, const float* ctx, const float* lse, float* delta, float* dqkv, float* dpk, float* dpv,
                            int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st,
-                           int zero_tail = 0, void* dqkv_planes = nullptr, long rows = 0) {
+                           int zero_tail = 0, void* dqkv_planes = nullptr, long rows = 0, const float* pmask = nullptr) {
   if (head_dim != D) return MTVAF_ERR_SHAPE;
   if (!cu && !addmask) return MTVAF_ERR_ARG;
   AttnArgs a{};
@@ -271,8 +290,9 @@ static int attn_bwd_launch(const float* dctx, const float* qkv, const float* pk,
   if (pad_rows < 0 || (pad_rows && !cu)) return MTVAF_ERR_ARG;
   const int nq = (S + 63) / 64;
   const dim3 grid(nq + (P + S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0));
-  if (attn_split_on()) return launch_attn_f32s_bwd(a, nq, grid, st);
-  hipLaunchKernelGGL(attn_bwd_kernel, grid, dim3(256), 0, st, a, nq);
+  if (attn_split_on()) return launch_attn_f32s_bwd(a, nq, grid, st, pmask);
+  if (pmask) hipLaunchKernelGGL(attn_bwd_pm_kernel, grid, dim3(256), 0, st, a, nq, pmask);
+  else hipLaunchKernelGGL(attn_bwd_kernel, grid, dim3(256), 0, st, a, nq);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -372,6 +392,37 @@ int mtvaf_prefix_attn_varlen_bwd_planes(const float* dctx, const float* qkv, con
   if (!cu || !dqkv_planes) return MTVAF_ERR_ARG;
   return attn_bwd_launch(dctx, qkv, pk, pv, nullptr, cu, pad_rows, ctx, lse, delta, dqkv, dpk, dpv, B, S, P, NH, head_dim, p_drop, seed,
                          offset, st, 0, dqkv_planes, rows);
+}
+
+// The packed-row attention with a per-sentence PREFIX-SLOT MASK: pmask [B, P] fp32 additive, 0 = sentence b owns the slot, -10000 =
+// it does not -- the prefix columns of the padded layout's addmask, added at the same place of the arithmetic, so a packed run with
+// a mask equals the padded run with the same mask to the degree the unmasked runs agree.  A masked slot has probability exactly 0
+// (exp2 underflows as in the padded layout) and its rows of dpk / dpv are exactly 0; a sentence with every slot masked attends to
+// its own text keys.  No tile is skipped: same products, same order, only the mask tile differs.  pmask_len = B * P, the element
+// count of pmask (MTVAF_ERR_ARG otherwise, and for a pmask with P == 0).  pmask == NULL (pmask_len ignored): the launch of
+// mtvaf_prefix_attn_varlen_fwd / _bwd, or of their _planes forms when ctx_planes / dqkv_planes is given (NULL: no plane image).
+static int pmask_check(const float* pmask, long pmask_len, int B, int P) {
+  if (!pmask) return MTVAF_OK;
+  if (P <= 0 || B <= 0 || pmask_len != (long)B * P) return MTVAF_ERR_ARG;
+  return MTVAF_OK;
+}
+int mtvaf_prefix_attn_varlen_fwd_pm(const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
+                                    const float* pmask, long pmask_len, float* ctx, float* lse, int B, int S, int P, int NH,
+                                    int head_dim, float p_drop, uint64_t seed, uint64_t offset, void* ctx_planes, int rows,
+                                    hipStream_t st) {
+  if (!cu) return MTVAF_ERR_ARG;
+  if (int rc = pmask_check(pmask, pmask_len, B, P)) return rc;
+  return attn_fwd_launch(qkv, pk, pv, nullptr, cu, pad_rows, ctx, lse, B, S, P, NH, head_dim, p_drop, seed, offset, st, ctx_planes,
+                         ctx_planes ? rows : 0, pmask);
+}
+int mtvaf_prefix_attn_varlen_bwd_pm(const float* dctx, const float* qkv, const float* pk, const float* pv, const int* cu, int pad_rows,
+                                    const float* pmask, long pmask_len, const float* ctx, const float* lse, float* delta, float* dqkv,
+                                    float* dpk, float* dpv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed,
+                                    uint64_t offset, void* dqkv_planes, int rows, hipStream_t st) {
+  if (!cu) return MTVAF_ERR_ARG;
+  if (int rc = pmask_check(pmask, pmask_len, B, P)) return rc;
+  return attn_bwd_launch(dctx, qkv, pk, pv, nullptr, cu, pad_rows, ctx, lse, delta, dqkv, dpk, dpv, B, S, P, NH, head_dim, p_drop, seed,
+                         offset, st, 0, dqkv_planes, dqkv_planes ? rows : 0, pmask);
 }
 
 }  // extern "C"

@@ -123,8 +123,16 @@ template <class Args>
 __device__ __forceinline__ int slot_sentence(const Args& a, int z) {
   return (a.cu && a.cu[0] < 0) ? a.cu[a.B + 1 + z] : z;
 }
-template <class Args>
-__device__ __forceinline__ float mask_at(const Args& a, int b, int Tf, int t) {
+// Additive mask of key t of sentence b.  PM (the *_pm kernels: packed rows with a per-sentence prefix-slot mask): pmask [B, P] holds
+// the prefix columns of the padded layout's addmask (0 = slot present, -10000 = absent), indexed by the SENTENCE (not the grid slot)
+// and added at the same place of the arithmetic, so a masked slot's probability underflows to exactly 0 as it does there; the text
+// keys of packed rows stay unmasked.  PM is a template parameter and pmask a kernel argument of its own: the kernels without a
+// mask are the code they were, argument block included.
+template <bool PM = false, class Args>
+__device__ __forceinline__ float mask_at(const Args& a, int b, int Tf, int t, const float* pmask = nullptr) {
+  if constexpr (PM) {
+    if (a.cu) return t < a.P ? pmask[(long)b * a.P + t] : 0.f;
+  }
   return a.cu ? 0.f : a.addmask[(long)b * Tf + t];
 }
 
@@ -211,8 +219,9 @@ int attn_check(const Args& a) {
 }
 
 // launchers of the split-product kernels (csrc/attention_f32s.hip); grid / block as the fp32-pipe kernels of attention.hip
-int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st);
-int launch_attn_f32s_bwd(const AttnArgs& a, int nq, dim3 grid, hipStream_t st);
+// (pmask: the per-sentence prefix-slot mask of a packed launch, mask_at<PM>; NULL: the kernels without one)
+int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st, const float* pmask = nullptr);
+int launch_attn_f32s_bwd(const AttnArgs& a, int nq, dim3 grid, hipStream_t st, const float* pmask = nullptr);
 int launch_attn_f32s_probs(const AttnArgs& a, const ProbsOut& o, dim3 grid, hipStream_t st);
 
 }  // namespace mtvaf

@@ -252,6 +252,25 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_bwd_kernel(Args a, int nq) {
   attn_bwd_body<Bf16>(a, nq, tile0, tile1, small, red, &t_eff_slot);
 }
 
+// ... with a per-sentence prefix-slot mask on packed rows (mask_at<PM>; pmask is an argument of its own: the kernels above keep
+// their argument block and their code)
+__global__ __launch_bounds__(256) void attn_bf16_fwd_pm_kernel(Args a, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) unsigned char Ks[KT * 128];
+  __shared__ __attribute__((aligned(16))) unsigned char Vs[KT * 128];
+  __shared__ __attribute__((aligned(16))) float Ms[KT];
+  __shared__ int t_eff_slot;
+  attn_fwd_body<Bf16, true>(a, Ks, Vs, Ms, &t_eff_slot, pmask);
+}
+
+__global__ __launch_bounds__(256, 2) void attn_bf16_bwd_pm_kernel(Args a, int nq, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) unsigned char tile0[KT * 128];
+  __shared__ __attribute__((aligned(16))) unsigned char tile1[KT * 128];
+  __shared__ __attribute__((aligned(16))) float small[3 * KT];
+  __shared__ __attribute__((aligned(16))) float red[8 * 64];
+  __shared__ int t_eff_slot;
+  attn_bwd_body<Bf16, true>(a, nq, tile0, tile1, small, red, &t_eff_slot, pmask);
+}
+
 static int check(const Args& a) {
   const int rc = attn_check(a);
   if (rc) return rc;
@@ -268,7 +287,7 @@ extern "C" {
 
 static int attn16_fwd_launch(const void* qkv16, const void* pk16, const void* pv16, const float* addmask, const int* cu, int pad_rows,
                              void* ctx16, float* lse, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
-                             hipStream_t st) {
+                             hipStream_t st, const float* pmask = nullptr) {
   if (head_dim != D) return MTVAF_ERR_SHAPE;
   ab::Args a{};
   a.qkv = static_cast<const __bf16*>(qkv16); a.pk = static_cast<const __bf16*>(pk16); a.pv = static_cast<const __bf16*>(pv16);
@@ -277,7 +296,9 @@ static int attn16_fwd_launch(const void* qkv16, const void* pk16, const void* pv
   int rc = ab::check(a);
   if (rc) return rc;
   if (!ctx16 || !lse || (!addmask && !cu) || pad_rows < 0 || (pad_rows && !cu)) return MTVAF_ERR_ARG;
-  hipLaunchKernelGGL(ab::attn_bf16_fwd_kernel, dim3((S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0)), dim3(256), 0, st, a);
+  const dim3 grid((S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0));
+  if (pmask) hipLaunchKernelGGL(ab::attn_bf16_fwd_pm_kernel, grid, dim3(256), 0, st, a, pmask);
+  else hipLaunchKernelGGL(ab::attn_bf16_fwd_kernel, grid, dim3(256), 0, st, a);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -285,7 +306,7 @@ static int attn16_fwd_launch(const void* qkv16, const void* pk16, const void* pv
 static int attn16_bwd_launch(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16, const float* addmask,
                              const int* cu, int pad_rows, const void* ctx16, const float* lse, void* dqkv16, float* dpk, float* dpv, float* partq,
                              float* partkv, int B, int S, int P, int NH, int head_dim, float p_drop, uint64_t seed, uint64_t offset,
-                             hipStream_t st, int zero_tail = 0) {
+                             hipStream_t st, int zero_tail = 0, const float* pmask = nullptr) {
   if (head_dim != D) return MTVAF_ERR_SHAPE;
   ab::Args a{};
   a.zero_tail = zero_tail;
@@ -301,7 +322,9 @@ static int attn16_bwd_launch(const void* dctx16, const void* qkv16, const void* 
   if (((uintptr_t)dctx16 | (uintptr_t)ctx16 | (uintptr_t)dqkv16) & 15) return MTVAF_ERR_ALIGN;
   if (pad_rows < 0 || (pad_rows && !cu)) return MTVAF_ERR_ARG;
   const int nq = (S + 63) / 64;
-  hipLaunchKernelGGL(ab::attn_bf16_bwd_kernel, dim3(nq + (P + S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0)), dim3(256), 0, st, a, nq);
+  const dim3 grid(nq + (P + S + 63) / 64, NH, B + (pad_rows > 0 ? 1 : 0));
+  if (pmask) hipLaunchKernelGGL(ab::attn_bf16_bwd_pm_kernel, grid, dim3(256), 0, st, a, nq, pmask);
+  else hipLaunchKernelGGL(ab::attn_bf16_bwd_kernel, grid, dim3(256), 0, st, a, nq);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -353,6 +376,26 @@ int mtvaf_prefix_attn_bf16_varlen_bwd(const void* dctx16, const void* qkv16, con
   if (!cu) return MTVAF_ERR_ARG;
   return attn16_bwd_launch(dctx16, qkv16, pk16, pv16, nullptr, cu, pad_rows, ctx16, lse, dqkv16, dpk, dpv, partq, partkv, B, S, P, NH,
                            head_dim, p_drop, seed, offset, st);
+}
+
+// ... with a per-sentence prefix-slot mask (see mtvaf_prefix_attn_varlen_fwd_pm): pmask [B, P] fp32 additive, pmask_len = B * P;
+// pmask == NULL: the launch of mtvaf_prefix_attn_bf16_varlen_fwd / _bwd.
+int mtvaf_prefix_attn_bf16_varlen_fwd_pm(const void* qkv16, const void* pk16, const void* pv16, const int* cu, int pad_rows,
+                                         const float* pmask, long pmask_len, void* ctx16, float* lse, int B, int S, int P, int NH,
+                                         int head_dim, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st) {
+  if (!cu) return MTVAF_ERR_ARG;
+  if (pmask && (P <= 0 || B <= 0 || pmask_len != (long)B * P)) return MTVAF_ERR_ARG;
+  return attn16_fwd_launch(qkv16, pk16, pv16, nullptr, cu, pad_rows, ctx16, lse, B, S, P, NH, head_dim, p_drop, seed, offset, st, pmask);
+}
+
+int mtvaf_prefix_attn_bf16_varlen_bwd_pm(const void* dctx16, const void* qkv16, const void* pk16, const void* pv16, const int* cu,
+                                         int pad_rows, const float* pmask, long pmask_len, const void* ctx16, const float* lse,
+                                         void* dqkv16, float* dpk, float* dpv, float* partq, float* partkv, int B, int S, int P, int NH,
+                                         int head_dim, float p_drop, uint64_t seed, uint64_t offset, hipStream_t st) {
+  if (!cu) return MTVAF_ERR_ARG;
+  if (pmask && (P <= 0 || B <= 0 || pmask_len != (long)B * P)) return MTVAF_ERR_ARG;
+  return attn16_bwd_launch(dctx16, qkv16, pk16, pv16, nullptr, cu, pad_rows, ctx16, lse, dqkv16, dpk, dpv, partq, partkv, B, S, P, NH,
+                           head_dim, p_drop, seed, offset, st, 0, pmask);
 }
 
 }  // extern "C"

@@ -241,10 +241,29 @@ __global__ __launch_bounds__(256, 2) void attn_f32s_bwd_kernel(AttnArgs a, int n
   attn_bwd_body<Split3>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot);
 }
 
+// ... with a per-sentence prefix-slot mask on packed rows (mask_at<PM>; pmask is an argument of its own: the kernels above keep
+// their argument block and their code)
+__global__ __launch_bounds__(256) void attn_f32s_fwd_pm_kernel(AttnArgs a, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) unsigned char Ks[TILE_B];
+  __shared__ __attribute__((aligned(16))) unsigned char Vs[TILE_B];
+  __shared__ __attribute__((aligned(16))) float Ms[KT];
+  __shared__ int t_eff_slot;
+  attn_fwd_body<Split3, true>(a, Ks, Vs, Ms, &t_eff_slot, pmask);
+}
+
+__global__ __launch_bounds__(256, 2) void attn_f32s_bwd_pm_kernel(AttnArgs a, int nq, const float* pmask) {
+  __shared__ __attribute__((aligned(16))) unsigned char tile0[TILE_B];
+  __shared__ __attribute__((aligned(16))) unsigned char tile1[TILE_B];
+  __shared__ __attribute__((aligned(16))) float small[3 * KT];
+  __shared__ int t_eff_slot;
+  attn_bwd_body<Split3, true>(a, nq, tile0, tile1, small, nullptr, &t_eff_slot, pmask);
+}
+
 }  // namespace as3
 
-int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL(as3::attn_f32s_fwd_kernel, grid, dim3(256), 0, st, a);
+int launch_attn_f32s_fwd(const AttnArgs& a, dim3 grid, hipStream_t st, const float* pmask) {
+  if (pmask) hipLaunchKernelGGL(as3::attn_f32s_fwd_pm_kernel, grid, dim3(256), 0, st, a, pmask);
+  else hipLaunchKernelGGL(as3::attn_f32s_fwd_kernel, grid, dim3(256), 0, st, a);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
@@ -253,8 +272,9 @@ int launch_attn_f32s_probs(const AttnArgs& a, const ProbsOut& o, dim3 grid, hipS
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }
-int launch_attn_f32s_bwd(const AttnArgs& a, int nq, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL(as3::attn_f32s_bwd_kernel, grid, dim3(256), 0, st, a, nq);
+int launch_attn_f32s_bwd(const AttnArgs& a, int nq, dim3 grid, hipStream_t st, const float* pmask) {
+  if (pmask) hipLaunchKernelGGL(as3::attn_f32s_bwd_pm_kernel, grid, dim3(256), 0, st, a, nq, pmask);
+  else hipLaunchKernelGGL(as3::attn_f32s_bwd_kernel, grid, dim3(256), 0, st, a, nq);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

@@ -67,9 +67,9 @@ __device__ __forceinline__ void kv_sources(const Args& a, const Sent& sn, int b,
 // forward: grid (ceil(S/64), NH, B [+ 1]), 256 threads; wave w owns queries q0 + 16 w .. + 15
 // Ms [KT]: additive mask * log2(e) of the tile's keys (-1e30 beyond T)
 // ---------------------------------------------------------------------------------------------
-template <class A>
+template <class A, bool PM = false>
 __device__ __forceinline__ void attn_fwd_body(const typename A::Args& a, typename A::RowTile Ks, typename A::ColTile Vs, float* Ms,
-                                              int* t_eff_slot) {
+                                              int* t_eff_slot, const float* pmask = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lq = lane & 15, g = lane >> 4;
   int bx = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
@@ -114,7 +114,7 @@ __device__ __forceinline__ void attn_fwd_body(const typename A::Args& a, typenam
   auto fetch = [&](int t0) {
     A::fetch_kv(kst, ksrc, a.P, T, ldt, t0);
     A::fetch_kv(vst, vsrc, a.P, T, ldt, t0);
-    if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
+    if (threadIdx.x < KT) mreg = mask_at<PM>(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1), pmask);
   };
   if constexpr (A::FWD_FETCH_AHEAD) fetch(0);
   for (int t0 = 0; t0 < T; t0 += KT) {
@@ -302,9 +302,10 @@ __device__ __forceinline__ void attn_probs_body(const typename A::Args& a, const
 // backward, query side: dQ for 64 queries per block; loop over key tiles as in the forward.  What leaves the block beside dQ is the
 // arithmetic's (its output hooks: delta = rowsum(dO.O), or the column sums of dQ through red)
 // ---------------------------------------------------------------------------------------------
-template <class A>
+template <class A, bool PM = false>
 __device__ __forceinline__ void attn_bwd_dq_body(const typename A::Args& a, int qtile, int b, int h, typename A::ColTile Ks,
-                                                 typename A::RowTile Vs, float* Ms, float* red, int* t_eff_slot) {
+                                                 typename A::RowTile Vs, float* Ms, float* red, int* t_eff_slot,
+                                                 const float* pmask = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lq = lane & 15, g = lane >> 4;
   const int q = qtile * 64 + wave * 16 + lq;
@@ -362,7 +363,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const typename A::Args& a, int 
   auto fetch = [&](int t0) {
     A::fetch_kv(kst, ksrc, a.P, T, ldt, t0);
     A::fetch_kv(vst, vsrc, a.P, T, ldt, t0);
-    if (threadIdx.x < KT) mreg = mask_at(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1));
+    if (threadIdx.x < KT) mreg = mask_at<PM>(a, b, Tf, min(t0 + (int)threadIdx.x, T - 1), pmask);
   };
   fetch(0);
   for (int t0 = 0; t0 < T; t0 += KT) {
@@ -413,10 +414,10 @@ __device__ __forceinline__ void attn_bwd_dq_body(const typename A::Args& a, int 
 // matching O rows so that this side does not depend on the query side (both run in one launch); rh_s [KT] = dropout row hashes of
 // the tile's queries.  Output hook: the column sums of dK | dV over the block's text keys (through red).
 // ---------------------------------------------------------------------------------------------
-template <class A>
+template <class A, bool PM = false>
 __device__ __forceinline__ void attn_bwd_dkv_body(const typename A::Args& a, int ktile, int b, int h, typename A::ColTile Qs,
                                                   typename A::ColTile dOs, float* lse_s, float* del_s, uint32_t* rh_s, float* red,
-                                                  int* t_eff_slot) {
+                                                  int* t_eff_slot, const float* pmask = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lk = lane & 15, g = lane >> 4;
   const Sent sn = sentence(a, b);
@@ -440,7 +441,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const typename A::Args& a, int
   const bool wave_live = (int)(ktile * 64 + wave * 16) < T;
   const int keyc = min(key, T - 1);
   const float inv_keep = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
-  const float mval2 = kok ? mask_at(a, b, Tf, key) * LOG2E : NEG_BIG;  // keys beyond T: probability exactly 0
+  const float mval2 = kok ? mask_at<PM>(a, b, Tf, key, pmask) * LOG2E : NEG_BIG;  // keys beyond T: probability exactly 0
   const float sc2 = a.scale * LOG2E;
   const uint32_t cterm = (uint32_t)key * ATTN_DROP_C2;
 
@@ -548,9 +549,9 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const typename A::Args& a, int
 // sides are independent (the key side recomputes delta), so they share the machine and need neither atomics nor a second stream.
 // tile0, tile1: two LDS tiles of the arithmetic; small [3 KT] floats; red: what the arithmetic's column-sum hooks reduce through
 // ([8 * 64] floats, or NULL where they are empty).
-template <class A>
+template <class A, bool PM = false>
 __device__ __forceinline__ void attn_bwd_body(const typename A::Args& a, int nq, typename A::Lds* tile0, typename A::Lds* tile1,
-                                              float* small, float* red, int* t_eff_slot) {
+                                              float* small, float* red, int* t_eff_slot, const float* pmask = nullptr) {
   if (a.cu && (int)blockIdx.z == a.B) {  // (block-uniform) zero dQ | dK | dV of the rows that pad the packed image
     const int r0 = a.cu[a.B], h = blockIdx.y;
     for (int r = blockIdx.x * 16 + (threadIdx.x >> 4); r < a.pad_rows; r += gridDim.x * 16)
@@ -563,10 +564,10 @@ __device__ __forceinline__ void attn_bwd_body(const typename A::Args& a, int nq,
   if constexpr (A::XCD_GROUP) xcd_group(gridDim.x, gridDim.y, a.B, bx, h, b);
   b = slot_sentence(a, b);
   if (bx < nq) {
-    attn_bwd_dq_body<A>(a, bx, b, h, typename A::ColTile{tile0}, typename A::RowTile{tile1}, small, red, t_eff_slot);
+    attn_bwd_dq_body<A, PM>(a, bx, b, h, typename A::ColTile{tile0}, typename A::RowTile{tile1}, small, red, t_eff_slot, pmask);
   } else {
-    attn_bwd_dkv_body<A>(a, bx - nq, b, h, typename A::ColTile{tile0}, typename A::ColTile{tile1}, small, small + KT,
-                         reinterpret_cast<uint32_t*>(small + 2 * KT), red, t_eff_slot);
+    attn_bwd_dkv_body<A, PM>(a, bx - nq, b, h, typename A::ColTile{tile0}, typename A::ColTile{tile1}, small, small + KT,
+                             reinterpret_cast<uint32_t*>(small + 2 * KT), red, t_eff_slot, pmask);
   }
 }
 

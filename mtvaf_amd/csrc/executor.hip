@@ -125,7 +125,10 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
   if (L->bf16) {
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KC, L->x_h, H, L->wqkv_h, H, nullptr, 0, L->qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE,
                                nullptr, 0, 0, nullptr, 0, nullptr, 0, 0, -1, 0, st));
-    if (L->cu) {
+    if (L->cu && L->pmask) {  // (a per-sentence prefix-slot mask: the same launch through mask_at<PM>)
+      MTVAF_TRY(mtvaf_prefix_attn_bf16_varlen_fwd_pm(L->qkv, L->pk, L->pv, L->cu, L->Mp - L->Mv, L->pmask, (long)L->B * L->P, L->cx, L->lse,
+                                                     L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset, st));
+    } else if (L->cu) {
       // (the rows that pad the packed image belong to no sentence: an extra slice of the launch zero-fills them)
       MTVAF_TRY(mtvaf_prefix_attn_bf16_varlen_fwd(L->qkv, L->pk, L->pv, L->cu, L->Mp - L->Mv, L->cx, L->lse, L->B, L->S, L->P, L->NH, 64,
                                                   L->p_attn, L->seed, L->offset, st));
@@ -154,9 +157,15 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
     // image -- weights written once per optimizer step, activations by the kernel that produces them (the attention forward, the
     // LayerNorms and the FFN-1 epilogue write plane images themselves)
     MTVAF_TRY(p16(0, L->x_p, L->wqkv_h, qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE, nullptr, 0, 0, L->ws, L->ws_bytes, nullptr, st));
-    MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_planes(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                                  L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset,
-                                                  L->cx_p, M, st));
+    if (L->pmask) {
+      MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_pm(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                L->Mp - L->Mv, L->pmask, (long)L->B * L->P, cx, L->lse, L->B, L->S, L->P, L->NH, 64,
+                                                L->p_attn, L->seed, L->offset, L->cx_p, M, st));
+    } else {
+      MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_planes(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                    L->Mp - L->Mv, cx, L->lse, L->B, L->S, L->P, L->NH, 64, L->p_attn, L->seed, L->offset,
+                                                    L->cx_p, M, st));
+    }
     MTVAF_TRY(dense_ln_fwd_p(L->cx_p, H, L->wo_h, L->bo, L->a, L->x, L->g1, L->b1, L->h1, L->mean1, L->rstd1, M, H, L->eps, L->p_hidden,
                              L->seed, L->offset + 1, L->ws, L->ws_bytes, L->h1_p, st));
     // (the GELU output is read by GEMMs only: it leaves the FFN-1 epilogue as a plane image, no fp32 copy -- L->act is not read)
@@ -168,7 +177,11 @@ int mtvaf_encoder_layer_fwd(const mtvaf_layer_t* L, hipStream_t st) {
   // (plain-bias products may use the deterministic split-K: the planner only splits when the tile grid underfills the chip)
   MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KC, L->x, H, L->wqkv, H, qkv, 3 * H, M, 3 * H, H, L->bqkv, MTVAF_EPI_NONE, nullptr, 0, 0, 1, L->ws,
                            L->ws_bytes, -1, -1, st));
-  if (L->cu) {
+  if (L->cu && L->pmask) {
+    MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd_pm(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                              L->Mp - L->Mv, L->pmask, (long)L->B * L->P, cx, L->lse, L->B, L->S, L->P, L->NH, 64,
+                                              L->p_attn, L->seed, L->offset, nullptr, 0, st));
+  } else if (L->cu) {
     // the rows that pad the packed image belong to no sentence: an extra slice of the launch zero-fills them (0 x NaN of an
     // unwritten row would poison dW)
     MTVAF_TRY(mtvaf_prefix_attn_varlen_fwd(qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
@@ -260,7 +273,11 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
                                nullptr, 1, g->ws_side, g->ws_side_bytes, 0, -1, 0, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_bf16x(MTVAF_KC, MTVAF_KM, g->da, H, L->wo_h, H, nullptr, 0, g->dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0,
                                nullptr, 0, nullptr, 0, 0, -1, 0, mainS));
-    if (L->cu) {
+    if (L->cu && L->pmask) {
+      MTVAF_TRY(mtvaf_prefix_attn_bf16_varlen_bwd_pm(g->dctx, L->qkv, L->pk, L->pv, L->cu, L->Mp - L->Mv, L->pmask, (long)B * P, L->cx,
+                                                     L->lse, g->dqkv, g->dpk, g->dpv, g->partq, g->partkv, B, S, P, NH, 64, L->p_attn,
+                                                     L->seed, L->offset, mainS));
+    } else if (L->cu) {
       MTVAF_TRY(mtvaf_prefix_attn_bf16_varlen_bwd(g->dctx, L->qkv, L->pk, L->pv, L->cu, L->Mp - L->Mv, L->cx, L->lse, g->dqkv, g->dpk,
                                                   g->dpv, g->partq, g->partkv, B, S, P, NH, 64, L->p_attn, L->seed, L->offset, mainS));
     } else {
@@ -309,9 +326,15 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
                                                      L->mean1, L->rstd1, nullptr, g->dh, 0, M, H, L->p_hidden, L->seed, L->offset + 1,
                                                      g->lnpart1, g->da_p, mainS));
       MTVAF_TRY(p16(1, g->da_p, L->wo_h, dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, g->ws_main, g->ws_main_bytes, nullptr, mainS));
-      MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_planes(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
-                                                    L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
-                                                    L->seed, L->offset, g->dqkv_p, M, mainS));
+      if (L->pmask) {
+        MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_pm(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                  L->Mp - L->Mv, L->pmask, (long)B * P, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P,
+                                                  NH, 64, L->p_attn, L->seed, L->offset, g->dqkv_p, M, mainS));
+      } else {
+        MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_planes(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                      L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
+                                                      L->seed, L->offset, g->dqkv_p, M, mainS));
+      }
       MTVAF_TRY(fork_to(mainS, side));
       // second stream: the four weight gradients as ONE launch.  The small reductions of the layer are COLUMN-SUM JOBS of it -- extra
       // blocks that fill the CUs its last round of tiles leaves idle: the QKV bias gradient = column sums of dQ|dK|dV, the FFN-1 bias
@@ -375,7 +398,11 @@ int mtvaf_encoder_layer_bwd(const mtvaf_layer_t* L, const mtvaf_layer_grads_t* g
                              g->ws_side_bytes, -1, -1, g->klist, g->kcnt, side));
     MTVAF_TRY(mtvaf_gemm_f32(MTVAF_KC, MTVAF_KM, da, H, L->wo, H, dctx, H, M, H, H, nullptr, MTVAF_EPI_NONE, nullptr, 0, 0, 1, g->ws_main,
                              g->ws_main_bytes, -1, -1, mainS));
-    if (L->cu) {
+    if (L->cu && L->pmask) {
+      MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd_pm(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
+                                                L->Mp - L->Mv, L->pmask, (long)B * P, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P,
+                                                NH, 64, L->p_attn, L->seed, L->offset, nullptr, 0, mainS));
+    } else if (L->cu) {
       MTVAF_TRY(mtvaf_prefix_attn_varlen_bwd(dctx, qkv, static_cast<const float*>(L->pk), static_cast<const float*>(L->pv), L->cu,
                                              L->Mp - L->Mv, cx, L->lse, g->delta, dqkv, g->dpk, g->dpv, B, S, P, NH, 64, L->p_attn,
                                              L->seed, L->offset, mainS));

@@ -206,6 +206,30 @@ __global__ void mean_rows_kernel(const float* __restrict__ row_loss, float* __re
   if (threadIdx.x == 0) *loss = s / B;
 }
 
+// ... over the rows that are present (present[b] != 0): sum of their terms / their number; 0 when none is.  All present: the sum,
+// its order and the divisor of mean_rows_kernel.
+__global__ void masked_mean_rows_kernel(const float* __restrict__ row_loss, const float* __restrict__ present, float* __restrict__ loss,
+                                        int B) {
+  float s = 0.f, n = 0.f;
+  for (int b = threadIdx.x; b < B; b += 64) {
+    const bool on = present[b] != 0.f;
+    s += on ? row_loss[b] : 0.f;
+    n += on ? 1.f : 0.f;
+  }
+  s = wave_sum(s);
+  n = wave_sum(n);
+  if (threadIdx.x == 0) *loss = n > 0.f ? s / n : 0.f;
+}
+// dlogits[r][:] (computed with the factor 1 / B) *= present[r] ? B / n : 0, n = the number of present rows (all present: * 1)
+__global__ __launch_bounds__(256) void scale_rows_present_kernel(float* __restrict__ dlogits, const float* __restrict__ present, int B,
+                                                                int N) {
+  const int r = blockIdx.x;
+  float n = 0.f;
+  for (int b = 0; b < B; ++b) n += present[b] != 0.f ? 1.f : 0.f;
+  const float f = present[r] != 0.f ? (float)B / n : 0.f;
+  for (int i = threadIdx.x; i < N; i += 256) dlogits[(long)r * N + i] *= f;
+}
+
 // out[n][c] = mean_l enc[n][l][c]   (prefix_guids.mean(dim=1), bert_model.py:550)  / and its backward
 __global__ void mean_l_kernel(const float* __restrict__ enc, float* __restrict__ out, long n, int L, int W4) {
   const long tot = n * (W4 / 4);
@@ -310,6 +334,28 @@ int mtvaf_kl_logsoftmax_fwd(const float* logits, const float* target, float* los
   hipLaunchKernelGGL(kl_logsoftmax_kernel, dim3(B), dim3(256), 0, st, logits, target, row_ws, (float*)nullptr,
                      (const float*)nullptr, 1.f, B, N);
   hipLaunchKernelGGL(mean_rows_kernel, dim3(1), dim3(64), 0, st, row_ws, loss, B);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+int mtvaf_kl_logsoftmax_masked_fwd(const float* logits, const float* target, const float* present, float* loss, float* row_ws,
+                                   int B, int N, hipStream_t st) {
+  if (B <= 0 || N <= 0) return MTVAF_ERR_SHAPE;
+  if (!present) return MTVAF_ERR_ARG;
+  hipLaunchKernelGGL(kl_logsoftmax_kernel, dim3(B), dim3(256), 0, st, logits, target, row_ws, (float*)nullptr,
+                     (const float*)nullptr, 1.f, B, N);
+  hipLaunchKernelGGL(masked_mean_rows_kernel, dim3(1), dim3(64), 0, st, row_ws, present, loss, B);
+  MTVAF_LAUNCH_CHECK();
+  return MTVAF_OK;
+}
+
+int mtvaf_kl_logsoftmax_masked_bwd(const float* grad_out, float gscale, const float* logits, const float* target,
+                                   const float* present, float* dlogits, int B, int N, hipStream_t st) {
+  if (B <= 0 || N <= 0) return MTVAF_ERR_SHAPE;
+  if (!present) return MTVAF_ERR_ARG;
+  hipLaunchKernelGGL(kl_logsoftmax_kernel, dim3(B), dim3(256), 0, st, logits, target, (float*)nullptr, dlogits, grad_out,
+                     gscale, B, N);
+  hipLaunchKernelGGL(scale_rows_present_kernel, dim3(B), dim3(256), 0, st, dlogits, present, B, N);
   MTVAF_LAUNCH_CHECK();
   return MTVAF_OK;
 }

@@ -381,6 +381,7 @@ CHECK_CONTRACT = os.environ.get("MTVAF_CHECK_CONTRACT", "0") == "1"
 # launch lasts as long as its busiest CU, and in sorted order a CU's blocks come from the long, middle and short third of the
 # batch).
 LAST_PACK = None  # the Packing of the most recent native forward (None: it ran padded)
+LAST_PMASK = None  # its prefix-slot mask [B, P] (None: the attention launches carried none -- padded, or no slot masked)
 _PENDING_PACK = None  # packing started by Packing.begin, consumed by the next Packing.build
 _PACK_HOST = {}
 _layouts = {}
@@ -481,6 +482,18 @@ class Packing:
         hip._ck(hip.lib().mtvaf_gather_rows(hip._p(xp), hip._p(self.inv), hip._p(out), self.B * self.S, xp.shape[1], hip._st()),
                 "mtvaf_gather_rows")
         return out
+
+
+def _prefix_slot_mask(addmask: torch.Tensor, Pn: int, cfg) -> Optional[torch.Tensor]:
+    """The per-sentence prefix-slot mask of a PACKED run: the prefix columns of addmask as a contiguous [B,P] tensor (the packed
+    attention launches read no addmask; csrc/attention_args.h, mask_at<PM>), or None when every sentence owns all P slots.
+    Decided without a host sync by the caller's word, cfg[6]: False = the prefix columns are all present (TVNetSAModel2 without a
+    prefix mask: nothing is allocated, the launches are the unmasked ones), True = some are masked, None / absent = unknown (a
+    direct BertModel / BertEncoder call with an attention_mask of its own): the mask is passed on -- an all-present mask gives the
+    bits of the unmasked launch."""
+    if not Pn or (len(cfg) > 6 and cfg[6] is False):
+        return None
+    return addmask[:, :Pn].contiguous()
 
 
 def attention_maps(h_in: torch.Tensor, w: "LayerWeights", pk: Optional[torch.Tensor], addmask: torch.Tensor, NH: int,
@@ -605,6 +618,7 @@ def _native_forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, params):
     dev = x.device
     # (the caller vouches that nothing downstream reads hidden states at masked positions: cfg[5], BertModel.allow_unpad)
     pack = Packing.build(addmask, Pn, B, S, H, I) if (UNPAD and len(cfg) > 5 and cfg[5]) else None
+    pmask = _prefix_slot_mask(addmask, Pn, cfg) if pack is not None else None
     if pack is not None:
         x = pack.pack(x)
         M = pack.Mp
@@ -643,6 +657,7 @@ def _native_forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, params):
         st = _layer_struct(w, B, S, Pn, NH, H, I, use_h, eps, p_hidden, p_attn, seed, planes)
         st.offset = off
         st.cu, st.Mv, st.Mp = (pack.cu.data_ptr(), pack.Mv, pack.Mp) if pack is not None else (None, 0, 0)
+        st.pmask = pmask.data_ptr() if pmask is not None else None
         st.x, st.x_h, st.addmask = x_ptr, xh_ptr, am_ptr
         st.pk = (pk_ptr + li * pk_layer) if Pn else None
         st.pv = (pk_ptr + li * pk_layer + pk_step) if Pn else None
@@ -671,10 +686,11 @@ def _native_forward(ctx, h0, pkv, addmask, cfg, weights, grad_sink, params):
     ctx.stash = (offs, weights, pkv, addmask, cfg, seed, (B, S, H, Pn), grad_sink, params)
     ctx.native = (use_h, pkv_k if (use_h and Pn) else None)
     ctx.pack = pack
+    ctx.pmask = pmask
     if getattr(ctx, "mix", None) is not None:  # (EncoderMixFunction: the fp32 residual-stream states, packed rows in a packed run)
         ctx.mix_states = [x] + [a[o_h2:o_h2 + M * H * 4].view(torch.float32).view(M, H) for a in arenas]
-    global LAST_PACK
-    LAST_PACK = pack
+    global LAST_PACK, LAST_PMASK
+    LAST_PACK, LAST_PMASK = pack, pmask
     if pack is not None and L > 1:
         ctx.mark_non_differentiable(*outs[:-1])
     if grad_sink is not None:
@@ -731,6 +747,7 @@ def _native_backward(ctx, douts):
     arenas = saved[2:] if (use_h or planes) else saved[1:]
     NH, eps, p_hidden, p_attn = cfg[:4]
     pack = ctx.pack
+    pmask = getattr(ctx, "pmask", None) if pack is not None else None
     L, M = len(weights), (pack.Mp if pack is not None else B * S)
     I = weights[0].w1.shape[0]
     dev = x0.device
@@ -838,6 +855,7 @@ def _native_backward(ctx, douts):
         st = _layer_struct(w, B, S, Pn, NH, H, I, use_h, eps, p_hidden, p_attn, seed, planes)
         st.offset = offs[li]
         st.cu, st.Mv, st.Mp = (pack.cu.data_ptr(), pack.Mv, pack.Mp) if pack is not None else (None, 0, 0)
+        st.pmask = pmask.data_ptr() if pmask is not None else None
         base = arenas[li].data_ptr()
         for name, o in flay:
             setattr(st, name, base + o if o >= 0 else None)
@@ -1727,16 +1745,26 @@ class WordPoolFunction(torch.autograd.Function):
 
 
 class KLFunction(torch.autograd.Function):
-    """KLDivLoss(reduction='batchmean')(log_softmax(logits), target) -> 0-dim tensor."""
+    """KLDivLoss(reduction='batchmean')(log_softmax(logits), target) -> 0-dim tensor.  ``present`` [B] fp32 (1 / 0), or None: the
+    mean over the rows that are present -- an absent row adds nothing, the divisor counts the present ones (0 when none is); all
+    present gives the bits of the call without it (the VAO loss of sentences without an image)."""
 
     @staticmethod
-    def forward(ctx, logits, target):
+    def forward(ctx, logits, target, present=None):
         B, N = logits.shape
         z, t = logits.contiguous(), target.contiguous().float()
         loss, row = _empty(1, like=z), _empty(B, like=z)
-        hip._ck(hip.lib().mtvaf_kl_logsoftmax_fwd(hip._p(z), hip._p(t), hip._p(loss), hip._p(row), B, N, hip._st()),
-                "mtvaf_kl_logsoftmax_fwd")
+        if present is None:
+            hip._ck(hip.lib().mtvaf_kl_logsoftmax_fwd(hip._p(z), hip._p(t), hip._p(loss), hip._p(row), B, N, hip._st()),
+                    "mtvaf_kl_logsoftmax_fwd")
+        else:
+            present = present.detach().to(torch.float32).contiguous()
+            if tuple(present.shape) != (B,):
+                raise ValueError(f"present is {tuple(present.shape)}, expected ({B},)")
+            hip._ck(hip.lib().mtvaf_kl_logsoftmax_masked_fwd(hip._p(z), hip._p(t), hip._p(present), hip._p(loss), hip._p(row), B, N,
+                                                             hip._st()), "mtvaf_kl_logsoftmax_masked_fwd")
         ctx.stash = (z, t)
+        ctx.present = present
         return loss.view(())
 
     @staticmethod
@@ -1745,9 +1773,13 @@ class KLFunction(torch.autograd.Function):
         B, N = z.shape
         g = gout.contiguous().view(1).float()
         dz = torch.empty_like(z)
-        hip._ck(hip.lib().mtvaf_kl_logsoftmax_bwd(hip._p(g), 1.0, hip._p(z), hip._p(t), hip._p(dz), B, N, hip._st()),
-                "mtvaf_kl_logsoftmax_bwd")
-        return dz, None
+        if ctx.present is None:
+            hip._ck(hip.lib().mtvaf_kl_logsoftmax_bwd(hip._p(g), 1.0, hip._p(z), hip._p(t), hip._p(dz), B, N, hip._st()),
+                    "mtvaf_kl_logsoftmax_bwd")
+        else:
+            hip._ck(hip.lib().mtvaf_kl_logsoftmax_masked_bwd(hip._p(g), 1.0, hip._p(z), hip._p(t), hip._p(ctx.present), hip._p(dz), B, N,
+                                                             hip._st()), "mtvaf_kl_logsoftmax_masked_bwd")
+        return dz, None, None
 
 
 # -------------------------------------------------------------------------------------------------

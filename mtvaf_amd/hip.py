@@ -61,6 +61,10 @@ _SIGS = {
     "mtvaf_prefix_attn_varlen_bwd": (c_int, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_varlen_fwd_planes": (c_int, [P, P, P, P, I, P, P, I, I, I, I, I, F, U64, U64, P, I, P]),
     "mtvaf_prefix_attn_varlen_bwd_planes": (c_int, [P, P, P, P, P, I, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P, I, P]),
+    "mtvaf_prefix_attn_varlen_fwd_pm": (c_int, [P, P, P, P, I, P, L, P, P, I, I, I, I, I, F, U64, U64, P, I, P]),
+    "mtvaf_prefix_attn_varlen_bwd_pm": (c_int, [P, P, P, P, P, I, P, L, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P, I, P]),
+    "mtvaf_prefix_attn_bf16_varlen_fwd_pm": (c_int, [P, P, P, P, I, P, L, P, P, I, I, I, I, I, F, U64, U64, P]),
+    "mtvaf_prefix_attn_bf16_varlen_bwd_pm": (c_int, [P, P, P, P, P, I, P, L, P, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_bf16_varlen_fwd": (c_int, [P, P, P, P, I, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_prefix_attn_bf16_varlen_bwd": (c_int, [P, P, P, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, F, U64, U64, P]),
     "mtvaf_gather_rows": (c_int, [P, P, P, I, I, P]),
@@ -97,6 +101,8 @@ _SIGS = {
     "mtvaf_prompt_mix_bwd_gate": (c_int, [P, P, P, P, P, P, I, I, I, I, I, P]),
     "mtvaf_prompt_mix_bwd_enc": (c_int, [P, P, P, P, I, I, I, I, I, P]),
     "mtvaf_kl_logsoftmax_fwd": (c_int, [P, P, P, P, I, I, P]),
+    "mtvaf_kl_logsoftmax_masked_fwd": (c_int, [P, P, P, P, P, I, I, P]),
+    "mtvaf_kl_logsoftmax_masked_bwd": (c_int, [P, F, P, P, P, P, I, I, P]),
     "mtvaf_kl_logsoftmax_bwd": (c_int, [P, F, P, P, P, I, I, P]),
     "mtvaf_mean_l_fwd": (c_int, [P, P, L, I, I, P]),
     "mtvaf_mean_l_bwd": (c_int, [P, P, L, I, I, P]),
@@ -207,7 +213,7 @@ class LayerStruct(ctypes.Structure):
                                          "bi1", "bi2", "g2", "b2", "x", "x_h", "pk", "pv", "addmask", "qkv", "cx", "lse", "a",
                                          "h1", "h1_h", "mean1", "rstd1", "pre", "act", "f", "h2", "h2_h", "mean2", "rstd2",
                                          "ws")] + [("ws_bytes", c_size_t), ("cu", c_void_p), ("Mv", c_int), ("Mp", c_int)] +
-                [(n, c_void_p) for n in ("x_p", "cx_p", "h1_p", "act_p", "h2_p")])
+                [(n, c_void_p) for n in ("x_p", "cx_p", "h1_p", "act_p", "h2_p", "pmask")])
 
 
 class LayerGradsStruct(ctypes.Structure):
@@ -724,6 +730,42 @@ def prefix_attn_bf16_varlen_bwd(dctx16, qkv16, pk16, pv16, cu, pad_rows, ctx16, 
     _ck(lib().mtvaf_prefix_attn_bf16_varlen_bwd(_p(dctx16), _p(qkv16), _p(pk16), _p(pv16), _p(cu), int(pad_rows), _p(ctx16),
                                                 _p(lse), _p(dqkv16), _p(dpk), _p(dpv), _p(partq), _p(partkv), B, S, Pn, NH, 64,
                                                 float(p), seed, offset, _st()), "mtvaf_prefix_attn_bf16_varlen_bwd")
+
+
+def _pmask_len(pmask):
+    if pmask is not None:
+        _f32(pmask)
+    return 0 if pmask is None else pmask.numel()
+
+
+def prefix_attn_varlen_fwd_pm(qkv, pk, pv, cu, pad_rows, pmask, ctx, lse, B, S, Pn, NH, p, seed, offset, ctx_planes=None, rows=0):
+    """prefix_attn_varlen_fwd with a per-sentence prefix-slot mask: pmask [B,P] fp32 additive (0 = slot present, -10000 = absent;
+    the prefix columns of the padded layout's addmask), or None for the unmasked launch.  ctx_planes: the plane image, as the
+    _planes form, or None."""
+    _ck(lib().mtvaf_prefix_attn_varlen_fwd_pm(_p(qkv), _p(pk), _p(pv), _p(cu), int(pad_rows), _p(pmask), _pmask_len(pmask), _p(ctx),
+                                              _p(lse), B, S, Pn, NH, 64, float(p), seed, offset, _p(ctx_planes), int(rows), _st()),
+        "mtvaf_prefix_attn_varlen_fwd_pm")
+
+
+def prefix_attn_varlen_bwd_pm(dctx, qkv, pk, pv, cu, pad_rows, pmask, ctx, lse, delta, dqkv, dpk, dpv, B, S, Pn, NH, p, seed, offset,
+                              dqkv_planes=None, rows=0):
+    _ck(lib().mtvaf_prefix_attn_varlen_bwd_pm(_p(dctx), _p(qkv), _p(pk), _p(pv), _p(cu), int(pad_rows), _p(pmask), _pmask_len(pmask),
+                                              _p(ctx), _p(lse), _p(delta), _p(dqkv), _p(dpk), _p(dpv), B, S, Pn, NH, 64, float(p), seed,
+                                              offset, _p(dqkv_planes), int(rows), _st()), "mtvaf_prefix_attn_varlen_bwd_pm")
+
+
+def prefix_attn_bf16_varlen_fwd_pm(qkv16, pk16, pv16, cu, pad_rows, pmask, ctx16, lse, B, S, Pn, NH, p, seed, offset):
+    _ck(lib().mtvaf_prefix_attn_bf16_varlen_fwd_pm(_p(qkv16), _p(pk16), _p(pv16), _p(cu), int(pad_rows), _p(pmask), _pmask_len(pmask),
+                                                   _p(ctx16), _p(lse), B, S, Pn, NH, 64, float(p), seed, offset, _st()),
+        "mtvaf_prefix_attn_bf16_varlen_fwd_pm")
+
+
+def prefix_attn_bf16_varlen_bwd_pm(dctx16, qkv16, pk16, pv16, cu, pad_rows, pmask, ctx16, lse, dqkv16, dpk, dpv, partq, partkv, B, S,
+                                   Pn, NH, p, seed, offset):
+    _ck(lib().mtvaf_prefix_attn_bf16_varlen_bwd_pm(_p(dctx16), _p(qkv16), _p(pk16), _p(pv16), _p(cu), int(pad_rows), _p(pmask),
+                                                   _pmask_len(pmask), _p(ctx16), _p(lse), _p(dqkv16), _p(dpk), _p(dpv), _p(partq),
+                                                   _p(partkv), B, S, Pn, NH, 64, float(p), seed, offset, _st()),
+        "mtvaf_prefix_attn_bf16_varlen_bwd_pm")
 
 
 def prefix_attn_bf16_fwd(qkv16, pk16, pv16, addmask, ctx16, lse, B, S, Pn, NH, p, seed, offset):

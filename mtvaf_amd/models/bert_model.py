@@ -176,6 +176,61 @@ def _accumulate_on_producer_stream():
             fn(False)
 
 
+SLOTS_PER_IMAGE = 4  # prefix slots one image contributes (`_region_features`): slots 0..3 the main image, then 4 per crop
+
+
+def image_slots(batch, n_aux, device, image_present=None, aux_present=None):
+    """``image_present`` [B] / ``aux_present`` [B, n_aux] (non-zero = the sentence has that image; None = all have it) expanded to
+    prefix slots: -> bool [B, 4 * (1 + n_aux)], slots 0..3 the main image's, each following group of 4 one crop's."""
+    main = torch.ones(batch, 1, dtype=torch.bool, device=device) if image_present is None \
+        else image_present.to(device).reshape(batch, 1) != 0
+    aux = torch.ones(batch, n_aux, dtype=torch.bool, device=device) if aux_present is None \
+        else aux_present.to(device).reshape(batch, -1) != 0
+    if aux.shape[1] != n_aux:
+        raise ValueError(f"aux_present covers {aux.shape[1]} crops, the prompt was built from {n_aux}")
+    return torch.cat([main, aux], dim=1).repeat_interleave(SLOTS_PER_IMAGE, dim=1)
+
+
+def _prefix_slots(model, B, n_slots, dev, prefix_mask=None, image_present=None, aux_present=None):
+    """Which sentence owns which of the prompt's ``n_slots`` slots -- THE place where a model decides it: -> bool
+    [B, P], or None when every sentence owns them all.  ``prefix_mask`` [B, P] (non-zero = slot present), ``image_present`` /
+    ``aux_present`` (`image_slots`) and, in training mode, args.modality_dropout = p (each sentence loses its whole prefix with
+    probability p: one ``torch.rand(B)`` on the device under ``model.modality_generator``, no host sync, capturable) compose by
+    AND.  None of them: None, and no tensor is created.  The decision is kept in ``model.last_prefix_slots``; the caller hands
+    ``prefix_masked = (slots is not None)`` to the encoder with the mask it builds from it."""
+    slots = None
+    if prefix_mask is not None:
+        if tuple(prefix_mask.shape) != (B, n_slots):
+            raise ValueError(f"prefix_mask is {tuple(prefix_mask.shape)}, the prompt has {n_slots} slots for {B} sentences")
+        slots = prefix_mask.to(dev) != 0
+    if image_present is not None or aux_present is not None:
+        img = image_slots(B, n_slots // SLOTS_PER_IMAGE - 1, dev, image_present, aux_present)
+        slots = img if slots is None else slots & img
+    p = float(_arg(model.args, "modality_dropout", 0.0) or 0.0)
+    if p > 0 and model.training:
+        keep = torch.rand(B, device=dev, generator=getattr(model, "modality_generator", None)) >= p
+        slots = keep[:, None].expand(B, n_slots) if slots is None else slots & keep[:, None]
+    model.last_prefix_slots = slots
+    return slots
+
+
+def _no_prefix(model, prefix_mask, image_present, aux_present):
+    """A model without ``use_prefix`` has no slots to mask: the arguments are an error, not ignored."""
+    if prefix_mask is not None or image_present is not None or aux_present is not None:
+        raise ValueError("prefix_mask / image_present / aux_present need args.use_prefix: this model has no visual prefix")
+    model.last_prefix_slots = None
+
+
+def _prompt_attention_mask(model, attention_mask, n_slots, prefix_mask=None, image_present=None, aux_present=None, slots=False):
+    """The attention mask extended over the prompt's ``n_slots`` slots: ones, or the slots `_prefix_slots` decides on (``slots``:
+    a decision made earlier in the same call, None included)."""
+    B, dev = attention_mask.size(0), attention_mask.device
+    if slots is False:
+        slots = _prefix_slots(model, B, n_slots, dev, prefix_mask, image_present, aux_present)
+    prefix = torch.ones((B, n_slots), device=dev, dtype=attention_mask.dtype) if slots is None else slots.to(attention_mask.dtype)
+    return torch.cat((prefix, attention_mask), dim=1)
+
+
 class ImageModel(nn.Module):
     """Frozen ResNet pyramid front-end (reference: models/bert_model.py:63-111).  It is UPSTREAM of the
     accelerated path and runs in plain torch (MIOpen convolutions) on the trunks of
@@ -252,6 +307,8 @@ class TVNetSAModel2(nn.Module):
         # (engine.UNPAD) may leave zeros at masked positions.  TVNetSAModel's position softmax reads every position: no flag.
         self.bert.allow_unpad = True
         self.last_prefix_mass = None  # [L,B,NH,S] after a forward with args.output_prefix_mass
+        self.last_prefix_slots = None  # bool [B,P] after a call that masked prefix slots (None: every sentence owned them all)
+        self.modality_generator = None  # torch.Generator of the args.modality_dropout draws (None: the device's default)
         self.last_tag_marginals = None  # [B,S,num_labels] after a forward with args.output_tag_marginals
         self.last_crf_risk = None  # detached device scalar after a forward with labels and args.crf_risk_weight > 0
         self.last_crf_entropy = None  # detached device scalar after a forward with a loss and args.crf_entropy_weight != 0
@@ -310,8 +367,11 @@ class TVNetSAModel2(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
-                images=None, aux_imgs=None, allowed_tags=None, token_to_word=None):
-        """reference: models/bert_model.py:480-532.  ``allowed_tags`` int64 [B,S] (`mtvaf_amd.constraints`: per-column tag sets of a
+                images=None, aux_imgs=None, allowed_tags=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
+        """reference: models/bert_model.py:480-532.  ``prefix_mask`` [B, P] (1 = the sentence owns that visual slot), or its
+        convenience form ``image_present`` [B] / ``aux_present`` [B, n_aux] (`image_slots`): a sentence without an image, or with
+        fewer crops, does not attend to those slots (args.modality_dropout drops whole prefixes in training).  None:
+        every sentence owns every slot, as always.  ``allowed_tags`` int64 [B,S] (`mtvaf_amd.constraints`: per-column tag sets of a
         partly annotated batch), given with ``labels=None``: the loss is ``-CRF.partial_llh`` -- the marginal likelihood of the
         paths the sets permit -- with args.crf_reduction, plus the same ``alpha * img_tag_loss`` term.  Without it the method runs
         the code it always ran.
@@ -328,7 +388,7 @@ class TVNetSAModel2(nn.Module):
         self._chain_only(allowed_tags is not None, "allowed_tags")
         word_mode = self._word_mode(token_to_word)
         prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
-                                                                                  aux_imgs)
+                                                                                  aux_imgs, prefix_mask, image_present, aux_present)
         # The attention maps are made on request only (the reference hard-codes output_attentions=True, bert_model.py:496-502, and
         # never reads them): args.output_attentions (True or layer indices) fills TokenClassifierOutput.attentions,
         # args.output_prefix_mass fills self.last_prefix_mass [L,B,NH,S] -- each token's attention on the visual slots --
@@ -337,7 +397,7 @@ class TVNetSAModel2(nn.Module):
         bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
                                 token_type_ids=token_type_ids, past_key_values=prefix_guids,
                                 output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
-                                return_dict=True, layer_mix=self.layer_mix)
+                                return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
         self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
         hidden = _head_state(bert_output, self.layer_mix)
         index = None
@@ -364,18 +424,29 @@ class TVNetSAModel2(nn.Module):
         return TokenClassifierOutput(loss=loss, logits=logits, attentions=bert_output.attentions)
 
     # ---- the pieces of `forward`, shared with `forward_consistent` -----------------------------------------------------
-    def _prompt_prologue(self, input_ids, attention_mask, imagelabel, images, aux_imgs):
+    def _prompt_prologue(self, input_ids, attention_mask, imagelabel, images, aux_imgs, prefix_mask=None, image_present=None,
+                         aux_present=None):
         """-> (prefix_guids, img_tag_loss, prompt_attention_mask): the visual prompt, its VAO loss (args.vao; else 0) and the attention
-        mask extended over the prompt's slots; (None, 0, attention_mask) without ``use_prefix``."""
+        mask extended over the prompt's slots (`_prompt_attention_mask`: the per-sentence slot mask enters here and nowhere else);
+        (None, 0, attention_mask) without ``use_prefix``."""
         if not _arg(self.args, "use_prefix"):
+            _no_prefix(self, prefix_mask, image_present, aux_present)
             return None, 0, attention_mask
+        # the slots are decided BEFORE the prompt is generated: the VAO losses leave out the images a sentence does not have
+        B, dev = input_ids.size(0), attention_mask.device
+        n_img = 1 + (0 if aux_imgs is None else aux_imgs.shape[1])
+        slots = _prefix_slots(self, B, SLOTS_PER_IMAGE * n_img, dev, prefix_mask, image_present, aux_present)
+        present = None
+        if slots is not None and _arg(self.args, "vao"):  # [images, B]: a sentence has an image while it owns one of its slots
+            present = slots.view(B, n_img, SLOTS_PER_IMAGE).any(-1).t().to(torch.float32).contiguous()
         prefix_guids, img_tag_loss, aux_img_tag_loss = _on_second_stream(
-            lambda: self.get_visual_prompt(images, aux_imgs, imagelabel), (images, aux_imgs, imagelabel),
+            lambda: self.get_visual_prompt(images, aux_imgs, imagelabel, present=present), (images, aux_imgs, imagelabel, present),
             join=_arg(self.args, "vao"))  # the VAO losses are consumed on the main stream right away
         img_tag_loss = img_tag_loss if _arg(self.args, "noauxloss") else img_tag_loss + sum(aux_img_tag_loss)
-        prefix_len = prefix_guids[0][0].shape[2]
-        prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
-        return prefix_guids, img_tag_loss, torch.cat((prefix_mask, attention_mask), dim=1)
+        if prefix_guids[0][0].shape[2] != SLOTS_PER_IMAGE * n_img:
+            raise ValueError(f"the prompt has {prefix_guids[0][0].shape[2]} slots, {n_img} images were expected to give "
+                             f"{SLOTS_PER_IMAGE * n_img}")
+        return prefix_guids, img_tag_loss, _prompt_attention_mask(self, attention_mask, SLOTS_PER_IMAGE * n_img, slots=slots)
 
     def _word_targets(self, attention_mask, token_to_word, labels, allowed_tags):
         """The word axis: one launch builds the index; from here on the mask, the labels and the constraint sets are those of the
@@ -497,7 +568,8 @@ class TVNetSAModel2(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def forward_consistent(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
-                           images=None, aux_imgs=None, allowed_tags=None, token_to_word=None, return_parts=False):
+                           images=None, aux_imgs=None, allowed_tags=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None,
+                           return_parts=False):
         """One training step's loss with a two-pass consistency term: the same batch goes through the encoder
         twice -- under two independent dropout masks (R-Drop), or once plain and once cut -- both passes are trained and a
         divergence between their predictive distributions joins the loss:
@@ -505,7 +577,8 @@ class TVNetSAModel2(nn.Module):
             1/2 (nll_1 + nll_2)   [args.consistency_ce = False: nll_1]
               + args.consistency_weight * divergence  +  alpha * img_tag_loss
 
-        Arguments as ``forward``; ``labels`` or ``allowed_tags`` is required (the nll is ``forward``'s, under args.crf_reduction).
+        Arguments as ``forward`` (``prefix_mask`` / ``image_present`` / ``aux_present`` included: one slot mask, drawn once with
+        args.modality_dropout, serves both passes); ``labels`` or ``allowed_tags`` is required (the nll is ``forward``'s, under args.crf_reduction).
         The visual prompt -- with args.vao its losses -- is computed once and serves both passes; ``alpha * img_tag_loss`` enters
         once.  Pass 1 is ``forward``'s pass.  Pass 2 runs the encoder again on the same prompt: in train mode under dropout masks
         of its own (as two ``forward`` calls draw them), and with args.consistency_aug ("span_cutoff" | "token_cutoff" |
@@ -531,7 +604,7 @@ class TVNetSAModel2(nn.Module):
         # TVNetSAModel.forward_with_cutoff; the sink goes back to its setting when that backward ends, or here if anything raises
         sink = self.bert.encoder.grad_sink if (_arg(self.args, "fused_accumulation") and torch.is_grad_enabled() and two) else None
         batch = (input_ids, attention_mask, token_type_ids, labels, imagelabel, images, aux_imgs, allowed_tags, token_to_word,
-                 return_parts)
+                 return_parts, prefix_mask, image_present, aux_present)
         if sink is None:
             return self._consistent_passes(opt, two, *batch)
         sink.begin_two_node_pass()
@@ -542,15 +615,15 @@ class TVNetSAModel2(nn.Module):
             raise
 
     def _consistent_passes(self, opt, two, input_ids, attention_mask, token_type_ids, labels, imagelabel, images, aux_imgs, allowed_tags,
-                           token_to_word, return_parts):
+                           token_to_word, return_parts, prefix_mask=None, image_present=None, aux_present=None):
         word_mode = self._word_mode(token_to_word)
         prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
-                                                                                  aux_imgs)
+                                                                                  aux_imgs, prefix_mask, image_present, aux_present)
         self.bert.encoder.output_prefix_mass = bool(_arg(self.args, "output_prefix_mass"))
         bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
                                 token_type_ids=token_type_ids, past_key_values=prefix_guids,
                                 output_attentions=_arg(self.args, "output_attentions"), output_hidden_states=True,
-                                return_dict=True, layer_mix=self.layer_mix)
+                                return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
         self.last_prefix_mass = self.bert.encoder.last_prefix_mass if self.bert.encoder.output_prefix_mass else None
         index = None
         if word_mode is not None:
@@ -568,7 +641,8 @@ class TVNetSAModel2(nn.Module):
             if opt["aug"] is None:
                 hidden_2 = _head_state(self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask,
                                                  token_type_ids=token_type_ids, past_key_values=prefix_guids,
-                                                 output_hidden_states=True, return_dict=True, layer_mix=self.layer_mix),
+                                                 output_hidden_states=True, return_dict=True, layer_mix=self.layer_mix,
+                                                 prefix_masked=self.last_prefix_slots is not None),
                                        self.layer_mix)
             else:
                 from ..modules.augument import Cutoff
@@ -639,7 +713,8 @@ class TVNetSAModel2(nn.Module):
             self._predict_tables = (key, t)
         return self._predict_tables[1]
 
-    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, token_to_word=None):
+    def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, token_to_word=None,
+                prefix_mask=None, image_present=None, aux_present=None):
         """Inference end to end with no host sync, in eval mode whatever mode the module is in: visual prompt -> encoder -> fc ->
         Viterbi -> `CRF.entities`.  Chunked columns: the run of attention_mask from column 1, minus the columns whose PREDICTED
         label is structural (`mtvaf_amd.metrics.structural_labels`: PAD, X, [CLS], [SEP]), and only those of ``word_mask``
@@ -648,7 +723,8 @@ class TVNetSAModel2(nn.Module):
         names the entities' type indices refer to; `mtvaf_amd.metrics.entities_to_lists` turns it into Python lists.
         With args.word_pooling, ``token_to_word`` int32 [B,S] (as in `forward`) puts fc, the decoder and `CRF.entities` on the word
         axis: tags [B,W] and entity columns are WORD columns (``self.last_word_index``); ``word_mask`` is refused beside it.  The
-        other ``predict_*`` methods take it the same way.
+        other ``predict_*`` methods take it the same way.  ``prefix_mask`` / ``image_present`` / ``aux_present``: as `forward` (eval
+        mode: args.modality_dropout never drops here); every ``predict_*`` method takes them.
         This and the other ``predict_*`` methods read the weights the module holds: to evaluate the averaged weights of a run with
         ``args.ema_decay``, call them inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         # (an eval pass still reserves dropout offsets: the counter is put back, so a training run draws the same masks with or
@@ -659,16 +735,15 @@ class TVNetSAModel2(nn.Module):
             with torch.no_grad():
                 if _arg(self.args, "use_prefix"):
                     prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
-                    prefix_len = prefix_guids[0][0].shape[2]
-                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
-                                             dtype=attention_mask.dtype)
-                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                    prompt_attention_mask = _prompt_attention_mask(self, attention_mask, prefix_guids[0][0].shape[2], prefix_mask,
+                                                                   image_present, aux_present)
                 else:
+                    _no_prefix(self, prefix_mask, image_present, aux_present)
                     prefix_guids, prompt_attention_mask = None, attention_mask
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True, layer_mix=self.layer_mix)
+                                        return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
                 hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
                                                          word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
@@ -693,7 +768,7 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_constrained(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                            allowed=None, token_to_word=None):
+                            allowed=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
         """`predict` with the decoder searching only among the tag sequences that the input's layout permits, instead of decoding
         freely and dropping the columns whose predicted label is structural afterwards: the same prologue (visual prompt ->
         encoder -> fc, eval mode, no host sync, dropout counter put back), then `CRF.decode_constrained` over ``allowed`` int64
@@ -709,16 +784,15 @@ class TVNetSAModel2(nn.Module):
             with torch.no_grad():
                 if _arg(self.args, "use_prefix"):
                     prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
-                    prefix_len = prefix_guids[0][0].shape[2]
-                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
-                                             dtype=attention_mask.dtype)
-                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                    prompt_attention_mask = _prompt_attention_mask(self, attention_mask, prefix_guids[0][0].shape[2], prefix_mask,
+                                                                   image_present, aux_present)
                 else:
+                    _no_prefix(self, prefix_mask, image_present, aux_present)
                     prefix_guids, prompt_attention_mask = None, attention_mask
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True, layer_mix=self.layer_mix)
+                                        return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
                 hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
                                                          word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
@@ -743,7 +817,7 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_posteriors(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                           threshold=0.5, token_to_word=None):
+                           threshold=0.5, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
         """`predict_constrained` plus the posterior of every chunk EVENT (`CRF.chunk_posteriors`): the same prologue and the same
         layout sets (`structural_sets` of the trainer's label map, the attention mask and ``word_mask``), the posteriors
         conditional on them.  Kept columns: the word columns between [CLS] and [SEP] (columns 1 .. L-2, and only those of
@@ -764,16 +838,15 @@ class TVNetSAModel2(nn.Module):
             with torch.no_grad():
                 if _arg(self.args, "use_prefix"):
                     prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
-                    prefix_len = prefix_guids[0][0].shape[2]
-                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
-                                             dtype=attention_mask.dtype)
-                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                    prompt_attention_mask = _prompt_attention_mask(self, attention_mask, prefix_guids[0][0].shape[2], prefix_mask,
+                                                                   image_present, aux_present)
                 else:
+                    _no_prefix(self, prefix_mask, image_present, aux_present)
                     prefix_guids, prompt_attention_mask = None, attention_mask
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True, layer_mix=self.layer_mix)
+                                        return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
                 hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
                                                          word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
@@ -810,7 +883,7 @@ class TVNetSAModel2(nn.Module):
                 "types": t["types"]}
 
     def predict_nbest(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, nbest=None,
-                      token_to_word=None):
+                      token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
         """`predict` with the ``nbest`` best tag sequences of every sentence instead of the best one (args.nbest, default 4; 1..8):
         the same prologue (visual prompt -> encoder -> fc, eval mode, no host sync, dropout counter put back), then
         `CRF.decode_nbest`, then every hypothesis through `CRF.entities` as one batch of B * K rows against the repeated emissions
@@ -827,16 +900,15 @@ class TVNetSAModel2(nn.Module):
             with torch.no_grad():
                 if _arg(self.args, "use_prefix"):
                     prefix_guids, _, _ = self.get_visual_prompt(images, aux_imgs, None, vao=False)
-                    prefix_len = prefix_guids[0][0].shape[2]
-                    prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device,
-                                             dtype=attention_mask.dtype)
-                    prompt_attention_mask = torch.cat((prefix_mask, attention_mask), dim=1)
+                    prompt_attention_mask = _prompt_attention_mask(self, attention_mask, prefix_guids[0][0].shape[2], prefix_mask,
+                                                                   image_present, aux_present)
                 else:
+                    _no_prefix(self, prefix_mask, image_present, aux_present)
                     prefix_guids, prompt_attention_mask = None, attention_mask
                 self.bert.encoder.output_prefix_mass = False
                 bert_output = self.bert(input_ids=input_ids, attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
                                         past_key_values=prefix_guids, output_attentions=False, output_hidden_states=True,
-                                        return_dict=True, layer_mix=self.layer_mix)
+                                        return_dict=True, layer_mix=self.layer_mix, prefix_masked=self.last_prefix_slots is not None)
                 hidden, attention_mask = self._word_axis(_head_state(bert_output, self.layer_mix), attention_mask, token_to_word,
                                                          word_mask)
                 emissions = engine.LinearFunction.apply(hidden, self.fc.weight, self.fc.bias, False)
@@ -883,10 +955,12 @@ class TVNetSAModel2(nn.Module):
             aux = [aux_imgs[:, i].reshape(bsz, L, -1).float() for i in range(aux_imgs.shape[1])]
         return feats, aux
 
-    def get_visual_prompt(self, images, aux_imgs, imagelabel, vao=True):
+    def get_visual_prompt(self, images, aux_imgs, imagelabel, vao=True, present=None):
         """reference: models/bert_model.py:534-588.  Returns (list of num_layers (K, V) [B,NH,P,64],
         img_tag_loss, [aux_img_tag_loss]).  ``vao=False`` (`predict`: there are no image labels at inference) leaves the VAO
-        losses of args.vao out."""
+        losses of args.vao out.  ``present`` [images, B] fp32 (1 / 0; None: every sentence has every image): the image-tag loss of
+        image k is the mean over the sentences that HAVE it -- one without contributes nothing and is not counted in the divisor
+        (0 when no sentence has it); all ones gives the bits of None."""
         feats, aux = self._region_features(images, aux_imgs)
         bsz, L, Fd = feats.shape
         cfg = self.bert.config
@@ -908,7 +982,7 @@ class TVNetSAModel2(nn.Module):
             for k in range(NI):
                 m = engine.dropout(means[k], self.img_dropout.p, self.training)
                 z = engine.LinearFunction.apply(m, heads[k].weight, heads[k].bias, False)
-                l = engine.KLFunction.apply(z, target)
+                l = engine.KLFunction.apply(z, target, None if present is None else present[k])
                 if k == 0:
                     img_tag_loss = l
                 else:
@@ -1006,9 +1080,10 @@ class TVNetSAModel(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, start_positions=None,
                 end_positions=None, span_starts=None, span_ends=None, polarity_labels=None, label_masks=None,
                 images=None, aux_imgs=None, valid_ids=None, adjacency_matrix=None, output_attention=False,
-                augument=False, labels=None, adj_matrix=None, src_mask=None, aspect_mask=None, polaritys=None):
-        """reference: models/bert_model.py:246-321 (use_probe / GCN branches excluded)."""
-        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True)
+                augument=False, labels=None, adj_matrix=None, src_mask=None, aspect_mask=None, polaritys=None, prefix_mask=None, image_present=None, aux_present=None):
+        """reference: models/bert_model.py:246-321 (use_probe / GCN branches excluded).  ``prefix_mask`` / ``image_present`` /
+        ``aux_present``: as `TVNetSAModel2.forward`."""
+        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True, prefix_mask, image_present, aux_present)
         loss, logits = self._loss_pass(prefix_guids, prompt_attention_mask, input_ids, attention_mask, token_type_ids,
                                        start_positions, end_positions, span_starts, span_ends, polarity_labels,
                                        label_masks, augument)
@@ -1018,7 +1093,7 @@ class TVNetSAModel(nn.Module):
                             end_positions=None, span_starts=None, span_ends=None, polarity_labels=None, label_masks=None,
                             images=None, aux_imgs=None, valid_ids=None, adjacency_matrix=None, output_attention=False,
                             labels=None, adj_matrix=None, src_mask=None, aspect_mask=None, polaritys=None,
-                            return_parts=False):
+                            prefix_mask=None, image_present=None, aux_present=None, return_parts=False):
         """One training step's loss with the cutoff augmentation on -- what ``SATrainer._step`` does when ``mode ==
         "train" and args.do_aug`` (modules/train.py:412-455 with cal_cut_loss / js_div, :523-538): a plain pass, a cut
         pass (``args.aug_type`` / ``args.aug_cutoff_ratio``) and
@@ -1041,18 +1116,19 @@ class TVNetSAModel(nn.Module):
                                                and (w_ce > 0 or w_js > 0)) else None
         if sink is None:
             return self._cutoff_passes(w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
-                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts)
+                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts, prefix_mask, image_present, aux_present)
         sink.begin_two_node_pass()
         try:
             return self._cutoff_passes(w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
-                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts)
+                                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts, prefix_mask, image_present, aux_present)
         except BaseException:
             sink.end_two_node_pass()
             raise
 
     def _cutoff_passes(self, w_ce, w_js, input_ids, attention_mask, token_type_ids, start_positions, end_positions, span_starts,
-                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts):
-        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True)
+                       span_ends, polarity_labels, label_masks, images, aux_imgs, return_parts, prefix_mask=None, image_present=None,
+                       aux_present=None):
+        prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, True, prefix_mask, image_present, aux_present)
         batch = (prompt_attention_mask, input_ids, attention_mask, token_type_ids, start_positions, end_positions,
                  span_starts, span_ends, polarity_labels, label_masks)
         loss, logits = self._loss_pass(prefix_guids, *batch, False)
@@ -1072,18 +1148,19 @@ class TVNetSAModel(nn.Module):
         out = TokenClassifierOutput(loss=combined, logits=logits)
         return (out, parts) if return_parts else out
 
-    def _prompt_prologue(self, input_ids, attention_mask, images, aux_imgs, second_stream):
+    def _prompt_prologue(self, input_ids, attention_mask, images, aux_imgs, second_stream, prefix_mask=None, image_present=None,
+                         aux_present=None):
         """-> (prefix_guids, prompt_attention_mask): the visual prompt and the attention mask extended over its slots
-        (:262-271); (None, attention_mask) without ``use_prefix``."""
+        (:262-271; `_prompt_attention_mask`: the per-sentence slot mask enters here); (None, attention_mask) without ``use_prefix``."""
         if not _arg(self.args, "use_prefix"):
+            _no_prefix(self, prefix_mask, image_present, aux_present)
             return None, attention_mask
         if second_stream:
             prefix_guids = _on_second_stream(lambda: self.get_visual_prompt(images, aux_imgs), (images, aux_imgs))
         else:
             prefix_guids = self.get_visual_prompt(images, aux_imgs)
-        prefix_len = prefix_guids[0][0].shape[2]
-        prefix_mask = torch.ones((input_ids.size(0), prefix_len), device=attention_mask.device, dtype=attention_mask.dtype)
-        return prefix_guids, torch.cat((prefix_mask, attention_mask), dim=1)
+        return prefix_guids, _prompt_attention_mask(self, attention_mask, prefix_guids[0][0].shape[2], prefix_mask, image_present,
+                                                    aux_present)
 
     def _loss_pass(self, prefix_guids, prompt_attention_mask, input_ids, attention_mask, token_type_ids, start_positions,
                    end_positions, span_starts, span_ends, polarity_labels, label_masks, augument):
@@ -1171,7 +1248,7 @@ class TVNetSAModel(nn.Module):
             threshold=_arg(self.args, "logit_threshold", 8.0), use_heuristics=_arg(self.args, "use_heuristics", True), nms=nms)
 
     def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, token_to_word=None,
-                word_key=None, gold=None):
+                word_key=None, gold=None, prefix_mask=None, image_present=None, aux_present=None):
         """Inference end to end with no host sync: visual prompt -> extraction logits -> `propose_spans` -> span classifier.
         -> dict: span_starts, span_ends, label_masks [B,n] int64, span_scores [B,n] fp32, logits [B,n,4] (polarity logits of
         every slot; padding slots have label_masks 0), start_logits / end_logits [B,S] the proposal read.
@@ -1182,7 +1259,8 @@ class TVNetSAModel(nn.Module):
         The weights read are the ones the module holds: to evaluate the averaged weights of a run with ``args.ema_decay``, call
         this inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         with torch.no_grad():
-            prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, False)
+            prefix_guids, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, images, aux_imgs, False, prefix_mask,
+                                                                        image_present, aux_present)
             ae_logits, sequence_output = self._extract(prompt_attention_mask, input_ids, prefix_guids, token_type_ids)
             if gold is not None and self.span_scorer is not None and token_to_word is None:
                 token_to_word = _mask_word_map(attention_mask, ae_logits.device)  # one map for proposal and score

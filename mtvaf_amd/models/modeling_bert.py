@@ -364,11 +364,14 @@ class BertEncoder(nn.Module):
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, encoder_hidden_states=None,
                 encoder_attention_mask=None, past_key_values=None, use_cache=None, output_attentions=False,
-                output_hidden_states=False, return_dict=True, unpad_ok=False, layer_mix=None):
+                output_hidden_states=False, return_dict=True, unpad_ok=False, layer_mix=None, prefix_masked=None):
         """``attention_mask`` is the additive extended mask [B,1,1,T] (or [B,T]) as in the reference.  ``unpad_ok``: the
         caller does not read hidden states at masked positions (padding-free execution may zero them, engine.UNPAD).
         ``layer_mix``: a `modules.layer_mix.LayerMix` -- the output then carries ``mixed_hidden_state`` [B,S,H], the learned
-        weighted sum of the chosen hidden states, computed (and differentiated) inside the encoder's node; None: nothing new."""
+        weighted sum of the chosen hidden states, computed (and differentiated) inside the encoder's node; None: nothing new.
+        ``prefix_masked``: the caller's word on the PREFIX columns of ``attention_mask`` -- False: none is masked (a padding-free run
+        then launches the unmasked attention), True: some are, None: unknown.  A masked prefix column is honoured on the
+        padding-free run as on the padded one (engine._prefix_slot_mask); only False skips it, so say it only when it is true."""
         if encoder_hidden_states is not None or (head_mask is not None and any(h is not None for h in head_mask)):
             raise NotImplementedError("cross-attention / head_mask are not on the MTVAF path")
         if not hidden_states.is_cuda:
@@ -386,7 +389,8 @@ class BertEncoder(nn.Module):
             raise ValueError(f"attention mask covers {addmask.shape[1]} keys, expected prefix {Pn} + text {S}")
         tr = self.training
         ecfg = (cfg.num_attention_heads, cfg.layer_norm_eps, cfg.hidden_dropout_prob if tr else 0.0,
-                cfg.attention_probs_dropout_prob if tr else 0.0, getattr(past_key_values, "ready_event", None), bool(unpad_ok))
+                cfg.attention_probs_dropout_prob if tr else 0.0, getattr(past_key_values, "ready_event", None), bool(unpad_ok),
+                None if prefix_masked is None else bool(prefix_masked))
         params = [p for l in self.layer for p in l.ordered_params()]
         mixed = None
         if layer_mix is None:
@@ -643,9 +647,12 @@ class BertModel(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, past_key_values=None,
-                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, layer_mix=None):
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, layer_mix=None,
+                prefix_masked=None):
         """``layer_mix``: a `modules.layer_mix.LayerMix` or None.  With one, the output object has the extra attribute
-        ``mixed_hidden_state`` [B,S,H]; ``last_hidden_state`` (and the pooler, which reads it) is what it is without."""
+        ``mixed_hidden_state`` [B,S,H]; ``last_hidden_state`` (and the pooler, which reads it) is what it is without.
+        ``attention_mask`` [B, P + S] covers the prefix slots of ``past_key_values`` too: a zero in a prefix column takes that slot
+        from that sentence, on the padded and on the padding-free run alike.  ``prefix_masked``: see `BertEncoder.forward`."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids (inputs_embeds is not on the MTVAF path)")
         if head_mask is not None or encoder_hidden_states is not None:
@@ -666,7 +673,8 @@ class BertModel(nn.Module):
         if self.embedding_tap is not None:
             emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
         enc = self.encoder(emb, attention_mask=ext, past_key_values=past_key_values, output_attentions=output_attentions,
-                           output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok, layer_mix=layer_mix)
+                           output_hidden_states=output_hidden_states, return_dict=True, unpad_ok=unpad_ok, layer_mix=layer_mix,
+                           prefix_masked=prefix_masked)
         seq = enc.last_hidden_state
         if layer_mix is not None and not return_dict:
             raise ValueError("layer_mix: the mixed state is an attribute of the output object (return_dict=True)")
@@ -690,13 +698,13 @@ class BertModel(nn.Module):
             emb = engine.EmbeddingTapFunction.apply(emb, self.embedding_tap)
         return emb
 
-    def get_bert_output(self, embedding_output, attention_mask=None, past_key_values=None, layer_mix=None):
+    def get_bert_output(self, embedding_output, attention_mask=None, past_key_values=None, layer_mix=None, prefix_masked=None):
         """reference: models/modeling_bert.py:1127-1157.  ``layer_mix`` (a `LayerMix`): the tuple gets a third entry, the mixed
         state."""
         assert attention_mask.dim() == 2
         ext = self.get_extended_attention_mask(attention_mask)
         enc = self.encoder(embedding_output, attention_mask=ext, past_key_values=past_key_values, return_dict=True,
-                           unpad_ok=bool(getattr(self, "allow_unpad", False)), layer_mix=layer_mix)
+                           unpad_ok=bool(getattr(self, "allow_unpad", False)), layer_mix=layer_mix, prefix_masked=prefix_masked)
         seq = enc.last_hidden_state
         pooled = self.pooler(seq) if (self.pooler is not None and not getattr(self, "skip_pooler", False)) else None
         return (seq, pooled) if layer_mix is None else (seq, pooled, enc.mixed_hidden_state)
