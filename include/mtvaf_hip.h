@@ -664,6 +664,47 @@ int mtvaf_crf_chunk_posteriors(const float* emissions, const int64_t* allowed, c
                                float* logz_a, int B, int S, int C, void* workspace, size_t workspace_bytes,
                                mtvaf_stream_t stream);
 
+/* Calibration of entity posteriors, the counting half: per entity type and log-probability bin, how many scored items there
+ * are, how many of them are gold chunks, sum p and sum (p - y)^2, ADDED into a device counter block.  Two launches on the
+ * stream (one block per sentence, then one block that sums the sentences in order); no host read-back, no allocation, no
+ * atomics on global memory and no floating-point atomics: safe under stream capture, and the same inputs give the same bits.
+ * gold [B,S] int64 labels, an id outside [0,C) reads as 0; mask [B,S] u8, a prefix mask (L_b = its leading ones); keep
+ * [B,S] u8 or NULL (= columns 1 .. L_b-1; only columns < L_b count); start_tab / end_tab / type_of / n_types exactly as
+ * mtvaf_crf_entities reads them.  The gold chunks of a sentence are the chunks mtvaf_crf_entities' chunker emits on the
+ * gold labels of the kept columns: every end with a start b <= j closes (type, b, j), b the greatest such start; an end
+ * without a start is dropped.
+ * edges [n_bins+1] fp32, ascending log-probability bin edges.  The bin of lp is the number of k in 1 .. n_bins-1 with
+ * lp >= edges[k], compared on the stored fp32 values: no exponential decides a bin, so a host that compares the same array
+ * agrees exactly.  edges[0] and edges[n_bins] are not read for binning.
+ * counter: 4*T*NB + 2*T + 1 words of 8 bytes (T = n_types, NB = n_bins), in this order:
+ *   n[T][NB] int64 scored items; hit[T][NB] int64 scored items that are a gold chunk; gold[T] int64 gold chunks;
+ *   gold_reachable[T] int64 gold chunks no wider than max_width kept columns (chunk form; = gold in the entity form);
+ *   sum_p[T][NB] double, sum of p = exp((double)lp); sum_sq[T][NB] double, sum of (p - y)^2, y = 1 on a hit, else 0;
+ *   sentences int64, + B per call.
+ * The double sums are reduced in a fixed order: within a wave in ascending lane order, the block's waves in wave order, the
+ * sentences in sentence order.  workspace: mtvaf_calibration_workspace_bytes(B, n_types, n_bins) bytes (0 for arguments out
+ * of range), MTVAF_ERR_WORKSPACE if NULL or short; it need not be cleared.
+ * mtvaf_chunk_calibration scores dense events: log_post [B,S,max_width,n_types] fp32 as mtvaf_crf_chunk_posteriors writes
+ * it (start column b, width w in kept columns, type).  Every element with lp > -inf is one scored item of its type; -inf
+ * and NaN elements are skipped and not counted.  It is a hit iff a gold chunk of that type starts at column b and ends at
+ * the kept column w places after b's ordinal among the kept columns.
+ * mtvaf_entity_calibration scores listed entities: ents [B,max_entities,3] int32 (start column, end column, type; -1 in
+ * an unused slot) and log_conf [B,max_entities] fp32, the format of mtvaf_crf_entities.  A slot whose type is outside
+ * [0,n_types) or whose columns are outside [0,S) is skipped (so is an unused one); every other slot is one scored item, a
+ * hit iff a gold chunk has the same start column, end column and type; a slot whose log_conf is -inf or NaN is counted in
+ * bin 0 with p = 0.  A slot listed twice counts twice.
+ * B >= 1, 1 <= S <= 512, 1 <= C <= 64 (MTVAF_ERR_SHAPE); 1 <= n_types <= 64, 1 <= max_width <= 16, 1 <= max_entities <= 64,
+ * 1 <= n_bins <= 64 (MTVAF_ERR_ARG): checked before any launch. */
+size_t mtvaf_calibration_workspace_bytes(int B, int n_types, int n_bins);
+int mtvaf_chunk_calibration(const float* log_post, const int64_t* gold, const uint8_t* mask, const uint8_t* keep,
+                            const uint8_t* start_tab, const uint8_t* end_tab, const int* type_of, const float* edges, int B,
+                            int S, int C, int n_types, int max_width, int n_bins, void* counter, void* workspace,
+                            size_t workspace_bytes, mtvaf_stream_t stream);
+int mtvaf_entity_calibration(const int32_t* ents, const float* log_conf, const int64_t* gold, const uint8_t* mask,
+                             const uint8_t* keep, const uint8_t* start_tab, const uint8_t* end_tab, const int* type_of,
+                             const float* edges, int B, int S, int C, int n_types, int max_entities, int n_bins, void* counter,
+                             void* workspace, size_t workspace_bytes, mtvaf_stream_t stream);
+
 /* Cutoff augmentation on the embedding output (modules/augument.py:99-159): out = x * row_keep[b,s] * col_keep[b,:]
  * (either mask may be NULL); x/out [B,S,H] fp32, row_keep [B*S], col_keep [B,H].  Self-adjoint: the backward is the
  * same call on the gradient. */

@@ -133,6 +133,9 @@ _SIGS = {
     "mtvaf_crf_entities": (c_int, [P, P, P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, P]),
     "mtvaf_crf_chunk_posteriors_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_chunk_posteriors": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, P, P, I, I, I, P, SZ, P]),
+    "mtvaf_calibration_workspace_bytes": (SZ, [I, I, I]),
+    "mtvaf_chunk_calibration": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, SZ, P]),
+    "mtvaf_entity_calibration": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, SZ, P]),
     "mtvaf_crf_lattice_workspace_bytes": (SZ, [I, I, I]),
     "mtvaf_crf_lattice_fwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P]),
     "mtvaf_crf_lattice_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, SZ, P]),
@@ -1457,6 +1460,86 @@ def crf_chunk_posteriors(em, allowed, mask_u8, keep, start, end, trans, start_ta
                                          _p(start_tab), _p(end_tab), _p(type_of), n_types, W, _p(log_post), _p(logz_a), B, S,
                                          C, _p(ws), wsb, _st()), "mtvaf_crf_chunk_posteriors")
     return log_post, logz_a
+
+
+CALIBRATION_MAX_S, CALIBRATION_MAX_C, CALIBRATION_MAX_T, CALIBRATION_MAX_W, CALIBRATION_MAX_E, CALIBRATION_MAX_BINS = \
+    512, 64, 64, 16, 64, 64
+
+
+def calibration_words(n_types, n_bins):
+    """8-byte words of the counter block of `chunk_calibration` / `entity_calibration` (include/mtvaf_hip.h): n [T,NB], hit
+    [T,NB], gold [T], gold_reachable [T] as int64, sum_p [T,NB], sum_sq [T,NB] as float64, sentences as int64."""
+    return 4 * n_types * n_bins + 2 * n_types + 1
+
+
+def _calibration_common(name, gold, mask_u8, keep, start_tab, end_tab, type_of, edges, n_types, counter):
+    """The checks both calibration entries share -> (B, S, C, n_bins)"""
+    if gold.dim() != 2:
+        raise ValueError(f"{name}: gold {tuple(gold.shape)}: expected [B, S]")
+    B, S = gold.shape
+    C, NB = type_of.numel() - 1, edges.numel() - 1
+    if not 1 <= S <= CALIBRATION_MAX_S:
+        raise ValueError(f"{name}: S={S} outside 1..{CALIBRATION_MAX_S}")
+    if not 1 <= C <= CALIBRATION_MAX_C:
+        raise ValueError(f"{name}: C={C} outside 1..{CALIBRATION_MAX_C}")
+    if not 1 <= n_types <= CALIBRATION_MAX_T:
+        raise ValueError(f"{name}: n_types={n_types} outside 1..{CALIBRATION_MAX_T}")
+    if not 1 <= NB <= CALIBRATION_MAX_BINS:
+        raise ValueError(f"{name}: {NB} bins outside 1..{CALIBRATION_MAX_BINS}")
+    if B < 1 or tuple(mask_u8.shape) != (B, S) or (keep is not None and tuple(keep.shape) != (B, S)):
+        raise ValueError(f"{name}: mask {tuple(mask_u8.shape)} / keep do not fit gold [{B}, {S}]")
+    if (start_tab.numel(), end_tab.numel()) != ((C + 1) ** 2, (C + 1) ** 2) or counter.numel() != calibration_words(n_types, NB):
+        raise ValueError(f"{name}: tables / counter block do not fit C, n_types and the bins")
+    assert gold.dtype == torch.int64 and gold.is_contiguous() and mask_u8.dtype == torch.uint8 and mask_u8.is_contiguous()
+    assert keep is None or (keep.dtype == torch.uint8 and keep.is_contiguous())
+    assert start_tab.dtype == end_tab.dtype == torch.uint8 and type_of.dtype == torch.int32 and edges.dtype == torch.float32
+    assert counter.dtype == torch.int64 and all(t.is_contiguous() for t in (start_tab, end_tab, type_of, edges, counter))
+    return B, S, C, NB
+
+
+def chunk_calibration(log_post, gold, mask_u8, keep, start_tab, end_tab, type_of, edges, counter):
+    """Adds the calibration counts of one batch's chunk events into ``counter`` (csrc/calibration.hip), two launches and no host
+    sync.  log_post [B,S,W,T] fp32 (`crf_chunk_posteriors`'), gold [B,S] int64, mask_u8 [B,S] uint8 (a prefix mask), keep [B,S]
+    uint8 or None (= columns 1 .. L-1); start_tab / end_tab [(C+1)^2] uint8, type_of [C+1] int32; edges [NB+1] fp32 ascending
+    log-probability bin edges; counter [`calibration_words`(T, NB)] int64 words (the two sums are float64 bit patterns)."""
+    if log_post.dim() != 4:
+        raise ValueError(f"chunk_calibration: log_post {tuple(log_post.shape)}: expected [B, S, W, T]")
+    W, T = int(log_post.shape[2]), int(log_post.shape[3])
+    if not 1 <= W <= CALIBRATION_MAX_W:
+        raise ValueError(f"chunk_calibration: max_width={W} outside 1..{CALIBRATION_MAX_W}")
+    B, S, C, NB = _calibration_common("chunk_calibration", gold, mask_u8, keep, start_tab, end_tab, type_of, edges, T, counter)
+    if tuple(log_post.shape[:2]) != (B, S):
+        raise ValueError(f"chunk_calibration: log_post {tuple(log_post.shape)} does not fit gold [{B}, {S}]")
+    _f32(log_post)
+    wsb = lib().mtvaf_calibration_workspace_bytes(B, T, NB)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=log_post.device)
+    _ck(lib().mtvaf_chunk_calibration(_p(log_post), _p(gold), _p(mask_u8), _p(keep), _p(start_tab), _p(end_tab), _p(type_of),
+                                      _p(edges), B, S, C, T, W, NB, _p(counter), _p(ws), wsb, _st()), "mtvaf_chunk_calibration")
+    return counter
+
+
+def entity_calibration(ents, log_conf, gold, mask_u8, keep, start_tab, end_tab, type_of, edges, n_types, counter):
+    """Adds the calibration counts of one batch's listed entities into ``counter`` (csrc/calibration.hip), two launches and no
+    host sync.  ents [B,E,3] int32 (start column, end column, type; -1 in unused slots) and log_conf [B,E] fp32 as `crf_entities`
+    returns them; the other arguments as `chunk_calibration`."""
+    if ents.dim() != 3 or ents.shape[2] != 3 or tuple(log_conf.shape) != tuple(ents.shape[:2]):
+        raise ValueError(f"entity_calibration: ents {tuple(ents.shape)}, log_conf {tuple(log_conf.shape)}: expected [B, E, 3] "
+                         "and [B, E]")
+    E, n_types = int(ents.shape[1]), int(n_types)
+    if not 1 <= E <= CALIBRATION_MAX_E:
+        raise ValueError(f"entity_calibration: max_entities={E} outside 1..{CALIBRATION_MAX_E}")
+    B, S, C, NB = _calibration_common("entity_calibration", gold, mask_u8, keep, start_tab, end_tab, type_of, edges, n_types,
+                                      counter)
+    if ents.shape[0] != B:
+        raise ValueError(f"entity_calibration: ents {tuple(ents.shape)} do not fit gold [{B}, {S}]")
+    _f32(log_conf)
+    assert ents.dtype == torch.int32 and ents.is_contiguous()
+    wsb = lib().mtvaf_calibration_workspace_bytes(B, n_types, NB)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=ents.device)
+    _ck(lib().mtvaf_entity_calibration(_p(ents), _p(log_conf), _p(gold), _p(mask_u8), _p(keep), _p(start_tab), _p(end_tab),
+                                       _p(type_of), _p(edges), B, S, C, n_types, E, NB, _p(counter), _p(ws), wsb, _st()),
+        "mtvaf_entity_calibration")
+    return counter
 
 
 def mask_mul(x, row_keep, col_keep, out):

@@ -307,6 +307,208 @@ class EntityScorer:
 
 
 # -------------------------------------------------------------------------------------------------
+# Calibration of the entity posteriors on the device (csrc/calibration.hip): threshold curves, reliability, ECE, Brier
+# -------------------------------------------------------------------------------------------------
+def default_log_edges(n_bins: int) -> np.ndarray:
+    """fp32 [n_bins + 1]: -inf, log(k / n_bins) for k = 1 .. n_bins - 1, 0 -- equal-width probability bins, stated in log space."""
+    e = np.empty(n_bins + 1, dtype=np.float32)
+    e[0], e[n_bins] = -np.inf, 0.0
+    e[1:n_bins] = np.log(np.arange(1, n_bins, dtype=np.float64) / n_bins).astype(np.float32)
+    return e
+
+
+def _curve(n, hit, gold):
+    """n / hit int [NB], gold int -> the threshold curve over the edges k = 0 .. NB-1: the items of the bins >= k are predicted."""
+    predicted = np.cumsum(n[::-1])[::-1]
+    correct = np.cumsum(hit[::-1])[::-1]
+    rows = [_prf(int(c), int(p), int(gold)) for p, c in zip(predicted, correct)]
+    return dict(predicted=predicted.tolist(), correct=correct.tolist(), precision=[r[0] for r in rows],
+                recall=[r[1] for r in rows], f1=[r[2] for r in rows])
+
+
+def _reliability(n, hit, sum_p, sum_sq, first_bin):
+    """-> (bins table, ece, brier): ece / brier over the bins >= first_bin"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        acc = np.where(n > 0, hit / np.maximum(n, 1), 0.0)
+        conf = np.where(n > 0, sum_p / np.maximum(n, 1), 0.0)
+    total = int(n[first_bin:].sum())
+    ece = float((n[first_bin:] / total * np.abs(acc[first_bin:] - conf[first_bin:])).sum()) if total else 0.0
+    brier = float(sum_sq[first_bin:].sum() / total) if total else 0.0
+    return dict(count=n.tolist(), hits=hit.tolist(), accuracy=acc.tolist(), confidence=conf.tolist()), ece, brier
+
+
+class CalibrationScorer:
+    """Precision / recall over the confidence threshold and the reliability of the tagger's entity posteriors, counted on the GPU.
+
+    An update adds one batch into a small device counter block (`mtvaf_chunk_calibration` / `mtvaf_entity_calibration` on the
+    current stream, no host sync); ``compute`` reads it once.  ``update_events`` scores every chunk EVENT of
+    `CRF.chunk_posteriors`' ``log_post`` (finite elements only), ``update_entities`` a list of entities with a log confidence
+    (`predict`, `predict_constrained`, hypothesis 0 of `predict_nbest`, the ``chunk_log_conf`` / ``selected`` lists of
+    `predict_posteriors`).  One instance takes one kind of update: mixing the two raises.  An item is a hit iff the gold labels,
+    chunked over the kept columns by the scheme's tables (`entity_tables`), hold that very chunk.
+
+    Bins live in log space: ``edges`` fp32 [n_bins + 1], ascending; the bin of a log-probability lp is the number of k in
+    1 .. n_bins-1 with ``lp >= edges[k]``.  The default is `default_log_edges`: log(k / n_bins), the ends -inf and 0.  The array is
+    built once on the host, and the kernel reads a copy of the same fp32 values, so host and device agree on every bin.
+    ``device=None``: the device of the first update."""
+
+    def __init__(self, label_map: Dict[str, int], scheme: str = "seqeval", skip: Sequence[str] = ("X", "[SEP]"), n_bins: int = 20,
+                 edges=None, device=None):
+        t = entity_tables(label_map, scheme, skip)
+        if t["C"] > 64:
+            raise ValueError(f"label ids up to {t['C'] - 1}: the calibration kernels read at most 64 labels (ids 0..63)")
+        e = default_log_edges(int(n_bins)) if edges is None else np.asarray(edges, dtype=np.float32).reshape(-1).copy()
+        self.n_bins = e.size - 1
+        if not 1 <= self.n_bins <= 64:
+            raise ValueError(f"{self.n_bins} bins: the calibration kernels read 1 to 64")
+        inner = e[1:self.n_bins]
+        if np.isnan(e).any() or (np.diff(inner) < 0).any():
+            raise ValueError("edges must be ascending log-probabilities without NaN")
+        self.scheme, self.types, self.primary, self.C = scheme, t["types"], t["primary"], t["C"]
+        self.edges = torch.from_numpy(e)  # the one array of edges: `compute` reads it, the kernels read its device copy
+        self._edges_dev = self.edges
+        self._tables = [torch.from_numpy(t[k]).reshape(-1) for k in ("start", "end", "type_of")]
+        self._skip = torch.from_numpy(t["gold_skip"].astype(bool))
+        self._has_skip = bool(t["gold_skip"].any())
+        T, NB = len(self.types), self.n_bins
+        self.block = torch.zeros(4 * T * NB + 2 * T + 1, dtype=torch.int64)  # layout: include/mtvaf_hip.h
+        self.kind = None  # "events" | "entities" after the first update
+        self.device = None
+        if device is not None:
+            self._place(torch.device(device))
+
+    def _place(self, device):
+        self._tables = [x.to(device) for x in self._tables]
+        self._skip = self._skip.to(device)
+        self._edges_dev = self.edges.to(device)
+        self.block = self.block.to(device)
+        self.device = device
+
+    def _fields(self, block=None):
+        """Views of the block -> n, hit [T,NB] int64; gold, gold_reachable [T] int64; sum_p, sum_sq [T,NB] float64; sentences"""
+        b = self.block if block is None else block
+        T, NB = len(self.types), self.n_bins
+        c = T * NB
+        return (b[:c].view(T, NB), b[c:2 * c].view(T, NB), b[2 * c:2 * c + T], b[2 * c + T:2 * c + 2 * T],
+                b[2 * c + 2 * T:3 * c + 2 * T].view(torch.float64).view(T, NB),
+                b[3 * c + 2 * T:4 * c + 2 * T].view(torch.float64).view(T, NB), b[4 * c + 2 * T:])
+
+    def _begin(self, kind, device, labels, attention_mask):
+        if self.kind not in (None, kind):
+            raise ValueError(f"this CalibrationScorer has taken {self.kind} updates: score {kind} with an instance of their own")
+        self.kind = kind
+        if self.device is None:
+            self._place(device)
+        mask = attention_mask if attention_mask.dtype == torch.uint8 else attention_mask.to(torch.uint8)
+        gold = labels if labels.dtype == torch.int64 else labels.to(torch.int64)
+        return gold.contiguous(), mask.contiguous()
+
+    def update_events(self, log_post: torch.Tensor, keep: torch.Tensor, labels: torch.Tensor, attention_mask: torch.Tensor) -> None:
+        """log_post [B,S,W,T] fp32 and keep [B,S] as `CRF.chunk_posteriors` wrote / read them (T = the scheme's types), labels
+        [B,S], attention_mask [B,S] (a prefix mask; uint8 is read in place, other dtypes cost a cast)."""
+        from . import hip
+        if log_post.dim() != 4 or log_post.shape[3] != len(self.types):
+            raise ValueError(f"log_post {tuple(log_post.shape)}: expected [B, S, W, {len(self.types)}] for the types {self.types}")
+        gold, mask = self._begin("events", log_post.device, labels, attention_mask)
+        keep = None if keep is None else keep.to(torch.uint8).contiguous()
+        hip.chunk_calibration(log_post.detach().contiguous(), gold, mask, keep, *self._tables, self._edges_dev, self.block)
+
+    def update_entities(self, entities: torch.Tensor, log_confidence: torch.Tensor, labels: torch.Tensor,
+                        attention_mask: torch.Tensor, keep=None) -> None:
+        """entities [B,E,3] int32 (start column, end column, type index; -1 in unused slots) and log_confidence [B,E] fp32 in
+        `CRF.entities`' format, labels [B,S], attention_mask [B,S].  ``keep`` [B,S]: the columns the gold labels are chunked
+        over; None: columns 1 .. L-1 minus those whose gold label is one of ``skip`` -- `EntityScorer`'s columns."""
+        from . import hip
+        gold, mask = self._begin("entities", entities.device, labels, attention_mask)
+        if keep is None:
+            if self._has_skip:
+                g = torch.where((gold >= 0) & (gold < self.C), gold, torch.zeros_like(gold))
+                keep = torch.cumprod(mask, dim=1).bool() & ~self._skip[g]
+                keep[:, 0] = False
+                keep = keep.to(torch.uint8)
+        else:
+            keep = keep.to(torch.uint8).contiguous()
+        ents = entities if entities.dtype == torch.int32 else entities.to(torch.int32)
+        hip.entity_calibration(ents.contiguous(), log_confidence.detach().to(torch.float32).contiguous(), gold, mask, keep,
+                               *self._tables, self._edges_dev, len(self.types), self.block)
+
+    def reset(self) -> None:
+        self.block.zero_()
+
+    def all_reduce(self, group=None) -> None:
+        """Sums the block over the process group (nothing without one): the integer fields as integers, the two sums as float64."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            ints_end = 2 * len(self.types) * (self.n_bins + 1)  # n, hit, gold, gold_reachable: one contiguous run
+            f64 = self.block[ints_end:-1].view(torch.float64)    # sum_p, sum_sq: the next
+            for part in (self.block[:ints_end], f64, self.block[-1:]):
+                dist.all_reduce(part, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self, first_bin: int = 1) -> dict:
+        """One small device->host copy -> a dict:
+
+        ``edges`` (log) and ``thresholds`` = exp(edges) [n_bins + 1]; per listed type under ``types[name]`` and over all types
+        under ``pooled``: ``bins`` = {count, hits, accuracy = hits / count, confidence = sum p / count} per bin, ``curve`` =
+        {predicted, correct, precision, recall, f1} per edge k = 0 .. n_bins-1, where the items of the bins >= k are the
+        predictions (``predicted[k]`` = sum of count over j >= k, ``correct[k]`` the same over hits; precision = correct /
+        predicted, recall = correct / gold), plus gold, gold_reachable, recall_ceiling, ece, brier.  ``micro`` is the pooled
+        curve.  ``best_f1`` / ``best_k`` / ``best_threshold``: the greatest micro F1, the LOWEST k that reaches it, and
+        ``exp(edges[k])`` (0.0 for k = 0: everything is predicted).  ``recall_ceiling`` = gold_reachable / gold: the recall no
+        threshold can exceed, below 1 when gold chunks are wider than the computed widths.  ``sentences``, ``kind``.
+
+        ``ece`` = sum_k (n_k / N) |accuracy_k - confidence_k| and ``brier`` = sum (p - y)^2 / N run over the bins >=
+        ``first_bin``, N their items.  The default ``first_bin=1`` leaves bin 0 out: among the dense events it holds the
+        near-impossible ones -- almost every span of a sentence -- whose |0 - p| ~ 0 would drown both figures; ``first_bin=0``
+        takes every scored item.  Types no B / I / E / S label carries are listed only with non-zero counts; x / 0 reads 0.0."""
+        if not 0 <= first_bin <= self.n_bins:
+            raise ValueError(f"first_bin={first_bin} outside 0..{self.n_bins}")
+        n, hit, gold, reach, sum_p, sum_sq, sentences = (x.numpy() for x in self._fields(self.block.cpu()))
+        edges = self.edges.numpy()
+        with np.errstate(over="ignore"):
+            thresholds = np.exp(edges.astype(np.float64))
+
+        def section(rows):
+            nn, hh, sp, sq = (x[rows].sum(axis=0) for x in (n, hit, sum_p, sum_sq))
+            g, r = int(gold[rows].sum()), int(reach[rows].sum())
+            bins, ece, brier = _reliability(nn, hh, sp, sq, first_bin)
+            return dict(bins=bins, curve=_curve(nn, hh, g), gold=g, gold_reachable=r, recall_ceiling=r / g if g else 0.0, ece=ece,
+                        brier=brier)
+        out = {"edges": edges.tolist(), "thresholds": thresholds.tolist(), "types": {}}
+        for t, name in enumerate(self.types):
+            if self.primary[t] or n[t].any() or gold[t]:
+                out["types"][name] = section([t])
+        pooled = section(list(range(len(self.types))))
+        f1 = pooled["curve"]["f1"]
+        best = max(range(self.n_bins), key=lambda k: (f1[k], -k))  # the lowest k among ties
+        out.update(pooled=pooled, micro=pooled["curve"], best_k=best, best_f1=f1[best], best_threshold=float(thresholds[best]),
+                   ece=pooled["ece"], brier=pooled["brier"], recall_ceiling=pooled["recall_ceiling"], sentences=int(sentences[0]),
+                   kind=self.kind, first_bin=first_bin)
+        return out
+
+
+def calibration_to_rows(result: dict) -> List[dict]:
+    """The dict of `CalibrationScorer.compute` -> plain rows for printing: one ``{"table": "bins", "type", "bin", "low", "high",
+    "count", "hits", "accuracy", "confidence"}`` per type (and "pooled") and bin, ``low`` / ``high`` the bin's probability range;
+    then one ``{"table": "curve", "type", "k", "threshold", "predicted", "correct", "precision", "recall", "f1"}`` per type (and
+    "micro") and edge."""
+    th = result["thresholds"]
+    sections = list(result["types"].items()) + [("pooled", result["pooled"])]
+    rows = []
+    for name, sec in sections:
+        b = sec["bins"]
+        for k in range(len(b["count"])):
+            rows.append(dict(table="bins", type=name, bin=k, low=th[k], high=th[k + 1], count=b["count"][k], hits=b["hits"][k],
+                             accuracy=b["accuracy"][k], confidence=b["confidence"][k]))
+    for name, sec in sections:
+        c = sec["curve"]
+        for k in range(len(c["predicted"])):
+            rows.append(dict(table="curve", type="micro" if name == "pooled" else name, k=k, threshold=th[k],
+                             predicted=c["predicted"][k], correct=c["correct"][k], precision=c["precision"][k],
+                             recall=c["recall"][k], f1=c["f1"][k]))
+    return rows
+
+
+# -------------------------------------------------------------------------------------------------
 # Aspect-level score of the span model on the device (csrc/span_score.hip): eval_absa's counts
 # -------------------------------------------------------------------------------------------------
 SPAN_CLASSES = ("other", "neutral", "positive", "negative")  # models/utils.py:17 id_to_label, the classifier's four outputs

@@ -102,6 +102,23 @@ def _entity_scorer(args, label_list):
     return EntityScorer({label: i for i, label in enumerate(label_list, 1)}, scheme="seqeval" if want is True else want)
 
 
+def _calibration_scorer(args, label_list, head):
+    """args.score_calibration: "events" (the chunk events of `predict_posteriors`) or "entities" (the entity lists of `predict` /
+    `predict_constrained`) -> an `mtvaf_amd.metrics.CalibrationScorer` over the trainer's label map in args.entity_scheme with
+    args.calibration_bins (20) bins; unset / False -> None.  The softmax head has no chain, hence no events."""
+    want = _arg(args, "score_calibration")
+    if not want:
+        return None
+    if want not in ("events", "entities"):
+        raise ValueError(f"args.score_calibration={want!r}: expected 'events' or 'entities'")
+    if want == "events" and head == "softmax":
+        raise ValueError("args.tag_head='softmax' has no chain: args.score_calibration='events' needs args.tag_head='crf' "
+                         "(score 'entities' instead)")
+    from ..metrics import CalibrationScorer
+    return CalibrationScorer({label: i for i, label in enumerate(label_list, 1)}, scheme=_arg(args, "entity_scheme", "seqeval"),
+                             n_bins=int(_arg(args, "calibration_bins", 20) or 20))
+
+
 def _span_scorer(args):
     """args.score_spans: True (the reference's class names) or a sequence of four class names -> an
     `mtvaf_amd.metrics.SpanScorer` over the span classifier's four outputs; unset / False -> None."""
@@ -359,6 +376,9 @@ class TVNetSAModel2(nn.Module):
         # args.score_entities: every forward with labels adds its entity counts to model.entity_scorer on the device (one small
         # launch behind the Viterbi kernel, on its tags); without the switch nothing is launched
         self.entity_scorer = _entity_scorer(args, label_list)
+        # args.score_calibration: `predict_posteriors` ("events") or `predict` / `predict_constrained` ("entities") with labels
+        # add their batch to model.calibration_scorer on the device; without the switch, or without labels, nothing is launched
+        self.calibration_scorer = _calibration_scorer(args, label_list, self.token_opt["head"])
         self.label_list = list(label_list)
         self._predict_tables = None  # (device, scheme) -> the scheme tables of `predict`, built at its first call
         if _arg(args, "use_probe"):
@@ -699,6 +719,17 @@ class TVNetSAModel2(nn.Module):
         self.last_word_index = index
         return engine.WordPoolFunction.apply(hidden, index, mode), index.word_mask
 
+    def _calibration_labels(self, kind, labels, token_to_word):
+        """The gold labels `self.calibration_scorer` chunks for a ``predict*`` call that scores ``kind``, on the axis the head ran
+        on (args.word_pooling: `words.word_labels` over the call's word index); None when nothing is to be scored -- no labels,
+        no scorer, or a scorer of the other kind."""
+        if labels is None or self.calibration_scorer is None or _arg(self.args, "score_calibration") != kind:
+            return None
+        if self._word_mode(token_to_word) is not None:
+            from ..words import word_labels
+            return word_labels(labels, self.last_word_index)
+        return labels
+
     def _entity_tables(self, device):
         """The tagging scheme of `predict` on ``device`` (args.entity_scheme, default "seqeval") over the trainer's label map
         (label_list enumerated from 1, MTVAF_training.py:369), plus the lookup of the structural predicted labels: built once."""
@@ -714,7 +745,7 @@ class TVNetSAModel2(nn.Module):
         return self._predict_tables[1]
 
     def predict(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None, token_to_word=None,
-                prefix_mask=None, image_present=None, aux_present=None):
+                prefix_mask=None, image_present=None, aux_present=None, labels=None):
         """Inference end to end with no host sync, in eval mode whatever mode the module is in: visual prompt -> encoder -> fc ->
         Viterbi -> `CRF.entities`.  Chunked columns: the run of attention_mask from column 1, minus the columns whose PREDICTED
         label is structural (`mtvaf_amd.metrics.structural_labels`: PAD, X, [CLS], [SEP]), and only those of ``word_mask``
@@ -725,6 +756,9 @@ class TVNetSAModel2(nn.Module):
         axis: tags [B,W] and entity columns are WORD columns (``self.last_word_index``); ``word_mask`` is refused beside it.  The
         other ``predict_*`` methods take it the same way.  ``prefix_mask`` / ``image_present`` / ``aux_present``: as `forward` (eval
         mode: args.modality_dropout never drops here); every ``predict_*`` method takes them.
+        ``labels`` [B,S] with args.score_calibration = "entities": the call then adds its entities and their log_confidence to
+        ``self.calibration_scorer`` (`mtvaf_amd.metrics.CalibrationScorer.update_entities`; gold columns: 1 .. L-1 minus the gold X
+        / [SEP]); the returned dict is the same either way, and without labels or the switch nothing more is launched.
         This and the other ``predict_*`` methods read the weights the module holds: to evaluate the averaged weights of a run with
         ``args.ema_decay``, call them inside ``with optimizer.averaged_parameters():`` (`mtvaf_amd.optim.AdamW`)."""
         # (an eval pass still reserves dropout offsets: the counter is put back, so a training run draws the same masks with or
@@ -760,6 +794,10 @@ class TVNetSAModel2(nn.Module):
                     keep &= word_mask.to(keep.device) != 0
                 out = self.crf.entities(emissions, mask_u8, t, tags=tags, keep=keep,
                                         max_entities=_arg(self.args, "max_entities", 32))
+                gold = self._calibration_labels("entities", labels, token_to_word)
+                if gold is not None:
+                    self.calibration_scorer.update_entities(out["entities"], out["log_confidence"], gold.to(emissions.device),
+                                                            mask_u8)
         finally:
             self.bert.encoder.output_prefix_mass = mass
             engine.RNG.offset = offset
@@ -768,14 +806,15 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_constrained(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                            allowed=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
+                            allowed=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None, labels=None):
         """`predict` with the decoder searching only among the tag sequences that the input's layout permits, instead of decoding
         freely and dropping the columns whose predicted label is structural afterwards: the same prologue (visual prompt ->
         encoder -> fc, eval mode, no host sync, dropout counter put back), then `CRF.decode_constrained` over ``allowed`` int64
         [B,S] (`mtvaf_amd.constraints`; None: `structural_sets` of the trainer's label map, the attention mask and ``word_mask``
         -- [CLS] / [SEP] at the ends, X on the columns outside ``word_mask``, no structural tag on a word column), then
         `CRF.entities` on those tags by `predict`'s column rule.  -> `predict`'s dict.  The reported confidence stays the
-        posterior of the decoded segment under the UNCONSTRAINED chain, p(y_b..y_e | x), not conditioned on the sets."""
+        posterior of the decoded segment under the UNCONSTRAINED chain, p(y_b..y_e | x), not conditioned on the sets.
+        ``labels`` with args.score_calibration = "entities": as `predict`."""
         self._chain_only(True, "predict_constrained")
         # (the prologue is `predict`'s, restated: that method is left as it is)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
@@ -809,6 +848,10 @@ class TVNetSAModel2(nn.Module):
                     keep &= word_mask.to(keep.device) != 0
                 out = self.crf.entities(emissions, mask_u8, t, tags=tags, keep=keep,
                                         max_entities=_arg(self.args, "max_entities", 32))
+                gold = self._calibration_labels("entities", labels, token_to_word)
+                if gold is not None:
+                    self.calibration_scorer.update_entities(out["entities"], out["log_confidence"], gold.to(emissions.device),
+                                                            mask_u8)
         finally:
             self.bert.encoder.output_prefix_mass = mass
             engine.RNG.offset = offset
@@ -817,7 +860,7 @@ class TVNetSAModel2(nn.Module):
         return out
 
     def predict_posteriors(self, input_ids, attention_mask, token_type_ids, images=None, aux_imgs=None, word_mask=None,
-                           threshold=0.5, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
+                           threshold=0.5, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None, labels=None):
         """`predict_constrained` plus the posterior of every chunk EVENT (`CRF.chunk_posteriors`): the same prologue and the same
         layout sets (`structural_sets` of the trainer's label map, the attention mask and ``word_mask``), the posteriors
         conditional on them.  Kept columns: the word columns between [CLS] and [SEP] (columns 1 .. L-2, and only those of
@@ -829,7 +872,10 @@ class TVNetSAModel2(nn.Module):
         posterior is >= ``threshold`` in `predict`'s entities / log_confidence / confidence / count format, ordered by end column,
         then start (`CRF.chunks_above`; args.max_entities); ``types``.  Two overlapping chunks exclude each other, so with
         ``threshold > 0.5`` the selected spans of a sentence cannot overlap.  `mtvaf_amd.metrics.posteriors_to_lists` makes
-        Python lists of it."""
+        Python lists of it.
+        ``labels`` [B,S] with args.score_calibration = "events": the call then adds every finite event of ``log_post`` to
+        ``self.calibration_scorer`` (`mtvaf_amd.metrics.CalibrationScorer.update_events`, gold chunked over ``keep``); the returned
+        dict is the same either way, and without labels or the switch nothing more is launched."""
         self._chain_only(True, "predict_posteriors")
         # (the prologue is `predict`'s, restated: that method is left as it is)
         was_training, mass, offset = self.training, self.bert.encoder.output_prefix_mass, engine.RNG.offset
@@ -874,6 +920,9 @@ class TVNetSAModel2(nn.Module):
                                                              max_width=_arg(self.args, "max_entity_width", 8))
                 decoded["chunk_log_conf"] = self.crf.entity_chunk_confidence(decoded["entities"], log_post, keep_w)
                 selected = self.crf.chunks_above(log_post, keep_w, threshold, _arg(self.args, "max_entities", 32))
+                gold = self._calibration_labels("events", labels, token_to_word)
+                if gold is not None:
+                    self.calibration_scorer.update_events(log_post, keep_w, gold.to(emissions.device), mask_u8)
         finally:
             self.bert.encoder.output_prefix_mass = mass
             engine.RNG.offset = offset
