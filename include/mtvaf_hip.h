@@ -1302,6 +1302,51 @@ int mtvaf_layer_mix_dots(const float* const* states, int K, const float* dy, con
 int mtvaf_layer_mix_inject(const float* coef, int j, int K, const float* dy, float* dh, long rows, int H, int accumulate,
                            mtvaf_stream_t stream);
 
+/* ---- masked-LM head (csrc/mlm.hip) ---------------------------------------------------------------------
+ * replaces the host collator's masking (HF DataCollatorForLanguageModeling.torch_mask_tokens) and BertLMPredictionHead's decoder +
+ * CrossEntropyLoss (modeling_bert.py, BertForMaskedLM) at vocabulary width.  All results are pure functions of their inputs: no
+ * atomics, fixed reduction orders, nothing read back to the host; `count` is always a device word.
+ *
+ * mtvaf_uniform_fill: out[i] = 24 random bits * 2^-24 in [0, 1), a function of (seed, offset, i) on the dropout generator
+ * (Philox4x32-10, and the registered device epoch if any).
+ * mtvaf_mlm_mask: input_ids [B,S] int64; live [B,S] u8 (non-zero = attended; any pattern); special_mask [B,S] u8 or NULL (non-zero =
+ * never selected); special_ids: n_special <= 8 ids on the HOST that are never selected; uniforms [B,S,3].  A live non-special token is
+ * selected iff u0 < probability; a selected token becomes mask_token_id if u1 < 0.8, else min(V - 1, (int)(u2 * V)) if u1 < 0.9, else
+ * stays.  Selected tokens are numbered in row-major order; the first `capacity` of them give positions [capacity] int32 (flat
+ * b * S + t, ascending; -1 from *count on), labels [capacity] int64 (the original id; -100 from *count on) and are corrupted in
+ * ids_out [B,S]; later ones stay unmasked and unpredicted.  count [1] int32 = min(selected, capacity); stats [3] int32 = eligible
+ * tokens, selected tokens, selected tokens dropped for capacity.  workspace: mtvaf_mlm_mask_workspace_bytes(B) bytes.
+ * mtvaf_scatter_rows: the backward of mtvaf_gather_rows for DISTINCT rows: dsrc [rows_src,H] = 0, then dsrc[map[r]] = d[r] for
+ * every map[r] in [0, rows_src). */
+int mtvaf_uniform_fill(float* out, long n, uint64_t seed, uint64_t offset, mtvaf_stream_t stream);
+size_t mtvaf_mlm_mask_workspace_bytes(int B);
+int mtvaf_mlm_mask(const int64_t* input_ids, const uint8_t* live, const uint8_t* special_mask, const float* uniforms,
+                   const int64_t* special_ids, int n_special, float probability, long mask_token_id, int vocab_size, int capacity,
+                   int64_t* ids_out, int* positions, int64_t* labels, int* count, int* stats, void* workspace, size_t workspace_bytes,
+                   int B, int S, mtvaf_stream_t stream);
+int mtvaf_scatter_rows(const float* d, const int* map, float* dsrc, int rows, int rows_src, int H, mtvaf_stream_t stream);
+/* out = dy * gelu_erf'(pre), n % 4 == 0 elements, 16-byte aligned: what MTVAF_EPI_DGELU applies, for a gradient that comes out of
+ * a row kernel (the LayerNorm backward of BertPredictionHeadTransform) and not out of a product. */
+int mtvaf_dgelu(const float* dy, const float* pre, float* out, long n, mtvaf_stream_t stream);
+/* Cross entropy over V classes from logits that exist one chunk [R, v1 - v0] at a time (row stride ld floats; the caller's GEMM
+ * wrote x . W[v0:v1]^T into it, bias [V] or NULL is added here).  A row is live iff row < *count and 0 <= labels[row] < V; dead
+ * rows are never read.  state: 4 R words (running maximum m, s = sum exp(l - m), the label's logit, the first index attaining m as
+ * int32), started by the chunk with v0 == 0 and folded in ASCENDING chunk order, one rescale of s per chunk; only l - m <= 0 is
+ * exponentiated.  mtvaf_vocab_ce_finish: loss_row [R] = m + log s - l_label and lse_row [R] (0 on dead rows); loss [1] = their sum
+ * in double and fixed order, divided by the live rows for reduction 0 (mean; +0.0 without live rows), as it is for reduction 1
+ * (sum); stats [3] int32 = live rows, rows whose first maximum is the label, rows below *count whose label is outside [0, V) and
+ * not -100.  mtvaf_vocab_ce_chunk_bwd, in place on a recomputed chunk: dl = g_row (exp(l + bias - lse_row) - [v == label]), exact
+ * zeros on dead rows; g_row = grad_rows[row], or *grad_out (divided by stats[0] for reduction 0) -- exactly one of the two is given.
+ * mtvaf_vocab_ce_workspace_bytes: one logits chunk [R, chunk] and the state -- no term in V. */
+size_t mtvaf_vocab_ce_workspace_bytes(int R, int H, int V, int chunk);
+int mtvaf_vocab_ce_chunk_fwd(const float* logits, int ld, const float* bias, const int64_t* labels, const int* count, float* state,
+                             int R, int V, int v0, int v1, mtvaf_stream_t stream);
+int mtvaf_vocab_ce_finish(const float* state, const int64_t* labels, const int* count, float* loss, float* loss_row, float* lse_row,
+                          int* stats, int R, int V, int reduction, mtvaf_stream_t stream);
+int mtvaf_vocab_ce_chunk_bwd(float* logits, int ld, const float* bias, const int64_t* labels, const int* count, const float* lse_row,
+                             const float* grad_out, const float* grad_rows, const int* stats, int R, int V, int v0, int v1,
+                             int reduction, mtvaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

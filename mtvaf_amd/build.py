@@ -20,7 +20,7 @@ PUBLIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "mtvaf_hip.h")
 # The flags are part of every object's stamp, so a variant can never be mistaken for the product build.
 LIBDIR = os.environ.get("MTVAF_LIBDIR") or os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmtvaf_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16x.hip", "gemm_bf16p.hip", "gemm_f32x3.hip", "gemm_f32p.hip", "gemm_f32pw.hip", "attention.hip", "attention_f32s.hip", "attention_bf16.hip", "rowops.hip", "crf.hip", "crf_wide.hip", "crf_entities.hip", "crf_chunks.hip", "crf_nbest.hip", "crf_sample.hip", "crf_lattice.hip", "crf_risk.hip", "crf_path.hip", "prompt.hip", "span.hip", "span_propose.hip", "span_score.hip", "consistency.hip", "token_ce.hip", "entity.hip", "calibration.hip", "optim.hip", "gradnorm.hip", "adversarial.hip", "wordpool.hip", "layermix.hip", "executor.hip", "runtime.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16x.hip", "gemm_bf16p.hip", "gemm_f32x3.hip", "gemm_f32p.hip", "gemm_f32pw.hip", "attention.hip", "attention_f32s.hip", "attention_bf16.hip", "rowops.hip", "crf.hip", "crf_wide.hip", "crf_entities.hip", "crf_chunks.hip", "crf_nbest.hip", "crf_sample.hip", "crf_lattice.hip", "crf_risk.hip", "crf_path.hip", "prompt.hip", "span.hip", "span_propose.hip", "span_score.hip", "consistency.hip", "token_ce.hip", "mlm.hip", "entity.hip", "calibration.hip", "optim.hip", "gradnorm.hip", "adversarial.hip", "wordpool.hip", "layermix.hip", "executor.hip", "runtime.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"] + os.environ.get("MTVAF_EXTRA_FLAGS", "").split()
 # The attention kernels read their MFMA results with VALU code every 16 products (softmax, dS): keeping the
 # accumulators in architectural VGPRs saves ~200 v_accvgpr moves per key tile (gfx950 has one unified file).

@@ -1983,3 +1983,151 @@ class MaskMulFunction(torch.autograd.Function):
         row_keep, col_keep = ctx.stash
         dyc = dy.contiguous()
         return hip.mask_mul(dyc, row_keep, col_keep, torch.empty_like(dyc)), None, None
+
+
+# -------------------------------------------------------------------------------------------------
+# masked-LM head (csrc/mlm.hip)
+# -------------------------------------------------------------------------------------------------
+# logits columns alive at a time.  Measured (tools/mlm_bench.py, profiles/mlm_bench.json; 1248 rows, H 768, V 30522, forward +
+# backward): 1024: 4.27 ms / 5 MB, 4096: 1.91 ms / 20 MB, 8192: 1.86 ms / 41 MB, V: 2.82 ms / 153 MB; eager 1.79 ms / 362 MB.
+# 4096 and 8192 are within each other's run-to-run range; 4096 holds half the memory.
+VOCAB_CE_CHUNK = 4096
+
+
+class GatherRowsFunction(torch.autograd.Function):
+    """``hidden`` [..., H] seen as rows, ``positions`` [cap] int32 (flat row, -1 = dead slot) -> [cap, H], zero rows in the dead
+    slots.  Backward: zeros, then one row per position (the positions of a masking call are distinct: no adds)."""
+
+    @staticmethod
+    def forward(ctx, hidden, positions):
+        H = hidden.shape[-1]
+        h2 = hidden.contiguous().float().view(-1, H)
+        out = _empty(positions.numel(), H, like=h2)
+        hip.gather_rows(h2, positions, out)
+        ctx.stash = (positions, hidden.shape, hidden.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        positions, shape, dtype = ctx.stash
+        dsrc = _empty(*shape, like=dout)
+        hip.scatter_rows(dout.contiguous().float(), positions, dsrc.view(-1, shape[-1]))
+        return dsrc.to(dtype), None
+
+
+class DenseGeluFunction(torch.autograd.Function):
+    """gelu_erf(x . W^T + b) on the GEMM's GELU epilogue (BertPredictionHeadTransform.dense + transform_act_fn); the backward
+    multiplies by gelu' of the kept pre-activation (mtvaf_dgelu: the arithmetic of the DGELU epilogue)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x2 = x.contiguous()
+        y, pre = _empty(x2.shape[0], weight.shape[0], like=x2), _empty(x2.shape[0], weight.shape[0], like=x2)
+        hip.linear_fwd(x2, weight, bias, y, epi=hip.EPI_GELU, aux=pre)
+        ctx.stash = (x2, weight, pre)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, weight, pre = ctx.stash
+        dpre = hip.dgelu(dy.contiguous(), pre, torch.empty_like(pre))
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x2)
+            hip.linear_bwd_input(dpre, weight, dx)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(weight)
+            hip.linear_bwd_weight(dpre, x2, dw)
+        if ctx.needs_input_grad[2]:
+            db = _empty(weight.shape[0], like=x2)
+            hip.colsum(dpre, db)
+        return dx, dw, db
+
+
+class RowLayerNormFunction(torch.autograd.Function):
+    """LayerNorm of [rows, H] on the encoder's row kernels (mtvaf_dropout_res_ln_*: no dropout, a zero residual)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x2 = x.contiguous()
+        M = x2.shape[0]
+        zero = torch.zeros_like(x2)
+        out, mean, rstd = torch.empty_like(x2), _empty(M, like=x2), _empty(M, like=x2)
+        hip.dropout_res_ln_fwd(x2, zero, gamma, beta, out, mean, rstd, eps, 0.0, 0, 0)
+        ctx.stash = (x2, zero, gamma, mean, rstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, zero, gamma, mean, rstd = ctx.stash
+        dx, dres = torch.empty_like(x2), torch.empty_like(x2)
+        dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
+        hip.dropout_res_ln_bwd(dout.contiguous(), x2, zero, gamma, mean, rstd, dx, dres, False, dg, db, False, 0.0, 0, 0)
+        return dx, dg, db, None
+
+
+class VocabCEFunction(torch.autograd.Function):
+    """Cross entropy of ``x . weight^T + bias`` against ``labels`` without the [rows, V] logits (include/mtvaf_hip.h,
+    mtvaf_vocab_ce_*): ``x`` [cap,H], ``weight`` [V,H], ``bias`` [V] or None, ``labels`` [cap] int64, ``count`` [1] int32 on the
+    device -- row r is live iff r < count and 0 <= labels[r] < V.  The logits exist ``chunk`` columns at a time: every chunk is one
+    product on the library's GEMM entry point (the process's compute mode) folded into a running log-sum-exp; the backward forms
+    every chunk again, turns it into its gradient in place and runs the three gradient products on it.  ``reduction`` "mean"
+    divides by the live rows (0 of them: +0.0), "sum" does not, "none" makes the per-row losses the differentiable output.
+    -> (loss 0-dim, loss_row [cap], lse_row [cap], stats int32 [3]: live rows, rows whose first argmax is the label, out-of-range
+    labels), all on the device; ``count`` is never read on the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, count, reduction="mean", chunk=None):
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"VocabCEFunction: reduction={reduction!r} (expected 'mean', 'sum' or 'none')")
+        if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or labels.numel() != x.shape[0]:
+            raise ValueError(f"VocabCEFunction: x {tuple(x.shape)}, weight {tuple(weight.shape)}, labels {tuple(labels.shape)}")
+        R, H = x.shape
+        V = weight.shape[0]
+        chunk = min(int(chunk or VOCAB_CE_CHUNK), V)
+        if chunk < V and chunk % 32:
+            raise ValueError(f"VocabCEFunction: chunk={chunk} (a multiple of 32, or at least the vocabulary)")
+        x2, w, b = x.contiguous().float(), weight.contiguous(), None if bias is None else bias.contiguous()
+        lab = labels.contiguous().view(-1).long()
+        per_row = reduction == "none"
+        red = hip.VOCAB_CE_REDUCTIONS["sum" if per_row else reduction]
+        ws = torch.empty(hip.vocab_ce_workspace_bytes(R, H, V, chunk), dtype=torch.uint8, device=x.device).view(torch.float32)
+        state = ws[ws.numel() - (4 * R + 63) // 64 * 64:]
+        for v0 in range(0, V, chunk):
+            v1 = min(V, v0 + chunk)
+            lg = ws[:R * (v1 - v0)].view(R, v1 - v0)
+            hip.linear_fwd(x2, w[v0:v1], None, lg)
+            hip.vocab_ce_chunk_fwd(lg, b, lab, count, state, V, v0, v1)
+        loss, rows, lse = _empty(1, like=x2), _empty(R, like=x2), _empty(R, like=x2)
+        stats = _empty(3, like=x2, dtype=torch.int32)
+        hip.vocab_ce_finish(state, lab, count, loss, rows, lse, stats, V, red)
+        ctx.stash = (x2, w, b, lab, count, lse, stats, red, per_row, chunk)
+        loss = loss.view(())
+        ctx.mark_non_differentiable(loss if per_row else rows, lse, stats)
+        return loss, rows, lse, stats
+
+    @staticmethod
+    def backward(ctx, gloss, grows, _glse, _gstats):
+        x2, w, b, lab, count, lse, stats, red, per_row, chunk = ctx.stash
+        R, H = x2.shape
+        V = w.shape[0]
+        gout = None if per_row else gloss.contiguous().view(1).float()
+        gr = grows.contiguous().float().view(-1) if per_row else None
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_db = b is not None and ctx.needs_input_grad[2]
+        dx = torch.empty_like(x2) if need_dx else None
+        dw = torch.empty_like(w) if need_dw else None
+        db = torch.empty_like(b) if need_db else None
+        ws = torch.empty(R * chunk, dtype=torch.float32, device=x2.device)
+        for v0 in range(0, V, chunk):  # ascending: dx accumulates in this order; every slice of dw / db is written once
+            v1 = min(V, v0 + chunk)
+            lg = ws[:R * (v1 - v0)].view(R, v1 - v0)
+            hip.linear_fwd(x2, w[v0:v1], None, lg)
+            hip.vocab_ce_chunk_bwd(lg, b, lab, count, lse, gout, gr, stats, V, v0, v1, red)
+            if need_dx:
+                hip.linear_bwd_input(lg, w[v0:v1], dx, accumulate=v0 > 0)
+            if need_dw:
+                hip.linear_bwd_weight(lg, x2, dw[v0:v1])
+            if need_db:
+                hip.colsum(lg, db[v0:v1])
+        return dx, dw, db, None, None, None, None

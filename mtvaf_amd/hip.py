@@ -206,6 +206,15 @@ _SIGS = {
     "mtvaf_layer_mix_fwd": (c_int, [P, I, P, P, P, L, I, P]),
     "mtvaf_layer_mix_dots": (c_int, [P, I, P, P, P, L, I, P, L, P, P, P, P]),
     "mtvaf_layer_mix_inject": (c_int, [P, I, I, P, P, L, I, I, P]),
+    "mtvaf_uniform_fill": (c_int, [P, L, U64, U64, P]),
+    "mtvaf_mlm_mask_workspace_bytes": (SZ, [I]),
+    "mtvaf_mlm_mask": (c_int, [P, P, P, P, P, I, F, L, I, I, P, P, P, P, P, P, SZ, I, I, P]),
+    "mtvaf_scatter_rows": (c_int, [P, P, P, I, I, I, P]),
+    "mtvaf_dgelu": (c_int, [P, P, P, L, P]),
+    "mtvaf_vocab_ce_workspace_bytes": (SZ, [I, I, I, I]),
+    "mtvaf_vocab_ce_chunk_fwd": (c_int, [P, I, P, P, P, P, I, I, I, I, P]),
+    "mtvaf_vocab_ce_finish": (c_int, [P, P, P, P, P, P, P, I, I, I, P]),
+    "mtvaf_vocab_ce_chunk_bwd": (c_int, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, P]),
 }
 
 class LayerStruct(ctypes.Structure):
@@ -2268,3 +2277,117 @@ def layer_mix_inject(coef, j, dy, dh=None):
     dh = _word_out(dh, dy.shape, torch.float32, dy.device, "layer_mix_inject: dh")
     _ck(lib().mtvaf_layer_mix_inject(_p(coef), int(j), K, _p(dy), _p(dh), dy.numel() // H, H, int(acc), _st()), "mtvaf_layer_mix_inject")
     return dh
+
+
+# -------------------------------------------------------------------------------------------------
+# masked-LM head (csrc/mlm.hip)
+# -------------------------------------------------------------------------------------------------
+VOCAB_CE_REDUCTIONS = {"mean": 0, "sum": 1}
+MLM_MAX_SPECIAL = 8
+
+
+def _i32(t, n, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n):
+        raise ValueError(f"{what}: {t.dtype} {tuple(t.shape)} on {t.device}: expected contiguous int32 [>= {n}] on the device")
+
+
+def uniform_fill(out, seed, offset):
+    """out (fp32, contiguous, device): uniforms in [0, 1) from the dropout generator at (seed, offset)."""
+    _f32(out)
+    _ck(lib().mtvaf_uniform_fill(_p(out), out.numel(), seed, offset, _st()), "mtvaf_uniform_fill")
+    return out
+
+
+def mlm_mask(input_ids, live_u8, special_u8, uniforms, special_ids, probability, mask_token_id, vocab_size, capacity):
+    """mtvaf_mlm_mask on [B,S] int64 ids, u8 masks and [B,S,3] fp32 uniforms (all contiguous, on the device).
+    -> ids_out [B,S] int64, positions [capacity] int32, labels [capacity] int64, count [1] int32, stats [3] int32."""
+    B, S = input_ids.shape
+    dev = input_ids.device
+    for t, dt, n, what in ((input_ids, torch.int64, B * S, "input_ids"), (live_u8, torch.uint8, B * S, "attention mask"),
+                           (special_u8, torch.uint8, B * S, "special_mask"), (uniforms, torch.float32, 3 * B * S, "uniforms")):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"mlm_mask: {what} {t.dtype} {tuple(t.shape)} on {t.device}: expected contiguous {dt} with {n} elements "
+                             "on the device")
+    special_ids = [int(i) for i in special_ids]
+    if len(special_ids) > MLM_MAX_SPECIAL:
+        raise ValueError(f"mlm_mask: {len(special_ids)} special ids (at most {MLM_MAX_SPECIAL}; use special_mask for more)")
+    if not 1 <= int(capacity) <= B * S:
+        raise ValueError(f"mlm_mask: capacity {capacity} outside 1 .. {B * S}")
+    sp = (c_int64 * MLM_MAX_SPECIAL)(*special_ids)
+    ids_out = torch.empty_like(input_ids)
+    positions = torch.empty(capacity, dtype=torch.int32, device=dev)
+    labels = torch.empty(capacity, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    stats = torch.empty(3, dtype=torch.int32, device=dev)
+    wsb = lib().mtvaf_mlm_mask_workspace_bytes(B)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _ck(lib().mtvaf_mlm_mask(_p(input_ids), _p(live_u8), _p(special_u8), _p(uniforms), sp, len(special_ids), float(probability),
+                             int(mask_token_id), int(vocab_size), int(capacity), _p(ids_out), _p(positions), _p(labels), _p(count),
+                             _p(stats), _p(ws), wsb, B, S, _st()), "mtvaf_mlm_mask")
+    return ids_out, positions, labels, count, stats
+
+
+def gather_rows(src, rowmap, out):
+    """out[r] = src[rowmap[r]] (zeros where rowmap[r] < 0); src [rows_src,H], out [rows,H] fp32, rowmap int32 [rows]."""
+    _f32(src, out)
+    _i32(rowmap, out.shape[0], "gather_rows: rowmap")
+    _ck(lib().mtvaf_gather_rows(_p(src), _p(rowmap), _p(out), out.shape[0], out.shape[1], _st()), "mtvaf_gather_rows")
+    return out
+
+
+def scatter_rows(d, rowmap, dsrc):
+    """dsrc = 0, then dsrc[rowmap[r]] = d[r] for the rows with rowmap[r] >= 0 (distinct): the backward of gather_rows."""
+    _f32(d, dsrc)
+    _i32(rowmap, d.shape[0], "scatter_rows: rowmap")
+    _ck(lib().mtvaf_scatter_rows(_p(d), _p(rowmap), _p(dsrc), d.shape[0], dsrc.shape[0], d.shape[1], _st()), "mtvaf_scatter_rows")
+    return dsrc
+
+
+def dgelu(dy, pre, out):
+    """out = dy * gelu_erf'(pre), elementwise (contiguous fp32 of one shape)."""
+    _f32(dy, pre, out)
+    assert dy.shape == pre.shape == out.shape, (dy.shape, pre.shape, out.shape)
+    _ck(lib().mtvaf_dgelu(_p(dy), _p(pre), _p(out), dy.numel(), _st()), "mtvaf_dgelu")
+    return out
+
+
+def vocab_ce_workspace_bytes(R, H, V, chunk):
+    return int(lib().mtvaf_vocab_ce_workspace_bytes(int(R), int(H), int(V), int(chunk)))
+
+
+def _vocab_ce_inputs(logits, bias, labels, count, V, v0, v1):
+    _f32(logits, bias)
+    R = logits.shape[0]
+    assert logits.shape[1] == v1 - v0 and 0 <= v0 < v1 <= V and (bias is None or bias.numel() == V), (tuple(logits.shape), v0, v1, V)
+    assert labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == R, (labels.dtype, R)
+    _i32(count, 1, "vocab_ce: count")
+    return R
+
+
+def vocab_ce_chunk_fwd(logits, bias, labels, count, state, V, v0, v1):
+    """Folds the logits chunk [R, v1 - v0] (+ bias[v0:v1]) into state (fp32 [4 R]); the chunk with v0 == 0 starts it."""
+    R = _vocab_ce_inputs(logits, bias, labels, count, V, v0, v1)
+    _f32(state)
+    assert state.numel() >= 4 * R
+    _ck(lib().mtvaf_vocab_ce_chunk_fwd(_p(logits), logits.stride(0), _p(bias), _p(labels), _p(count), _p(state), R, V, v0, v1, _st()),
+        "mtvaf_vocab_ce_chunk_fwd")
+
+
+def vocab_ce_finish(state, labels, count, loss, loss_row, lse_row, stats, V, reduction):
+    R = labels.numel()
+    _f32(state, loss, loss_row, lse_row)
+    _i32(count, 1, "vocab_ce: count")
+    _i32(stats, 3, "vocab_ce: stats")
+    assert state.numel() >= 4 * R and loss_row.numel() >= R and lse_row.numel() >= R
+    _ck(lib().mtvaf_vocab_ce_finish(_p(state), _p(labels), _p(count), _p(loss), _p(loss_row), _p(lse_row), _p(stats), R, V,
+                                    int(reduction), _st()), "mtvaf_vocab_ce_finish")
+
+
+def vocab_ce_chunk_bwd(logits, bias, labels, count, lse_row, gout, grows, stats, V, v0, v1, reduction):
+    """In place: the chunk becomes its gradient.  Exactly one of gout [1] and grows [R] is given."""
+    R = _vocab_ce_inputs(logits, bias, labels, count, V, v0, v1)
+    _f32(lse_row, gout, grows)
+    _i32(stats, 3, "vocab_ce: stats")
+    assert lse_row.numel() >= R and (grows is None or grows.numel() == R)
+    _ck(lib().mtvaf_vocab_ce_chunk_bwd(_p(logits), logits.stride(0), _p(bias), _p(labels), _p(count), _p(lse_row), _p(gout), _p(grows),
+                                       _p(stats), R, V, v0, v1, int(reduction), _st()), "mtvaf_vocab_ce_chunk_bwd")

@@ -304,6 +304,40 @@ class _PackedLinears:
         return self.ptrs == [m.weight.data_ptr() for m in mods] + [m.bias.data_ptr() for m in mods]
 
 
+def _mlm_options(args, config, tokenizer):
+    """The masked-LM switches, checked: args.mlm_head, args.mlm_weight (>= 0; > 0 implies the head),
+    args.mlm_probability (0.15), args.mlm_tie (True), args.mlm_chunk (None: the engine's default), args.mlm_mask_token_id and
+    args.mlm_special_ids -- from the tokenizer when there is one, else the ids of the bert / roberta base vocabularies."""
+    weight = float(_arg(args, "mlm_weight", 0.0) or 0.0)
+    if weight < 0:
+        raise ValueError(f"args.mlm_weight={weight!r}: expected a number >= 0")
+    opt = {"head": bool(_arg(args, "mlm_head", False)) or weight > 0, "weight": weight,
+           "probability": float(_arg(args, "mlm_probability", 0.15)), "tie": bool(_arg(args, "mlm_tie", True)),
+           "chunk": _arg(args, "mlm_chunk", None), "mask_token_id": None, "special_ids": ()}
+    if not opt["head"]:
+        return opt
+    if not 0.0 < opt["probability"] <= 1.0:
+        raise ValueError(f"args.mlm_probability={opt['probability']!r}: expected a number in (0, 1]")
+    roberta = "roberta" in args.bert_name
+    mask_id, special = _arg(args, "mlm_mask_token_id", None), _arg(args, "mlm_special_ids", None)
+    if mask_id is None:
+        mask_id = getattr(tokenizer, "mask_token_id", None)
+    if mask_id is None:
+        mask_id = 50264 if roberta else 103
+    if special is None:
+        special = getattr(tokenizer, "all_special_ids", None)
+    if special is None:
+        special = (0, 1, 2, 3, 50264) if roberta else (0, 100, 101, 102, 103)
+    special = tuple(sorted({int(i) for i in special}))
+    if not 0 <= int(mask_id) < config.vocab_size:
+        raise ValueError(f"masked-LM: mask token id {mask_id} is outside the vocabulary of {config.vocab_size} "
+                         "(args.mlm_mask_token_id)")
+    if len(special) > 8:
+        raise ValueError(f"masked-LM: {len(special)} special ids, the kernel takes 8 (args.mlm_special_ids)")
+    opt["mask_token_id"], opt["special_ids"] = int(mask_id), special
+    return opt
+
+
 class TVNetSAModel2(nn.Module):
     def __init__(self, label_list, tokenizer, args, type_num=None, use_weight=False):
         super().__init__()
@@ -384,8 +418,45 @@ class TVNetSAModel2(nn.Module):
         if _arg(args, "use_probe"):
             raise NotImplementedError("the structural probe (probes/) is off the hot path and its import chain is "
                                       "broken in the reference (models/bert_model.py:468-475)")
+        # args.mlm_head (or args.mlm_weight > 0): a masked-LM head on the encoder, its decoder tied to the word table (DESIGN.md
+        # section 4.32) -- `forward_mlm`, and with the weight an auxiliary term of `forward`.  Without either nothing is built.
+        self.mlm_opt = _mlm_options(args, self.bert.config, tokenizer)
+        self.last_mlm_loss = None  # detached device scalar after a forward with labels and args.mlm_weight > 0
+        self.last_mlm_stats = None  # int32 [3] on the device after a masking call: eligible, selected, dropped for capacity
+        if self.mlm_opt["head"]:
+            from ..modules.mlm_head import MaskedLMHead
+            self.mlm_head = MaskedLMHead(self.bert.config, self.bert.get_input_embeddings(),
+                                         style="roberta" if "roberta" in args.bert_name else "bert", tie=self.mlm_opt["tie"],
+                                         chunk=self.mlm_opt["chunk"])
 
     # ------------------------------------------------------------------------------------------------
+    def _mlm_pass(self, input_ids, attention_mask, token_type_ids, prefix_guids, prompt_attention_mask, probability=None):
+        """Masks on the device and runs the encoder on the masked ids under the given prompt -> the MLM loss (mean over the
+        selected tokens).  The selected positions are attended tokens, so the padding-free run holds their hidden rows."""
+        from .. import mlm
+        opt = self.mlm_opt
+        if not opt["head"]:
+            raise ValueError("this model was built without args.mlm_head")
+        picked = mlm.mask_tokens(input_ids, attention_mask, mask_token_id=opt["mask_token_id"], vocab_size=self.bert.config.vocab_size,
+                                 special_ids=opt["special_ids"], probability=opt["probability"] if probability is None else probability)
+        was = self.bert.encoder.output_prefix_mass
+        self.bert.encoder.output_prefix_mass = False
+        out = self.bert(input_ids=picked["input_ids"], attention_mask=prompt_attention_mask, token_type_ids=token_type_ids,
+                        past_key_values=prefix_guids, return_dict=True, prefix_masked=self.last_prefix_slots is not None)
+        self.bert.encoder.output_prefix_mass = was
+        self.last_mlm_stats = picked["stats"]
+        return self.mlm_head(out.last_hidden_state, picked["positions"], picked["labels"], picked["count"])
+
+    def forward_mlm(self, input_ids=None, attention_mask=None, token_type_ids=None, images=None, aux_imgs=None, prefix_mask=None,
+                    image_present=None, aux_present=None, mlm_probability=None):
+        """Masked-LM conditioned on the image prefix (args.mlm_head): the visual prompt is computed once,
+        tokens are chosen and corrupted on the device (`mtvaf_amd.mlm.mask_tokens`: args.mlm_probability 0.15, the dropout
+        generator), the encoder runs on the masked ids and the head returns the mean cross entropy of the chosen tokens.  No image
+        labels: the VAO losses are not formed.  ``self.mlm_head.last_accuracy`` / ``last_count`` stay on the device."""
+        prefix_guids, _, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, None, images, aux_imgs, prefix_mask,
+                                                                       image_present, aux_present, vao=False)
+        return self._mlm_pass(input_ids, attention_mask, token_type_ids, prefix_guids, prompt_attention_mask, mlm_probability)
+
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, imagelabel=None,
                 images=None, aux_imgs=None, allowed_tags=None, token_to_word=None, prefix_mask=None, image_present=None, aux_present=None):
         """reference: models/bert_model.py:480-532.  ``prefix_mask`` [B, P] (1 = the sentence owns that visual slot), or its
@@ -407,6 +478,7 @@ class TVNetSAModel2(nn.Module):
         the CRF head adds ``weight * CE(batch_mean)`` of the same emissions; ``self.last_token_ce`` keeps the unweighted value."""
         self._chain_only(allowed_tags is not None, "allowed_tags")
         word_mode = self._word_mode(token_to_word)
+        text_mask = attention_mask  # (the word axis replaces attention_mask below; the MLM term masks pieces)
         prefix_guids, img_tag_loss, prompt_attention_mask = self._prompt_prologue(input_ids, attention_mask, imagelabel, images,
                                                                                   aux_imgs, prefix_mask, image_present, aux_present)
         # The attention maps are made on request only (the reference hard-codes output_attentions=True, bert_model.py:496-502, and
@@ -437,6 +509,15 @@ class TVNetSAModel2(nn.Module):
             if torch.is_tensor(extra) or extra != 0:  # (adding the literal 0.0 of a VAO-less run is two kernels for nothing)
                 loss = loss + extra
         loss = self._posterior_terms(loss, emissions, mask_u8, labels, logits, decoded)
+        self.last_mlm_loss = None
+        if self.mlm_opt["weight"] > 0 and labels is not None:
+            # args.mlm_weight > 0 adds weight * the masked-LM loss of a second pass over the masked ids, under the prompt of the
+            # first; self.last_mlm_loss keeps the unweighted value.  At the default 0 the step launches nothing for it.
+            if _arg(self.args, "fused_accumulation") and torch.is_grad_enabled():
+                self.bert.encoder.grad_sink.begin_two_node_pass()  # (two encoder nodes under one backward, as forward_consistent)
+            mlm_loss = self._mlm_pass(input_ids, text_mask, token_type_ids, prefix_guids, prompt_attention_mask)
+            self.last_mlm_loss = mlm_loss.detach()
+            loss = loss + self.mlm_opt["weight"] * mlm_loss
         if decoded is not None:
             # the decode reads the CRF parameters: whatever follows on the main stream (optimizer.step() updates them in
             # place) is ordered behind it here, not only by the join inside the encoder backward (frozen encoders skip it)
@@ -445,10 +526,12 @@ class TVNetSAModel2(nn.Module):
 
     # ---- the pieces of `forward`, shared with `forward_consistent` -----------------------------------------------------
     def _prompt_prologue(self, input_ids, attention_mask, imagelabel, images, aux_imgs, prefix_mask=None, image_present=None,
-                         aux_present=None):
+                         aux_present=None, vao=None):
         """-> (prefix_guids, img_tag_loss, prompt_attention_mask): the visual prompt, its VAO loss (args.vao; else 0) and the attention
         mask extended over the prompt's slots (`_prompt_attention_mask`: the per-sentence slot mask enters here and nowhere else);
-        (None, 0, attention_mask) without ``use_prefix``."""
+        (None, 0, attention_mask) without ``use_prefix``.  ``vao=False``: the VAO losses are left out whatever args.vao says (a
+        call without image labels: `forward_mlm`)."""
+        vao = _arg(self.args, "vao") if vao is None else vao
         if not _arg(self.args, "use_prefix"):
             _no_prefix(self, prefix_mask, image_present, aux_present)
             return None, 0, attention_mask
@@ -457,11 +540,11 @@ class TVNetSAModel2(nn.Module):
         n_img = 1 + (0 if aux_imgs is None else aux_imgs.shape[1])
         slots = _prefix_slots(self, B, SLOTS_PER_IMAGE * n_img, dev, prefix_mask, image_present, aux_present)
         present = None
-        if slots is not None and _arg(self.args, "vao"):  # [images, B]: a sentence has an image while it owns one of its slots
+        if slots is not None and vao:  # [images, B]: a sentence has an image while it owns one of its slots
             present = slots.view(B, n_img, SLOTS_PER_IMAGE).any(-1).t().to(torch.float32).contiguous()
         prefix_guids, img_tag_loss, aux_img_tag_loss = _on_second_stream(
-            lambda: self.get_visual_prompt(images, aux_imgs, imagelabel, present=present), (images, aux_imgs, imagelabel, present),
-            join=_arg(self.args, "vao"))  # the VAO losses are consumed on the main stream right away
+            lambda: self.get_visual_prompt(images, aux_imgs, imagelabel, vao=bool(vao), present=present),
+            (images, aux_imgs, imagelabel, present), join=vao)  # the VAO losses are consumed on the main stream right away
         img_tag_loss = img_tag_loss if _arg(self.args, "noauxloss") else img_tag_loss + sum(aux_img_tag_loss)
         if prefix_guids[0][0].shape[2] != SLOTS_PER_IMAGE * n_img:
             raise ValueError(f"the prompt has {prefix_guids[0][0].shape[2]} slots, {n_img} images were expected to give "

@@ -708,3 +708,52 @@ class BertModel(nn.Module):
         seq = enc.last_hidden_state
         pooled = self.pooler(seq) if (self.pooler is not None and not getattr(self, "skip_pooler", False)) else None
         return (seq, pooled) if layer_mix is None else (seq, pooled, enc.mixed_hidden_state)
+
+
+class BertForMaskedLM(nn.Module):
+    """reference: models/modeling_bert.py, BertForMaskedLM -- ``bert.*`` plus the head under ``cls.*``, decoder tied to the word
+    table.  The loss runs on the selected rows only (``modules.mlm_head.MaskedLMHead``): ``labels`` [B,S]
+    with -100 at the positions not predicted (the Hugging Face convention) are compacted on the device, or the caller hands in
+    the ``positions`` / ``mlm_labels`` / ``count`` triple of `mtvaf_amd.mlm.mask_tokens`.  ``attention_mask`` covers the prefix
+    slots of ``past_key_values`` too, as in `BertModel.forward`.
+    -> ``(loss,)`` or ``(loss, logits)`` with ``output_logits``: the logits [capacity, V] of the SELECTED rows.
+    ``capacity``: with ``labels`` the number of labelled positions is known on the device only, so the head runs on B * S rows
+    unless the caller gives a bound here (labelled positions beyond it are dropped); the triple of `mask_tokens` carries its own
+    (twice the expected selection) -- the form a training loop should use."""
+
+    encoder_class = BertModel
+    encoder_name = "bert"
+    head_name = "cls"
+    head_style = "bert"
+
+    def __init__(self, config, tie: bool = True, chunk: Optional[int] = None):
+        super().__init__()
+        from ..modules.mlm_head import MaskedLMHead
+        self.config = config
+        setattr(self, self.encoder_name, self.encoder_class(config, add_pooling_layer=False))
+        setattr(self, self.head_name, MaskedLMHead(config, self.encoder.get_input_embeddings(), style=self.head_style, tie=tie,
+                                                   chunk=chunk))
+
+    @property
+    def encoder(self):
+        return getattr(self, self.encoder_name)
+
+    @property
+    def head(self):
+        return getattr(self, self.head_name)
+
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, past_key_values=None, positions=None,
+                mlm_labels=None, count=None, reduction="mean", output_logits=False, capacity=None):
+        from .. import mlm
+        if (labels is None) == (positions is None):
+            raise ValueError("BertForMaskedLM: give labels [B,S] (-100 = not predicted) or the positions / mlm_labels / count triple")
+        if labels is not None:
+            positions, mlm_labels, count = mlm.compact_labels(labels, self.config.vocab_size, capacity)
+        elif mlm_labels is None or count is None:
+            raise ValueError("BertForMaskedLM: positions come with mlm_labels and count")
+        out = self.encoder(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids,
+                           past_key_values=past_key_values)
+        hidden = out.last_hidden_state
+        if output_logits:
+            return self.head(hidden, positions, mlm_labels, count, reduction=reduction, return_logits=True)
+        return (self.head(hidden, positions, mlm_labels, count, reduction=reduction),)

@@ -13,7 +13,7 @@ import torch
 from torch import nn
 from transformers import RobertaConfig
 
-from .modeling_bert import BertEmbeddings, BertModel
+from .modeling_bert import BertEmbeddings, BertForMaskedLM, BertModel
 
 
 class RobertaEmbeddings(BertEmbeddings):
@@ -48,3 +48,13 @@ class RobertaModel(BertModel):
                              num_hidden_layers=24 if large else 12, num_attention_heads=16 if large else 12,
                              intermediate_size=4096 if large else 3072, max_position_embeddings=514,
                              type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=1)
+
+
+class RobertaForMaskedLM(BertForMaskedLM):
+    """reference: models/modeling_roberta.py, RobertaForMaskedLM -- ``roberta.*`` plus ``lm_head.*`` (dense, layer_norm, decoder,
+    bias)."""
+
+    encoder_class = RobertaModel
+    encoder_name = "roberta"
+    head_name = "lm_head"
+    head_style = "roberta"

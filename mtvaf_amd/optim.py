@@ -1013,19 +1013,31 @@ def _is_layer_mix(name: str) -> bool:
     return name.startswith("layer_mix.") or ".layer_mix." in name
 
 
+def _is_mlm_head(name: str) -> bool:
+    """A parameter of a model's `MaskedLMHead` (args.mlm_head) under its own name.  The tied word table is not one: it is listed
+    once, under the encoder's name, and trains with the encoder."""
+    return name.startswith("mlm_head.") or ".mlm_head." in name
+
+
+def _mlm_no_decay(name: str) -> bool:
+    """... exempt from weight decay whatever ``no_decay`` names: its LayerNorm, the dense bias and the vocabulary bias."""
+    return _is_mlm_head(name) and (name.endswith(".bias") or "LayerNorm." in name or "layer_norm." in name)
+
+
 def reference_param_groups(model: torch.nn.Module, lr: float, use_prefix: bool = True) -> List[Dict]:
     """The parameter groups of modules/train.py:887-916 (by parameter name, in the reference's order).  A model with args.layer_mix
     (not the reference's) gets one more group behind them: the mix's two parameters, at the head's lr (``lr`` without a prefix),
-    weight decay 0."""
+    weight decay 0.  A model with args.mlm_head (not the reference's either): the head's dense weight (and an untied decoder) join
+    the head group, its LayerNorm and biases the weight-decay-0 group behind it (shared with the mix)."""
     named = list(model.named_parameters())
-    mix = [p for n, p in named if _is_layer_mix(n)]
-    named = [(n, p) for n, p in named if not _is_layer_mix(n)]
+    mix = [p for n, p in named if _is_layer_mix(n) or _mlm_no_decay(n)]
+    named = [(n, p) for n, p in named if not (_is_layer_mix(n) or _mlm_no_decay(n))]
     if not use_prefix:  # bert_before_train: every parameter, one group
         return [{"params": [p for _, p in named], "lr": lr}] + ([{"params": mix, "lr": lr, "weight_decay": 0.0}] if mix else [])
     groups = [
         {"lr": lr, "weight_decay": 1e-2, "params": [p for n, p in named if "bert" in n]},
         {"lr": lr, "weight_decay": 1e-2, "params": [p for n, p in named if "encoder_conv" in n or "gates" in n]},
-        {"lr": 5e-2, "weight_decay": 1e-2, "params": [p for n, p in named if "crf" in n or n.startswith("fc")]},
+        {"lr": 5e-2, "weight_decay": 1e-2, "params": [p for n, p in named if "crf" in n or n.startswith("fc") or _is_mlm_head(n)]},
     ]
     if mix:
         groups.append({"lr": 5e-2, "weight_decay": 0.0, "params": mix})
@@ -1048,7 +1060,9 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
       * the encoder is split by depth: layer ``l`` of ``L`` (``encoder.layer.<l>.``) trains at ``lr * layer_lr_decay ** (L - 1 - l)``,
         the embeddings at ``lr * layer_lr_decay ** L``, whatever sits above the last layer (the pooler) at ``lr``.
     The two parameters of a `LayerMix` (``layer_mix.scalars``, ``layer_mix.gamma``; args.layer_mix) belong to the head partition and
-    are always exempt from weight decay, whatever ``no_decay`` names.
+    are always exempt from weight decay, whatever ``no_decay`` names.  So do the parameters of a `MaskedLMHead` (``mlm_head.*``;
+    args.mlm_head): the dense weight (and an untied decoder) with weight decay, the LayerNorm and the biases always without; the
+    tied word table is the encoder's.
     Groups come in the order their first parameter has in ``named_parameters()``.  With ``no_decay=()`` and ``layer_lr_decay=1`` these
     are the reference groups.  An encoder layer then holds two groups; ``AdamW`` still updates it with one launch (``layer_segments``)."""
     import re
@@ -1057,7 +1071,7 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
     if use_prefix:
         parts = [(lr, [(n, p) for n, p in named if "bert" in n], True),
                  (lr, [(n, p) for n, p in named if "encoder_conv" in n or "gates" in n], False),
-                 (head_lr, [(n, p) for n, p in named if "crf" in n or n.startswith("fc") or _is_layer_mix(n)], False)]
+                 (head_lr, [(n, p) for n, p in named if "crf" in n or n.startswith("fc") or _is_layer_mix(n) or _is_mlm_head(n)], False)]
     else:
         parts = [(lr, named, True)]
     layer_of = lambda n: re.search(r"encoder\.layer\.(\d+)\.", n)
@@ -1069,7 +1083,7 @@ def finetune_param_groups(model: torch.nn.Module, lr: float, weight_decay: float
             power = 0
             if by_depth and layer_lr_decay != 1.0:
                 power = L - 1 - int(layer_of(n).group(1)) if layer_of(n) else (L if "embeddings." in n else 0)
-            split.setdefault((power, any(s in n for s in no_decay) or _is_layer_mix(n)), []).append(p)
+            split.setdefault((power, any(s in n for s in no_decay) or _is_layer_mix(n) or _mlm_no_decay(n)), []).append(p)
         if not split:  # (the reference keeps its empty second group too)
             split[(0, False)] = []
         groups.extend({"lr": base_lr * layer_lr_decay ** power, "weight_decay": 0.0 if exempt else weight_decay, "params": ps}
